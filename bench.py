@@ -31,6 +31,10 @@ What the JSON line carries beyond the contract fields:
                           maximum_parallel_thread model); cpu_baseline_1thread: median of >= 20 single-scan runs after
                           3 warm-ups; cpu_baseline_shipped_config: the shipped operating point (Q-pipe, 200 blocks)
 
+A plain run (`--steps K --warmup W`) sets up, warms up, times the K headline steps and prints the contract fields (value,
+ms_per_step, ...); everything listed above beyond `value` / `ms_per_step` is measured only with --full.  --dump-outputs DIR
+writes the headline loop's last results as DIR/<name>.npy (float64; inputs are seeded, so two builds compare file for file).
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -86,6 +90,10 @@ def parse():
     ap.add_argument("--in-flight", type=int, default=3, help="batches in flight in the timed loop (extractor handle + registrar each)")
     ap.add_argument("--cpu-runs", type=int, default=20, help="timed single-thread oracle runs (after 3 warm-ups); their median is cpu_baseline_1thread")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the all-core CPU baseline (0 = os.cpu_count())")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the one-batch-at-a-time, streamed, single-scan "
+                    "and Q-pipe figures, kernel times and rooflines, CPU baselines and the oracle audit (a plain run times the headline loop only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the headline loop's last step "
+                    "returned (poses, accept flags, per-scan reports) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -199,6 +207,46 @@ def pipeline_schedule(k_steps, n_slots, start, collect):
     return o
 
 
+REPORT_FIELDS = ("final_cost", "initial_cost", "inlier_threshold", "angular_diff_deg", "t_diff", "icp_iterations", "n_blocks_last",
+                 "corner_avail", "surf_avail", "lm_iterations_total", "accepted", "gated", "aborted")
+
+
+def dump_outputs(out_dir, out):
+    """--dump-outputs: what Point_cloud_registration.collect returned for the last timed batch, as float64 .npy files (a few
+    hundred KB at B = 256): accept flags, final and incremental poses (B x 7, quaternion xyzw + translation), every per-scan
+    report field"""
+    res, pc, pi, reps = out
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"accepted": res, "pose_w_curr": pc, "pose_incremental": pi}
+    arrays.update({"report_" + f: [getattr(r, f) for r in reps] for f in REPORT_FIELDS})
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def make_scans(synth, world_model, seeds, n):
+    """synth.make_scan for every seed, in worker processes: one at a time they are most of a run's set-up (~0.14 s each on one
+    core).  Fresh interpreters (spawn) that never open the GPU; each scan depends on its seed only, so the batch is the same
+    whatever the worker count."""
+    import functools
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    workers = min(16, len(os.sched_getaffinity(0)), len(seeds))
+    if workers <= 1:
+        return [synth.make_scan(world_model, k, n=n) for k in seeds]
+    with ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("spawn")) as ex:
+        return list(ex.map(functools.partial(synth.make_scan, world_model, n=n), seeds, chunksize=max(1, len(seeds) // (4 * workers))))
+
+
+def config_line(args, vox, corner, surf, n_distinct, world, pipeline_note):
+    return {"workload": "C2: 24k-pt Mid-40 scan vs 5M-pt corner+surface map, 10 ICP iters (fixed), k=5, "
+                        + ("Q-pipe (device VoxelGrid 0.1/0.4 before registration)" if vox else "Q-full"),
+            "scan_points": args.scan_points, "map_points": int(len(corner) + len(surf)), "map_corner": int(len(corner)),
+            "map_surf": int(len(surf)), "icp_iters": args.icp_iters, "batch_scans_per_step_per_gpu": args.batch,
+            "distinct_scans_in_batch": n_distinct,
+            "parallelism": f"replicas x{world} (independent scans, no data-path collective)"
+                           + ("" if pipeline_note is None else f"; {pipeline_note['batches_in_flight']} batches in flight per GPU (extraction / registration of batch i+1 overlaps registration of batch i)")}
+
+
 def free_port():
     import socket
     with socket.socket() as so:
@@ -271,7 +319,7 @@ def main():
     t0 = time.time()
     world_model, corner, surf = synth.make_maps(args.map_points)
     n_distinct = max(1, min(args.distinct_scans, B))
-    base = [synth.make_scan(world_model, 1000 * rank + k, n=N) for k in range(n_distinct)]
+    base = make_scans(synth, world_model, [1000 * rank + k for k in range(n_distinct)], N)
     rng = np.random.default_rng(4242 + rank)
     # page-locked host copies of the batch: the streamed figure uploads from here with asynchronous copies
     scans_t = torch.empty((B, N, 4), dtype=torch.float32).pin_memory()
@@ -341,40 +389,43 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    for _ in range(args.warmup):
-        step()
-    barrier()
-    t0 = time.perf_counter()
+    def over_ranks(el):
+        """-> (max-over-ranks elapsed, per-rank scans/s)"""
+        per = [round(B * args.steps / el, 2)]
+        if dist is not None:
+            mine = torch.tensor([B * args.steps / el], device="cuda", dtype=torch.float64)
+            allr = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(allr, mine)
+            per = [round(float(x.item()), 2) for x in allr]
+            t = torch.tensor([el], device="cuda", dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            el = float(t.item())
+        return el, per
+
+    if dist is not None:
+        world = dist.get_world_size()  # what RCCL saw
+    total_scans = B * args.steps * world
     k_ms = np.zeros(3)
     k_n = np.zeros(3)
     out = None
-    for _ in range(args.steps):
-        out = step()
-        ms, n = reg.kernel_times()
-        k_ms += ms
-        k_n += n
-    barrier()
-    elapsed = time.perf_counter() - t0
-    per_rank = [round(B * args.steps / elapsed, 2)]
-    if dist is not None:
-        mine = torch.tensor([B * args.steps / elapsed], device="cuda", dtype=torch.float64)
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        per_rank = [round(float(x.item()), 2) for x in allr]
-        t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-        world = dist.get_world_size()  # what RCCL saw
-    res, pc, pi, reps = out
-    nc, ns, nf, n_amb = fe.counts(B)
-    nc_fe, ns_fe = nc, ns
-    if vox:  # what the registrar saw
-        nc, ns = vox[0].counts(B)[0], vox[1].counts(B)[0]
-    total_scans = B * args.steps * world
-    value = total_scans / elapsed
-    ms_per_step = 1e3 * elapsed / args.steps
     sequential, pipeline_note = None, None
-    seq_ms_per_step = ms_per_step
+    # the one-batch-at-a-time loop: the value with --no-pipeline, otherwise measured with --full only (the `sequential` figure; the
+    # kernel times and rooflines are taken in it)
+    if args.full or args.no_pipeline:
+        for _ in range(args.warmup):
+            step()
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out = step()
+            ms, n = reg.kernel_times()
+            k_ms += ms
+            k_n += n
+        barrier()
+        elapsed, per_rank = over_ranks(time.perf_counter() - t0)
+        value = total_scans / elapsed
+        ms_per_step = 1e3 * elapsed / args.steps
+        seq_ms_per_step = ms_per_step
 
     # ---- the same K steps, consecutive batches overlapped: two extractor handles (both hold the resident scans) and two registrars
     #      on their own streams; batch i+1 is extracted and its registration enqueued while batch i's kernels run, so the device
@@ -399,22 +450,39 @@ def main():
         tp = time.perf_counter()
         out_p = pipelined(args.steps, slots)
         barrier()
-        el_p = time.perf_counter() - tp
-        per_rank_p = [round(B * args.steps / el_p, 2)]
-        if dist is not None:
-            mine = torch.tensor([B * args.steps / el_p], device="cuda", dtype=torch.float64)
-            allr = [torch.zeros_like(mine) for _ in range(world)]
-            dist.all_gather(allr, mine)
-            per_rank_p = [round(float(x.item()), 2) for x in allr]
-            t = torch.tensor([el_p], device="cuda", dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            el_p = float(t.item())
-        same = bool(np.array_equal(out_p[0], res) and np.array_equal(out_p[1], pc) and np.array_equal(out_p[2], pi))
-        sequential = {"value": round(value, 2), "unit": "scans/s", "ms_per_step": round(ms_per_step, 3), "per_rank_scans_per_s": per_rank,
-                      "note": "one batch at a time: extract, fix up labels, select, register, download, then the next batch"}
+        el_p, per_rank_p = over_ranks(time.perf_counter() - tp)
+        pipeline_note = {"batches_in_flight": D}
+        if out is not None:
+            pipeline_note["results_equal_sequential_bitwise"] = bool(np.array_equal(out_p[0], out[0]) and np.array_equal(out_p[1], out[1])
+                                                                    and np.array_equal(out_p[2], out[2]))
+            sequential = {"value": round(value, 2), "unit": "scans/s", "ms_per_step": round(ms_per_step, 3), "per_rank_scans_per_s": per_rank,
+                          "note": "one batch at a time: extract, fix up labels, select, register, download, then the next batch"}
+        pipeline_note["what"] = f"{D} extractor handles + {D} registrars on their own streams; batch i+1 is extracted and enqueued while batch i runs"
         value, ms_per_step, per_rank = total_scans / el_p, 1e3 * el_p / args.steps, per_rank_p
-        pipeline_note = {"batches_in_flight": D, "results_equal_sequential_bitwise": same,
-                         "what": f"{D} extractor handles + {D} registrars on their own streams; batch i+1 is extracted and enqueued while batch i runs"}
+    out_headline = out if slots is None else out_p   # the timed path's last step: what --dump-outputs writes
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_headline)
+
+    res, pc, pi, reps = out_headline if out is None else out
+    nc, ns, nf, n_amb = fe.counts(B)
+    nc_fe, ns_fe = nc, ns
+    if vox:  # what the registrar saw
+        nc, ns = vox[0].counts(B)[0], vox[1].counts(B)[0]
+    if not args.full:
+        result = {"metric": "scans_per_s", "value": round(value, 2), "unit": "scans/s", "n_gpus": world, "steps": args.steps,
+                  "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
+                  "vs_baseline": None, "dtype": "f32 points / f64 solve", "data": "synthetic",
+                  "config": config_line(args, vox, corner, surf, n_distinct, world, pipeline_note),
+                  "per_rank_scans_per_s": per_rank, "pipeline": pipeline_note,
+                  "features_per_scan": {"corner": float(nc.mean()), "surface": float(ns.mean())}, "accepted_frac": float(np.mean(res)),
+                  "setup_s": {"synthetic_data": round(t_data, 1), "map_upload_grid_build": round(t_map, 2)},
+                  "note": "headline loop only; the other figures, rooflines and CPU baselines: --full"}
+        if rank == 0:
+            print(json.dumps(result))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the same steps with the scans crossing PCIe inside the timed region (SURVEY 8d "end-to-end ... of one scan") ----
     streamed = None
@@ -651,13 +719,7 @@ def main():
         "metric": "scans_per_s", "value": round(value, 2), "unit": "scans/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32 points / f64 solve", "data": "synthetic",
-        "config": {"workload": "C2: 24k-pt Mid-40 scan vs 5M-pt corner+surface map, 10 ICP iters (fixed), k=5, "
-                               + ("Q-pipe (device VoxelGrid 0.1/0.4 before registration)" if vox else "Q-full"),
-                   "scan_points": N, "map_points": int(len(corner) + len(surf)), "map_corner": int(len(corner)),
-                   "map_surf": int(len(surf)), "icp_iters": args.icp_iters, "batch_scans_per_step_per_gpu": B,
-                   "distinct_scans_in_batch": n_distinct,
-                   "parallelism": f"replicas x{world} (independent scans, no data-path collective)"
-                                  + ("" if pipeline_note is None else f"; {pipeline_note['batches_in_flight']} batches in flight per GPU (extraction / registration of batch i+1 overlaps registration of batch i)")},
+        "config": config_line(args, vox, corner, surf, n_distinct, world, pipeline_note),
         "per_rank_scans_per_s": per_rank,
         # a device-side clock beside the wall clock: HIP events on the registrar's stream around every launch class, summed (the
         # extraction kernels run on the extractor's stream and are not in it: ~0.3 ms per step)

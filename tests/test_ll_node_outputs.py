@@ -5,7 +5,7 @@ cloud on /velodyne_cloud_registered (:1570-1575), nav_msgs/Odometry on /aft_mapp
 tenth frame, the camera_init -> aft_mapped transform (:1613-1653) -- plus /laser_cloud_surround from the full-cloud cell map (:1151-1200).
 
 The checker is the reference's own text: tests/verbatim_build.py pulls those line ranges out of /root/reference and compiles them
-against stub ROS message types into tests/cpp/_verbatim/verbatim_mapping_io (the binary travels to the GPU box like oracle/_ref).
+against stub ROS message types into oracle/_ref/verbatim/verbatim_mapping_io (the binary travels to the GPU box with oracle/_ref).
 Both programs are driven by the same io record ("LLIO0001": handler calls, process passes, publish calls) and log every message they
 hand to a publisher; the logs must be equal line for line.
 
@@ -31,7 +31,7 @@ from tests.test_ll_node import build_node, sequence  # noqa: E402
 def harness():
     exe = verbatim_build.build_mapping_io()
     if exe is None:
-        pytest.skip("tests/cpp/_verbatim/verbatim_mapping_io not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/verbatim/verbatim_mapping_io not built (needs the reference sources at build time)")
     return exe
 
 

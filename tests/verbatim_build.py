@@ -2,12 +2,12 @@
 (laser_mapping.hpp:1266-1297 init_pointcloud_registration, :1405-1445 / :1494-1512 process_new_scan) wrapped in a harness
 with a main(), compiled twice from the same text --
 
-    tests/cpp/_verbatim/verbatim_adapter    Point_cloud_registration = loam_livox_hip::Point_cloud_registration (links the C-ABI library)
-    tests/cpp/_verbatim/verbatim_reference  Point_cloud_registration = the reference's own class (point_cloud_registration.hpp
+    oracle/_ref/verbatim/verbatim_adapter    Point_cloud_registration = loam_livox_hip::Point_cloud_registration (links the C-ABI library)
+    oracle/_ref/verbatim/verbatim_reference  Point_cloud_registration = the reference's own class (point_cloud_registration.hpp
                                             against oracle/ref_stubs, the recipe of oracle/Makefile's `ref` target)
 
 The excerpts are pulled out of /root/reference by line range at build time; the translation unit lives in a temporary
-directory and only the binaries stay (git-ignored, like oracle/_ref; they travel to the GPU box with the tree).  Test
+directory and only the binaries stay (under the git-ignored oracle/_ref, which travels to the GPU box with the tree).  Test
 infrastructure only."""
 import os
 import subprocess
@@ -18,7 +18,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 REF = "/root/reference"
-OUT = os.path.join(ROOT, "tests", "cpp", "_verbatim")
+OUT = os.path.join(ROOT, "oracle", "_ref", "verbatim")
+
+
+def link_lib(lib):
+    """link the C-ABI library by name, found next to the tree's own build at run time: the binaries travel with oracle/_ref and
+    run against the library of the checkout they land in"""
+    rel = os.path.relpath(os.path.dirname(lib), OUT)
+    return ["-L", os.path.dirname(lib), "-l" + os.path.basename(lib)[3:-3], "-Wl,-rpath,$ORIGIN/" + rel]
+
+
 EXE_A, EXE_B = os.path.join(OUT, "verbatim_adapter"), os.path.join(OUT, "verbatim_reference")
 
 HEAD = r'''
@@ -203,7 +212,7 @@ def build(force=False):
         inc = ["-I", os.path.join(stubs, "override"), "-I-", "-I", stubs, "-I", os.path.join(REF, "source"), "-I", os.path.join(REF, "include"),
                "-I", os.path.join(REF, "include", "tools"), "-I", os.path.join(ROOT, "include")]
         common = ["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-fno-fast-math", "-w"]
-        subprocess.check_call(common + ["-DLL_USE_ADAPTER"] + inc + [src, "-o", EXE_A, lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath,/opt/rocm/lib", "-lpthread"])
+        subprocess.check_call(common + ["-DLL_USE_ADAPTER"] + inc + [src, "-o", EXE_A, *link_lib(lib), "-Wl,-rpath,/opt/rocm/lib", "-lpthread"])
         subprocess.check_call(common + inc + [src, "-o", EXE_B, "-lpthread"])
     return EXE_A, EXE_B
 
@@ -421,7 +430,7 @@ def build_sequence(force=False):
         inc = ["-I", os.path.join(stubs, "override"), "-I-", "-I", stubs, "-I", os.path.join(REF, "source"), "-I", os.path.join(REF, "include"),
                "-I", os.path.join(REF, "include", "tools"), "-I", os.path.join(ROOT, "include")]
         common = ["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-fno-fast-math", "-w"]
-        subprocess.check_call(common + ["-DLL_USE_ADAPTER"] + inc + [src, "-o", EXE_SA, lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath,/opt/rocm/lib", "-lpthread"])
+        subprocess.check_call(common + ["-DLL_USE_ADAPTER"] + inc + [src, "-o", EXE_SA, *link_lib(lib), "-Wl,-rpath,/opt/rocm/lib", "-lpthread"])
         subprocess.check_call(common + ["-DLL_USE_SEQ_REF"] + inc + [src, "-o", EXE_SB, "-lpthread"])
     return EXE_SA, EXE_SB
 
@@ -631,7 +640,7 @@ def build_feature(force=False):
         inc = ["-I", os.path.join(stubs, "override"), "-I-", "-I", stubs, "-I", os.path.join(REF, "source"), "-I", os.path.join(REF, "include"),
                "-I", os.path.join(REF, "include", "tools"), "-I", os.path.join(ROOT, "include")]
         common = ["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-fno-fast-math", "-w"]
-        subprocess.check_call(common + ["-DLL_USE_ADAPTER"] + inc + [src, "-o", EXE_FA, lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath,/opt/rocm/lib", "-lpthread"])
+        subprocess.check_call(common + ["-DLL_USE_ADAPTER"] + inc + [src, "-o", EXE_FA, *link_lib(lib), "-Wl,-rpath,/opt/rocm/lib", "-lpthread"])
         subprocess.check_call(common + inc + [src, "-o", EXE_FB, "-lpthread"])
     return EXE_FA, EXE_FB
 

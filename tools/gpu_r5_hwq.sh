@@ -1,9 +1,10 @@
 #!/bin/bash
-cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out
+REPO=$(cd "$(dirname "$0")/.." && pwd)
+cd "$REPO" || exit 1
+mkdir -p bench_out
 for Q in 6 8 12 16 32 8 16; do
-  GPU_MAX_HW_QUEUES=$Q timeout 600 python bench.py --no-cpu-baseline --no-streamed --steps 20 --warmup 5 > gpurun_out/r5q_hwq$Q.json 2> gpurun_out/r5q_hwq$Q.err
-  python - gpurun_out/r5q_hwq$Q.json $Q <<'PY'
+  GPU_MAX_HW_QUEUES=$Q timeout 600 python bench.py --full --no-cpu-baseline --no-streamed --steps 20 --warmup 5 > bench_out/r5q_hwq$Q.json 2> bench_out/r5q_hwq$Q.err
+  python - bench_out/r5q_hwq$Q.json $Q <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])
 q=d.get("q_pipe") or {}

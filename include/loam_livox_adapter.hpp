@@ -334,6 +334,71 @@ class Livox_laser {
 };
 
 // ------------------------------------------------------------------------------------------------------------
+// The spinning-lidar branch of Laser_feature::laserCloudHandler (lidar_type != "livox", laser_feature_extractor.hpp:393-787):
+// the reference has no class for it; extract() replaces the body between the start-up gate and the publishes and fills the five
+// clouds the node publishes (/laser_points_2, /laser_cloud_sharp, /laser_cloud_less_sharp, /laser_cloud_flat,
+// /laser_cloud_less_flat).  Cloud is pcl::PointCloud<pcl::PointXYZI> or anything with
+// points[i].x / y / z / intensity.  Set the parameters before the first call (ROS feature_extraction/*, :137-140).
+class Spinning_laser {
+   public:
+    int scan_line = 16;             // feature_extraction/scan_line; 16 or 64 (:160-164)
+    float minimum_range = 0.1f;     // feature_extraction/minimum_range
+    float plane_resolution = 0.8f;  // feature_extraction/mapping_plane_resolution
+    int device = 0;
+    int max_points = 0;             // 0: sized for the first scan seen (grown on demand)
+    int max_line_points = 8192;
+    Spinning_laser() = default;
+    Spinning_laser(const Spinning_laser &) = delete;
+    Spinning_laser &operator=(const Spinning_laser &) = delete;
+    ~Spinning_laser()
+    {
+        if (h_) ll_spin_destroy(h_);
+    }
+
+    template <class Cloud>
+    void extract(const Cloud &in, Cloud &full, Cloud &sharp, Cloud &less_sharp, Cloud &flat, Cloud &less_flat)
+    {
+        const std::vector<float> raw = cloud_to_xyzi(in);
+        const int n = (int)in.points.size();
+        ensure_handle(n);
+        const float dummy[4] = {0, 0, 0, 0};
+        const int st = ll_spin_extract(h_, n ? raw.data() : dummy, n);
+        check(st, "ll_spin_extract");
+        if (st != LL_SPIN_STATUS_OK) throw std::runtime_error("ll_spin_extract: a line holds more less-flat points than max_line_points");
+        Cloud *outs[5] = {&full, &sharp, &less_sharp, &flat, &less_flat};
+        for (int which = 0; which < 5; which++) {
+            int32_t m = 0;
+            check(ll_spin_cloud(h_, 0, which, buf_.data(), nullptr, &m), "ll_spin_cloud");
+            xyzi_to_cloud(buf_.data(), m, *outs[which]);
+        }
+    }
+
+   private:
+    void ensure_handle(int n)
+    {
+        if (h_ && n <= cap_) return;
+        if (h_) ll_spin_destroy(h_);
+        h_ = nullptr;
+        ll_spin_params p;
+        ll_spin_default_params(&p);
+        p.scan_line = scan_line;
+        p.minimum_range = minimum_range;
+        p.plane_resolution = plane_resolution;
+        p.device = device;
+        cap_ = max_points > 0 ? max_points : (n > p.max_points ? n : p.max_points);
+        p.max_points = cap_;
+        p.max_scans = 1;
+        p.max_line_points = max_line_points;
+        runtime_hints();
+        check(ll_spin_create(&p, &h_), "ll_spin_create");
+        buf_.assign((size_t)cap_ * 4, 0.f);
+    }
+    ll_spin *h_ = nullptr;
+    int cap_ = 0;
+    std::vector<float> buf_;
+};
+
+// ------------------------------------------------------------------------------------------------------------
 // pcl::VoxelGrid<PointType> as the node shells use it: setLeafSize / setInputCloud / filter
 // (laser_feature_extractor.hpp:192-193,372-381; laser_mapping.hpp:742-743,1367-1373,1434-1437,533-537).
 // CloudPtr is anything that dereferences to a cloud (std::shared_ptr, boost::shared_ptr, raw pointer).

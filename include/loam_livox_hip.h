@@ -497,6 +497,78 @@ int ll_reg_debug_cycles(ll_reg *r, int32_t scan, long long out[16]);
  * out[2] / out[3] = the same for surface queries. */
 int ll_reg_debug_worklists(ll_reg *r, int32_t n_scans, int64_t out[4]);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Spinning-lidar feature extraction: the branch of Laser_feature::laserCloudHandler the reference runs when
+ * common/lidar_type is not "livox" or is missing (laser_feature_extractor.hpp:393-787, m_lidar_type = 0 at :831-851):
+ * classic LOAM features of a VLP-16 / HDL-64 scan.  One message in, five clouds out:
+ *   LL_SPIN_FULL        laserCloud, the kept points line after line (:513-521), published on /laser_points_2;
+ *                       intensity = scanID + 0.1 * relTime (:501-502)
+ *   LL_SPIN_SHARP       /laser_cloud_sharp       (:657-714, label 2)
+ *   LL_SPIN_LESS_SHARP  /laser_cloud_less_sharp  (label 2 and 1)
+ *   LL_SPIN_FLAT        /laser_cloud_flat        (:716-757, label -1)
+ *   LL_SPIN_LESS_FLAT   /laser_cloud_less_flat   (:760-776: label <= 0, per-line VoxelGrid of leaf plane_resolution / 2,
+ *                       PCL 1.9 semantics as ll_voxel_filter)
+ *   LL_SPIN_LESS_FLAT_PRE  the less-flat points before the VoxelGrid (positions only; not published by the reference)
+ * Every cloud is in the reference's order.  Index sets, x, y, z and the less-flat centroids are bit-exact with the host C
+ * library; the intensity of laserCloud comes from the device atan2f and may differ from the host's in the last bits
+ * (discrete outcomes never do: see ll_spin_resolve).
+ *
+ * Edges the reference leaves undefined, defined here:
+ *   - startOri / endOri and the orientation loop use the first / last point of the FILTERED cloud (the reference takes
+ *     cloudSize before the filters of :399-400); identical whenever nothing is filtered;
+ *   - a sharp-point walk (+-500, :687-710) stops at either end of laserCloud;
+ *   - no point gets a curvature (none is selected) when laserCloud has 10 points or fewer (`cloudSize - 5` is a size_t);
+ *   - non-finite points are always removed (removeNaNFromPointCloud skips clouds marked is_dense);
+ *   - more than max_points (<= 400 000, the size of the reference's member arrays) points is an error, not a crash;
+ *   - a line with more less-flat points than max_line_points is reported as status LL_SPIN_STATUS_LINE_OVERFLOW. */
+typedef struct ll_spin ll_spin; /* replaces the lidar_type = velodyne branch of Laser_feature (laser_feature_extractor.hpp:393-787) */
+
+enum { LL_SPIN_FULL = 0, LL_SPIN_SHARP = 1, LL_SPIN_LESS_SHARP = 2, LL_SPIN_FLAT = 3, LL_SPIN_LESS_FLAT = 4, LL_SPIN_LESS_FLAT_PRE = 5 };
+enum { LL_SPIN_STATUS_OK = 0, LL_SPIN_STATUS_LINE_OVERFLOW = 2 };
+#define LL_SPIN_MAX_POINTS 400000
+
+typedef struct {
+    int32_t scan_line;       /* ROS feature_extraction/scan_line (:137, default 16); 16 or 64 (:160-164) */
+    float minimum_range;     /* ROS feature_extraction/minimum_range (:140, default 0.1; used as float, :399) */
+    float plane_resolution;  /* ROS feature_extraction/mapping_plane_resolution (:138, default 0.8); leaf = value / 2 */
+    int32_t device;          /* HIP device ordinal */
+    int32_t max_points;      /* capacity: input points per scan, <= LL_SPIN_MAX_POINTS */
+    int32_t max_scans;       /* capacity: scans resident at once */
+    int32_t max_line_points; /* capacity: less-flat points of one line handed to the VoxelGrid */
+} ll_spin_params;
+
+void ll_spin_default_params(ll_spin_params *p); /* node defaults; max_points 32768, max_scans 1, max_line_points 8192 */
+/* Fails for a scan_line other than 16 / 64 (the reference refuses them at :160-164) and for bad capacities. */
+int ll_spin_create(const ll_spin_params *p, ll_spin **out);
+void ll_spin_destroy(ll_spin *h);
+/* Uploads n_scans scans into slots first_scan ..: scan b has n_points[b] points at xyzi + b * stride_points * 4 (pcl::PointXYZI
+ * payloads, as pcl::fromROSMsg gives them at :396).  Also computes startOri / endOri of each scan with the host C library
+ * (:403-415).  A scan of more than max_points points fails the call before anything is changed.  Synchronous. */
+int ll_spin_upload(ll_spin *h, int32_t first_scan, int32_t n_scans, const float *xyzi, const int32_t *n_points, int32_t stride_points);
+/* Extracts the features of slots 0 .. n_scans-1 (:397-776).  Asynchronous on the handle's stream. */
+int ll_spin_extract_batch(ll_spin *h, int32_t n_scans);
+/* The scan-ID bins, the range tests, the +-2 pi unwrap tests and the halfPassed flip are decided from atanf / atan2f.  The
+ * kernels list every point whose result lies within a few ulps of such a decision; this call re-decides them with the host
+ * C library (what the reference executable computes on this machine), patches them and, when a decision changed, runs the
+ * extraction of the last ll_spin_extract_batch again.  Synchronises.  Returns the number of listed points. */
+int ll_spin_resolve(ll_spin *h);
+int ll_spin_sync(ll_spin *h);
+/* counts: [n_scans][5] sizes of LL_SPIN_FULL .. LL_SPIN_LESS_FLAT; status (may be NULL): [n_scans] LL_SPIN_STATUS_*.  Synchronises. */
+int ll_spin_counts(ll_spin *h, int32_t n_scans, int32_t *counts, int32_t *status);
+/* Cloud `which` of slot `scan`: xyzi [*n][4] and idx [*n] (either may be NULL).  idx: for LL_SPIN_FULL the index of each point
+ * in the uploaded scan; for SHARP, LESS_SHARP, FLAT, LESS_FLAT_PRE the position in the LL_SPIN_FULL cloud; LL_SPIN_LESS_FLAT
+ * (voxel centroids) has no index and requires idx == NULL.  Buffers hold max_points entries.  Synchronises. */
+int ll_spin_cloud(ll_spin *h, int32_t scan, int32_t which, float *xyzi, int32_t *idx, int32_t *n);
+/* laserCloudScans of slot `scan` as ranges of the LL_SPIN_FULL cloud: line i is [line_start[i], line_start[i] + line_n[i])
+ * (scan_line entries each).  The per-line clouds of m_if_pub_each_line (/laser_scanid_<i>, :804-812).  Synchronises. */
+int ll_spin_lines(ll_spin *h, int32_t scan, int32_t *line_start, int32_t *line_n);
+/* One message (laserCloudHandler body :393-787 without the publishes): upload into slot 0, extract, resolve.  Synchronous.
+ * Returns the scan's status (0, or LL_SPIN_STATUS_LINE_OVERFLOW), < 0 on error. */
+int ll_spin_extract(ll_spin *h, const float *xyzi, int32_t n);
+/* Milliseconds of the phases of the last ll_spin_extract_batch from HIP events (after a synchronising call): [0] assign,
+ * [1] lines, [2] curvature, [3] sort, [4] select, [5] VoxelGrid + gather. */
+int ll_spin_kernel_times(ll_spin *h, float ms[6]);
+
 /* The HIP stream the handle launches on (hipStream_t), for callers that want their own events on it. */
 void *ll_reg_stream(ll_reg *r);
 void *ll_fe_stream(ll_fe *h);

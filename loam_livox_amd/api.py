@@ -6,6 +6,8 @@ Class and method names follow hku-mars/loam_livox so that parity tests read like
   Point_cloud_registration  source/point_cloud_registration.hpp:38    (find_out_incremental_transfrom :163/:585,
                                                                        pointcloudAssociateToMap :673)
   Map_buffer                the (cloud, KdTreeFLANN) pairs of source/laser_mapping.hpp:539-546
+  Spinning_laser            the lidar_type != "livox" branch of Laser_feature::laserCloudHandler,
+                            source/laser_feature_extractor.hpp:393-787
 
 Poses are numpy float64[7] = (qx,qy,qz,qw,tx,ty,tz).  PyTorch is not needed here: device memory and streams are
 owned by the library.
@@ -132,6 +134,106 @@ class Livox_laser:
 
     def sync(self):
         check(self.L.ll_fe_sync(self.h), "ll_fe_sync")
+
+
+class Spinning_laser:
+    """The spinning-lidar branch of Laser_feature::laserCloudHandler (lidar_type != "livox",
+    source/laser_feature_extractor.hpp:393-787) on the device: one message in, the five published clouds out
+    (include/loam_livox_hip.h, ll_spin_*).  `extract` is the one-message call, `extract_batch` the batched one."""
+
+    TOPICS = ("/laser_points_2", "/laser_cloud_sharp", "/laser_cloud_less_sharp", "/laser_cloud_flat", "/laser_cloud_less_flat")
+    FULL, SHARP, LESS_SHARP, FLAT, LESS_FLAT, LESS_FLAT_PRE = range(6)
+
+    def __init__(self, scan_line: int = 16, minimum_range: float = 0.1, plane_resolution: float = 0.8, max_points: int = 32768,
+                 max_scans: int = 1, max_line_points: int = 8192, device: int = 0):
+        self.L = capi.load()
+        p = capi.spin_default_params()
+        p.scan_line, p.minimum_range, p.plane_resolution = scan_line, minimum_range, plane_resolution
+        p.max_points, p.max_scans, p.max_line_points, p.device = max_points, max_scans, max_line_points, device
+        self.params = p
+        self.h = C.c_void_p()
+        check(self.L.ll_spin_create(C.byref(p), C.byref(self.h)), "ll_spin_create")
+        self.n_ambiguous = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.ll_spin_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def upload(self, scans, first_scan: int = 0):
+        """scans: a list of (n_b, 4) clouds"""
+        n = np.array([len(c) for c in scans], np.int32)
+        stride = max(1, int(n.max()) if len(n) else 1)
+        buf = np.zeros((len(scans), stride, 4), np.float32)
+        for b, c in enumerate(scans):
+            buf[b, :len(c)] = capi.as_f32(c, 4)
+        check(self.L.ll_spin_upload(self.h, first_scan, len(scans), ptr(buf), ptr(n), stride), "ll_spin_upload")
+
+    def extract_batch(self, scans) -> list:
+        """Uploads, extracts, resolves; returns one dict of clouds per scan (see `clouds`)."""
+        self.upload(scans)
+        B = len(scans)
+        check(self.L.ll_spin_extract_batch(self.h, B), "ll_spin_extract_batch")
+        self.n_ambiguous = check(self.L.ll_spin_resolve(self.h), "ll_spin_resolve")
+        return [self.clouds(b) for b in range(B)]
+
+    def extract(self, xyzi) -> dict:
+        """One message (laserCloudHandler :393-787 without the publishes)."""
+        pts = capi.as_f32(xyzi, 4)
+        if len(pts) == 0:
+            pts = np.zeros((0, 4), np.float32)
+        buf = pts if len(pts) else np.zeros((1, 4), np.float32)
+        st = check(self.L.ll_spin_extract(self.h, ptr(buf), len(pts)), "ll_spin_extract")
+        if st != 0:
+            raise capi.LoamLivoxError(f"ll_spin_extract: status {st} (a line holds more less-flat points than max_line_points)")
+        return self.clouds(0)
+
+    def counts(self, n_scans: int):
+        c = np.zeros((n_scans, 5), np.int32)
+        st = np.zeros(n_scans, np.int32)
+        check(self.L.ll_spin_counts(self.h, n_scans, ptr(c), ptr(st)), "ll_spin_counts")
+        return c, st
+
+    def cloud(self, scan: int, which: int, with_idx: bool = True):
+        cap = self.params.max_points
+        xyzi = np.zeros((cap, 4), np.float32)
+        idx = np.zeros(cap, np.int32) if with_idx and which != self.LESS_FLAT else None
+        n = C.c_int32(0)
+        check(self.L.ll_spin_cloud(self.h, scan, which, ptr(xyzi), ptr(idx), C.byref(n)), "ll_spin_cloud")
+        return xyzi[:n.value].copy(), (idx[:n.value].copy() if idx is not None else None)
+
+    def lines(self, scan: int = 0):
+        L = self.params.scan_line
+        st, n = np.zeros(L, np.int32), np.zeros(L, np.int32)
+        check(self.L.ll_spin_lines(self.h, scan, ptr(st), ptr(n)), "ll_spin_lines")
+        return st, n
+
+    def clouds(self, scan: int = 0) -> dict:
+        """The five published clouds keyed by topic, plus index arrays: full_src (input index of each laserCloud point),
+        sharp / less_sharp / flat / less_flat_pre (positions in laserCloud), line_start / line_n (laserCloudScans)."""
+        out = {}
+        full, src = self.cloud(scan, self.FULL)
+        out[self.TOPICS[0]], out["full_src"] = full, src
+        for which, key in ((self.SHARP, "sharp"), (self.LESS_SHARP, "less_sharp"), (self.FLAT, "flat"), (self.LESS_FLAT_PRE, "less_flat_pre")):
+            xyzi, idx = self.cloud(scan, which)
+            out[key] = idx
+            if which != self.LESS_FLAT_PRE:
+                out[self.TOPICS[which]] = xyzi
+        out[self.TOPICS[4]] = self.cloud(scan, self.LESS_FLAT, with_idx=False)[0]
+        out["line_start"], out["line_n"] = self.lines(scan)
+        return out
+
+    def kernel_times(self):
+        """milliseconds of the phases of the last batch: assign, lines, curvature, sort, select, VoxelGrid + gather"""
+        ms = np.zeros(6, np.float32)
+        check(self.L.ll_spin_kernel_times(self.h, ptr(ms)), "ll_spin_kernel_times")
+        return ms
 
 
 class VoxelGrid:

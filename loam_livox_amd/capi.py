@@ -25,6 +25,11 @@ class FeParams(C.Structure):
                 ("max_points", C.c_int32), ("max_scans", C.c_int32), ("piecewise_number", C.c_int32)]
 
 
+class SpinParams(C.Structure):
+    _fields_ = [("scan_line", C.c_int32), ("minimum_range", C.c_float), ("plane_resolution", C.c_float), ("device", C.c_int32),
+                ("max_points", C.c_int32), ("max_scans", C.c_int32), ("max_line_points", C.c_int32)]
+
+
 class RegParams(C.Structure):
     _fields_ = [("if_motion_deblur", C.c_int32), ("icp_max_iterations", C.c_int32), ("ceres_max_iterations", C.c_int32),
                 ("ceres_prerun_times", C.c_int32), ("icp_line", C.c_int32), ("icp_plane", C.c_int32),
@@ -129,6 +134,18 @@ SYMBOLS = {
     "ll_history_cell_map": (_vp, [_vp, _i32]),
     "ll_history_refresh_cells": (_i32, [_vp, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, _vp, _vp]),
     "ll_debug_quintic": (_i32, [_i32, _vp, _i32, _vp, _vp]),
+    "ll_spin_default_params": (None, [C.POINTER(SpinParams)]),
+    "ll_spin_create": (_i32, [C.POINTER(SpinParams), C.POINTER(_vp)]),
+    "ll_spin_destroy": (None, [_vp]),
+    "ll_spin_upload": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32]),
+    "ll_spin_extract_batch": (_i32, [_vp, _i32]),
+    "ll_spin_resolve": (_i32, [_vp]),
+    "ll_spin_sync": (_i32, [_vp]),
+    "ll_spin_counts": (_i32, [_vp, _i32, _vp, _vp]),
+    "ll_spin_cloud": (_i32, [_vp, _i32, _i32, _vp, _vp, C.POINTER(_i32)]),
+    "ll_spin_lines": (_i32, [_vp, _i32, _vp, _vp]),
+    "ll_spin_extract": (_i32, [_vp, _vp, _i32]),
+    "ll_spin_kernel_times": (_i32, [_vp, _vp]),
     "ll_reg_stream": (_vp, [_vp]),
     "ll_fe_stream": (_vp, [_vp]),
     "ll_runtime_hint_hw_queues": (_i32, [_i32]),
@@ -207,6 +224,12 @@ def ptr(a):
 def fe_default_params() -> FeParams:
     p = FeParams()
     load().ll_fe_default_params(C.byref(p))
+    return p
+
+
+def spin_default_params() -> SpinParams:
+    p = SpinParams()
+    load().ll_spin_default_params(C.byref(p))
     return p
 
 

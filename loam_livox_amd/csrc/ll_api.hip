@@ -70,6 +70,12 @@ static int check_device(int device)
     return 0;
 }
 
+// the other translation units of the C ABI (ll_spin_api.hip) report through the same ll_last_error
+namespace ll {
+int api_error(const char *where, const char *what) { return set_err(where, what); }
+int api_check_device(int device) { return check_device(device); }
+}  // namespace ll
+
 // ============================================================================================== extractor
 
 struct ll_fe {

@@ -12,18 +12,29 @@ list of (full, surface, corners) triples, one per published piece:
     concatenation over all lidars of their latest clouds for that piece (:348-358) -- the Mid-100's three heads;
   * surface / corner clouds pass the voxel filters (leaf plane_res / 2 and line_res, :192-193, 372-381);
   * in odometry mode only the first piece is published (:385-388).
+
+With lidar_type other than "livox" the handler runs the spinning-lidar branch instead (:393-787, ll_spin_* on the device)
+after the same m_para_system_delay gate, and returns the five clouds it publishes keyed by topic: /laser_points_2,
+/laser_cloud_sharp, /laser_cloud_less_sharp, /laser_cloud_flat, /laser_cloud_less_flat.  The reference treats a missing
+common/lidar_type as velodyne (:842-851); this class defaults to "livox" so that existing callers keep their behaviour.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .api import Livox_laser, VoxelGrid
+from .api import Livox_laser, Spinning_laser, VoxelGrid
 
 
 class Laser_feature:
     def __init__(self, max_points: int = 24000, piecewise_number: int = 3, if_motion_deblur: int = 0,
                  maximum_input_lidar_pointcloud: int = 3, mapping_plane_resolution: float = 0.8, mapping_line_resolution: float = 0.8,
-                 odom_mode: int = 0, para_system_delay: int = 20, device: int = 0, **livox_tunables):
+                 odom_mode: int = 0, para_system_delay: int = 20, device: int = 0, lidar_type: str = "livox", scan_line: int = 16,
+                 minimum_range: float = 0.1, **livox_tunables):
+        self.m_lidar_type = 1 if lidar_type == "livox" else 0  # :839-851
+        self.m_spin = None
+        if not self.m_lidar_type:  # one device extractor for the spinning branch; :160-164 refuses scan_line other than 16 / 64
+            self.m_spin = Spinning_laser(scan_line=scan_line, minimum_range=minimum_range, plane_resolution=mapping_plane_resolution,
+                                         max_points=max_points, device=device)
         self.m_piecewise_number = piecewise_number
         self.m_if_motion_deblur = if_motion_deblur
         self.m_maximum_input_lidar_pointcloud = maximum_input_lidar_pointcloud
@@ -47,8 +58,9 @@ class Laser_feature:
         self.m_laser_scan_number = 0
 
     def close(self):
-        for h in (self.m_livox, self.m_voxel_filter_for_surface, self.m_voxel_filter_for_corner):
-            h.close()
+        for h in (self.m_livox, self.m_voxel_filter_for_surface, self.m_voxel_filter_for_corner, self.m_spin):
+            if h is not None:
+                h.close()
 
     def _filter(self, vg: VoxelGrid, cloud: np.ndarray) -> np.ndarray:
         if len(cloud) == 0:
@@ -57,15 +69,19 @@ class Laser_feature:
         return vg.filter()
 
     def laserCloudHandler(self, laserCloudIn: np.ndarray, stamp: float, current_lidar_index: int = 0):
-        """Returns the list of published (livox_full, livox_surface, livox_corners) triples of this message."""
+        """Returns the list of published (livox_full, livox_surface, livox_corners) triples of this message (lidar_type
+        "livox"), or the dict of the five published clouds keyed by topic (other lidar types; None while the delay gate holds)."""
         assert 0 <= current_lidar_index < self.m_maximum_input_lidar_pointcloud  # :254
         if not self.m_para_systemInited:  # :258-267
             self.m_para_system_init_count += 1
             if self.m_para_system_init_count >= self.m_para_system_delay:
                 self.m_para_systemInited = True
             else:
-                return []
+                return [] if self.m_lidar_type else None
         xyzi = np.ascontiguousarray(laserCloudIn, np.float32).reshape(-1, 4)
+        if not self.m_lidar_type:  # :393-812
+            c = self.m_spin.extract(xyzi)
+            return {t: c[t] for t in Spinning_laser.TOPICS}
         n_clouds = self.m_livox.extract_laser_features(xyzi, stamp)  # :285
         if n_clouds <= 5:  # :287-290
             return []

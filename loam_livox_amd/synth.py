@@ -369,3 +369,41 @@ def make_moving_scan(world: World, k: int = 0, n: int = 24000, inc_true=None, ya
 
 def transform_points(pose, pts):
     return (pts.astype(np.float64) @ quat_to_mat(pose[:4]).T + pose[4:]).astype(np.float32)
+
+
+# spinning multi-beam lidars (the lidar_type != "livox" branch of the feature node): beam elevations in degrees, in firing order
+VLP16_ELEVATIONS = np.array([-15, 1, -13, 3, -11, 5, -9, 7, -7, 9, -5, 11, -3, 13, -1, 15], np.float64)
+HDL64_ELEVATIONS = np.r_[2.0 - np.arange(32) / 3.0, -8.83 - 0.5 * np.arange(32)]  # 2 .. -8.33 in 1/3 deg, -8.83 .. -24.33 in 1/2 deg
+
+
+def make_spin_scan(world: World, k: int = 0, scan_line: int = 16, n_azimuth: int | None = None, seed: int | None = None,
+                   range_sigma: float = 0.01, p_nan: float = 0.0, p_near: float = 0.0) -> Scan:
+    """One revolution of a VLP-16 (scan_line 16) or an HDL-64-like sensor (64), level, ray-cast into `world` in firing order:
+    azimuth columns clockwise seen from above (so -atan2(y, x) grows), every beam of a column in turn.  No-return rays are
+    dropped, as drivers do.  p_nan / p_near: fractions of points replaced by NaN / by a point 5 cm from the sensor.
+    range_sigma 0 gives a noise-free scan.  Seed 5000+k unless given."""
+    rng = np.random.default_rng(5000 + k if seed is None else seed)
+    elev = VLP16_ELEVATIONS if scan_line == 16 else HDL64_ELEVATIONS
+    if n_azimuth is None:
+        n_azimuth = 1800 if scan_line == 16 else 2000
+    pose = sensor_pose_in_world(world, rng)
+    pose[:4] = quat_from_rpy(0.0, 0.0, 0.0)
+    yaw0 = rng.uniform(-np.pi, np.pi)
+    az = yaw0 - 2 * np.pi * np.arange(n_azimuth) / n_azimuth
+    el = np.deg2rad(elev)
+    ca, sa = np.cos(az)[:, None], np.sin(az)[:, None]
+    ce, se = np.cos(el)[None, :], np.sin(el)[None, :]
+    shape = (n_azimuth, len(el))
+    dirs = np.stack([np.broadcast_to(ca * ce, shape), np.broadcast_to(sa * ce, shape), np.broadcast_to(se, shape)], axis=2).reshape(-1, 3)
+    rng_m = raycast(world, pose[4:], dirs)
+    hit = np.isfinite(rng_m)
+    r = rng_m + (rng.normal(0.0, range_sigma, len(rng_m)) if range_sigma > 0 else 0.0)
+    pts = (dirs * r[:, None]).astype(np.float32)[hit]
+    inten = rng.uniform(1.0, 100.0, len(pts)).astype(np.float32)
+    u = rng.uniform(0.0, 1.0, len(pts))
+    pts[u < p_nan] = np.nan
+    near = (u >= p_nan) & (u < p_nan + p_near)
+    pts[near] = (dirs[hit][near] * 0.05).astype(np.float32)
+    xyzi = np.concatenate([pts, inten[:, None]], axis=1).astype(np.float32)
+    return Scan(np.ascontiguousarray(xyzi), pose, pose.copy(), seed=5000 + k if seed is None else seed,
+                meta=dict(scan_line=scan_line, n_azimuth=n_azimuth))

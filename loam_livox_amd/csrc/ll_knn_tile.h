@@ -219,9 +219,13 @@ LL_HD bool tile5_finish(const Grid &g, const Tile5 &t, const TileQ &tq, float ma
                 n = i + 1;
             }
         }
-        float first_out = t.d[4];  // the nearest point at or beyond the radius that was seen (static indices: registers on the device)
-        for (int i = 3; i >= 0; i--)
-            if (!(t.d[i] < max_d2)) first_out = t.d[i];
+        // a lower bound on every point at or beyond the radius that was offered: the list is ordered by TRUNCATED distance and collisions
+        // beyond the radius are not searched again (tilek_collision), so a later entry, or a point behind the sixth key, can be nearer
+        // than the first entry there -- the smallest of those entries and t.lb, which bounds everything offered that is not in the list
+        // (static indices: registers on the device)
+        float first_out = t.lb;
+        for (int i = 0; i < 5; i++)
+            if (!(t.d[i] < max_d2)) first_out = fminf(first_out, t.d[i]);
         r.count = n;
         r.lb2 = fminf(b2, max_d2);         // (everything outside the list is at or beyond the radius)
         r.out2 = fminf(first_out, b2);     // ... or the block's edge

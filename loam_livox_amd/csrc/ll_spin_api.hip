@@ -73,12 +73,15 @@ static int spin_create_impl(const ll_spin_params *p, ll_spin *h)
         dm(&d.flat, SP) || dm(&d.lf_pos, SP) || dm(&d.vox_in, (size_t)S * h->n_vlines * p->max_line_points) ||
         dm(&d.vox_n, (size_t)S * h->n_vlines) || dm(&d.less_flat, SP) || dm(&d.cnt, (size_t)S * SPIN_NCNT))
         return -1;
-    SC(hipMemset(d.n_in, 0, S * sizeof(int)));
-    SC(hipMemset(d.cnt, 0, (size_t)S * SPIN_NCNT * sizeof(int)));
-    SC(hipMemset(d.line_off, 0, (size_t)S * (SPIN_MAX_LINES + 1) * sizeof(int)));
     const char *err = nullptr;
     if (voxel_alloc(h->vox, S * h->n_vlines, p->max_line_points, &err)) return api_error("ll_spin_create", err);
     SC(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    // zeroed on the handle's own stream: a non-blocking stream is not ordered after the null stream, so a null-stream hipMemset could
+    // still land after the first extraction's kernels and wipe the counts and line offsets they wrote
+    SC(hipMemsetAsync(d.n_in, 0, S * sizeof(int), h->stream));
+    SC(hipMemsetAsync(d.cnt, 0, (size_t)S * SPIN_NCNT * sizeof(int), h->stream));
+    SC(hipMemsetAsync(d.line_off, 0, (size_t)S * (SPIN_MAX_LINES + 1) * sizeof(int), h->stream));
+    SC(hipStreamSynchronize(h->stream));
     for (auto &e : h->ev) SC(hipEventCreate(&e));
     h->h_n.assign(S, 0);
     return 0;

@@ -105,19 +105,22 @@ class Grid:
         lib().hc_knn5(self.h, _p(q), q.shape[0], max_d2, _p(idx), _p(d2))
         return idx, d2
 
-    def knn5_tile(self, q, max_d2):
+    def knn5_tile(self, q, max_d2, bounds=False):
         """host model of the wavefront tile search (ll_knn_tile.h), 64 queries per wavefront in the order given:
-        (idx5, d2, lb2, stats = [rounds, candidates staged, lanes that fell back to the per-lane search, wavefronts])"""
+        (idx5, d2, lb2, stats = [rounds, candidates staged, lanes that fell back to the per-lane search, wavefronts]);
+        bounds=True appends out2 and settled (1 where the lane's tile settled the result, 0 where it ran knn5_search)"""
         q = np.ascontiguousarray(q, np.float32).reshape(-1, 3)
         idx = np.zeros((q.shape[0], 5), np.int32)
         d2 = np.zeros((q.shape[0], 5), np.float32)
         lb2 = np.zeros(q.shape[0], np.float32)
+        out2 = np.zeros(q.shape[0], np.float32)
+        settled = np.zeros(q.shape[0], np.int32)
         stats = np.zeros(4, np.int64)
         L = lib()
-        L.hc_knn5_tile.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 4
-        rc = L.hc_knn5_tile(self.h, _p(q), q.shape[0], max_d2, _p(idx), _p(d2), _p(lb2), _p(stats))
+        L.hc_knn5_tile.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 6
+        rc = L.hc_knn5_tile(self.h, _p(q), q.shape[0], max_d2, _p(idx), _p(d2), _p(lb2), _p(stats), _p(out2), _p(settled))
         assert rc == 0, "tile of more than 25 rows"
-        return idx, d2, lb2, stats
+        return (idx, d2, lb2, stats, out2, settled) if bounds else (idx, d2, lb2, stats)
 
     def knn5_run_cands(self, q, max_d2):
         """candidates examined per run of the 3x3x3 block, [nq][9] (-1 = run not scanned)"""

@@ -307,8 +307,10 @@ int hc_knn5_reuse_chain(const hc_grid *G, const float *path, int n_hops, int nq,
 // cell order of reg_qsort_kernel); per "wavefront" the rounds, tiles and candidate order of the device code, the per-lane
 // arithmetic from the shared header (tile_query / tile5_offer / tile5_finish); lanes the tile does not settle run knn5_search.
 // idx: original indices (-1 where fewer than five inside the radius); stats[0] rounds, [1] candidates staged, [2] lanes that
-// fell back, [3] wavefronts.
-int hc_knn5_tile(const hc_grid *G, const float *q, int nq, float max_d2, int32_t *idx, float *d2, float *lb2, int64_t *stats)
+// fell back, [3] wavefronts.  out2 / settled (either may be null): the result's out2 and whether the lane's tile settled it (1) or
+// the lane fell back to knn5_search (0).
+int hc_knn5_tile(const hc_grid *G, const float *q, int nq, float max_d2, int32_t *idx, float *d2, float *lb2, int64_t *stats,
+                 float *out2, int32_t *settled)
 {
     const Grid &g = G->g;
     stats[0] = stats[1] = stats[2] = stats[3] = 0;
@@ -416,6 +418,8 @@ int hc_knn5_tile(const hc_grid *G, const float *q, int nq, float max_d2, int32_t
                 d2[5 * i + k] = knn5_d2(r[l], k);
             }
             lb2[i] = r[l].lb2;
+            if (out2) out2[i] = r[l].out2;
+            if (settled) settled[i] = fin[l] ? 1 : 0;
         }
     }
     return 0;

@@ -96,6 +96,19 @@ def test_edges_small_nan_near_empty(gpu_lib, world):
     dev.close()
 
 
+def test_first_extraction_of_fresh_handles(gpu_lib, world):
+    """the handle's counters and line offsets are zeroed at creation on the handle's own stream: a zeroing that were not ordered before
+    the first extraction's kernels could land after them and wipe the counts and line offsets they wrote (empty clouds, zero lines) --
+    the first extraction right after ll_spin_create, on many fresh handles"""
+    sc = synth.make_spin_scan(world, 7, scan_line=16, n_azimuth=200)
+    ref = spin_ref.extract(sc.xyzi[:10], scan_line=16)
+    ref_big = spin_ref.extract(sc.xyzi, scan_line=16)
+    for k in range(24):
+        dev = Spinning_laser(scan_line=16, max_points=32768, max_scans=1 + k % 3)
+        compare(dev.extract(sc.xyzi[:10] if k % 2 == 0 else sc.xyzi), ref if k % 2 == 0 else ref_big)
+        dev.close()
+
+
 def test_walk_reaching_the_ends_of_the_cloud(gpu_lib):
     """a dense line of sharp points next to the cloud ends: the +-500 walks stop at the ends (the defined edge)"""
     t = np.linspace(0, 1, 400, dtype=np.float32)

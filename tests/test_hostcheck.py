@@ -178,6 +178,52 @@ def test_tile_search_settles_queries_just_outside_the_grid():
             assert lb2[i] <= np.delete(d2_all, ti[i]).min() * (1 + 1e-5) + 1e-6
 
 
+def _d2_fp32(q, pts):
+    """squared distances in the search's fp32 arithmetic (dist2_xyz: x, y, z accumulated in that order, no contraction)"""
+    dx, dy, dz = (q[:, None, k] - pts[None, :, k] for k in range(3))
+    return (dx * dx + dy * dy) + dz * dz
+
+
+def _short_list_out2_violations(pts, q, cell, max_d2):
+    """(short lists the tile settled, queries whose out2 exceeds the nearest map point at or beyond the radius)"""
+    g = hc.Grid(pts, cell)
+    q = q[_cell_order(q, cell, pts.min(axis=0))]
+    ti, _, _, _, out2, settled = g.knn5_tile(q, max_d2, bounds=True)
+    sel = np.flatnonzero((settled == 1) & (ti[:, 4] < 0))
+    bad = []
+    for c0 in range(0, len(sel), 1024):
+        s = sel[c0:c0 + 1024]
+        d2 = _d2_fp32(q[s], pts)
+        far = np.where(d2 >= np.float32(max_d2), d2, np.float32(np.inf)).min(axis=1)
+        bad += [(int(i), float(out2[i]), float(f)) for i, f in zip(s, far) if not out2[i] <= f]
+    return len(sel), bad
+
+
+def test_tile_short_list_out2_bounds_every_point_beyond_the_radius():
+    """A list the tile settles with fewer than five neighbours inside the radius (the line radius, 1.41 m, inside the corner map's
+    1.45 m block) reports out2: the bound knn5_reuse_margin turns into "nothing moves inside the radius".  The tile ranks candidates by
+    a key that keeps 15 mantissa bits of d2, and collisions beyond the radius are not searched again, so the first entry beyond the
+    radius need not be the nearest point there.  out2 must bound every map point at or beyond the radius, in the search's fp32 distance
+    and without slack: the truncation (up to 2^-15 relative) would hide inside the (1 + 1e-5) the lb2 checks allow.  Six trials at the
+    density where the host model first showed it (6000 points, h = 1.45, max_d2 = 2.0: 2 of ~10^5 short lists), then a map of near
+    twins, where two points beyond the radius share a key for most queries."""
+    rng = np.random.default_rng(31)
+    n_short, bad = 0, []
+    for trial in range(6):
+        pts = rng.uniform(0, 30, (6000, 3)).astype(np.float32)
+        q = rng.uniform(0, 30, (20000, 3)).astype(np.float32)
+        n, b = _short_list_out2_violations(pts, q, 1.45, 2.0)
+        n_short += n
+        bad += [(trial,) + x for x in b]
+    assert n_short > 0.7 * 6 * 20000
+    base = rng.uniform(0, 30, (3000, 3)).astype(np.float32)
+    pts = np.concatenate([base, base + rng.normal(0, 1e-5, base.shape).astype(np.float32)])
+    n, b = _short_list_out2_violations(pts, rng.uniform(0, 30, (20000, 3)).astype(np.float32), 1.45, 2.0)
+    bad += [("twins",) + x for x in b]
+    assert n > 2000
+    assert not bad, (len(bad), bad[:8])
+
+
 def test_tile_offer_network_equals_ordered_insertion():
     """tile5_offer against a sort: random streams with repeated values"""
     rng = np.random.default_rng(5)

@@ -373,6 +373,24 @@ class Spinning_laser {
         }
     }
 
+    // The same extraction with nothing downloaded: the clouds stay on the device for
+    // Point_cloud_registration::find_out_incremental_transfrom( spin ) and History_buffer::add( spin, pose ) (corner stack =
+    // /laser_cloud_less_sharp, surface stack = /laser_cloud_less_flat).  Returns the scan's status
+    // (LL_SPIN_STATUS_OK or LL_SPIN_STATUS_LINE_OVERFLOW: the hand-off takes the clouds a download would return either way).
+    template <class Cloud>
+    int extract_device(const Cloud &in)
+    {
+        const std::vector<float> raw = cloud_to_xyzi(in);
+        const int n = (int)in.points.size();
+        ensure_handle(n);
+        const float dummy[4] = {0, 0, 0, 0};
+        const int st = ll_spin_extract(h_, n ? raw.data() : dummy, n);
+        check(st, "ll_spin_extract");
+        return st;
+    }
+    ll_spin *handle() { return h_; }  // null before the first extraction
+    int capacity() const { return cap_; }
+
    private:
     void ensure_handle(int n)
     {
@@ -504,6 +522,14 @@ class History_buffer {
         check(ll_history_add(h_, c.data(), (int32_t)(c.size() / 4), s.data(), (int32_t)(s.size() / 4), pose, history_add_t_step,
                              history_add_angle_step, &added),
               "ll_history_add");
+        return added != 0;
+    }
+    // the same for the scan a Spinning_laser holds (extract_device), device to device: its less-sharp and less-flat clouds
+    bool add(Spinning_laser &spin, const double pose[7], double history_add_t_step = 0.0, double history_add_angle_step = 0.0)
+    {
+        if (!spin.handle()) throw std::runtime_error("History_buffer::add: the Spinning_laser has not extracted a scan");
+        int32_t added = 0;
+        check(ll_history_add_spin(h_, spin.handle(), 0, pose, history_add_t_step, history_add_angle_step, &added), "ll_history_add_spin");
         return added != 0;
     }
     // The add-frame rule (laser_mapping.hpp:1439-1451) reads the node's m_q_w_curr / m_t_w_curr, which is still the pose
@@ -902,15 +928,49 @@ class Point_cloud_registration {
         return register_scan(scan_corner, scan_surf, nullptr);
     }
 
+    // The scan a Spinning_laser holds (Spinning_laser::extract_device), registered against map() where the extractor left it:
+    // corner stack = its less-sharp cloud, surface stack = its less-flat cloud (ll_reg_enqueue_spin).  The same bits as the
+    // 2-argument form on the downloaded clouds.  m_if_motion_deblur must be 0 (the call throws otherwise: the spinning
+    // extractor's intensity is not a time stamp).
+    int find_out_incremental_transfrom(Spinning_laser &spin)
+    {
+        if (!spin.handle()) throw std::runtime_error("find_out_incremental_transfrom: the Spinning_laser has not extracted a scan");
+        const int need = spin.capacity() > max_features ? spin.capacity() : max_features;
+        if (reg_ && reg_cap_ < need) {
+            Handle_pool::instance().release(reg_);
+            reg_ = nullptr;
+        }
+        if (!reg_) reg_ = Handle_pool::instance().acquire(device, reg_cap_ = need);
+        ll_reg_params p;
+        fill_params(p);
+        pose_from_members();
+        check(ll_reg_enqueue_spin(reg_, map(), spin.handle(), 1, &p, m_para_buffer_RT_last, m_para_buffer_RT, m_para_buffer_incremental),
+              "ll_reg_enqueue_spin");
+        return collect();
+    }
+
     // void pointAssociateToMap ... see below
    private:
     template <class CloudPtr>
     int register_scan(CloudPtr scan_corner, CloudPtr scan_surf, std::unique_lock<std::mutex> *held_until_enqueued)
     {
-        if (!reg_) reg_ = Handle_pool::instance().acquire(device, max_features);
+        if (!reg_) reg_ = Handle_pool::instance().acquire(device, reg_cap_ = max_features);
         ll_map *m = map();
         const std::vector<float> c = cloud_to_xyzi(*scan_corner), s = cloud_to_xyzi(*scan_surf);
         ll_reg_params p;
+        fill_params(p);
+        pose_from_members();
+        // ll_reg_solve in its three steps (upload the scan's features, enqueue = pin the map snapshots + launch, collect)
+        const int32_t nc = (int32_t)(c.size() / 4), ns = (int32_t)(s.size() / 4);
+        const float dummy[4] = {0, 0, 0, 0};
+        check(ll_reg_upload_features(reg_, 1, nc ? c.data() : dummy, &nc, nc > 0 ? nc : 1, ns ? s.data() : dummy, &ns, ns > 0 ? ns : 1),
+              "ll_reg_upload_features");
+        check(ll_reg_enqueue_uploaded(reg_, m, 1, &p, m_para_buffer_RT_last, m_para_buffer_RT, m_para_buffer_incremental), "ll_reg_enqueue_uploaded");
+        if (held_until_enqueued) held_until_enqueued->unlock();
+        return collect();
+    }
+    void fill_params(ll_reg_params &p) const
+    {
         ll_reg_default_params(&p);
         p.if_motion_deblur = m_if_motion_deblur;
         p.icp_max_iterations = m_para_icp_max_iterations;
@@ -935,15 +995,10 @@ class Point_cloud_registration {
         p.max_final_cost = m_max_final_cost;
         p.minimum_pt_time_stamp = m_minimum_pt_time_stamp;
         p.maximum_pt_time_stamp = m_maximum_pt_time_stamp;
-        pose_from_members();
+    }
+    int collect()
+    {
         ll_reg_report rep;
-        // ll_reg_solve in its three steps (upload the scan's features, enqueue = pin the map snapshots + launch, collect)
-        const int32_t nc = (int32_t)(c.size() / 4), ns = (int32_t)(s.size() / 4);
-        const float dummy[4] = {0, 0, 0, 0};
-        check(ll_reg_upload_features(reg_, 1, nc ? c.data() : dummy, &nc, nc > 0 ? nc : 1, ns ? s.data() : dummy, &ns, ns > 0 ? ns : 1),
-              "ll_reg_upload_features");
-        check(ll_reg_enqueue_uploaded(reg_, m, 1, &p, m_para_buffer_RT_last, m_para_buffer_RT, m_para_buffer_incremental), "ll_reg_enqueue_uploaded");
-        if (held_until_enqueued) held_until_enqueued->unlock();
         int32_t ret = 0;
         check(ll_reg_collect(reg_, 1, m_para_buffer_RT, m_para_buffer_incremental, &rep, &ret), "ll_reg_collect");
         members_from_pose();
@@ -985,7 +1040,7 @@ class Point_cloud_registration {
     template <class Cloud>
     unsigned int pointcloudAssociateToMap(const Cloud &pc_in, Cloud &pt_out, int /*if_undistore*/ = 0)
     {
-        if (!reg_) reg_ = Handle_pool::instance().acquire(device, max_features);
+        if (!reg_) reg_ = Handle_pool::instance().acquire(device, reg_cap_ = max_features);
         pose_from_members();
         const std::vector<float> in = cloud_to_xyzi(pc_in);
         std::vector<float> out(in.size());
@@ -1047,6 +1102,7 @@ class Point_cloud_registration {
         k = now;
     }
     ll_reg *reg_ = nullptr;
+    int reg_cap_ = 0;  // the feature capacity reg_ was acquired with
 };
 
 }  // namespace loam_livox_hip

@@ -569,6 +569,44 @@ int ll_spin_extract(ll_spin *h, const float *xyzi, int32_t n);
  * [1] lines, [2] curvature, [3] sort, [4] select, [5] VoxelGrid + gather. */
 int ll_spin_kernel_times(ll_spin *h, float ms[6]);
 
+/* Hand-off of a spin handle's clouds to the registrar, the history and a device sub-map without leaving the device: the _spin forms of
+ * ll_reg_enqueue_fe, ll_reg_enqueue_fe_downsampled, ll_history_add_fe and ll_cloud_transform_fe_device, with the same semantics
+ * (collect with ll_reg_collect; ll_history_add_voxel serves the down-sampled stacks).
+ *
+ * The reference's mapping node subscribes to none of the spinning branch's topics (laser_mapping.hpp:596-598 reads /pc2_corners,
+ * /pc2_surface, /pc2_full), so which clouds feed find_out_incremental_transfrom is this project's decision, the LOAM mapping convention:
+ *   corner stack = LL_SPIN_LESS_SHARP, surface stack = LL_SPIN_LESS_FLAT, full cloud = LL_SPIN_FULL.
+ * The results are bit for bit those of the host round trip (ll_spin_cloud -> ll_reg_upload_features / ll_history_add / ll_cloud_transform).
+ *
+ *   - The hand-off takes the handle's CURRENT outputs, ordered after everything queued on the handle's stream; it does not wait for the
+ *     host.  Callers that want the host-libm-exact discrete decisions call ll_spin_resolve first, as for a download.
+ *   - if_motion_deblur must be 0.  The spinning extractor writes intensity = scanID + scanPeriod * relTime
+ *     (laser_feature_extractor.hpp:502), not a time stamp in [minimum_pt_time_stamp, maximum_pt_time_stamp]; refine_blur
+ *     (point_cloud_registration.hpp:128-141) would misread it.  A non-zero flag is refused with an error, never ignored.
+ *   - A scan whose status is LL_SPIN_STATUS_LINE_OVERFLOW is handed over with the clouds a download returns for it; the status stays
+ *     readable through ll_spin_counts.
+ *   - The less-sharp cloud holds at most 200 points x 6 sub-regions x scan_line (laser_feature_extractor.hpp:667-676): the packed corner
+ *     clouds are [max_scans][min(max_points, 1200 * scan_line)] points, allocated by the first hand-off (ll_spin_create does not grow).
+ *   - Until it has been collected, the registration reads the handle's buffers: extract the next batch on another handle meanwhile.
+ * Errors (non-zero, text in ll_last_error; the handles stay usable): null handle, handles on different devices, n_scans above the
+ * extractor's or the registrar's capacity, registrar feature capacity below the extractor's max_points, voxel filter capacity too small
+ * (corner: n_scans clouds of min(max_points, 1200 * scan_line) points; surface: n_scans clouds of max_points points),
+ * if_motion_deblur != 0, `which` out of range or LL_SPIN_LESS_FLAT_PRE. */
+int ll_reg_enqueue_spin(ll_reg *r, const ll_map *map, ll_spin *spin, int32_t n_scans, const ll_reg_params *prm,
+                        const double *poses_last, const double *poses_curr, const double *poses_incre);
+int ll_reg_enqueue_spin_downsampled(ll_reg *r, const ll_map *map, ll_spin *spin, ll_voxel *vox_corner, ll_voxel *vox_surf, float line_res,
+                                    float plane_res, int32_t n_scans, const ll_reg_params *prm, const double *poses_last,
+                                    const double *poses_curr, const double *poses_incre);
+/* Slot `scan` of the handle: its less-sharp and less-flat clouds, as ll_history_add_fe takes a Livox scan's features.  Synchronises. */
+int ll_history_add_spin(ll_history *h, ll_spin *spin, int32_t scan, const double pose[7], double history_add_t_step,
+                        double history_add_angle_step, int32_t *added);
+/* Cloud `which` (LL_SPIN_FULL .. LL_SPIN_LESS_FLAT) of every accepted scan of slots 0 .. n_scans-1, moved with its pose and appended to
+ * dev_out_xyzi from point *n_points on, as ll_cloud_transform_fe_device.  *n_points is left untouched when the buffer is too small. */
+int ll_cloud_transform_spin_device(ll_reg *r, ll_spin *spin, int32_t n_scans, int32_t which, const int32_t *accept, const double *poses7,
+                                   float *dev_out_xyzi, int64_t capacity_points, int64_t *n_points);
+/* Milliseconds of the kernel that packed the corner stack for the last hand-off, from HIP events on the handle's stream.  Waits for it. */
+int ll_spin_handoff_time(ll_spin *h, float *ms);
+
 /* The HIP stream the handle launches on (hipStream_t), for callers that want their own events on it. */
 void *ll_reg_stream(ll_reg *r);
 void *ll_fe_stream(ll_fe *h);

@@ -183,6 +183,18 @@ class Spinning_laser:
         self.n_ambiguous = check(self.L.ll_spin_resolve(self.h), "ll_spin_resolve")
         return [self.clouds(b) for b in range(B)]
 
+    def extract_batch_async(self, n_scans: int):
+        """ll_spin_extract_batch on the slots already uploaded: asynchronous, nothing is downloaded (the device hand-offs
+        Point_cloud_registration.enqueue_spin / History_buffer.add_spin take the clouds where they are)"""
+        check(self.L.ll_spin_extract_batch(self.h, int(n_scans)), "ll_spin_extract_batch")
+
+    def resolve(self) -> int:
+        self.n_ambiguous = check(self.L.ll_spin_resolve(self.h), "ll_spin_resolve")
+        return self.n_ambiguous
+
+    def sync(self):
+        check(self.L.ll_spin_sync(self.h), "ll_spin_sync")
+
     def extract(self, xyzi) -> dict:
         """One message (laserCloudHandler :393-787 without the publishes)."""
         pts = capi.as_f32(xyzi, 4)
@@ -228,6 +240,12 @@ class Spinning_laser:
         out[self.TOPICS[4]] = self.cloud(scan, self.LESS_FLAT, with_idx=False)[0]
         out["line_start"], out["line_n"] = self.lines(scan)
         return out
+
+    def handoff_time(self) -> float:
+        """milliseconds of the pack kernel of the last device hand-off (ll_spin_handoff_time)"""
+        ms = C.c_float(0.0)
+        check(self.L.ll_spin_handoff_time(self.h, C.byref(ms)), "ll_spin_handoff_time")
+        return float(ms.value)
 
     def kernel_times(self):
         """milliseconds of the phases of the last batch: assign, lines, curvature, sort, select, VoxelGrid + gather"""
@@ -332,6 +350,14 @@ class History_buffer:
         added = C.c_int32(0)
         check(self.L.ll_history_add_fe(self.h, fe.h, scan, ptr(pose), history_add_t_step, history_add_angle_step, C.byref(added)),
               "ll_history_add_fe")
+        return bool(added.value)
+
+    def add_spin(self, spin: "Spinning_laser", scan: int, pose, history_add_t_step: float = 0.0, history_add_angle_step: float = 0.0) -> bool:
+        """add_fe for a spinning-lidar handle: the less-sharp and the less-flat cloud of slot `scan`, device to device"""
+        pose = np.ascontiguousarray(pose, np.float64)
+        added = C.c_int32(0)
+        check(self.L.ll_history_add_spin(self.h, spin.h, scan, ptr(pose), history_add_t_step, history_add_angle_step, C.byref(added)),
+              "ll_history_add_spin")
         return bool(added.value)
 
     def add_voxel(self, vox_corner: "VoxelGrid", vox_surf: "VoxelGrid", cloud: int, pose, history_add_t_step: float = 0.0,
@@ -696,6 +722,22 @@ class Point_cloud_registration:
         check(self.L.ll_reg_enqueue_fe_downsampled(self.h, map_buffer.h, fe.h, vox_corner.h, vox_surf.h, line_res, plane_res, n_scans,
                                                    C.byref(self.params), ptr(pl), ptr(pc), None), "ll_reg_enqueue_fe_downsampled")
 
+    def enqueue_spin(self, map_buffer: Map_buffer, spin: "Spinning_laser", n_scans: int, poses_last, poses_curr):
+        """enqueue_fe for a spinning-lidar handle: corner stack = its less-sharp cloud, surface stack = its less-flat cloud, read where
+        the extractor left them (ll_reg_enqueue_spin).  params.if_motion_deblur must be 0."""
+        pl = np.ascontiguousarray(poses_last, np.float64).reshape(n_scans, 7)
+        pc = np.ascontiguousarray(poses_curr, np.float64).reshape(n_scans, 7)
+        check(self.L.ll_reg_enqueue_spin(self.h, map_buffer.h, spin.h, n_scans, C.byref(self.params), ptr(pl), ptr(pc), None),
+              "ll_reg_enqueue_spin")
+
+    def enqueue_spin_downsampled(self, map_buffer: Map_buffer, spin: "Spinning_laser", vox_corner: "VoxelGrid", vox_surf: "VoxelGrid",
+                                 line_res: float, plane_res: float, n_scans: int, poses_last, poses_curr):
+        """enqueue_fe_downsampled for a spinning-lidar handle (m_if_input_downsample_mode, laser_mapping.hpp:1367-1373)"""
+        pl = np.ascontiguousarray(poses_last, np.float64).reshape(n_scans, 7)
+        pc = np.ascontiguousarray(poses_curr, np.float64).reshape(n_scans, 7)
+        check(self.L.ll_reg_enqueue_spin_downsampled(self.h, map_buffer.h, spin.h, vox_corner.h, vox_surf.h, line_res, plane_res, n_scans,
+                                                     C.byref(self.params), ptr(pl), ptr(pc), None), "ll_reg_enqueue_spin_downsampled")
+
     def collect(self, n_scans: int):
         pc = np.zeros((n_scans, 7), np.float64)
         pi = np.zeros((n_scans, 7), np.float64)
@@ -770,6 +812,17 @@ class Point_cloud_registration:
         n = C.c_int64(int(n_used))
         check(self.L.ll_cloud_transform_fe_device(self.h, fe.h, int(n_scans), int(kind), ptr(acc), ptr(ps), C.c_void_p(out.data_ptr()),
                                                   int(out.shape[0]), C.byref(n)), "ll_cloud_transform_fe_device")
+        return int(n.value)
+
+    def append_to_submap_device_spin(self, spin: "Spinning_laser", n_scans: int, which: int, accept: np.ndarray, poses: np.ndarray, out,
+                                     n_used: int) -> int:
+        """append_to_submap_device for a spinning-lidar handle: cloud `which` (Spinning_laser.FULL .. LESS_FLAT) of every accepted scan"""
+        acc = np.ascontiguousarray(accept, np.int32)
+        ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        assert out.is_contiguous() and out.shape[1] == 4 and acc.shape[0] >= n_scans and ps.shape[0] >= n_scans
+        n = C.c_int64(int(n_used))
+        check(self.L.ll_cloud_transform_spin_device(self.h, spin.h, int(n_scans), int(which), ptr(acc), ptr(ps), C.c_void_p(out.data_ptr()),
+                                                    int(out.shape[0]), C.byref(n)), "ll_cloud_transform_spin_device")
         return int(n.value)
 
     def pointcloudAssociateToMap(self, pc_in: np.ndarray, pose: np.ndarray | None = None) -> np.ndarray:

@@ -146,6 +146,11 @@ SYMBOLS = {
     "ll_spin_lines": (_i32, [_vp, _i32, _vp, _vp]),
     "ll_spin_extract": (_i32, [_vp, _vp, _i32]),
     "ll_spin_kernel_times": (_i32, [_vp, _vp]),
+    "ll_reg_enqueue_spin": (_i32, [_vp, _vp, _vp, _i32, C.POINTER(RegParams), _vp, _vp, _vp]),
+    "ll_reg_enqueue_spin_downsampled": (_i32, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i32, C.POINTER(RegParams), _vp, _vp, _vp]),
+    "ll_history_add_spin": (_i32, [_vp, _vp, _i32, _vp, C.c_double, C.c_double, _vp]),
+    "ll_cloud_transform_spin_device": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "ll_spin_handoff_time": (_i32, [_vp, _vp]),
     "ll_reg_stream": (_vp, [_vp]),
     "ll_fe_stream": (_vp, [_vp]),
     "ll_runtime_hint_hw_queues": (_i32, [_i32]),

@@ -21,6 +21,7 @@
 #include "ll_reg_core.h"
 #include "ll_cellmap.h"
 #include "ll_voxel.h"
+#include "ll_spin.h"
 
 using namespace ll;
 
@@ -2308,6 +2309,136 @@ extern "C" int ll_cloud_transform_fe_device(ll_reg *r, ll_fe *fe, int32_t n_scan
     if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
     (void)hipFree(d_poses);
     if (e != hipSuccess) return set_err("ll_cloud_transform_fe_device", hipGetErrorString(e));
+    *n_points = total;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- spinning-lidar hand-off
+// The registrar's inputs out of a spin handle (ll_spin_api.hip), device to device: corner stack = LL_SPIN_LESS_SHARP (packed by
+// spin_pack_kernel), surface stack = LL_SPIN_LESS_FLAT.  The forms mirror the _fe ones above.
+static const char *kSpinDeblur =
+    "if_motion_deblur must be 0: the spinning extractor writes intensity = scanID + scanPeriod * relTime "
+    "(laser_feature_extractor.hpp:502), which refine_blur (point_cloud_registration.hpp:128-141) would misread as a time stamp";
+
+// the argument checks ll_reg_enqueue_spin and ll_reg_enqueue_spin_downsampled share (nothing is launched before they all pass)
+static int reg_spin_check(const char *where, ll_reg *r, ll_spin *sp, int n_scans, const ll_reg_params *prm, SpinView *v)
+{
+    if (!r || !sp) return set_err(where, "null handle");
+    if (!prm) return set_err(where, "null argument");
+    spin_view(sp, v);
+    if (v->device != r->device) return set_err(where, "extractor lives on another device");
+    if (n_scans < 1) return set_err(where, "n_scans must be at least 1");
+    if (n_scans > v->max_scans) return set_err(where, "n_scans exceeds the extractor capacity");
+    if (n_scans > r->max_scans) return set_err(where, "n_scans exceeds the registrar capacity");
+    if (v->max_points > r->max_feat) return set_err(where, "registrar feature capacity < extractor max_points");
+    if (prm->if_motion_deblur != 0) return set_err(where, kSpinDeblur);
+    return 0;
+}
+
+extern "C" int ll_reg_enqueue_spin(ll_reg *r, const ll_map *map, ll_spin *sp, int32_t n_scans, const ll_reg_params *prm,
+                                   const double *poses_last, const double *poses_curr, const double *poses_incre)
+{
+    SpinView v;
+    if (reg_spin_check("ll_reg_enqueue_spin", r, sp, n_scans, prm, &v)) return -1;
+    if (spin_handoff(sp, n_scans, &v)) return -1;
+    HC(hipSetDevice(r->device));
+    // order after the extractor's stream (the extraction and the pack kernel behind it)
+    HC(hipEventRecord(r->ev_wait, v.stream));
+    HC(hipStreamWaitEvent(r->stream, r->ev_wait, 0));
+    r->dev.corner_feat = v.corner;
+    r->dev.surf_feat = v.surf;
+    r->dev.n_corner = v.n_corner;
+    r->dev.n_surf = v.n_surf;
+    r->dev.feat_stride_c = v.pack_stride;
+    r->dev.feat_stride_s = v.max_points;
+    return reg_enqueue(r, map, n_scans, prm, poses_last, poses_curr, poses_incre);
+}
+
+extern "C" int ll_reg_enqueue_spin_downsampled(ll_reg *r, const ll_map *map, ll_spin *sp, ll_voxel *vc, ll_voxel *vs, float line_res,
+                                               float plane_res, int32_t n_scans, const ll_reg_params *prm, const double *poses_last,
+                                               const double *poses_curr, const double *poses_incre)
+{
+    const char *where = "ll_reg_enqueue_spin_downsampled";
+    if (!vc || !vs) return set_err(where, "null handle");
+    SpinView v;
+    if (reg_spin_check(where, r, sp, n_scans, prm, &v)) return -1;
+    if (vc->device != r->device || vs->device != r->device) return set_err(where, "handles live on different devices");
+    if (vc == vs) return set_err(where, "corner and surface need their own voxel filter handle");
+    if (n_scans > vc->dev.max_clouds || n_scans > vs->dev.max_clouds || v.pack_stride > vc->dev.stride || v.max_points > vs->dev.stride)
+        return set_err(where, "voxel filter capacity too small: the corner filter needs n_scans clouds of min(max_points, 1200 * scan_line) "
+                              "points, the surface filter n_scans clouds of max_points points");
+    if (spin_handoff(sp, n_scans, &v)) return -1;
+    HC(hipSetDevice(r->device));
+    // extractor (+ pack) -> (voxel filters, on the registrar's stream) -> registrar
+    HC(hipEventRecord(r->ev_wait, v.stream));
+    HC(hipStreamWaitEvent(r->stream, r->ev_wait, 0));
+    const char *err = nullptr;
+    const float lc[3] = {line_res, line_res, line_res}, ls[3] = {plane_res, plane_res, plane_res};
+    if (voxel_filter(vc->dev, v.corner, v.n_corner, v.pack_stride, n_scans, lc, r->stream, &err)) return set_err(where, err);
+    if (voxel_filter(vs->dev, v.surf, v.n_surf, v.max_points, n_scans, ls, r->stream, &err)) return set_err(where, err);
+    vc->last_stream = vs->last_stream = r->stream;
+    r->dev.corner_feat = vc->dev.out;
+    r->dev.surf_feat = vs->dev.out;
+    r->dev.n_corner = vc->dev.n_out;
+    r->dev.n_surf = vs->dev.n_out;
+    r->dev.feat_stride_c = vc->dev.out_stride;
+    r->dev.feat_stride_s = vs->dev.out_stride;
+    return reg_enqueue(r, map, n_scans, prm, poses_last, poses_curr, poses_incre);
+}
+
+extern "C" int ll_history_add_spin(ll_history *h, ll_spin *sp, int32_t scan, const double pose[7], double history_add_t_step,
+                                   double history_add_angle_step, int32_t *added)
+{
+    if (!h || !sp || !pose) return set_err("ll_history_add_spin", "null argument");
+    SpinView v;
+    spin_view(sp, &v);
+    if (v.device != h->device) return set_err("ll_history_add_spin", "extractor lives on another device");
+    if (scan < 0 || scan >= v.max_scans) return set_err("ll_history_add_spin", "scan slot out of range");
+    if (spin_handoff(sp, scan + 1, &v)) return -1;
+    HC(hipSetDevice(h->device));
+    HC(hipStreamSynchronize(v.stream));
+    int nc = 0, ns = 0;
+    HC(hipMemcpy(&nc, v.n_corner + scan, sizeof(int), hipMemcpyDeviceToHost));
+    HC(hipMemcpy(&ns, v.n_surf + scan, sizeof(int), hipMemcpyDeviceToHost));
+    return history_add_common(h, v.corner + (size_t)scan * v.pack_stride, nc, v.surf + (size_t)scan * v.max_points, ns, pose,
+                              history_add_t_step, history_add_angle_step, added);
+}
+
+extern "C" int ll_cloud_transform_spin_device(ll_reg *r, ll_spin *sp, int32_t n_scans, int32_t which, const int32_t *accept,
+                                              const double *poses7, float *dev_out_xyzi, int64_t capacity_points, int64_t *n_points)
+{
+    const char *where = "ll_cloud_transform_spin_device";
+    if (!r || !sp || !accept || !poses7 || !dev_out_xyzi || !n_points) return set_err(where, "null argument");
+    SpinView v;
+    spin_view(sp, &v);
+    if (v.device != r->device) return set_err(where, "extractor lives on another device");
+    if (which == LL_SPIN_LESS_FLAT_PRE) return set_err(where, "LL_SPIN_LESS_FLAT_PRE is a list of positions, not a cloud the reference publishes");
+    if (which < LL_SPIN_FULL || which > LL_SPIN_LESS_FLAT) return set_err(where, "unknown cloud");
+    if (n_scans < 0 || n_scans > v.max_scans) return set_err(where, "n_scans exceeds the extractor capacity");
+    if (*n_points < 0) return set_err(where, "bad argument");
+    if (n_scans == 0) return 0;
+    const float4 *src = nullptr;
+    int stride = 0;
+    std::vector<int> cnt((size_t)n_scans);
+    if (spin_device_cloud(sp, n_scans, which, &src, &stride, cnt.data())) return -1;  // (synchronises the extractor's stream)
+    HC(hipSetDevice(r->device));
+    int64_t total = *n_points;
+    for (int b = 0; b < n_scans; b++)
+        if (accept[b]) total += cnt[(size_t)b];
+    if (total > capacity_points) return set_err(where, "device buffer too small");
+    double *d_poses = nullptr;
+    DM(d_poses, (size_t)n_scans * 7);
+    hipError_t e = hipMemcpyAsync(d_poses, poses7, (size_t)n_scans * 7 * sizeof(double), hipMemcpyHostToDevice, r->stream);
+    int64_t at = *n_points;
+    for (int b = 0; b < n_scans && e == hipSuccess; b++) {
+        if (!accept[b] || cnt[(size_t)b] == 0) continue;
+        launch_cloud_transform(src + (size_t)b * stride, (float4 *)dev_out_xyzi + at, cnt[(size_t)b], d_poses + (size_t)b * 7, r->stream);
+        at += cnt[(size_t)b];
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    (void)hipFree(d_poses);
+    if (e != hipSuccess) return set_err(where, hipGetErrorString(e));
     *n_points = total;
     return 0;
 }

@@ -34,6 +34,15 @@ struct ll_spin {
     hipEvent_t ev[8] = {};  // [0]-[1] assign; [2] start of the later phases, [3]-[7] after lines, curvature, sort, select, VoxelGrid
     std::vector<int> h_n;      // points per slot as uploaded
     int last_batch = 0;        // n_scans of the last ll_spin_extract_batch
+    // hand-off to device consumers (ll_reg_enqueue_spin, ll_history_add_spin, ll_cloud_transform_spin_device): allocated by the first
+    // hand-off, so that callers who only extract and download pay nothing
+    int pack_stride = 0;
+    float4 *pack = nullptr;    // [S][pack_stride] the less-sharp cloud (corner stack)
+    int *pack_nc = nullptr, *pack_ns = nullptr;  // [S] sizes of the corner and the surface stack
+    int packed_n = 0;          // slots 0 .. packed_n-1 of `pack` hold the handle's current outputs (0 after every extraction)
+    float4 *pack_x = nullptr;  // [S][pack_stride] the cloud ll_cloud_transform_spin_device asked for (the corner stack may be in use)
+    int *pack_xn = nullptr;    // [S]
+    hipEvent_t ev_pack[2] = {};  // around the last pack of the corner stack (ll_spin_handoff_time)
 };
 
 extern "C" void ll_spin_default_params(ll_spin_params *p)
@@ -59,6 +68,10 @@ static int spin_create_impl(const ll_spin_params *p, ll_spin *h)
 {
     h->prm = *p;
     h->n_vlines = p->scan_line == 16 ? 16 : 51;
+    {  // at most 200 less-sharp picks per sub-region (:667-676), 6 sub-regions per line
+        const long long bound = 1200ll * p->scan_line;
+        h->pack_stride = (int)(bound < p->max_points ? bound : p->max_points);
+    }
     const int S = p->max_scans;
     const size_t P = (size_t)p->max_points, SP = (size_t)S * P;
     SpinDev &d = h->d;
@@ -111,11 +124,14 @@ extern "C" void ll_spin_destroy(ll_spin *h)
     (void)hipSetDevice(h->prm.device);
     SpinDev &d = h->d;
     void *ptrs[] = {d.in, d.n_in, d.ori_se, d.raw_sid, d.raw_ori, d.n_ambig, d.ambig, d.ambig_p, d.ambig_sid, d.ambig_ori, d.line_off, d.full, d.full_src, d.curv, d.flags,
-                    d.label, d.order, d.sharp, d.less_sharp, d.flat, d.lf_pos, d.vox_in, d.vox_n, d.less_flat, d.cnt};
+                    d.label, d.order, d.sharp, d.less_sharp, d.flat, d.lf_pos, d.vox_in, d.vox_n, d.less_flat, d.cnt,
+                    h->pack, h->pack_nc, h->pack_ns, h->pack_x, h->pack_xn};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     voxel_free(h->vox);
     for (auto &e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : h->ev_pack)
         if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -178,6 +194,7 @@ static int spin_run_rest(ll_spin *h, int n_scans)
 {
     const int L = h->prm.scan_line;
     const int mn = max_n(h, n_scans);
+    h->packed_n = 0;  // the packed corner stack no longer holds the handle's outputs
     SC(hipEventRecord(h->ev[2], h->stream));
     spin_launch_lines(h->d, n_scans, L, h->stream);
     SC(hipEventRecord(h->ev[3], h->stream));
@@ -333,6 +350,77 @@ extern "C" int ll_spin_extract(ll_spin *h, const float *xyzi, int32_t n)
     return status;
 }
 
+// ---------------------------------------------------------------------------------------------------- hand-off
+namespace ll {
+
+void spin_view(const ll_spin *h, SpinView *v)
+{
+    memset(v, 0, sizeof(*v));
+    v->device = h->prm.device;
+    v->max_scans = h->prm.max_scans;
+    v->max_points = h->prm.max_points;
+    v->scan_line = h->prm.scan_line;
+    v->pack_stride = h->pack_stride;
+    v->stream = h->stream;
+}
+
+int spin_handoff(ll_spin *h, int n_scans, SpinView *v)
+{
+    if (n_scans < 1 || n_scans > h->prm.max_scans) return api_error("ll_spin (hand-off)", "n_scans out of range");
+    SC(hipSetDevice(h->prm.device));
+    const size_t S = h->prm.max_scans;
+    if (!h->pack) {
+        if (dm(&h->pack, S * h->pack_stride) || dm(&h->pack_nc, S) || dm(&h->pack_ns, S)) return -1;
+        for (auto &e : h->ev_pack) SC(hipEventCreate(&e));
+    }
+    // On the handle's own stream: behind the extraction that wrote the lists, and ahead of the event every consumer waits for.  Nothing
+    // is zeroed: the kernel writes both counts of every slot it hands over, and no consumer reads a cloud beyond its count.
+    if (h->packed_n < n_scans) {
+        SC(hipEventRecord(h->ev_pack[0], h->stream));
+        spin_launch_pack(h->d, h->d.less_sharp, SPIN_C_LESS_SHARP, h->pack, h->pack_stride, h->pack_nc, h->pack_ns, n_scans, h->stream);
+        SC(hipEventRecord(h->ev_pack[1], h->stream));
+        SC(hipGetLastError());
+        h->packed_n = n_scans;
+    }
+    spin_view(h, v);
+    v->corner = h->pack;
+    v->n_corner = h->pack_nc;
+    v->surf = h->d.less_flat;
+    v->n_surf = h->pack_ns;
+    return 0;
+}
+
+int spin_device_cloud(ll_spin *h, int n_scans, int which, const float4 **src, int *stride, int *counts)
+{
+    if (n_scans < 1 || n_scans > h->prm.max_scans) return api_error("ll_spin (hand-off)", "n_scans out of range");
+    SC(hipSetDevice(h->prm.device));
+    const size_t S = h->prm.max_scans;
+    static const int slot[5] = {SPIN_C_FULL, SPIN_C_SHARP, SPIN_C_LESS_SHARP, SPIN_C_FLAT, SPIN_C_LESS_FLAT};
+    if (which == LL_SPIN_FULL || which == LL_SPIN_LESS_FLAT) {
+        *src = which == LL_SPIN_FULL ? h->d.full : h->d.less_flat;
+        *stride = h->d.stride;
+    } else {
+        if (!h->pack_x) {
+            if (dm(&h->pack_x, S * h->pack_stride) || dm(&h->pack_xn, S)) return -1;
+        }
+        const int *list = which == LL_SPIN_SHARP ? h->d.sharp : which == LL_SPIN_LESS_SHARP ? h->d.less_sharp : h->d.flat;
+        spin_launch_pack(h->d, list, slot[which], h->pack_x, h->pack_stride, h->pack_xn, nullptr, n_scans, h->stream);
+        SC(hipGetLastError());
+        *src = h->pack_x;
+        *stride = h->pack_stride;
+    }
+    SC(hipStreamSynchronize(h->stream));
+    std::vector<int> c((size_t)n_scans * SPIN_NCNT);
+    SC(hipMemcpy(c.data(), h->d.cnt, c.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int b = 0; b < n_scans; b++) {
+        const int m = c[(size_t)b * SPIN_NCNT + slot[which]];
+        counts[b] = m < *stride ? m : *stride;
+    }
+    return 0;
+}
+
+}  // namespace ll
+
 extern "C" int ll_spin_kernel_times(ll_spin *h, float ms[6])
 {
     if (!h || !ms) return api_error("ll_spin_kernel_times", "null argument");
@@ -340,5 +428,15 @@ extern "C" int ll_spin_kernel_times(ll_spin *h, float ms[6])
     SC(hipEventSynchronize(h->ev[7]));
     SC(hipEventElapsedTime(&ms[0], h->ev[0], h->ev[1]));
     for (int k = 1; k < 6; k++) SC(hipEventElapsedTime(&ms[k], h->ev[k + 1], h->ev[k + 2]));
+    return 0;
+}
+
+extern "C" int ll_spin_handoff_time(ll_spin *h, float *ms)
+{
+    if (!h || !ms) return api_error("ll_spin_handoff_time", "null argument");
+    if (!h->ev_pack[1]) return api_error("ll_spin_handoff_time", "nothing has been handed over yet");
+    SC(hipSetDevice(h->prm.device));
+    SC(hipEventSynchronize(h->ev_pack[1]));
+    SC(hipEventElapsedTime(ms, h->ev_pack[0], h->ev_pack[1]));
     return 0;
 }

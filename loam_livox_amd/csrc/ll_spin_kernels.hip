@@ -13,6 +13,7 @@
 //   spin_select_kernel  : one wavefront per scan, sub-regions in reference order (:631-767): candidates are consumed 64 at a
 //                         time with ballots against a picked bitmap in LDS; the neighbour walks run 64 steps per ballot
 //   spin_gather_kernel  : concatenates the per-line VoxelGrid outputs (:769-776; the filter is ll_voxel_kernels.hip's)
+//   spin_pack_kernel    : hand-off: a list of positions (sharp / less-sharp / flat) -> a packed cloud + the [S] count arrays
 #include <hip/hip_runtime.h>
 
 #include "ll_spin.h"
@@ -366,6 +367,27 @@ __global__ __launch_bounds__(256) void spin_gather_kernel(SpinDev d, const float
     }
 }
 
+// hand-off to the registrar: out[s][i] = full[s][list[s][i]], one lane per output point (16-byte stores, contiguous per scan); the
+// sizes leave cnt[][] for the [S] arrays the registrar reads.  blockIdx.y strides over the points of a scan.
+__global__ __launch_bounds__(256) void spin_pack_kernel(SpinDev d, const int *list, int cnt_slot, float4 *out, int out_stride, int *n_out, int *n_surf)
+{
+    const int s = blockIdx.x;
+    const int *cnt = d.cnt + s * SPIN_NCNT;
+    const int n = min(min(cnt[cnt_slot], out_stride), d.stride);
+    const size_t base = (size_t)s * d.stride;
+    const float4 *full = d.full + base;
+    const int *pos = list + base;
+    float4 *dst = out + (size_t)s * out_stride;
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += 256 * gridDim.y) {
+        const int p = pos[i];
+        dst[i] = (unsigned)p < (unsigned)d.stride ? full[p] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+        n_out[s] = n;
+        if (n_surf) n_surf[s] = min(cnt[SPIN_C_LESS_FLAT], d.stride);
+    }
+}
+
 __global__ __launch_bounds__(256) void spin_ambig_kernel(SpinDev d, int n, int patch)
 {
     const int k = blockIdx.x * 256 + threadIdx.x;
@@ -380,6 +402,13 @@ __global__ __launch_bounds__(256) void spin_ambig_kernel(SpinDev d, int n, int p
         d.ambig_sid[k] = d.raw_sid[o];
         d.ambig_ori[k] = d.raw_ori[o];
     }
+}
+
+void spin_launch_pack(const SpinDev &d, const int *list, int cnt_slot, float4 *out, int out_stride, int *n_out, int *n_surf, int n_scans,
+                      hipStream_t st)
+{
+    // the clouds are a few hundred points (up to out_stride): two workgroups per scan keep short batches on enough CUs
+    hipLaunchKernelGGL(spin_pack_kernel, dim3(n_scans, 2), dim3(256), 0, st, d, list, cnt_slot, out, out_stride, n_out, n_surf);
 }
 
 void spin_launch_ambig(const SpinDev &d, int n, bool patch, hipStream_t st)

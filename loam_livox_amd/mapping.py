@@ -13,10 +13,18 @@ from __future__ import annotations
 
 import numpy as np
 
-from .api import History_buffer, Livox_laser, Map_buffer, Point_cloud_registration, VoxelGrid
+from .api import History_buffer, Livox_laser, Map_buffer, Point_cloud_registration, Spinning_laser, VoxelGrid
 
 
 class Laser_mapping:
+    """lidar_type (common/lidar_type of the feature node, laser_feature_extractor.hpp:831-851): "livox" (default) runs the Livox
+    extractor; any other value runs the spinning-lidar one (scan_line 16 or 64, minimum_range, mapping_plane_resolution: the feature
+    node's parameters) and hands its less-sharp / less-flat clouds to the registrar and the history on the device
+    (Point_cloud_registration.enqueue_spin, History_buffer.add_spin): extract -> resolve -> register -> history -> refresh, with the
+    same prefetch of the next scan on a second handle.  The reference's mapping node has no spinning input; the cloud choice is the
+    project's.  Spinning lidars run in history mode (matching_mode 0) only: cell-map matching, keep_cell_maps and
+    loop closure are refused at construction with a ValueError, and process_clouds stays the Livox node path."""
+
     def __init__(self, scan_points: int = 24000, device: int = 0, maximum_history_size: int = 100, line_res: float = 0.1,
                  plane_res: float = 0.4, init_accumulate_frames: int = 50, input_downsample_mode: int = 1, icp_max_iterations: int = 20,
                  ceres_max_iterations: int = 100, max_allow_incre_R: float = 200.0 / 50.0, max_allow_incre_T: float = 100.0 / 50.0,
@@ -25,8 +33,17 @@ class Laser_mapping:
                  subsample_seed: int = 1, matching_mode: int = 0, cell_resolution: float = 1.0, threshold_cell_revisit: int = 5000,
                  maximum_search_range_corner: float = 100.0, maximum_search_range_surface: float = 100.0,
                  maximum_in_fov_angle: float = 30.0, down_sample_replace: int = 1, cell_map_max_points: int = 1 << 21,
-                 loop_closure_if_enable: int = 0, loop_closure: dict | None = None, keep_cell_maps: bool = False):
-        self.fe = Livox_laser(max_points=scan_points, max_scans=1, device=device, piecewise_number=1)
+                 loop_closure_if_enable: int = 0, loop_closure: dict | None = None, keep_cell_maps: bool = False,
+                 lidar_type: str = "livox", scan_line: int = 16, minimum_range: float = 0.1, mapping_plane_resolution: float = 0.8):
+        self.lidar_type = lidar_type
+        self._spin = lidar_type != "livox"
+        if self._spin:
+            if matching_mode or keep_cell_maps or loop_closure_if_enable:
+                raise ValueError(f'lidar_type "{lidar_type}" (spinning lidar) runs in history mode only: matching_mode, keep_cell_maps and '
+                                 "loop_closure_if_enable must be 0")
+            self._spin_args = dict(scan_line=scan_line, minimum_range=minimum_range, plane_resolution=mapping_plane_resolution,
+                                   max_points=scan_points, max_scans=1, max_line_points=min(scan_points, 8192), device=device)
+        self.fe = self._new_extractor(scan_points, device)
         # The feature node and the mapping node are separate processes in the reference: scan k + 1 is extracted while scan k is
         # registered.  process_new_scan( scan, next_xyzi = ... ) does the same with a second extractor handle (own stream): the next
         # scan's upload, extraction and selection are issued between this scan's enqueue and its collect.
@@ -98,11 +115,33 @@ class Laser_mapping:
         if self.keep_cell_maps:
             self.history.sync_cell_maps()
 
+    def _new_extractor(self, scan_points, device):
+        if self._spin:
+            return Spinning_laser(**self._spin_args)
+        return Livox_laser(max_points=scan_points, max_scans=1, device=device, piecewise_number=1)
+
     def _extract(self, fe, xyzi, time_stamp):
+        if self._spin:  # laserCloudHandler :393-776; the time stamp plays no part in this branch
+            fe.upload([xyzi])
+            fe.extract_batch_async(1)
+            fe.resolve()
+            return
         fe.upload(xyzi[None], np.full(1, time_stamp))
         fe.extract_batch(1)
         fe.resolve()
         fe.select_batch(1, -1, 0.0, 1.0)
+
+    def _enqueue(self, fe, pose):
+        reg = self.reg
+        if self._spin:
+            if self.m_if_input_downsample_mode:  # :1367-1373
+                reg.enqueue_spin_downsampled(self.map, fe, self.vox[0], self.vox[1], self.line_res, self.plane_res, 1, pose, pose)
+            else:
+                reg.enqueue_spin(self.map, fe, 1, pose, pose)
+        elif self.m_if_input_downsample_mode:  # :1367-1373
+            reg.enqueue_fe_downsampled(self.map, fe, self.vox[0], self.vox[1], self.line_res, self.plane_res, 1, pose, pose)
+        else:
+            reg.enqueue_fe(self.map, fe, 1, pose, pose)
 
     def process_new_scan(self, xyzi: np.ndarray, time_stamp: float = 1.0, next_xyzi: np.ndarray | None = None, next_time_stamp: float = 1.0,
                          scan_id=None, next_scan_id=None) -> int:
@@ -134,14 +173,11 @@ class Laser_mapping:
         reg.params.current_frame_index = self.m_current_frame_index  # init_pointcloud_registration runs before the increment
         self.m_current_frame_index += 1
         pose = self.pose[None]
-        if self.m_if_input_downsample_mode:  # :1367-1373
-            reg.enqueue_fe_downsampled(self.map, fe, self.vox[0], self.vox[1], self.line_res, self.plane_res, 1, pose, pose)
-        else:
-            reg.enqueue_fe(self.map, fe, 1, pose, pose)
+        self._enqueue(fe, pose)
         if next_xyzi is not None:  # the next frame's extraction runs beside this frame's ICP kernels
             other = 1 if fe is self._fe_pair[0] else 0
             if self._fe_pair[other] is None:
-                self._fe_pair[other] = Livox_laser(max_points=self._scan_points, max_scans=1, device=self._device, piecewise_number=1)
+                self._fe_pair[other] = self._new_extractor(self._scan_points, self._device)
             self._extract(self._fe_pair[other], next_xyzi, next_time_stamp)
             self._prefetched = (next_xyzi, next_time_stamp, self._fe_pair[other], next_scan_id)
         res, pc, _, reps = reg.collect(1)
@@ -154,10 +190,7 @@ class Laser_mapping:
             # the caller's other debug / A-B flags left as they are.  (An abort with the groups already off has another cause -- the small
             # solver could not hold the scan -- which a repeat would not cure: the scan stays rejected.)
             reg.set_debug_flags(flags | 32)
-            if self.m_if_input_downsample_mode:
-                reg.enqueue_fe_downsampled(self.map, fe, self.vox[0], self.vox[1], self.line_res, self.plane_res, 1, pose, pose)
-            else:
-                reg.enqueue_fe(self.map, fe, 1, pose, pose)
+            self._enqueue(fe, pose)
             res, pc, _, reps = reg.collect(1)
             reg.set_debug_flags(flags)
         self.last_report = reps[0]
@@ -169,6 +202,8 @@ class Laser_mapping:
         self.history.set_gate_pose(self.pose)  # m_q_w_curr is still the pre-registration pose at LM:1439-1451
         if self.m_if_input_downsample_mode:
             self.history.add_voxel(self.vox[0], self.vox[1], 0, pc[0], self.history_add_t_step, self.history_add_angle_step)
+        elif self._spin:
+            self.history.add_spin(fe, 0, pc[0], self.history_add_t_step, self.history_add_angle_step)
         else:
             self.history.add_fe(fe, 0, pc[0], self.history_add_t_step, self.history_add_angle_step)
         self.pose = pc[0].copy()  # :1496-1500

@@ -389,13 +389,20 @@ def make_spin_scan(world: World, k: int = 0, scan_line: int = 16, n_azimuth: int
     pose = sensor_pose_in_world(world, rng)
     pose[:4] = quat_from_rpy(0.0, 0.0, 0.0)
     yaw0 = rng.uniform(-np.pi, np.pi)
+    xyzi = _spin_revolution(world, pose, yaw0, elev, n_azimuth, rng, range_sigma, p_nan, p_near)
+    return Scan(xyzi, pose, pose.copy(), seed=5000 + k if seed is None else seed, meta=dict(scan_line=scan_line, n_azimuth=n_azimuth))
+
+
+def _spin_revolution(world: World, pose, yaw0: float, elev, n_azimuth: int, rng, range_sigma: float, p_nan: float = 0.0, p_near: float = 0.0):
+    """One revolution from `pose` (sensor -> world), first column at sensor azimuth yaw0, in the sensor frame (see make_spin_scan)."""
     az = yaw0 - 2 * np.pi * np.arange(n_azimuth) / n_azimuth
     el = np.deg2rad(elev)
     ca, sa = np.cos(az)[:, None], np.sin(az)[:, None]
     ce, se = np.cos(el)[None, :], np.sin(el)[None, :]
     shape = (n_azimuth, len(el))
     dirs = np.stack([np.broadcast_to(ca * ce, shape), np.broadcast_to(sa * ce, shape), np.broadcast_to(se, shape)], axis=2).reshape(-1, 3)
-    rng_m = raycast(world, pose[4:], dirs)
+    R = quat_to_mat(pose[:4])
+    rng_m = raycast(world, pose[4:], dirs if np.array_equal(R, np.eye(3)) else dirs @ R.T)
     hit = np.isfinite(rng_m)
     r = rng_m + (rng.normal(0.0, range_sigma, len(rng_m)) if range_sigma > 0 else 0.0)
     pts = (dirs * r[:, None]).astype(np.float32)[hit]
@@ -405,5 +412,31 @@ def make_spin_scan(world: World, k: int = 0, scan_line: int = 16, n_azimuth: int
     near = (u >= p_nan) & (u < p_nan + p_near)
     pts[near] = (dirs[hit][near] * 0.05).astype(np.float32)
     xyzi = np.concatenate([pts, inten[:, None]], axis=1).astype(np.float32)
-    return Scan(np.ascontiguousarray(xyzi), pose, pose.copy(), seed=5000 + k if seed is None else seed,
-                meta=dict(scan_line=scan_line, n_azimuth=n_azimuth))
+    return np.ascontiguousarray(xyzi)
+
+
+def pose_inverse(p):
+    R = quat_to_mat(p[:4])
+    return np.r_[-p[0], -p[1], -p[2], p[3], -(R.T @ p[4:])]
+
+
+def make_spin_sequence(world: World, n_frames: int = 9, n_static: int = 3, scan_line: int = 16, n_azimuth: int | None = None, seed: int = 77,
+                       step_xy=(0.04, 0.015), step_yaw_deg: float = 0.4, range_sigma: float = 0.01):
+    """A level spinning sensor on a slow trajectory: frames 0 .. n_static-1 from the start pose (they seed a map), then every
+    frame moves by step_xy metres in the sensor's own x / y and turns by step_yaw_deg about the vertical.  Every revolution
+    starts at an azimuth of its own and carries its own range noise.  Returns (scans, poses): the clouds [(n_k, 4) float32] and
+    the true sensor poses relative to frame 0 (the frame a map built from frame 0 lives in).  Deterministic in `seed`."""
+    rng = np.random.default_rng(seed)
+    elev = VLP16_ELEVATIONS if scan_line == 16 else HDL64_ELEVATIONS
+    if n_azimuth is None:
+        n_azimuth = 1800 if scan_line == 16 else 2000
+    start = sensor_pose_in_world(world, rng)
+    start[:4] = quat_from_rpy(0.0, 0.0, rng.uniform(-np.pi, np.pi))
+    step = np.r_[quat_from_rpy(0.0, 0.0, np.deg2rad(step_yaw_deg)), step_xy[0], step_xy[1], 0.0]
+    scans, poses, cur = [], [], start
+    for k in range(n_frames):
+        if k >= n_static:
+            cur = pose_compose(cur, step)
+        scans.append(_spin_revolution(world, cur, rng.uniform(-np.pi, np.pi), elev, n_azimuth, rng, range_sigma))
+        poses.append(pose_compose(pose_inverse(start), cur))
+    return scans, poses

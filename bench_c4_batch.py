@@ -1,0 +1,153 @@
+#!/usr/bin/env python3
+"""BASELINE config C4 on ONE GPU: S independent sub-sequences with local map growth, two ways in one process.
+
+  one_by_one   S loam_livox_amd.mapping.Laser_mapping loops back to back, each with the prefetch of the next scan (bench_c4.py's loop):
+               one scan per launch, what the sequential path offers;
+  lockstep     loam_livox_amd.mapping.Laser_mapping_batch: frame k of all S sequences is one batch -- one batched extraction, one
+               VoxelGrid pair, one registration with a map per slot (ll_reg_enqueue_fe_downsampled_maps) -- then S history adds and
+               match-buffer refreshes on a small pool of host threads.
+
+The sequences are bench_c4.py's with the sequence index where it has the rank (start-pose seed 9000 + s, scan seeds 7000 + 1000 s + k,
+turn sign by parity), under its args_map without cell maps on both routes.  The routes alternate after both are warm; every timed loop
+ends in a device synchronise.  Prints one JSON line per S: aggregate frames/s of both routes (best and all repeats), their ratio, the
+host time per phase and the number of sequences whose poses differ in any bit between the routes (must be 0).
+
+  python bench_c4_batch.py [--sequences 1,8,64] [--frames 200] [--distinct-frames 100] [--out profiles/bench_c4_batch.json]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")  # (bench_c4.py: every handle has a stream of its own)
+
+
+def make_sequence(job):
+    """bench_c4.py's generator for sequence s (there: rank): D distinct scans of an out-and-back trajectory of period 50"""
+    s, n_scans, n_points = job
+    from loam_livox_amd import synth
+    world = synth.world_for_map_size(200_000)
+    rng = np.random.default_rng(9000 + s)
+    start = synth.sensor_pose_in_world(world, rng)
+    sgn = 1.0 if s % 2 == 0 else -1.0
+    step = np.r_[synth.quat_from_axis_angle(np.array([0.1, 0.2, 1.0]), np.deg2rad(0.2 * sgn)), np.array([-0.02, 0.01 * sgn, 0.0])]
+    back = synth.pose_inverse(step)
+    ident = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)
+    scans, cur = [], start
+    for k in range(n_scans):
+        if k >= 3:
+            cur = synth.pose_compose(cur, step if ((k - 3) // 25) % 2 == 0 else back)
+        scans.append(synth.make_moving_scan(world, 7000 + 1000 * s + k, n_points, inc_true=ident, pose_start=cur, t_phase=0.13 * k).xyzi)
+    return scans
+
+
+def frame_scan(scans, k, D):
+    """frame k of a sequence that replays D distinct scans (the trajectory has period 50 from frame 3 on)"""
+    while k >= D + 3:
+        k -= D
+    return scans[k]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sequences", default="1,8,64")
+    ap.add_argument("--frames", type=int, default=200)
+    ap.add_argument("--distinct-frames", type=int, default=100, help="distinct scans per sequence (a multiple of 50, at least 100), replayed")
+    ap.add_argument("--scan-points", type=int, default=24000)
+    ap.add_argument("--history", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--refresh-threads", type=int, default=0, help="0 = Laser_mapping_batch's default")
+    ap.add_argument("--workers", type=int, default=8, help="processes that generate the synthetic scans")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    S_list = [int(x) for x in args.sequences.split(",")]
+    F, D, N = args.frames, args.distinct_frames, args.scan_points
+    assert D >= F or (D % 50 == 0 and D >= 100), "--distinct-frames must be a multiple of 50 and at least 100"
+    n_gen = min(F, D + 3)
+    # the scans first, in worker processes started before this process touches the device
+    from concurrent.futures import ProcessPoolExecutor
+    jobs = [(s, n_gen, N) for s in range(max(S_list))]
+    if args.workers > 1 and len(jobs) > 1:
+        with ProcessPoolExecutor(max_workers=min(args.workers, 16, len(jobs))) as ex:
+            seqs = list(ex.map(make_sequence, jobs))
+    else:
+        seqs = [make_sequence(j) for j in jobs]
+
+    import torch
+    from loam_livox_amd.mapping import Laser_mapping, Laser_mapping_batch
+    args_map = dict(maximum_history_size=args.history, init_accumulate_frames=2, line_res=0.1, plane_res=0.15, icp_max_iterations=10,
+                    ceres_max_iterations=20, max_allow_incre_R=20.0, max_allow_incre_T=0.3, minimum_icp_R_diff=1e-3, minimum_icp_T_diff=1e-4)
+    lines = []
+    for S in S_list:
+        def one_by_one(frames):
+            lms = [Laser_mapping(scan_points=N, **args_map) for _ in range(S)]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            poses, accepted = [], 0
+            for s, lm in enumerate(lms):
+                ps = []
+                for k in range(frames):
+                    nxt = frame_scan(seqs[s], k + 1, D) if k + 1 < frames else None
+                    accepted += lm.process_new_scan(frame_scan(seqs[s], k, D), next_xyzi=nxt)
+                    ps.append(lm.pose.copy())
+                poses.append(np.stack(ps))
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            stage = np.sum([lm.stage_s for lm in lms], axis=0)
+            for lm in lms:
+                lm.close()
+            return dt, poses, accepted, stage
+
+        def lockstep(frames):
+            kw = dict(refresh_threads=args.refresh_threads) if args.refresh_threads else {}
+            lb = Laser_mapping_batch(S, scan_points=N, **kw, **args_map)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            poses, accepted = [[] for _ in range(S)], 0
+            for k in range(frames):
+                out = lb.process_new_scans([frame_scan(seqs[s], k, D) for s in range(S)])
+                accepted += int((out == 1).sum())
+                for s in range(S):
+                    poses[s].append(lb.poses[s].copy())
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            stage, threads = lb.stage_s.copy(), lb.refresh_threads
+            lb.close()
+            return dt, [np.stack(p) for p in poses], accepted, stage, threads
+
+        one_by_one(min(6, F))  # warm-up: code objects load lazily, the ICP kernels first run on frame 3
+        lockstep(min(6, F))
+        t_a, t_b = [], []
+        for _ in range(args.repeats):
+            a = one_by_one(F)
+            b = lockstep(F)
+            t_a.append(a[0])
+            t_b.append(b[0])
+        differing = sum(0 if np.array_equal(a[1][s].view(np.uint64), b[1][s].view(np.uint64)) else 1 for s in range(S))
+        n = S * F
+        line = {
+            "metric": "frames_per_s", "sequences": S, "frames_per_sequence": F, "scan_points": N,
+            "one_by_one": {"frames_per_s": round(n / min(t_a), 1), "all_repeats": [round(n / t, 1) for t in t_a], "accepted": a[2],
+                           "ms_per_frame_by_stage": dict(zip(("extract_register", "history_add", "match_buffer_refresh"),
+                                                             [round(1e3 * float(v) / n, 4) for v in a[3][:3]]))},
+            "lockstep": {"frames_per_s": round(n / min(t_b), 1), "all_repeats": [round(n / t, 1) for t in t_b], "accepted": b[2], "refresh_threads": b[4],
+                         "ms_per_step_wall": {"extract_register": round(1e3 * float(b[3][0]) / F, 4), "history_add_and_refresh": round(1e3 * float(b[3][4]) / F, 4)},
+                         "ms_per_frame_thread_time": {"history_add": round(1e3 * float(b[3][1]) / n, 4), "match_buffer_refresh": round(1e3 * float(b[3][2]) / n, 4)}},
+            "lockstep_over_one_by_one": round(min(t_a) / min(t_b), 3),
+            "sequences_with_differing_poses": differing,
+        }
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()

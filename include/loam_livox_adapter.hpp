@@ -949,6 +949,29 @@ class Point_cloud_registration {
         return collect();
     }
 
+    // A map per slot (ll_reg_enqueue_fe_maps / ll_reg_enqueue_fe_downsampled_maps): scan b of a batched extractor registered against
+    // maps[b] (nullptr = idle slot) with frame_index[b] (nullptr = m_current_frame_index for every slot), the start-up gate decided
+    // per slot.  The batch handles are the caller's C handles (a registrar created with max_scans >= n_scans; voxel filters with
+    // max_clouds >= n_scans); this object contributes its configuration fields.  Collect with ll_reg_collect( reg, n_scans, ... ).
+    // m_if_motion_deblur must be 0 (the call throws otherwise).
+    void enqueue_fe_maps(ll_reg *reg, const ll_map *const *maps, ll_fe *fe, int n_scans, const int32_t *frame_index, const double *poses_last,
+                         const double *poses_curr) const
+    {
+        ll_reg_params p;
+        fill_params(p);
+        check(ll_reg_enqueue_fe_maps(reg, maps, fe, n_scans, &p, frame_index, poses_last, poses_curr, nullptr), "ll_reg_enqueue_fe_maps");
+    }
+    // ... with the corner / surface clouds voxel-filtered on the device first (m_if_input_downsample_mode, laser_mapping.hpp:1367-1373)
+    void enqueue_fe_maps(ll_reg *reg, const ll_map *const *maps, ll_fe *fe, ll_voxel *vox_corner, ll_voxel *vox_surf, float line_res,
+                         float plane_res, int n_scans, const int32_t *frame_index, const double *poses_last, const double *poses_curr) const
+    {
+        ll_reg_params p;
+        fill_params(p);
+        check(ll_reg_enqueue_fe_downsampled_maps(reg, maps, fe, vox_corner, vox_surf, line_res, plane_res, n_scans, &p, frame_index, poses_last,
+                                                 poses_curr, nullptr),
+              "ll_reg_enqueue_fe_downsampled_maps");
+    }
+
     // void pointAssociateToMap ... see below
    private:
     template <class CloudPtr>

@@ -323,6 +323,26 @@ int ll_voxel_filter(ll_voxel *v, int32_t n_clouds, const float *xyzi, const int3
 int ll_reg_enqueue_fe_downsampled(ll_reg *r, const ll_map *map, ll_fe *fe, ll_voxel *vox_corner, ll_voxel *vox_surf,
                                   float line_res, float plane_res, int32_t n_scans, const ll_reg_params *prm,
                                   const double *poses_last, const double *poses_curr, const double *poses_incre);
+/* A MAP PER SLOT: ll_reg_enqueue_fe / ll_reg_enqueue_fe_downsampled with scan b registered against maps[b] -- S independent sequences
+ * that advance in lock step, frame k of all of them one batch, each against the match buffer its own earlier frames built.  Collect
+ * with ll_reg_collect.
+ *   maps[b] == NULL          an idle slot: comes back as a gated scan does (report.gated 1, result 1, pose untouched), whatever the
+ *                            extractor slot holds.  The same handle may appear in several slots.
+ *   frame_index              [n_scans], or NULL = prm->current_frame_index for every slot.
+ *   gate                     the start-up gate (map sizes, frame index > mapping_init_accumulate_frames) is decided PER SLOT: a gated
+ *                            slot comes back gated while its neighbours register.
+ *   snapshots                both snapshots of every distinct map are pinned from the enqueue to ll_reg_collect.
+ *   results                  slot b's pose, increment, result and report are those of ll_reg_enqueue_fe[_downsampled] for that scan
+ *                            alone (n_scans = 1) against maps[b] with that frame index, bit for bit, whatever n_scans is: the solver form
+ *                            is chosen per slot as for the scan alone.
+ * Refused: null arguments, a map on another device, n_scans out of range, prm->if_motion_deblur != 0 (all before anything is
+ * launched), and a batch with a running scan beyond the compact solver's size (Mid-100 sweeps). */
+int ll_reg_enqueue_fe_maps(ll_reg *r, const ll_map *const *maps, ll_fe *fe, int32_t n_scans, const ll_reg_params *prm,
+                           const int32_t *frame_index, const double *poses_last, const double *poses_curr, const double *poses_incre);
+int ll_reg_enqueue_fe_downsampled_maps(ll_reg *r, const ll_map *const *maps, ll_fe *fe, ll_voxel *vox_corner, ll_voxel *vox_surf,
+                                       float line_res, float plane_res, int32_t n_scans, const ll_reg_params *prm,
+                                       const int32_t *frame_index, const double *poses_last, const double *poses_curr,
+                                       const double *poses_incre);
 /* the filtered feature counts of the last ll_reg_enqueue_fe_downsampled (after ll_reg_collect) */
 int ll_voxel_counts(ll_voxel *v, int32_t n_clouds, int32_t *n_out, int32_t *status);
 

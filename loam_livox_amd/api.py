@@ -722,6 +722,33 @@ class Point_cloud_registration:
         check(self.L.ll_reg_enqueue_fe_downsampled(self.h, map_buffer.h, fe.h, vox_corner.h, vox_surf.h, line_res, plane_res, n_scans,
                                                    C.byref(self.params), ptr(pl), ptr(pc), None), "ll_reg_enqueue_fe_downsampled")
 
+    def _maps_args(self, maps, n_scans: int, poses_last, poses_curr, frame_index):
+        """the handle table, poses and frame indices of a map-per-slot enqueue (None in maps = an idle slot)"""
+        if len(maps) != n_scans:
+            raise ValueError(f"maps has {len(maps)} entries for {n_scans} scans")
+        tab = (C.c_void_p * n_scans)(*[None if m is None else m.h for m in maps])
+        pl = np.ascontiguousarray(poses_last, np.float64).reshape(n_scans, 7)
+        pc = np.ascontiguousarray(poses_curr, np.float64).reshape(n_scans, 7)
+        fi = None
+        if frame_index is not None:
+            fi = np.ascontiguousarray(frame_index, np.int32).reshape(n_scans)
+        return tab, pl, pc, fi
+
+    def enqueue_fe_maps(self, maps, fe: Livox_laser, n_scans: int, poses_last, poses_curr, frame_index=None):
+        """enqueue_fe with a map per slot (ll_reg_enqueue_fe_maps): scan b is registered against maps[b] (a Map_buffer, or None for an
+        idle slot) with frame_index[b] (None: params.current_frame_index for every slot); the start-up gate is decided per slot."""
+        tab, pl, pc, fi = self._maps_args(maps, n_scans, poses_last, poses_curr, frame_index)
+        check(self.L.ll_reg_enqueue_fe_maps(self.h, tab, fe.h, n_scans, C.byref(self.params), None if fi is None else ptr(fi), ptr(pl), ptr(pc), None),
+              "ll_reg_enqueue_fe_maps")
+
+    def enqueue_fe_downsampled_maps(self, maps, fe: Livox_laser, vox_corner: "VoxelGrid", vox_surf: "VoxelGrid", line_res: float, plane_res: float,
+                                    n_scans: int, poses_last, poses_curr, frame_index=None):
+        """enqueue_fe_downsampled with a map per slot (ll_reg_enqueue_fe_downsampled_maps)"""
+        tab, pl, pc, fi = self._maps_args(maps, n_scans, poses_last, poses_curr, frame_index)
+        check(self.L.ll_reg_enqueue_fe_downsampled_maps(self.h, tab, fe.h, vox_corner.h, vox_surf.h, line_res, plane_res, n_scans,
+                                                        C.byref(self.params), None if fi is None else ptr(fi), ptr(pl), ptr(pc), None),
+              "ll_reg_enqueue_fe_downsampled_maps")
+
     def enqueue_spin(self, map_buffer: Map_buffer, spin: "Spinning_laser", n_scans: int, poses_last, poses_curr):
         """enqueue_fe for a spinning-lidar handle: corner stack = its less-sharp cloud, surface stack = its less-flat cloud, read where
         the extractor left them (ll_reg_enqueue_spin).  params.if_motion_deblur must be 0."""

@@ -105,6 +105,8 @@ SYMBOLS = {
     "ll_voxel_filter": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ll_voxel_counts": (_i32, [_vp, _i32, _vp, _vp]),
     "ll_reg_enqueue_fe_downsampled": (_i32, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i32, C.POINTER(RegParams), _vp, _vp, _vp]),
+    "ll_reg_enqueue_fe_maps": (_i32, [_vp, _vp, _vp, _i32, C.POINTER(RegParams), _vp, _vp, _vp, _vp]),
+    "ll_reg_enqueue_fe_downsampled_maps": (_i32, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i32, C.POINTER(RegParams), _vp, _vp, _vp, _vp]),
     "ll_history_create": (_i32, [_i32, _i32, _i32, _f, _f, C.POINTER(_vp)]),
     "ll_history_destroy": (None, [_vp]),
     "ll_history_add": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, C.c_double, C.c_double, _vp]),

@@ -740,6 +740,10 @@ struct ll_reg {
     std::vector<RegState> h_state;
     std::vector<int> h_nc, h_ns;
     std::shared_ptr<MapSnap> pinned[2];  // map snapshots of the solve in flight (released once it has been collected)
+    // a map per slot (ll_reg_enqueue_fe_maps): both snapshots of every distinct map of the solve in flight, and the grid table
+    std::vector<std::shared_ptr<MapSnap>> pinned_maps;
+    Grid *d_map_tab = nullptr;     // [2 * max_scans] corner, surface grid of slot b at 2 b, 2 b + 1
+    std::vector<Grid> h_map_tab;
     int debug = 0, profiling = 0;
     int debug_knn_iter = 0;  // ll_reg_set_debug_knn_iteration
     int last_n_scans = 0, last_gated = 0;
@@ -834,6 +838,8 @@ static int reg_create_impl(int32_t device, int32_t max_scans, int32_t max_featur
     DM(r->d_nc, B);
     DM(r->d_ns, B);
     DM(r->d_pose_tmp, 8);
+    DM(r->d_map_tab, 2 * B);
+    r->h_map_tab.resize(2 * B);
     HC(hipMemsetAsync(d.blk_flag, 0, B * d.cap, r->stream));  // (on the registrar's stream: a null-stream memset is not ordered with it)
     r->h_state.resize(B);
     r->h_nc.assign(B, 0);
@@ -863,7 +869,7 @@ extern "C" void ll_reg_destroy(ll_reg *r)
     (void)hipSetDevice(r->device);
     RegDev &d = r->dev;
     void *ptrs[] = {d.state, d.blk_f, d.blk_av, d.blk_id, d.pl_tab, d.blk_flag, d.nn, d.qperm, d.qsorted, d.qperm_c, d.qw, d.ref_q, d.ref_p, d.ref_s, d.blk_flag0, d.work_search, d.work_build, d.work_cnt, d.work_off, d.grp_ctl, d.solve_order, d.grp_part, d.grp_xch, d.blk_l1, d.hash, d.dbg_idx, d.dbg_d2,
-                    r->d_corner, r->d_surf, r->d_nc, r->d_ns, r->d_pose_tmp};
+                    r->d_corner, r->d_surf, r->d_nc, r->d_ns, r->d_pose_tmp, r->d_map_tab};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : r->ev) (void)hipEventDestroy(e);
@@ -986,7 +992,8 @@ static int reg_enqueue(ll_reg *r, const ll_map *map, int n_scans, const ll_reg_p
     r->rc.debug_knn_iter = r->debug_knn_iter;
     // A solve enqueued earlier on this handle and never collected still reads its snapshots: let it finish before its pins are
     // replaced (the snapshots could otherwise be recycled and rebuilt under its kernels by a concurrent ll_map_upload / refresh).
-    if (r->pinned[0] || r->pinned[1]) HC(hipStreamSynchronize(r->stream));
+    if (r->pinned[0] || r->pinned[1] || !r->pinned_maps.empty()) HC(hipStreamSynchronize(r->stream));
+    r->pinned_maps.clear();
     // PCR:199 gate
     // the snapshots this solve runs against, whatever ll_map_upload / ll_history_refresh* publish meanwhile
     r->pinned[0] = map_pin(map, 0);
@@ -1098,6 +1105,7 @@ extern "C" int ll_reg_collect(ll_reg *r, int32_t n_scans, double *poses_curr, do
     HC(hipStreamSynchronize(r->stream));
     r->pinned[0].reset();  // the solve has left the device: its map snapshots may be recycled
     r->pinned[1].reset();
+    r->pinned_maps.clear();
     int n_aborted = 0;
     for (int b = 0; b < n_scans; b++) {
         const RegState &s = r->h_state[b];
@@ -1220,6 +1228,168 @@ extern "C" int ll_reg_enqueue_fe(ll_reg *r, const ll_map *map, ll_fe *fe, int32_
     return reg_enqueue(r, map, n_scans, prm, poses_last, poses_curr, poses_incre);
 }
 
+
+// ---- a map per slot ---------------------------------------------------------------------------------------------------------------
+// what can be refused before anything is launched
+static int reg_maps_check(const char *where, ll_reg *r, const ll_map *const *maps, int n_scans, const ll_reg_params *prm, const double *poses_last,
+                          const double *poses_curr)
+{
+    if (!r || !maps || !prm || !poses_last || !poses_curr) return set_err(where, "null argument");
+    if (n_scans < 1 || n_scans > r->max_scans) return set_err(where, "n_scans out of range");
+    if (prm->icp_max_iterations < 0 || prm->ceres_max_iterations < 0 || prm->ceres_prerun_times < 0) return set_err(where, "negative iteration count");
+    if (prm->icp_max_iterations > (1 << 19)) return set_err(where, "icp_max_iterations above 524288");
+    if (prm->if_motion_deblur)
+        return set_err(where, "motion deblur is not supported with a map per slot (if_motion_deblur must be 0): register such scans through the single-map entry points");
+    for (int b = 0; b < n_scans; b++)
+        if (maps[b] && maps[b]->device != r->device) return set_err(where, "map lives on another device");
+    return 0;
+}
+
+// reg_enqueue with a map per slot; the feature pointers in r->dev must be set and reg_maps_check passed.  The gate of PCR:199 is
+// decided per slot from that slot's map and frame index; maps[b] == nullptr is an idle slot (comes back gated).
+static int reg_enqueue_maps(const char *where, ll_reg *r, const ll_map *const *maps, int n_scans, const ll_reg_params *prm, const int32_t *frame_index,
+                            const double *poses_last, const double *poses_curr, const double *poses_incre)
+{
+    static const int debug_or = getenv("LL_DEBUG_OR") ? atoi(getenv("LL_DEBUG_OR")) : 0;
+    make_reg_const(prm, r->debug | debug_or, &r->rc);
+    r->rc.debug_knn_iter = r->debug_knn_iter;
+    r->rc.knn_tile = 0;   // (no table form: their work items are not bound to one scan per workgroup; the lists are the same bit for bit)
+    r->rc.knn_reuse = 0;
+    if (r->pinned[0] || r->pinned[1] || !r->pinned_maps.empty()) HC(hipStreamSynchronize(r->stream));
+    r->pinned[0].reset();
+    r->pinned[1].reset();
+    r->pinned_maps.clear();
+    struct PinGuard {  // an enqueue that fails after this point must not leave its pins behind (reg_enqueue)
+        ll_reg *r;
+        bool keep = false;
+        ~PinGuard()
+        {
+            if (!keep) {
+                (void)hipStreamSynchronize(r->stream);
+                r->pinned_maps.clear();
+            }
+        }
+    } pin_guard{r};
+    // every distinct map is pinned once: slots that name the same handle see the same pair of snapshots
+    std::vector<const ll_map *> seen;
+    std::vector<int> pin_of(n_scans, -1);
+    for (int b = 0; b < n_scans; b++) {
+        if (!maps[b]) continue;
+        size_t k = 0;
+        while (k < seen.size() && seen[k] != maps[b]) k++;
+        if (k == seen.size()) {
+            seen.push_back(maps[b]);
+            r->pinned_maps.push_back(map_pin(maps[b], 0));
+            r->pinned_maps.push_back(map_pin(maps[b], 1));
+        }
+        pin_of[b] = (int)k;
+    }
+    const MapKind empty_kind{};
+    int n_run = 0;
+    for (int b = 0; b < n_scans; b++) {
+        const MapSnap *s0 = pin_of[b] >= 0 ? r->pinned_maps[2 * pin_of[b]].get() : nullptr, *s1 = pin_of[b] >= 0 ? r->pinned_maps[2 * pin_of[b] + 1].get() : nullptr;
+        const MapKind &mk0 = s0 ? s0->mk : empty_kind, &mk1 = s1 ? s1->mk : empty_kind;
+        const int fi = frame_index ? frame_index[b] : prm->current_frame_index;
+        const bool run = mk0.n > 0 && mk1.n > 50 && fi > prm->mapping_init_accumulate_frames;  // PCR:199, per slot
+        if (run && (!mk0.pts || !mk1.pts)) return set_err(where, "map not uploaded (or converted to fp16 points: the registrar needs the fp32 records)");
+        Grid g0{}, g1{};
+        if (run) g0 = mk0.grid, g1 = mk1.grid;  // (guard 0: nothing reuses neighbours here)
+        g0.guard = g1.guard = 0.0f;
+        r->h_map_tab[2 * b] = g0;
+        r->h_map_tab[2 * b + 1] = g1;
+        n_run += run ? 1 : 0;
+        RegState &s = r->h_state[b];
+        memset(&s, 0, sizeof(s));
+        for (int i = 0; i < 7; i++) {
+            s.pose_last[i] = poses_last[7 * b + i];
+            s.pose_curr[i] = poses_curr[7 * b + i];
+            s.inc[i] = poses_incre ? poses_incre[7 * b + i] : (i == 3 ? 1.0 : 0.0);
+        }
+        s.prev_q[3] = 1.0;
+        s.gated = run ? 0 : 1;
+        s.done = run ? 0 : 1;
+        s.result = 1;
+        s.accepted = 1;
+    }
+    r->last_gated = n_run ? 0 : 1;
+    r->last_n_scans = n_scans;
+    for (hipEvent_t e : r->ev) (void)hipEventDestroy(e);
+    r->ev.clear();
+    r->ev_class.clear();
+    HC(hipMemcpyAsync(r->dev.state, r->h_state.data(), (size_t)n_scans * sizeof(RegState), hipMemcpyHostToDevice, r->stream));
+    HC(hipMemcpyAsync(r->d_map_tab, r->h_map_tab.data(), (size_t)n_scans * 2 * sizeof(Grid), hipMemcpyHostToDevice, r->stream));
+    HC(hipMemcpyAsync(r->h_nc.data(), r->dev.n_corner, (size_t)n_scans * sizeof(int), hipMemcpyDeviceToHost, r->stream));
+    HC(hipMemcpyAsync(r->h_ns.data(), r->dev.n_surf, (size_t)n_scans * sizeof(int), hipMemcpyDeviceToHost, r->stream));
+    HC(hipStreamSynchronize(r->stream));
+    int max_nc = 0, max_ns = 0;  // over the slots that run: the others launch nothing
+    RegMapsClasses cls{};        // ... and per solver form (reg_maps_class: the form each scan would get alone)
+    int max_tot[4] = {0, 0, 0, 0};
+    cls.grp_min = r->rc.solve_group == 1 ? 0x7fffffff : LL_GRP_MIN_BLOCKS;  // (debug bit 5: no groups)
+    for (int b = 0; b < n_scans; b++) {
+        if (r->h_state[b].done) continue;
+        const int nc = r->h_nc[b], ns = r->h_ns[b], c = reg_maps_class(r->rc, nc, ns, cls.grp_min);
+        max_nc = nc > max_nc ? nc : max_nc;
+        max_ns = ns > max_ns ? ns : max_ns;
+        cls.n[c]++;
+        cls.max_nc[c] = nc > cls.max_nc[c] ? nc : cls.max_nc[c];
+        cls.max_ns[c] = ns > cls.max_ns[c] ? ns : cls.max_ns[c];
+        max_tot[c] = nc + ns > max_tot[c] ? nc + ns : max_tot[c];
+    }
+    // The small solver sizes itself (wavefronts, rounds, LDS) by max_nc + max_ns.  The two maxima may come from different scans and add up to
+    // more than any scan has -- beyond 1024 for a class whose scans all stay below, which would select the eight-wavefront form for scans that
+    // take the four-wavefront form alone.  Hand it the largest scan's total instead (only the sum and max_nc are read).
+    for (int c = 0; c < 2; c++) cls.max_ns[c] = max_tot[c] - cls.max_nc[c];
+    if (max_nc > r->dev.cap_c || max_ns > r->dev.cap_s) return set_err(where, "feature count exceeds the registrar capacity");
+    if (!prm->subsample_seed && (max_nc > prm->maximum_allow_residual_block || max_ns > prm->maximum_allow_residual_block))
+        return set_err(where, "feature count exceeds maximum_allow_residual_block and subsample_seed is 0 (strict mode): raise the "
+                              "limit, or set a seed to get the reference's sub-sampling with a reproducible random stream");
+    r->rc.solve_group = cls.n[3] ? LL_GRP : 1;  // (here: whether the grouped solver's bookkeeping is needed; the launcher sets it per launch)
+    if (n_run) {
+        if ((cls.n[2] && !reg_solve_fast_eligible(r->rc, cls.max_nc[2], cls.max_ns[2])) || (cls.n[3] && !reg_solve_fast_eligible(r->rc, cls.max_nc[3], cls.max_ns[3])))
+            return set_err(where, "a scan of this batch is beyond the compact solver's size (or the general solver was forced): not supported with a map "
+                                  "per slot, register such scans through the single-map entry points");
+        if (r->rc.solve_group > 1)
+            HC(hipMemsetAsync(r->dev.grp_xch, 0, (size_t)n_scans * 2 * LL_GRP * 56 * sizeof(unsigned long long), r->stream));
+        for (int it = 0; it < prm->icp_max_iterations; it++) {
+            r->rc.xch_epoch = it + 1;
+            prof_begin(r, 0);
+            launch_reg_knn_build_maps(r->dev, r->rc, r->d_map_tab, n_scans, it, max_nc, max_ns, r->stream);
+            prof_end(r);
+            prof_begin(r, 1);
+            if (r->rc.solve_group > 1) HC(hipMemsetAsync(r->dev.grp_ctl, 0, (size_t)(2 * n_scans + 1) * sizeof(int), r->stream));
+            launch_reg_solve_maps(r->dev, r->rc, r->d_map_tab, n_scans, cls, it, r->stream);
+            prof_end(r);
+        }
+    }
+    prof_begin(r, 2);
+    launch_reg_finalize(r->dev, r->rc, n_scans, r->stream);
+    prof_end(r);
+    HC(hipGetLastError());
+    pin_guard.keep = true;  // released by ll_reg_collect
+    return 0;
+}
+
+extern "C" int ll_reg_enqueue_fe_maps(ll_reg *r, const ll_map *const *maps, ll_fe *fe, int32_t n_scans, const ll_reg_params *prm,
+                                      const int32_t *frame_index, const double *poses_last, const double *poses_curr, const double *poses_incre)
+{
+    static const char *where = "ll_reg_enqueue_fe_maps";
+    if (!r || !fe) return set_err(where, "null handle");
+    if (reg_maps_check(where, r, maps, n_scans, prm, poses_last, poses_curr)) return -1;
+    if (fe->prm.device != r->device) return set_err(where, "extractor lives on another device");
+    if (n_scans > fe->prm.max_scans) return set_err(where, "n_scans exceeds the extractor capacity");
+    if (fe->prm.max_points > r->max_feat) return set_err(where, "registrar feature capacity < extractor max_points");
+    HC(hipSetDevice(r->device));
+    HC(hipEventRecord(r->ev_wait, fe->stream));
+    HC(hipStreamWaitEvent(r->stream, r->ev_wait, 0));
+    r->dev.corner_feat = fe->dev.corner_feat;
+    r->dev.surf_feat = fe->dev.surf_feat;
+    r->dev.n_corner = fe->dev.n_corner;
+    r->dev.n_surf = fe->dev.n_surf;
+    r->dev.feat_stride_c = fe->dev.stride;
+    r->dev.feat_stride_s = fe->dev.stride;
+    return reg_enqueue_maps(where, r, maps, n_scans, prm, frame_index, poses_last, poses_curr, poses_incre);
+}
+
 // ---------------------------------------------------------------------------------------------------- voxel grid
 struct ll_voxel {
     int device = 0;
@@ -1324,6 +1494,35 @@ extern "C" int ll_reg_enqueue_fe_downsampled(ll_reg *r, const ll_map *map, ll_fe
     r->dev.feat_stride_c = vc->dev.out_stride;
     r->dev.feat_stride_s = vs->dev.out_stride;
     return reg_enqueue(r, map, n_scans, prm, poses_last, poses_curr, poses_incre);
+}
+
+extern "C" int ll_reg_enqueue_fe_downsampled_maps(ll_reg *r, const ll_map *const *maps, ll_fe *fe, ll_voxel *vc, ll_voxel *vs, float line_res,
+                                                  float plane_res, int32_t n_scans, const ll_reg_params *prm, const int32_t *frame_index,
+                                                  const double *poses_last, const double *poses_curr, const double *poses_incre)
+{
+    static const char *where = "ll_reg_enqueue_fe_downsampled_maps";
+    if (!r || !fe || !vc || !vs) return set_err(where, "null handle");
+    if (reg_maps_check(where, r, maps, n_scans, prm, poses_last, poses_curr)) return -1;
+    if (fe->prm.device != r->device || vc->device != r->device || vs->device != r->device) return set_err(where, "handles live on different devices");
+    if (n_scans > fe->prm.max_scans) return set_err(where, "n_scans exceeds the extractor capacity");
+    if (n_scans > vc->dev.max_clouds || n_scans > vs->dev.max_clouds) return set_err(where, "n_scans exceeds the voxel filters' max_clouds");
+    if (fe->prm.max_points > r->max_feat) return set_err(where, "registrar feature capacity < extractor max_points");
+    if (vc == vs) return set_err(where, "corner and surface need their own voxel filter handle");
+    HC(hipSetDevice(r->device));
+    HC(hipEventRecord(r->ev_wait, fe->stream));
+    HC(hipStreamWaitEvent(r->stream, r->ev_wait, 0));
+    const char *err = nullptr;
+    const float lc[3] = {line_res, line_res, line_res}, ls[3] = {plane_res, plane_res, plane_res};
+    if (voxel_filter(vc->dev, fe->dev.corner_feat, fe->dev.n_corner, fe->dev.stride, n_scans, lc, r->stream, &err)) return set_err(where, err);
+    if (voxel_filter(vs->dev, fe->dev.surf_feat, fe->dev.n_surf, fe->dev.stride, n_scans, ls, r->stream, &err)) return set_err(where, err);
+    vc->last_stream = vs->last_stream = r->stream;
+    r->dev.corner_feat = vc->dev.out;
+    r->dev.surf_feat = vs->dev.out;
+    r->dev.n_corner = vc->dev.n_out;
+    r->dev.n_surf = vs->dev.n_out;
+    r->dev.feat_stride_c = vc->dev.out_stride;
+    r->dev.feat_stride_s = vs->dev.out_stride;
+    return reg_enqueue_maps(where, r, maps, n_scans, prm, frame_index, poses_last, poses_curr, poses_incre);
 }
 
 // ---------------------------------------------------------------------------------------------------- cell map

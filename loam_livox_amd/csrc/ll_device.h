@@ -204,6 +204,27 @@ bool reg_solve_small_eligible(const RegConst &rc, int max_nc, int max_ns);
 bool reg_solve_fast_eligible(const RegConst &rc, int max_nc, int max_ns);
 void launch_reg_solve_small(const RegDev &rd, const RegConst &rc, const Grid &gs, int n_scans, int max_nc, int max_ns, int iter, hipStream_t s);
 int reg_solve_small_waves(const RegConst &rc, int n_scans, int max_nc, int max_ns);
+// A map per slot (ll_reg_enqueue_fe_maps): map_tab[2 b] / map_tab[2 b + 1] are the corner / surface grid of scan b, in device memory.
+// Per-lane or per-wavefront searches of every query in every ICP iteration (no tile search, no reuse lists), the small solver or
+// reg_solve_kernel's table form; the caller refuses motion deblur and batches beyond reg_solve_fast_eligible.
+void launch_reg_knn_build_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, int iter, int max_nc, int max_ns, hipStream_t s);
+// The solver form is chosen PER SLOT, as the single-map entry points would choose it for that scan alone (the forms group their sums
+// differently and agree to rounding only; a slot must give the bits of its own registration): class 0 = the small solver's
+// four-wavefront form (up to 1024 blocks; whatever the batch size: the one- and two-wavefront forms of large single-map batches are
+// not used), 1 = its eight-wavefront form (up to LL_SMALL_MAX_BLOCKS), 2 = reg_solve_kernel's table form on one
+// workgroup, 3 = the same spread over a group of LL_GRP workgroups (grp_min features or more: LL_GRP_MIN_BLOCKS, or INT_MAX with the groups off).
+// One launch per class that has a scan; a workgroup whose scan belongs to another class leaves at once.
+__host__ __device__ inline int reg_maps_class(const RegConst &rc, int nc, int ns, int grp_min)
+{
+    const bool small = !rc.force_general && !rc.no_small_solver && nc + ns > 0 && nc + ns <= LL_SMALL_MAX_BLOCKS && nc <= 1024;  // reg_solve_small_eligible for the scan alone
+    return small ? (nc + ns <= 1024 ? 0 : 1) : (nc + ns < grp_min ? 2 : 3);
+}
+struct RegMapsClasses {
+    int n[4], max_nc[4], max_ns[4];  // running scans of each class and their largest feature counts
+    int grp_min;
+};
+void launch_reg_solve_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, const RegMapsClasses &cls, int iter, hipStream_t s);
+void launch_reg_solve_small_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, int cls, int max_nc, int max_ns, int iter, hipStream_t s);
 void launch_reg_finalize(const RegDev &rd, const RegConst &rc, int n_scans, hipStream_t s);
 void launch_cloud_transform(const float4 *in, float4 *out, int n, const double *d_pose, hipStream_t s);
 #define LL_HIST_CONCAT_MAX 1023  // frames one history_concat_kernel launch gathers (longer histories: the per-frame copies)

@@ -39,6 +39,7 @@ namespace ll {
 #define HASH_EMPTY 0xffffffffffffffffull
 
 
+#ifndef LL_REG_MAPS_TU  // (ll_reg_maps_kernels.hip compiles this file for the solver below alone: see its header)
 // ---------------------------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------------------------
 // Per-iteration query kernels (corner and surface queries share every launch, blockIdx.z = kind).
@@ -346,6 +347,8 @@ __global__ __launch_bounds__(RL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8
         }
     }
 }
+#endif  // LL_REG_MAPS_TU
+
 
 // Evaluation context as plain locals (R_inc / t_inc for the plain blocks, axis-angle for the motion-deblur ones);
 // DEBLUR is a template constant, so the unused half disappears from each kernel instantiation.
@@ -1599,6 +1602,7 @@ __device__ __noinline__ void solver_eval3(const RegDev &rd, int b, int nC, int n
 #undef LL3_PIPE
 
 
+#ifndef LL_REG_MAPS_TU
 // test tap (ll_debug_quintic): the sequential and the wavefront form of the fit on n argument sets, one wavefront each
 __global__ __launch_bounds__(64) void debug_quintic_kernel(const double *args, int n, double *out_seq, double *out_wave)
 {
@@ -1615,6 +1619,7 @@ void launch_debug_quintic(const double *args, int n, double *out_seq, double *ou
 {
     if (n > 0) hipLaunchKernelGGL(debug_quintic_kernel, dim3(n), dim3(64), 0, s, args, n, out_seq, out_wave);
 }
+#endif
 
 // one ceres::Solve on the plane-table layout: starts at x0, leaves the result in sh.ctl
 template <bool WANT_L1, bool GROUPED>
@@ -1809,8 +1814,10 @@ __device__ void solve_fast3(const RegDev &rd, const RegConst &rc, const f4 *map_
 #endif
 }
 
+#ifndef LL_REG_MAPS_TU
 // The Mid-40 batches: no motion deblur, every scan within FAST_MAX_BLOCKS (launch_reg_solve decides per batch from the host's feature
 // counts; everything else goes to reg_solve_big_kernel, ll_reg_big_path.h).
+// (reg_solve_maps_kernel at the end of this file repeats this kernel's prologue -- ticket, size check, group fields -- by hand: keep the two in step)
 __global__ __launch_bounds__(RS_THREADS) void reg_solve_kernel(RegDev rd, RegConst rc, const f4 *map_surf)
 {
     __shared__ SolveShared sh;
@@ -1852,6 +1859,49 @@ __global__ __launch_bounds__(RS_THREADS) void reg_solve_kernel(RegDev rd, RegCon
         solve_fast3<true>(rd, rc, map_surf, b, st, sh, s_raw);
     else
         solve_fast3<false>(rd, rc, map_surf, b, st, sh, s_raw);
+}
+
+// ---- a map per slot (ll_reg_enqueue_fe_maps) --------------------------------------------------------------------------------------
+// Scan b is searched and solved against map_tab[2 b] (corner) / map_tab[2 b + 1] (surface).  The scan is uniform per workgroup
+// (blockIdx.y, or the solver's ticket), so a workgroup reads its two grids once through scalar loads and then runs the same
+// knn_one / build_one / solve_fast3 as the single-map kernels above.  A slot that does not run (gated, idle) has st->done set by
+// the host and zeroed table entries that nobody reads.
+__global__ __launch_bounds__(KB_THREADS) __attribute__((amdgpu_waves_per_eu(KNN_WAVES_PER_EU, 8)))
+void reg_knn_maps_kernel(RegDev rd, RegConst rc, const Grid *__restrict__ map_tab, int iter, int skip_kinds)
+{
+    const int b = blockIdx.y, kind = blockIdx.z;
+    if ((skip_kinds >> kind) & 1) return;  // reg_knn_coop_maps_kernel has them
+    const RegState *st = rd.state + b;
+    if (st->done) return;
+    const int n = kind ? rd.n_surf[b] : rd.n_corner[b];
+    const int q = blockIdx.x * KB_THREADS + threadIdx.x;
+    if (q >= n) return;
+    const Grid gc = map_tab[2 * b], gs = map_tab[2 * b + 1];
+    knn_one(rd, rc, gc, gs, b, (kind ? rd.cap_c : 0) + q, iter);
+}
+
+__global__ __launch_bounds__(KC_THREADS) void reg_knn_coop_maps_kernel(RegDev rd, RegConst rc, const Grid *__restrict__ map_tab, int iter, int kinds)
+{
+    const int b = blockIdx.y, kind = blockIdx.z;
+    if (!((kinds >> kind) & 1)) return;
+    const RegState *st = rd.state + b;
+    if (st->done) return;
+    const int q = (int)((blockIdx.x * KC_THREADS + threadIdx.x) >> 6);
+    if (q >= (kind ? rd.n_surf[b] : rd.n_corner[b])) return;  // (whole wavefronts)
+    const Grid gc = map_tab[2 * b], gs = map_tab[2 * b + 1];
+    knn_one_coop(rd, rc, gc, gs, b, (kind ? rd.cap_c : 0) + q, iter);
+}
+
+__global__ __launch_bounds__(KB_THREADS) void reg_build_maps_kernel(RegDev rd, RegConst rc, const Grid *__restrict__ map_tab)
+{
+    const int b = blockIdx.y, kind = blockIdx.z;
+    const RegState *st = rd.state + b;
+    if (st->done) return;
+    const int n = kind ? rd.n_surf[b] : rd.n_corner[b];
+    const int q = blockIdx.x * KB_THREADS + threadIdx.x;
+    if (q >= n) return;
+    const Grid gc = map_tab[2 * b], gs = map_tab[2 * b + 1];
+    build_one(rd, rc, gc, gs, b, (kind ? rd.cap_c : 0) + q);
 }
 
 #include "ll_reg_big_path.h"
@@ -1968,6 +2018,34 @@ void launch_reg_solve(const RegDev &rd, const RegConst &rc, const Grid &gs, int 
     else
         hipLaunchKernelGGL(reg_solve_big_kernel<0>, dim3(n_scans), dim3(RS_THREADS), 0, s, rd, rc, gs.pts);
 }
+// A map per slot: every query of every running scan is searched in every ICP iteration -- per lane (reg_knn_maps_kernel), or per
+// wavefront for the batches the single-map launcher serves that way -- and every block is rebuilt.  The tile search and the reuse
+// lists have no table form (their work items are not bound to one scan per workgroup); the caller clears rc.knn_tile and
+// rc.knn_reuse.  Every search form returns the same neighbour lists, so a slot gets the bits of its single-map registration.
+void launch_reg_knn_build_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, int iter, int max_nc, int max_ns, hipStream_t s)
+{
+    (void)iter;
+    const int mx = max_nc > max_ns ? max_nc : max_ns;
+    if (mx <= 0) return;
+    const dim3 grid((mx + KB_THREADS - 1) / KB_THREADS, n_scans, 2);
+    hipLaunchKernelGGL(reg_transform_kernel, grid, dim3(KB_THREADS), 0, s, rd, rc, 0);
+    int coop_kinds = 0;
+    if (rc.knn_coop && n_scans <= LL_KNN_COOP_MAX_SCANS) {
+        if (max_nc > 0) coop_kinds |= 1;
+        if (max_ns > 0 && max_ns <= LL_KNN_COOP_MAX_SURF) coop_kinds |= 2;
+    }
+    if (coop_kinds) {
+        const int mq = (coop_kinds & 2) ? mx : max_nc;
+        hipLaunchKernelGGL(reg_knn_coop_maps_kernel, dim3((mq * 64 + KC_THREADS - 1) / KC_THREADS, n_scans, 2), dim3(KC_THREADS), 0, s, rd, rc, map_tab, iter,
+                           coop_kinds);
+    }
+    if ((max_nc > 0 && !(coop_kinds & 1)) || (max_ns > 0 && !(coop_kinds & 2))) {
+        const int mk = (coop_kinds & 2) ? max_nc : ((coop_kinds & 1) ? max_ns : mx);
+        hipLaunchKernelGGL(reg_knn_maps_kernel, dim3((mk + KB_THREADS - 1) / KB_THREADS, n_scans, 2), dim3(KB_THREADS), 0, s, rd, rc, map_tab, iter,
+                           coop_kinds);
+    }
+    hipLaunchKernelGGL(reg_build_maps_kernel, grid, dim3(KB_THREADS), 0, s, rd, rc, map_tab);
+}
 void launch_reg_finalize(const RegDev &rd, const RegConst &rc, int n_scans, hipStream_t s)
 {
     hipLaunchKernelGGL(reg_finalize_kernel, dim3((n_scans + 63) / 64), dim3(64), 0, s, rd, rc, n_scans);
@@ -2032,5 +2110,70 @@ void launch_cloud_transform(const float4 *in, float4 *out, int n, const double *
     if (n <= 0) return;
     hipLaunchKernelGGL(cloud_transform_kernel, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n, d_pose);
 }
+
+#else  // LL_REG_MAPS_TU
+// ---- the solver of a map per slot (ll_reg_enqueue_fe_maps), a translation unit of its own (ll_reg_maps_kernels.hip) ------------
+// A second kernel built on solve_fast3 in reg_solve_kernel's module changes how that kernel is compiled (two SGPR and two VGPR
+// spills moved when it was tried); compiled apart, reg_solve_kernel is the code it was.
+// reg_solve_kernel with the surface map of the scan the workgroup turns out to work on (the prologue is repeated rather than shared:
+// reg_solve_kernel keeps its code, registers and spills to the last one)
+__global__ __launch_bounds__(RS_THREADS) void reg_solve_maps_kernel(RegDev rd, RegConst rc, const Grid *map_tab, int grp_min)
+{
+    __shared__ SolveShared sh;
+    __shared__ uint4 s_raw[PT_LDS_BYTES / 16];
+    int b = blockIdx.x, g = 0, G = 1;
+    if (rc.solve_group > 1) {  // grouped launch (n_scans * G workgroups): scan and rank by ticket, see group_barrier
+        if (threadIdx.x == 0) sh.grp_seq = atomicAdd(rd.grp_ctl, 1);
+        __syncthreads();
+        G = rc.solve_group;
+        b = sh.grp_seq / G;
+        g = sh.grp_seq - b * G;
+        __syncthreads();
+    }
+    RegState *st = rd.state + b;
+    if (st->done) return;  // the same answer for every member: the epilogue that sets it runs behind the group's barriers
+    {
+        const int nS_ = rd.n_surf[b], nC_ = rd.n_corner[b];
+        if (reg_maps_class(rc, nC_, nS_, grp_min) != (G > 1 ? 3 : 2)) return;  // (the small solver's launches, or this kernel's other launch, have it)
+        if ((nS_ + RS_THREADS - 1) / RS_THREADS * RS_THREADS + nC_ > FAST_MAX_BLOCKS || !scan_is_compact(rd, rc, b)) {
+            // cannot happen (the host launches this kernel only for batches it holds): fail loudly -- rejected and reported -- instead of answering
+            if (g == 0 && threadIdx.x == 0) {
+                st->aborted = 1;
+                st->done = 1;
+                st->icp_iters += 1;
+            }
+            return;
+        }
+    }
+    if (threadIdx.x == 0) {
+        sh.grp_g = g;
+        sh.grp_G = G;
+        sh.grp_seq = 0;
+        sh.xch_seq = 0;
+        sh.xch_epoch = rc.xch_epoch;
+        sh.grp_abort = (rc.test_group_abort && G > 1) ? 1 : 0;  // test switch: behave as if the first barrier had timed out
+    }
+    __syncthreads();
+    const f4 *map_surf = map_tab[2 * b + 1].pts;
+    if (G > 1)
+        solve_fast3<true>(rd, rc, map_surf, b, st, sh, s_raw);
+    else
+        solve_fast3<false>(rd, rc, map_surf, b, st, sh, s_raw);
+}
+
+// (the caller has checked that one of the two table forms holds the batch: no motion deblur, nothing beyond reg_solve_kernel's size)
+void launch_reg_solve_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, const RegMapsClasses &cls, int iter, hipStream_t s)
+{
+    for (int c = 0; c < 2; c++)
+        if (cls.n[c] > 0) launch_reg_solve_small_maps(rd, rc, map_tab, n_scans, c, cls.max_nc[c], cls.max_ns[c], iter, s);
+    RegConst one = rc;  // (rc.solve_group is what the kernel reads: one workgroup per scan, or a group of LL_GRP)
+    one.solve_group = 1;
+    if (cls.n[2] > 0) hipLaunchKernelGGL(reg_solve_maps_kernel, dim3(n_scans), dim3(RS_THREADS), 0, s, rd, one, map_tab, cls.grp_min);
+    if (cls.n[3] > 0) {
+        one.solve_group = LL_GRP;
+        hipLaunchKernelGGL(reg_solve_maps_kernel, dim3(n_scans * LL_GRP), dim3(RS_THREADS), 0, s, rd, one, map_tab, cls.grp_min);
+    }
+}
+#endif  // LL_REG_MAPS_TU
 
 }  // namespace ll

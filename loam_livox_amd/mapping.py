@@ -260,3 +260,166 @@ class Laser_mapping:
             self._keyframe_step(full)
         self.map_sizes = self.history.refresh(self.map)
         return 1
+
+
+class Laser_mapping_batch:
+    """n_sequences independent Laser_mapping loops advanced in lock step (BASELINE config C4: batched offline map building from
+    independent sub-sequences with local map growth).  Frame k of all sequences is ONE batch: one batched extraction, one VoxelGrid
+    pair over all slots, one registration in which slot s is searched and solved against sequence s's own match buffer
+    (Point_cloud_registration.enqueue_fe[_downsampled]_maps), then per sequence the history add and the match-buffer refresh --
+    those on a small pool of host threads (refresh_threads; every history has its own stream), because a refresh drains its stream
+    four times and S of them on one thread would serialise.
+
+    Per sequence this is Laser_mapping._process_new_scan line for line -- the frame index handed to the gate, the gate pose of the
+    add rule, the repeat of an aborted grouped solve on one workgroup -- and gives the same bits as a Laser_mapping run alone on that
+    sequence.  Takes the arguments of Laser_mapping; Livox scans in history mode only: lidar_type other than "livox", matching_mode,
+    loop_closure_if_enable and keep_cell_maps raise ValueError."""
+
+    def __init__(self, n_sequences: int, refresh_threads: int | None = None, **kw):
+        import inspect
+        sig = inspect.signature(Laser_mapping.__init__)
+        unknown = set(kw) - set(sig.parameters)
+        if unknown:
+            raise TypeError(f"unexpected argument(s) {sorted(unknown)}: Laser_mapping_batch takes the arguments of Laser_mapping")
+        a = {k: p.default for k, p in sig.parameters.items() if k != "self"}
+        a.update(kw)
+        if n_sequences < 1:
+            raise ValueError("n_sequences must be at least 1")
+        if a["lidar_type"] != "livox":
+            raise ValueError(f'lidar_type "{a["lidar_type"]}": the batched loop takes Livox scans only')
+        if a["matching_mode"]:
+            raise ValueError("matching_mode must be 0: the batched loop matches against the history buffers only")
+        if a["loop_closure_if_enable"]:
+            raise ValueError("loop_closure_if_enable must be 0 in the batched loop")
+        if a["keep_cell_maps"]:
+            raise ValueError("keep_cell_maps is not offered by the batched loop")
+        if refresh_threads is None:
+            refresh_threads = min(4, n_sequences)
+        if not 1 <= int(refresh_threads) <= 16:
+            raise ValueError("refresh_threads must be between 1 and 16")
+        S, scan_points, device = int(n_sequences), a["scan_points"], a["device"]
+        self.n_sequences, self.refresh_threads = S, int(refresh_threads)
+        self._scan_points = scan_points
+        self.fe = Livox_laser(max_points=scan_points, max_scans=S, device=device, piecewise_number=1)
+        self.reg = Point_cloud_registration(max_scans=S, max_features=scan_points, device=device)
+        self.vox = (VoxelGrid(scan_points, S, device=device), VoxelGrid(scan_points, S, device=device))
+        self.maps = [Map_buffer(device=device) for _ in range(S)]
+        self.histories = [History_buffer(a["maximum_history_size"], scan_points, a["line_res"], a["plane_res"], device=device) for _ in range(S)]
+        self.line_res, self.plane_res = a["line_res"], a["plane_res"]
+        self.m_if_input_downsample_mode = a["input_downsample_mode"]
+        self.history_add_t_step, self.history_add_angle_step = a["history_add_t_step"], a["history_add_angle_step"]
+        p = self.reg.params
+        p.icp_max_iterations, p.ceres_max_iterations = a["icp_max_iterations"], a["ceres_max_iterations"]
+        p.para_max_angular_rate, p.para_max_speed, p.max_final_cost = a["max_allow_incre_R"], a["max_allow_incre_T"], a["max_allow_final_cost"]
+        p.mapping_init_accumulate_frames = a["init_accumulate_frames"]
+        p.minimum_icp_R_diff, p.minimum_icp_T_diff = a["minimum_icp_R_diff"], a["minimum_icp_T_diff"]
+        p.maximum_allow_residual_block = a["maximum_residual_blocks"] if a["maximum_residual_blocks"] > 0 else scan_points
+        p.subsample_seed = a["subsample_seed"] if a["maximum_residual_blocks"] > 0 else 0
+        self.frame_index = np.zeros(S, np.int32)                                  # m_current_frame_index of every sequence
+        self.poses = np.tile(np.array([0, 0, 0, 1, 0, 0, 0], np.float64), (S, 1))  # m_q_w_curr / m_t_w_curr
+        self.map_sizes = [(0, 0)] * S
+        self.last_reports = [None] * S
+        self.aborted_solves = 0
+        # cumulative host time: extract + register (wall), history add and refresh (summed over the pool's threads), steps, and the
+        # wall time of the add + refresh phase
+        self.stage_s = np.zeros(5)
+        self._pool = None
+        if self.refresh_threads > 1:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=self.refresh_threads)
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+        for h in [self.fe, self.reg, self.vox[0], self.vox[1]] + self.maps + self.histories:
+            h.close()
+
+    def _upload(self, scans, stamps, active):
+        S = self.n_sequences
+        arrs = [None if scans[s] is None else np.ascontiguousarray(scans[s], np.float32) for s in range(S)]
+        if all(active) and len({x.shape for x in arrs}) == 1:
+            self.fe.upload(np.stack(arrs), stamps)
+            return
+        empty = np.zeros((1, 0, 4), np.float32)
+        for s in range(S):  # an idle slot holds an empty scan: nothing is extracted for it
+            self.fe.upload(arrs[s][None] if active[s] else empty, stamps[s:s + 1], first_scan=s)
+
+    def _enqueue(self, maps, fi):
+        S = self.n_sequences
+        if self.m_if_input_downsample_mode:  # laser_mapping.hpp:1367-1373
+            self.reg.enqueue_fe_downsampled_maps(maps, self.fe, self.vox[0], self.vox[1], self.line_res, self.plane_res, S, self.poses, self.poses, fi)
+        else:
+            self.reg.enqueue_fe_maps(maps, self.fe, S, self.poses, self.poses, fi)
+
+    def _add_and_refresh(self, s, pose_before, pose_new):
+        import time
+        t0 = time.perf_counter()
+        h = self.histories[s]
+        h.set_gate_pose(pose_before)  # m_q_w_curr is still the pre-registration pose at LM:1439-1451
+        if self.m_if_input_downsample_mode:
+            h.add_voxel(self.vox[0], self.vox[1], s, pose_new, self.history_add_t_step, self.history_add_angle_step)
+        else:
+            h.add_fe(self.fe, s, pose_new, self.history_add_t_step, self.history_add_angle_step)
+        t1 = time.perf_counter()
+        sizes = h.refresh(self.maps[s])
+        return s, sizes, t1 - t0, time.perf_counter() - t1
+
+    def process_new_scans(self, scans, time_stamps=None) -> np.ndarray:
+        """One step of every sequence: scans[s] is sequence s's next scan, or None when it has none this step.  Returns an int array:
+        -1 idle, 0 rejected, 1 accepted (laser_mapping.hpp:1311-1520 per sequence)."""
+        import time
+        S = self.n_sequences
+        if len(scans) != S:
+            raise ValueError(f"{len(scans)} scans for {S} sequences")
+        t0 = time.perf_counter()
+        active = [x is not None for x in scans]
+        out = np.full(S, -1, np.int32)
+        if not any(active):
+            return out
+        stamps = np.ones(S, np.float64) if time_stamps is None else np.ascontiguousarray(time_stamps, np.float64).reshape(S)
+        fe, reg = self.fe, self.reg
+        self._upload(scans, stamps, active)
+        fe.extract_batch(S)
+        fe.resolve()
+        fe.select_batch(S, -1, 0.0, 1.0)
+        fi = self.frame_index.copy()  # init_pointcloud_registration runs before the increment
+        self.frame_index[active] += 1
+        maps = [self.maps[s] if active[s] else None for s in range(S)]
+        self._enqueue(maps, fi)
+        res, pc, _, reps = reg.collect(S)
+        flags = getattr(reg, "debug_flags", 0)
+        again = [s for s in range(S) if active[s] and reps[s].aborted]
+        self.aborted_solves += len(again)
+        if again and not (flags & 32):
+            # Laser_mapping's repeat of a registration the grouped solver abandoned: those slots once more on one workgroup each,
+            # the others idle
+            reg.set_debug_flags(flags | 32)
+            self._enqueue([self.maps[s] if s in again else None for s in range(S)], fi)
+            res2, pc2, _, reps2 = reg.collect(S)
+            reg.set_debug_flags(flags)
+            for s in again:
+                res[s], pc[s], reps[s] = res2[s], pc2[s], reps2[s]
+        t1 = time.perf_counter()
+        jobs = []
+        for s in range(S):
+            if not active[s]:
+                continue
+            self.last_reports[s] = reps[s]
+            out[s] = 1 if res[s] else 0
+            if res[s]:  # :1413-1416
+                jobs.append((s, self.poses[s].copy(), pc[s].copy()))
+        if self._pool is not None and len(jobs) > 1:
+            done = list(self._pool.map(lambda j: self._add_and_refresh(*j), jobs))
+        else:
+            done = [self._add_and_refresh(*j) for j in jobs]
+        for (s, sizes, t_add, t_ref), j in zip(done, jobs):
+            self.map_sizes[s] = sizes
+            self.poses[s] = j[2]  # :1496-1500
+            self.stage_s[1] += t_add
+            self.stage_s[2] += t_ref
+        t2 = time.perf_counter()
+        self.stage_s[0] += t1 - t0
+        self.stage_s[3] += 1
+        self.stage_s[4] += t2 - t1
+        return out

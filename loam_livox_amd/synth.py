@@ -440,3 +440,27 @@ def make_spin_sequence(world: World, n_frames: int = 9, n_static: int = 3, scan_
         scans.append(_spin_revolution(world, cur, rng.uniform(-np.pi, np.pi), elev, n_azimuth, rng, range_sigma))
         poses.append(pose_compose(pose_inverse(start), cur))
     return scans, poses
+
+
+def make_livox_sequence(world: World, seed: int, n_frames: int = 9, n_static: int = 3, n_points: int = 12000, teleport=None):
+    """A Livox sensor on a slow trajectory: frames 0 .. n_static-1 from the start pose (they seed a map, the registrar's start-up
+    gate), then every frame turns by 0.4 degrees and moves by (0.04, 0.015, 0) m in the sensor's own frame.  The start pose is drawn
+    from default_rng( seed ); scan k is make_moving_scan( world, 500 + 100 * ( seed - 77 ) + k, ... ) taken at rest from the pose of
+    frame k.  teleport = ( frame, metres ): that one frame is taken `metres` along the sensor's x axis away from its pose (a scan the
+    registration must reject); the trajectory itself goes on from where it was.  Returns (scans, poses): [(n_points, 4) float32] and
+    the true poses relative to frame 0 (of the trajectory: the teleported frame's entry is the pose it should have had)."""
+    rng = np.random.default_rng(seed)
+    ident = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)
+    start = sensor_pose_in_world(world, rng)
+    step = np.r_[quat_from_axis_angle(np.array([0.1, 0.2, 1.0]), np.deg2rad(0.4)), np.array([0.04, 0.015, 0.0])]
+    poses, scans, cur = [], [], start
+    for k in range(n_frames):
+        if k >= n_static:
+            cur = pose_compose(cur, step)
+        at = cur
+        if teleport is not None and k == int(teleport[0]):
+            at = pose_compose(cur, np.r_[0.0, 0.0, 0.0, 1.0, float(teleport[1]), 0.0, 0.0])
+        sc = make_moving_scan(world, 500 + 100 * (seed - 77) + k, n_points, inc_true=ident, pose_start=at, t_phase=0.13 * k)
+        scans.append(sc.xyzi)
+        poses.append(pose_compose(pose_inverse(start), cur))
+    return scans, poses

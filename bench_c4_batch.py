@@ -1,18 +1,22 @@
 #!/usr/bin/env python3
-"""BASELINE config C4 on ONE GPU: S independent sub-sequences with local map growth, two ways in one process.
+"""BASELINE config C4 on ONE GPU: S independent sub-sequences with local map growth, three ways in one process.
 
   one_by_one   S loam_livox_amd.mapping.Laser_mapping loops back to back, each with the prefetch of the next scan (bench_c4.py's loop):
                one scan per launch, what the sequential path offers;
   lockstep     loam_livox_amd.mapping.Laser_mapping_batch: frame k of all S sequences is one batch -- one batched extraction, one
                VoxelGrid pair, one registration with a map per slot (ll_reg_enqueue_fe_downsampled_maps) -- then S history adds and
-               match-buffer refreshes on a small pool of host threads.
+               match-buffer refreshes on a small pool of host threads;
+  lockstep_batched  the same loop with batched_history=True: the histories of all S sequences in one History_buffer_batch, one add and
+               one refresh per step whose launches and host waits do not grow with S.
 
 The sequences are bench_c4.py's with the sequence index where it has the rank (start-pose seed 9000 + s, scan seeds 7000 + 1000 s + k,
-turn sign by parity), under its args_map without cell maps on both routes.  The routes alternate after both are warm; every timed loop
-ends in a device synchronise.  Prints one JSON line per S: aggregate frames/s of both routes (best and all repeats), their ratio, the
-host time per phase and the number of sequences whose poses differ in any bit between the routes (must be 0).
+turn sign by parity), under its args_map without cell maps on both routes.  The routes alternate after all are warm; every timed loop
+ends in a device synchronise.  Prints one JSON line per S: aggregate frames/s of the routes (best and all repeats), their ratios, the
+host time per phase and the number of sequences whose poses differ in any bit between the routes (must be 0; for lockstep_batched:
+from either other route).
 
-  python bench_c4_batch.py [--sequences 1,8,64] [--frames 200] [--distinct-frames 100] [--out profiles/bench_c4_batch.json]"""
+  python bench_c4_batch.py [--sequences 1,8,64] [--frames 200] [--distinct-frames 100] [--out profiles/bench_c4_batch.json]
+  python bench_c4_batch.py --routes lockstep_batched --sequences 8 --frames 12 --repeats 1   # one route alone, e.g. under a kernel trace"""
 import argparse
 import json
 import os
@@ -62,9 +66,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--refresh-threads", type=int, default=0, help="0 = Laser_mapping_batch's default")
     ap.add_argument("--workers", type=int, default=8, help="processes that generate the synthetic scans")
+    ap.add_argument("--routes", default="one_by_one,lockstep,lockstep_batched", help="the routes to run (all three for the JSON line of record)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     S_list = [int(x) for x in args.sequences.split(",")]
+    routes = args.routes.split(",")
+    assert routes and set(routes) <= {"one_by_one", "lockstep", "lockstep_batched"}, "--routes: one_by_one, lockstep, lockstep_batched"
     F, D, N = args.frames, args.distinct_frames, args.scan_points
     assert D >= F or (D % 50 == 0 and D >= 100), "--distinct-frames must be a multiple of 50 and at least 100"
     n_gen = min(F, D + 3)
@@ -102,8 +109,10 @@ def main():
                 lm.close()
             return dt, poses, accepted, stage
 
-        def lockstep(frames):
+        def lockstep(frames, batched_history=False):
             kw = dict(refresh_threads=args.refresh_threads) if args.refresh_threads else {}
+            if batched_history:
+                kw["batched_history"] = True
             lb = Laser_mapping_batch(S, scan_points=N, **kw, **args_map)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -119,27 +128,49 @@ def main():
             lb.close()
             return dt, [np.stack(p) for p in poses], accepted, stage, threads
 
-        one_by_one(min(6, F))  # warm-up: code objects load lazily, the ICP kernels first run on frame 3
-        lockstep(min(6, F))
-        t_a, t_b = [], []
+        run = {"one_by_one": one_by_one, "lockstep": lockstep, "lockstep_batched": lambda frames: lockstep(frames, True)}
+        for r in routes:
+            run[r](min(6, F))  # warm-up: code objects load lazily, the ICP kernels first run on frame 3
+        times, last = {r: [] for r in routes}, {}
         for _ in range(args.repeats):
-            a = one_by_one(F)
-            b = lockstep(F)
-            t_a.append(a[0])
-            t_b.append(b[0])
-        differing = sum(0 if np.array_equal(a[1][s].view(np.uint64), b[1][s].view(np.uint64)) else 1 for s in range(S))
+            for r in routes:
+                last[r] = run[r](F)
+                times[r].append(last[r][0])
         n = S * F
-        line = {
-            "metric": "frames_per_s", "sequences": S, "frames_per_sequence": F, "scan_points": N,
-            "one_by_one": {"frames_per_s": round(n / min(t_a), 1), "all_repeats": [round(n / t, 1) for t in t_a], "accepted": a[2],
-                           "ms_per_frame_by_stage": dict(zip(("extract_register", "history_add", "match_buffer_refresh"),
-                                                             [round(1e3 * float(v) / n, 4) for v in a[3][:3]]))},
-            "lockstep": {"frames_per_s": round(n / min(t_b), 1), "all_repeats": [round(n / t, 1) for t in t_b], "accepted": b[2], "refresh_threads": b[4],
-                         "ms_per_step_wall": {"extract_register": round(1e3 * float(b[3][0]) / F, 4), "history_add_and_refresh": round(1e3 * float(b[3][4]) / F, 4)},
-                         "ms_per_frame_thread_time": {"history_add": round(1e3 * float(b[3][1]) / n, 4), "match_buffer_refresh": round(1e3 * float(b[3][2]) / n, 4)}},
-            "lockstep_over_one_by_one": round(min(t_a) / min(t_b), 3),
-            "sequences_with_differing_poses": differing,
-        }
+
+        def differing(x, y):
+            return sum(0 if np.array_equal(last[x][1][s].view(np.uint64), last[y][1][s].view(np.uint64)) else 1 for s in range(S))
+
+        def rate(r):
+            return {"frames_per_s": round(n / min(times[r]), 1), "all_repeats": [round(n / t, 1) for t in times[r]], "accepted": last[r][2]}
+
+        def wall(st):
+            return {"extract_register": round(1e3 * float(st[0]) / F, 4), "history_add_and_refresh": round(1e3 * float(st[4]) / F, 4)}
+
+        line = {"metric": "frames_per_s", "sequences": S, "frames_per_sequence": F, "scan_points": N}
+        if "one_by_one" in routes:
+            line["one_by_one"] = dict(rate("one_by_one"), ms_per_frame_by_stage=dict(zip(("extract_register", "history_add", "match_buffer_refresh"),
+                                                                                       [round(1e3 * float(v) / n, 4) for v in last["one_by_one"][3][:3]])))
+        if "lockstep" in routes:
+            st = last["lockstep"][3]
+            line["lockstep"] = dict(rate("lockstep"), refresh_threads=last["lockstep"][4], ms_per_step_wall=wall(st),
+                                    ms_per_frame_thread_time={"history_add": round(1e3 * float(st[1]) / n, 4), "match_buffer_refresh": round(1e3 * float(st[2]) / n, 4)})
+        if "one_by_one" in routes and "lockstep" in routes:
+            line["lockstep_over_one_by_one"] = round(min(times["one_by_one"]) / min(times["lockstep"]), 3)
+            line["sequences_with_differing_poses"] = differing("one_by_one", "lockstep")
+        if "lockstep_batched" in routes:
+            st = last["lockstep_batched"][3]
+            line["lockstep_batched"] = dict(rate("lockstep_batched"), ms_per_step_wall=wall(st),
+                                            ms_per_step_by_stage={"history_add": round(1e3 * float(st[1]) / F, 4), "match_buffer_refresh": round(1e3 * float(st[2]) / F, 4)})
+            if "lockstep" in routes:
+                line["lockstep_batched_over_lockstep"] = round(min(times["lockstep"]) / min(times["lockstep_batched"]), 3)
+            if "one_by_one" in routes:
+                line["lockstep_batched_over_one_by_one"] = round(min(times["one_by_one"]) / min(times["lockstep_batched"]), 3)
+            others = [r for r in ("one_by_one", "lockstep") if r in routes]
+            if others:  # sequences whose poses differ in any bit from EITHER other route
+                line["lockstep_batched_sequences_with_differing_poses"] = sum(
+                    1 if any(not np.array_equal(last["lockstep_batched"][1][s].view(np.uint64), last[r][1][s].view(np.uint64)) for r in others) else 0
+                    for s in range(S))
         print(json.dumps(line), flush=True)
         lines.append(line)
     if args.out:

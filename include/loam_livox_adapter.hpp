@@ -592,6 +592,64 @@ class History_buffer {
 };
 
 // ------------------------------------------------------------------------------------------------------------
+// The history match buffers of n_sequences Laser_mapping instances advanced in lock step, in one handle (ll_history_batch_*):
+// slot s behaves as a History_buffer of its own -- add-frame rule with the gate pose, FIFO, refresh into maps[s] -- while one
+// add() and one refresh() serve all slots with a fixed number of launches and host waits.  active: n_sequences flags or nullptr
+// (all); an inactive slot is neither read nor changed.  poses / gate_poses: n_sequences x {qx,qy,qz,qw,tx,ty,tz}, the registered
+// poses and the poses before the registration (nullptr: the registered poses gate).
+class History_batch {
+   public:
+    History_batch(int n_sequences, int maximum_history_size, int max_points_per_frame, float line_res, float plane_res, int device = 0)
+        : n_(n_sequences)
+    {
+        runtime_hints();
+        check(ll_history_batch_create(device, n_sequences, maximum_history_size, max_points_per_frame, line_res, plane_res, &h_),
+              "ll_history_batch_create");
+    }
+    ~History_batch()
+    {
+        if (h_) ll_history_batch_destroy(h_);
+    }
+    History_batch(const History_batch &) = delete;
+    History_batch &operator=(const History_batch &) = delete;
+
+    // slot s takes scan s of the extractor; added (optional): n_sequences flags, 1 where the frame was pushed
+    void add(ll_fe *fe, const double *poses, const double *gate_poses = nullptr, const int32_t *active = nullptr,
+             double history_add_t_step = 0.0, double history_add_angle_step = 0.0, int32_t *added = nullptr)
+    {
+        check(ll_history_batch_add_fe(h_, fe, active, poses, gate_poses, history_add_t_step, history_add_angle_step, added), "ll_history_batch_add_fe");
+    }
+    // slot s takes cloud s of the two filters (the down-sampled stacks of the last enqueue_fe_maps with filters)
+    void add(ll_voxel *vox_corner, ll_voxel *vox_surf, const double *poses, const double *gate_poses = nullptr, const int32_t *active = nullptr,
+             double history_add_t_step = 0.0, double history_add_angle_step = 0.0, int32_t *added = nullptr)
+    {
+        check(ll_history_batch_add_voxel(h_, vox_corner, vox_surf, active, poses, gate_poses, history_add_t_step, history_add_angle_step, added),
+              "ll_history_batch_add_voxel");
+    }
+    // update_buff_for_matching() of every active slot: new search grids of both kinds in maps[s]
+    void refresh(ll_map *const *maps, const int32_t *active = nullptr, int64_t *n_corner = nullptr, int64_t *n_surf = nullptr)
+    {
+        check(ll_history_batch_refresh(h_, maps, active, n_corner, n_surf), "ll_history_batch_refresh");
+    }
+    template <class Cloud>
+    void map_cloud(int sequence, int kind, Cloud &out)
+    {
+        const int64_t n = ll_history_batch_map_cloud(h_, sequence, kind, nullptr, 0);
+        if (n < 0) check(-1, "ll_history_batch_map_cloud");
+        std::vector<float> v((size_t)n * 4);
+        if (n > 0 && ll_history_batch_map_cloud(h_, sequence, kind, v.data(), n) < 0) check(-1, "ll_history_batch_map_cloud");
+        xyzi_to_cloud(v.data(), (int)n, out);
+    }
+    int size(int sequence) const { return ll_history_batch_size(h_, sequence); }
+    int n_sequences() const { return n_; }
+    ll_history_batch *handle() { return h_; }
+
+   private:
+    ll_history_batch *h_ = nullptr;
+    int n_ = 0;
+};
+
+// ------------------------------------------------------------------------------------------------------------
 // Points_cloud_map<float> (cell_map_keyframe.hpp:477-790) with the cell statistics and key-frame descriptors the loop
 // detection reads (determine_feature :436-473, Maps_keyframe::analyze :1385-1493), resident on the device.
 class Points_cloud_map {

@@ -389,6 +389,43 @@ int64_t ll_history_map_cloud(ll_history *h, int32_t kind, float *xyzi, int64_t c
 int ll_history_map_cloud_device(ll_history *h, int32_t kind, const float **dev_xyzi, int64_t *n_points);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Match buffers of S sequences in one handle (the lock-step mapping loop: one registration serves S sequences, slot s against
+ * maps[s]).  Per slot the semantics are exactly those of ll_history_add_voxel / ll_history_add_fe with
+ * ll_history_set_gate_pose, and of ll_history_refresh: the add-frame rule with the gate pose, the FIFO of
+ * maximum_history_size frames, the oldest-first concatenation, VoxelGrid at line_res / plane_res, and a new snapshot of both
+ * kinds published into maps[s] (ll_map_generation + 1 per kind).  What differs is the cost: an add and a refresh are each ONE
+ * fixed chain of launches and host waits over all slots, whatever S is.
+ *   active      [S] or NULL (= all slots).  An inactive slot is not read and not changed: its frames, its last-push pose, its
+ *               match-buffer clouds and its map stay as they were, and added[s] comes back 0.
+ *   poses7      [S][7] the registered poses the clouds are moved with; gate_poses7 [S][7] the poses BEFORE the registration
+ *               (NULL: poses7 gates, as without ll_history_set_gate_pose)
+ *   maps        [S]; maps[s] may be NULL only for an inactive slot, and no map may appear in two active slots
+ * Slot s takes cloud s of the two filters (what ll_reg_enqueue_fe_downsampled_maps left there) or scan s of the extractor.
+ * Refused before anything is enqueued, with the handle still usable: null handles or poses, handles on different devices,
+ * filters / an extractor with fewer slots than n_sequences, a frame larger than max_points_per_frame, a map twice; at create,
+ * n_sequences * maximum_history_size * max_points_per_frame >= 2^31 (the sorts index with 32 bits).
+ * The search grids of one refresh share pooled storage that lives as long as any snapshot built in it is published or pinned
+ * by a registration in flight: a registration enqueued before a refresh and collected after it reads the old snapshots.
+ * ll_map_to_f16 refuses such a snapshot.  There are no cell maps on this handle. */
+typedef struct ll_history_batch ll_history_batch;
+int ll_history_batch_create(int32_t device, int32_t n_sequences, int32_t maximum_history_size, int32_t max_points_per_frame,
+                            float line_res, float plane_res, ll_history_batch **out);
+void ll_history_batch_destroy(ll_history_batch *h);
+int ll_history_batch_add_voxel(ll_history_batch *h, ll_voxel *vox_corner, ll_voxel *vox_surf, const int32_t *active,
+                               const double *poses7, const double *gate_poses7, double history_add_t_step,
+                               double history_add_angle_step, int32_t *added);
+int ll_history_batch_add_fe(ll_history_batch *h, ll_fe *fe, const int32_t *active, const double *poses7, const double *gate_poses7,
+                            double history_add_t_step, double history_add_angle_step, int32_t *added);
+int ll_history_batch_refresh(ll_history_batch *h, ll_map *const *maps, const int32_t *active, int64_t *n_map_corner,
+                             int64_t *n_map_surf);
+int32_t ll_history_batch_size(const ll_history_batch *h, int32_t sequence);
+int64_t ll_history_batch_map_cloud(ll_history_batch *h, int32_t sequence, int32_t kind, float *xyzi, int64_t capacity_points);
+/* Host arithmetic only (no device needed): the geometry ll_map_upload and both refreshes give the search grid over the bounding
+ * box {min x, y, z, max x, y, z} of a cloud's finite points (min > max: no finite point) with cells of cell_size metres.  The
+ * cell grows by 1.5 x until the dense table has at most 2^27 cells. */
+int ll_map_grid_geometry(const float bbox_min_max[6], float cell_size, int32_t dims[3], float *cell, float *slack);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Match buffer, cell ("cube") mode  (m_matching_mode == 1, the default in code,
  * laser_mapping.hpp:689).  Device-resident stand-in for
  *   Points_cloud_map<float> m_pt_cell_map_corners / m_pt_cell_map_planes   laser_mapping.hpp:274-275, 617-624

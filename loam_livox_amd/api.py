@@ -426,6 +426,86 @@ class History_buffer:
         return torch.as_tensor(_DeviceView(p.value, n.value), device=f"cuda:{self.device}").clone()
 
 
+class History_buffer_batch:
+    """The match buffers of n_sequences sequences in one handle (include/loam_livox_hip.h, ll_history_batch_*): slot s is a
+    History_buffer in every result -- add rule with the gate pose, FIFO, concatenation, VoxelGrid, the snapshots published into
+    maps[s] -- while one add_voxel / add_fe and one refresh serve all slots with a fixed number of launches and host waits."""
+
+    def __init__(self, n_sequences: int, maximum_history_size: int = 100, max_points_per_frame: int = 24000, line_res: float = 0.1,
+                 plane_res: float = 0.4, device: int = 0):
+        self.L = capi.load()
+        self.h = C.c_void_p()
+        self.device, self.n_sequences = device, int(n_sequences)
+        check(self.L.ll_history_batch_create(device, n_sequences, maximum_history_size, max_points_per_frame, line_res, plane_res,
+                                             C.byref(self.h)), "ll_history_batch_create")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.ll_history_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _slots(self, active, poses, gate_poses):
+        S = self.n_sequences
+        act = None if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.int32).reshape(S)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(S, 7)
+        gate = None if gate_poses is None else np.ascontiguousarray(gate_poses, np.float64).reshape(S, 7)
+        return act, poses, gate, np.zeros(S, np.int32)
+
+    def add_voxel(self, vox_corner: "VoxelGrid", vox_surf: "VoxelGrid", poses, gate_poses=None, active=None, history_add_t_step: float = 0.0,
+                  history_add_angle_step: float = 0.0) -> np.ndarray:
+        """slot s takes cloud s of the two filters; returns the added flags [S] (bool)"""
+        act, poses, gate, added = self._slots(active, poses, gate_poses)
+        check(self.L.ll_history_batch_add_voxel(self.h, vox_corner.h, vox_surf.h, ptr(act), ptr(poses), ptr(gate), history_add_t_step,
+                                                history_add_angle_step, ptr(added)), "ll_history_batch_add_voxel")
+        return added.astype(bool)
+
+    def add_fe(self, fe: "Livox_laser", poses, gate_poses=None, active=None, history_add_t_step: float = 0.0,
+               history_add_angle_step: float = 0.0) -> np.ndarray:
+        """slot s takes the features selected for scan s of the extractor; returns the added flags [S] (bool)"""
+        act, poses, gate, added = self._slots(active, poses, gate_poses)
+        check(self.L.ll_history_batch_add_fe(self.h, fe.h, ptr(act), ptr(poses), ptr(gate), history_add_t_step, history_add_angle_step,
+                                             ptr(added)), "ll_history_batch_add_fe")
+        return added.astype(bool)
+
+    def refresh(self, maps, active=None):
+        """maps: n_sequences Map_buffer (None allowed for an inactive slot).  Returns (n_corner [S], n_surf [S]) of the match buffers."""
+        S = self.n_sequences
+        if len(maps) != S:
+            raise ValueError(f"{len(maps)} maps for {S} sequences")
+        act = None if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.int32).reshape(S)
+        arr = (C.c_void_p * S)(*[None if m is None else m.h for m in maps])
+        nc, ns = np.zeros(S, np.int64), np.zeros(S, np.int64)
+        check(self.L.ll_history_batch_refresh(self.h, arr, ptr(act), ptr(nc), ptr(ns)), "ll_history_batch_refresh")
+        return nc, ns
+
+    def size(self, sequence: int) -> int:
+        return int(self.L.ll_history_batch_size(self.h, sequence))
+
+    def map_cloud(self, sequence: int, kind: int) -> np.ndarray:
+        n = self.L.ll_history_batch_map_cloud(self.h, sequence, kind, None, 0)
+        if n < 0:
+            check(-1, "ll_history_batch_map_cloud")
+        out = np.zeros((n, 4), np.float32)
+        if n > 0:
+            check(min(0, self.L.ll_history_batch_map_cloud(self.h, sequence, kind, ptr(out), n)), "ll_history_batch_map_cloud")
+        return out
+
+
+def map_grid_geometry(bbox_min_max, cell_size: float):
+    """ll_map_grid_geometry (host arithmetic): ((nx, ny, nz), cell, slack) of the search grid over a bounding box"""
+    bb = np.ascontiguousarray(bbox_min_max, np.float32).reshape(6)
+    dims = np.zeros(3, np.int32)
+    h, slack = C.c_float(0), C.c_float(0)
+    check(capi.load().ll_map_grid_geometry(ptr(bb), cell_size, ptr(dims), C.byref(h), C.byref(slack)), "ll_map_grid_geometry")
+    return (int(dims[0]), int(dims[1]), int(dims[2])), h.value, slack.value
+
+
 class _DeviceView:
     """(n, 4) float32 at a raw device address, for torch.as_tensor (zero copy)"""
 

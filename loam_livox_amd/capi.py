@@ -117,6 +117,14 @@ SYMBOLS = {
     "ll_history_map_cloud": (_i64, [_vp, _i32, _vp, _i64]),
     "ll_history_set_gate_pose": (_i32, [_vp, _vp]),
     "ll_history_map_cloud_device": (_i32, [_vp, _i32, _vp, _vp]),
+    "ll_history_batch_create": (_i32, [_i32, _i32, _i32, _i32, _f, _f, C.POINTER(_vp)]),
+    "ll_history_batch_destroy": (None, [_vp]),
+    "ll_history_batch_add_voxel": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp]),
+    "ll_history_batch_add_fe": (_i32, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp]),
+    "ll_history_batch_refresh": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "ll_history_batch_size": (_i32, [_vp, _i32]),
+    "ll_history_batch_map_cloud": (_i64, [_vp, _i32, _i32, _vp, _i64]),
+    "ll_map_grid_geometry": (_i32, [_vp, _f, _vp, _vp, _vp]),
     "ll_cellmap_create": (_i32, [_i32, _i64, C.c_float, _i32, _vp]),
     "ll_cellmap_destroy": (None, [_vp]),
     "ll_cellmap_reserve": (_i32, [_vp, _i64]),

@@ -93,6 +93,8 @@ struct MapKind {
 // builds the grid for `n` device-resident raw points (stride floats apart); fills mk. Returns 0 or a HIP error.
 int map_build(MapKind &mk, const float *d_raw, int stride, int64_t n, float cell, hipStream_t s, const char **err);
 void map_free(MapKind &mk);
+// dimensions, origin, cell size and slack of the grid over a bounding box (host arithmetic; fills the geometry fields of g only)
+void map_grid_geometry(const float mm[6], float cell, Grid &g);
 // replaces the fp32 records of a built map by fp16-point records (BASELINE config C5); returns 0 or -1 with *err set
 int map_to_f16(MapKind &mk, hipStream_t s, const char **err);
 // dequantised coordinates of an fp16-point map in ORIGINAL index order (d_out: n_valid... n points x 3 floats, NaN where dropped)

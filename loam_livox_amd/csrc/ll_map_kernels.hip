@@ -110,24 +110,12 @@ static int grow(T **p, size_t *cap, size_t need, const char **err)
     return 0;
 }
 
-int map_build(MapKind &mk, const float *d_raw, int stride, int64_t n, float cell, hipStream_t s, const char **err)
+// Geometry of the search grid over the bounding box mm = {min x, y, z, max x, y, z} of a cloud's finite points (min > max: it has none)
+// with cells of `cell` metres: dimensions, origin, cell size, slack.  The one place this arithmetic lives: map_build and the batched
+// match-buffer refresh (ll_history_batch_refresh) both call it.
+void map_grid_geometry(const float mm_in[6], float cell, Grid &g)
 {
-    if (mk.pts16) (void)hipFree(mk.pts16);  // a previous fp16 conversion does not survive a rebuild
-    if (mk.perm) (void)hipFree(mk.perm);
-    mk.pts16 = nullptr;
-    mk.perm = nullptr;
-    mk.n = n;
-    mk.n_valid = 0;
-    if (!mk.b_mm) HIPCHK(hipMalloc((void **)&mk.b_mm, 6 * sizeof(float)));
-    float *d_mm = mk.b_mm;
-    const float init[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    HIPCHK(hipMemcpyAsync(d_mm, init, sizeof(init), hipMemcpyHostToDevice, s));
-    if (n > 0)  // (a match buffer of a few thousand points: 1024 mostly idle workgroups contending on six atomics cost 12 us per rebuild)
-        hipLaunchKernelGGL(aabb_kernel, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0, s, d_raw, stride, n, d_mm, d_mm + 3);
-    float mm[6];
-    HIPCHK(hipMemcpyAsync(mm, d_mm, sizeof(mm), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    Grid g{};
+    float mm[6] = {mm_in[0], mm_in[1], mm_in[2], mm_in[3], mm_in[4], mm_in[5]};
     if (!(mm[0] <= mm[3])) {  // no finite point
         mm[0] = mm[1] = mm[2] = 0.f;
         mm[3] = mm[4] = mm[5] = 0.f;
@@ -154,6 +142,27 @@ int map_build(MapKind &mk, const float *d_raw, int stride, int64_t n, float cell
                       fmaxf(mm[3] - mm[0], fmaxf(mm[4] - mm[1], mm[5] - mm[2]));
     g.slack = 1e-3f * h + 2e-6f * ext;
     g.guard = 0.0f;
+}
+
+int map_build(MapKind &mk, const float *d_raw, int stride, int64_t n, float cell, hipStream_t s, const char **err)
+{
+    if (mk.pts16) (void)hipFree(mk.pts16);  // a previous fp16 conversion does not survive a rebuild
+    if (mk.perm) (void)hipFree(mk.perm);
+    mk.pts16 = nullptr;
+    mk.perm = nullptr;
+    mk.n = n;
+    mk.n_valid = 0;
+    if (!mk.b_mm) HIPCHK(hipMalloc((void **)&mk.b_mm, 6 * sizeof(float)));
+    float *d_mm = mk.b_mm;
+    const float init[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    HIPCHK(hipMemcpyAsync(d_mm, init, sizeof(init), hipMemcpyHostToDevice, s));
+    if (n > 0)  // (a match buffer of a few thousand points: 1024 mostly idle workgroups contending on six atomics cost 12 us per rebuild)
+        hipLaunchKernelGGL(aabb_kernel, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0, s, d_raw, stride, n, d_mm, d_mm + 3);
+    float mm[6];
+    HIPCHK(hipMemcpyAsync(mm, d_mm, sizeof(mm), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    Grid g{};
+    map_grid_geometry(mm, cell, g);
     const size_t ncell = (size_t)g.nx * g.ny * g.nz;
     mk.ncell = ncell;
 

@@ -28,5 +28,8 @@ int voxel_alloc(VoxelDev &v, int max_clouds, int stride, const char **err);
 void voxel_free(VoxelDev &v);
 int voxel_filter(VoxelDev &v, const float4 *in, const int *n, int in_stride, int n_clouds, const float leaf[3], hipStream_t s,
                  const char **err);
+// the same with a host-side bound on every n[b]: selects the one-workgroup filter by the clouds' sizes instead of by the stride
+int voxel_filter_bounded(VoxelDev &v, const float4 *in, const int *n, int in_stride, int n_clouds, const float leaf[3], int max_n, hipStream_t s,
+                         const char **err);
 
 }  // namespace ll

@@ -478,6 +478,16 @@ void voxel_free(VoxelDev &v)
 int voxel_filter(VoxelDev &v, const float4 *in, const int *n, int in_stride, int n_clouds, const float leaf[3], hipStream_t s,
                  const char **err)
 {
+    return voxel_filter_bounded(v, in, n, in_stride, n_clouds, leaf, in_stride, s, err);
+}
+
+// max_n: what the host knows no n[b] exceeds (in_stride when it knows nothing).  The path is chosen by it, not by the stride: clouds of
+// different lengths that share a wide stride (the concatenations of a batched match-buffer refresh) still take the one-workgroup
+// filter, each in the instantiation its own size selects -- the one a call with that cloud alone would run.
+int voxel_filter_bounded(VoxelDev &v, const float4 *in, const int *n, int in_stride, int n_clouds, const float leaf[3], int max_n, hipStream_t s,
+                         const char **err)
+{
+    if (max_n > in_stride || max_n < 0) max_n = in_stride;
     if (n_clouds < 1 || n_clouds > v.max_clouds || in_stride > v.stride || in_stride < 1) {
         *err = "cloud count or stride exceeds the capacity of the voxel filter";
         return -1;
@@ -491,13 +501,13 @@ int voxel_filter(VoxelDev &v, const float4 *in, const int *n, int in_stride, int
     // Any number of clouds: a batch of 2 048 voxel-filtered scans is 8 rounds of 70 us for the surface clouds and one of 19 us for the
     // 300-point corner clouds, where the multi-kernel pipeline sorts the whole [clouds][stride] index space -- 49 M mostly padding
     // entries for the corner clouds (round 4 sent only batches of <= 16 clouds here)
-    if (v.block_path && in_stride <= VB_THREADS * 24) {
+    if (v.block_path && max_n <= VB_THREADS * 24) {
         hipLaunchKernelGGL(vox_block_kernel<4>, dim3(n_clouds), dim3(VB_THREADS), 0, s, in, n, in_stride, inv[0], inv[1], inv[2], v.out, v.n_out, v.status, -1,
                            VB_THREADS * 4);
-        if (in_stride > VB_THREADS * 4)
+        if (max_n > VB_THREADS * 4)
             hipLaunchKernelGGL(vox_block_kernel<8>, dim3(n_clouds), dim3(VB_THREADS), 0, s, in, n, in_stride, inv[0], inv[1], inv[2], v.out, v.n_out, v.status,
                                VB_THREADS * 4, VB_THREADS * 8);
-        if (in_stride > VB_THREADS * 8)
+        if (max_n > VB_THREADS * 8)
             hipLaunchKernelGGL(vox_block_kernel<24>, dim3(n_clouds), dim3(VB_THREADS), 0, s, in, n, in_stride, inv[0], inv[1], inv[2], v.out, v.n_out, v.status,
                                VB_THREADS * 8, VB_THREADS * 24);
         VXCHK(hipGetLastError());

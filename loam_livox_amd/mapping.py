@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .api import History_buffer, Livox_laser, Map_buffer, Point_cloud_registration, Spinning_laser, VoxelGrid
+from .api import History_buffer, History_buffer_batch, Livox_laser, Map_buffer, Point_cloud_registration, Spinning_laser, VoxelGrid
 
 
 class Laser_mapping:
@@ -262,6 +262,19 @@ class Laser_mapping:
         return 1
 
 
+class _History_slot:
+    """slot s of a History_buffer_batch, read the way a History_buffer is: len() and map_cloud(kind)"""
+
+    def __init__(self, batch: "History_buffer_batch", sequence: int):
+        self.batch, self.sequence = batch, sequence
+
+    def __len__(self):
+        return self.batch.size(self.sequence)
+
+    def map_cloud(self, kind: int) -> np.ndarray:
+        return self.batch.map_cloud(self.sequence, kind)
+
+
 class Laser_mapping_batch:
     """n_sequences independent Laser_mapping loops advanced in lock step (BASELINE config C4: batched offline map building from
     independent sub-sequences with local map growth).  Frame k of all sequences is ONE batch: one batched extraction, one VoxelGrid
@@ -273,9 +286,13 @@ class Laser_mapping_batch:
     Per sequence this is Laser_mapping._process_new_scan line for line -- the frame index handed to the gate, the gate pose of the
     add rule, the repeat of an aborted grouped solve on one workgroup -- and gives the same bits as a Laser_mapping run alone on that
     sequence.  Takes the arguments of Laser_mapping; Livox scans in history mode only: lidar_type other than "livox", matching_mode,
-    loop_closure_if_enable and keep_cell_maps raise ValueError."""
+    loop_closure_if_enable and keep_cell_maps raise ValueError.
 
-    def __init__(self, n_sequences: int, refresh_threads: int | None = None, **kw):
+    batched_history=True keeps all histories in ONE History_buffer_batch: the slots a step accepted go through one add and one
+    refresh, whose launches and host waits do not grow with n_sequences (no thread pool, no per-sequence handles; refresh_threads is
+    ignored).  Same bits per sequence; histories[s] is then a view of slot s that offers len() and map_cloud(kind)."""
+
+    def __init__(self, n_sequences: int, refresh_threads: int | None = None, batched_history: bool = False, **kw):
         import inspect
         sig = inspect.signature(Laser_mapping.__init__)
         unknown = set(kw) - set(sig.parameters)
@@ -304,7 +321,13 @@ class Laser_mapping_batch:
         self.reg = Point_cloud_registration(max_scans=S, max_features=scan_points, device=device)
         self.vox = (VoxelGrid(scan_points, S, device=device), VoxelGrid(scan_points, S, device=device))
         self.maps = [Map_buffer(device=device) for _ in range(S)]
-        self.histories = [History_buffer(a["maximum_history_size"], scan_points, a["line_res"], a["plane_res"], device=device) for _ in range(S)]
+        self.batched_history = bool(batched_history)
+        if self.batched_history:
+            self.history_batch = History_buffer_batch(S, a["maximum_history_size"], scan_points, a["line_res"], a["plane_res"], device=device)
+            self.histories = [_History_slot(self.history_batch, s) for s in range(S)]
+        else:
+            self.history_batch = None
+            self.histories = [History_buffer(a["maximum_history_size"], scan_points, a["line_res"], a["plane_res"], device=device) for _ in range(S)]
         self.line_res, self.plane_res = a["line_res"], a["plane_res"]
         self.m_if_input_downsample_mode = a["input_downsample_mode"]
         self.history_add_t_step, self.history_add_angle_step = a["history_add_t_step"], a["history_add_angle_step"]
@@ -324,7 +347,7 @@ class Laser_mapping_batch:
         # wall time of the add + refresh phase
         self.stage_s = np.zeros(5)
         self._pool = None
-        if self.refresh_threads > 1:
+        if self.refresh_threads > 1 and not self.batched_history:
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(max_workers=self.refresh_threads)
 
@@ -332,7 +355,7 @@ class Laser_mapping_batch:
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
-        for h in [self.fe, self.reg, self.vox[0], self.vox[1]] + self.maps + self.histories:
+        for h in [self.fe, self.reg, self.vox[0], self.vox[1]] + self.maps + ([self.history_batch] if self.batched_history else self.histories):
             h.close()
 
     def _upload(self, scans, stamps, active):
@@ -364,6 +387,27 @@ class Laser_mapping_batch:
         t1 = time.perf_counter()
         sizes = h.refresh(self.maps[s])
         return s, sizes, t1 - t0, time.perf_counter() - t1
+
+    def _add_and_refresh_batched(self, jobs):
+        """the accepted slots of a step through one add and one refresh; rejected and idle slots are inactive"""
+        import time
+        S = self.n_sequences
+        t0 = time.perf_counter()
+        on = np.zeros(S, bool)
+        gate, new = self.poses.copy(), self.poses.copy()
+        for s, pose_before, pose_new in jobs:
+            on[s] = True
+            gate[s], new[s] = pose_before, pose_new  # m_q_w_curr is still the pre-registration pose at LM:1439-1451
+        hb = self.history_batch
+        if self.m_if_input_downsample_mode:
+            hb.add_voxel(self.vox[0], self.vox[1], new, gate, on, self.history_add_t_step, self.history_add_angle_step)
+        else:
+            hb.add_fe(self.fe, new, gate, on, self.history_add_t_step, self.history_add_angle_step)
+        t1 = time.perf_counter()
+        nc, ns = hb.refresh([self.maps[s] if on[s] else None for s in range(S)], on)
+        t2 = time.perf_counter()
+        k = max(len(jobs), 1)
+        return [(s, (int(nc[s]), int(ns[s])), (t1 - t0) / k, (t2 - t1) / k) for s, _, _ in jobs]
 
     def process_new_scans(self, scans, time_stamps=None) -> np.ndarray:
         """One step of every sequence: scans[s] is sequence s's next scan, or None when it has none this step.  Returns an int array:
@@ -409,7 +453,9 @@ class Laser_mapping_batch:
             out[s] = 1 if res[s] else 0
             if res[s]:  # :1413-1416
                 jobs.append((s, self.poses[s].copy(), pc[s].copy()))
-        if self._pool is not None and len(jobs) > 1:
+        if self.batched_history:
+            done = self._add_and_refresh_batched(jobs) if jobs else []
+        elif self._pool is not None and len(jobs) > 1:
             done = list(self._pool.map(lambda j: self._add_and_refresh(*j), jobs))
         else:
             done = [self._add_and_refresh(*j) for j in jobs]

@@ -1,29 +1,7 @@
 // ll_spin_api.hip -- host side of the ll_spin_* entry points of include/loam_livox_hip.h (spinning-lidar feature
 // extraction, hku-mars/loam_livox source/laser_feature_extractor.hpp:393-787).  Device memory, launch order and the
 // host-libm resolve of ambiguous atanf / atan2f decisions; the arithmetic runs in ll_spin_kernels.hip.
-#include <hip/hip_runtime.h>
-
-#include <math.h>
-#include <string.h>
-
-#include <vector>
-
-#include "../../include/loam_livox_hip.h"
-#include "ll_spin.h"
-#include "ll_voxel.h"
-
-namespace ll {
-int api_error(const char *where, const char *what);
-int api_check_device(int device);
-}  // namespace ll
-
-using namespace ll;
-
-#define SC(call)                                                                 \
-    do {                                                                         \
-        hipError_t e_ = (call);                                                  \
-        if (e_ != hipSuccess) return api_error(#call, hipGetErrorString(e_));    \
-    } while (0)
+#include "ll_api_internal.h"
 
 struct ll_spin {
     ll_spin_params prm;
@@ -57,13 +35,6 @@ extern "C" void ll_spin_default_params(ll_spin_params *p)
     p->max_line_points = 8192;
 }
 
-template <typename T>
-static int dm(T **p, size_t count)
-{
-    SC(hipMalloc((void **)p, (count > 0 ? count : 1) * sizeof(T)));
-    return 0;
-}
-
 static int spin_create_impl(const ll_spin_params *p, ll_spin *h)
 {
     h->prm = *p;
@@ -80,35 +51,35 @@ static int spin_create_impl(const ll_spin_params *p, ll_spin *h)
     d.line_cap = p->max_line_points;
     d.ambig_cap = (int)(SP / 16 > 4096 ? SP / 16 : 4096);
     d.thres = p->minimum_range;
-    if (dm(&d.in, SP) || dm(&d.n_in, S) || dm(&d.ori_se, S) || dm(&d.raw_sid, SP) || dm(&d.raw_ori, SP) || dm(&d.n_ambig, 1) ||
-        dm(&d.ambig, d.ambig_cap) || dm(&d.ambig_p, d.ambig_cap) || dm(&d.ambig_sid, d.ambig_cap) || dm(&d.ambig_ori, d.ambig_cap) || dm(&d.line_off, (size_t)S * (SPIN_MAX_LINES + 1)) || dm(&d.full, SP) || dm(&d.full_src, SP) ||
-        dm(&d.curv, SP) || dm(&d.flags, SP) || dm(&d.label, SP) || dm(&d.order, SP) || dm(&d.sharp, SP) || dm(&d.less_sharp, SP) ||
-        dm(&d.flat, SP) || dm(&d.lf_pos, SP) || dm(&d.vox_in, (size_t)S * h->n_vlines * p->max_line_points) ||
-        dm(&d.vox_n, (size_t)S * h->n_vlines) || dm(&d.less_flat, SP) || dm(&d.cnt, (size_t)S * SPIN_NCNT))
+    if (dmalloc(&d.in, SP) || dmalloc(&d.n_in, S) || dmalloc(&d.ori_se, S) || dmalloc(&d.raw_sid, SP) || dmalloc(&d.raw_ori, SP) || dmalloc(&d.n_ambig, 1) ||
+        dmalloc(&d.ambig, d.ambig_cap) || dmalloc(&d.ambig_p, d.ambig_cap) || dmalloc(&d.ambig_sid, d.ambig_cap) || dmalloc(&d.ambig_ori, d.ambig_cap) || dmalloc(&d.line_off, (size_t)S * (SPIN_MAX_LINES + 1)) || dmalloc(&d.full, SP) || dmalloc(&d.full_src, SP) ||
+        dmalloc(&d.curv, SP) || dmalloc(&d.flags, SP) || dmalloc(&d.label, SP) || dmalloc(&d.order, SP) || dmalloc(&d.sharp, SP) || dmalloc(&d.less_sharp, SP) ||
+        dmalloc(&d.flat, SP) || dmalloc(&d.lf_pos, SP) || dmalloc(&d.vox_in, (size_t)S * h->n_vlines * p->max_line_points) ||
+        dmalloc(&d.vox_n, (size_t)S * h->n_vlines) || dmalloc(&d.less_flat, SP) || dmalloc(&d.cnt, (size_t)S * SPIN_NCNT))
         return -1;
     const char *err = nullptr;
-    if (voxel_alloc(h->vox, S * h->n_vlines, p->max_line_points, &err)) return api_error("ll_spin_create", err);
-    SC(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    if (voxel_alloc(h->vox, S * h->n_vlines, p->max_line_points, &err)) return set_err("ll_spin_create", err);
+    HC(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     // zeroed on the handle's own stream: a non-blocking stream is not ordered after the null stream, so a null-stream hipMemset could
     // still land after the first extraction's kernels and wipe the counts and line offsets they wrote
-    SC(hipMemsetAsync(d.n_in, 0, S * sizeof(int), h->stream));
-    SC(hipMemsetAsync(d.cnt, 0, (size_t)S * SPIN_NCNT * sizeof(int), h->stream));
-    SC(hipMemsetAsync(d.line_off, 0, (size_t)S * (SPIN_MAX_LINES + 1) * sizeof(int), h->stream));
-    SC(hipStreamSynchronize(h->stream));
-    for (auto &e : h->ev) SC(hipEventCreate(&e));
+    HC(hipMemsetAsync(d.n_in, 0, S * sizeof(int), h->stream));
+    HC(hipMemsetAsync(d.cnt, 0, (size_t)S * SPIN_NCNT * sizeof(int), h->stream));
+    HC(hipMemsetAsync(d.line_off, 0, (size_t)S * (SPIN_MAX_LINES + 1) * sizeof(int), h->stream));
+    HC(hipStreamSynchronize(h->stream));
+    for (auto &e : h->ev) HC(hipEventCreate(&e));
     h->h_n.assign(S, 0);
     return 0;
 }
 
 extern "C" int ll_spin_create(const ll_spin_params *p, ll_spin **out)
 {
-    if (!p || !out) return api_error("ll_spin_create", "null argument");
-    if (p->scan_line != 16 && p->scan_line != 64) return api_error("ll_spin_create", "only support velodyne with 16 or 64 scan line!");
+    if (!p || !out) return set_err("ll_spin_create", "null argument");
+    if (p->scan_line != 16 && p->scan_line != 64) return set_err("ll_spin_create", "only support velodyne with 16 or 64 scan line!");
     if (p->max_points < 1 || p->max_points > LL_SPIN_MAX_POINTS || p->max_scans < 1 || p->max_line_points < 1)
-        return api_error("ll_spin_create", "bad capacity (max_points must be in 1 .. 400000)");
-    if (!(p->plane_resolution > 0.f)) return api_error("ll_spin_create", "plane_resolution must be positive");
-    if ((size_t)p->max_scans * p->max_points >= 0x7fffffffull) return api_error("ll_spin_create", "max_scans * max_points must stay below 2^31");
-    if (api_check_device(p->device)) return -1;
+        return set_err("ll_spin_create", "bad capacity (max_points must be in 1 .. 400000)");
+    if (!(p->plane_resolution > 0.f)) return set_err("ll_spin_create", "plane_resolution must be positive");
+    if ((size_t)p->max_scans * p->max_points >= 0x7fffffffull) return set_err("ll_spin_create", "max_scans * max_points must stay below 2^31");
+    if (check_device(p->device)) return -1;
     ll_spin *h = new ll_spin();
     if (spin_create_impl(p, h)) {
         ll_spin_destroy(h);
@@ -144,14 +115,14 @@ static bool survives(const float *q, float thres)
 
 extern "C" int ll_spin_upload(ll_spin *h, int32_t first_scan, int32_t n_scans, const float *xyzi, const int32_t *n_points, int32_t stride_points)
 {
-    if (!h || (!xyzi && n_scans > 0) || !n_points) return api_error("ll_spin_upload", "null argument");
-    if (first_scan < 0 || n_scans < 0 || first_scan + n_scans > h->prm.max_scans) return api_error("ll_spin_upload", "scan slots out of range");
+    if (!h || (!xyzi && n_scans > 0) || !n_points) return set_err("ll_spin_upload", "null argument");
+    if (first_scan < 0 || n_scans < 0 || first_scan + n_scans > h->prm.max_scans) return set_err("ll_spin_upload", "scan slots out of range");
     for (int b = 0; b < n_scans; b++) {
-        if (n_points[b] < 0 || n_points[b] > stride_points) return api_error("ll_spin_upload", "n_points out of range");
-        if (n_points[b] > h->prm.max_points) return api_error("ll_spin_upload", "scan has more points than max_points");
+        if (n_points[b] < 0 || n_points[b] > stride_points) return set_err("ll_spin_upload", "n_points out of range");
+        if (n_points[b] > h->prm.max_points) return set_err("ll_spin_upload", "scan has more points than max_points");
     }
-    SC(hipSetDevice(h->prm.device));
-    SC(hipStreamSynchronize(h->stream));
+    HC(hipSetDevice(h->prm.device));
+    HC(hipStreamSynchronize(h->stream));
     const float thres = h->prm.minimum_range;
     std::vector<float2> se(n_scans);
     for (int b = 0; b < n_scans; b++) {
@@ -171,14 +142,14 @@ extern "C" int ll_spin_upload(ll_spin *h, int32_t first_scan, int32_t n_scans, c
         }
         se[b] = make_float2(startOri, endOri);
         if (n > 0)
-            SC(hipMemcpyAsync(h->d.in + (size_t)(first_scan + b) * h->d.stride, c, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+            HC(hipMemcpyAsync(h->d.in + (size_t)(first_scan + b) * h->d.stride, c, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
         h->h_n[first_scan + b] = n;
     }
     if (n_scans > 0) {
-        SC(hipMemcpyAsync(h->d.n_in + first_scan, n_points, n_scans * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        SC(hipMemcpyAsync(h->d.ori_se + first_scan, se.data(), n_scans * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+        HC(hipMemcpyAsync(h->d.n_in + first_scan, n_points, n_scans * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HC(hipMemcpyAsync(h->d.ori_se + first_scan, se.data(), n_scans * sizeof(float2), hipMemcpyHostToDevice, h->stream));
     }
-    SC(hipStreamSynchronize(h->stream));
+    HC(hipStreamSynchronize(h->stream));
     return 0;
 }
 
@@ -195,66 +166,66 @@ static int spin_run_rest(ll_spin *h, int n_scans)
     const int L = h->prm.scan_line;
     const int mn = max_n(h, n_scans);
     h->packed_n = 0;  // the packed corner stack no longer holds the handle's outputs
-    SC(hipEventRecord(h->ev[2], h->stream));
+    HC(hipEventRecord(h->ev[2], h->stream));
     spin_launch_lines(h->d, n_scans, L, h->stream);
-    SC(hipEventRecord(h->ev[3], h->stream));
+    HC(hipEventRecord(h->ev[3], h->stream));
     spin_launch_curv(h->d, n_scans, mn, h->stream);
-    SC(hipEventRecord(h->ev[4], h->stream));
+    HC(hipEventRecord(h->ev[4], h->stream));
     spin_launch_sort(h->d, n_scans, L, h->stream);
-    SC(hipEventRecord(h->ev[5], h->stream));
+    HC(hipEventRecord(h->ev[5], h->stream));
     spin_launch_select(h->d, n_scans, L, h->n_vlines, h->stream);
-    SC(hipEventRecord(h->ev[6], h->stream));
+    HC(hipEventRecord(h->ev[6], h->stream));
     const float leaf1 = h->prm.plane_resolution / 2;  // :192 setLeafSize(m_plane_resolution / 2, ...) in float
     const float leaf[3] = {leaf1, leaf1, leaf1};
     const char *err = nullptr;
     if (voxel_filter(h->vox, h->d.vox_in, h->d.vox_n, h->prm.max_line_points, n_scans * h->n_vlines, leaf, h->stream, &err))
-        return api_error("ll_spin_extract_batch", err);
+        return set_err("ll_spin_extract_batch", err);
     spin_launch_gather(h->d, h->vox.out, h->vox.n_out, h->vox.out_stride, n_scans, h->n_vlines, h->stream);
-    SC(hipEventRecord(h->ev[7], h->stream));
-    SC(hipGetLastError());
+    HC(hipEventRecord(h->ev[7], h->stream));
+    HC(hipGetLastError());
     return 0;
 }
 
 extern "C" int ll_spin_extract_batch(ll_spin *h, int32_t n_scans)
 {
-    if (!h) return api_error("ll_spin_extract_batch", "null handle");
-    if (n_scans < 1 || n_scans > h->prm.max_scans) return api_error("ll_spin_extract_batch", "n_scans out of range");
-    SC(hipSetDevice(h->prm.device));
-    SC(hipMemsetAsync(h->d.n_ambig, 0, sizeof(int), h->stream));
-    SC(hipEventRecord(h->ev[0], h->stream));
+    if (!h) return set_err("ll_spin_extract_batch", "null handle");
+    if (n_scans < 1 || n_scans > h->prm.max_scans) return set_err("ll_spin_extract_batch", "n_scans out of range");
+    HC(hipSetDevice(h->prm.device));
+    HC(hipMemsetAsync(h->d.n_ambig, 0, sizeof(int), h->stream));
+    HC(hipEventRecord(h->ev[0], h->stream));
     spin_launch_assign(h->d, n_scans, h->prm.scan_line, max_n(h, n_scans), h->stream);
-    SC(hipEventRecord(h->ev[1], h->stream));
+    HC(hipEventRecord(h->ev[1], h->stream));
     h->last_batch = n_scans;
     return spin_run_rest(h, n_scans);
 }
 
 extern "C" int ll_spin_sync(ll_spin *h)
 {
-    if (!h) return api_error("ll_spin_sync", "null handle");
-    SC(hipSetDevice(h->prm.device));
-    SC(hipStreamSynchronize(h->stream));
+    if (!h) return set_err("ll_spin_sync", "null handle");
+    HC(hipSetDevice(h->prm.device));
+    HC(hipStreamSynchronize(h->stream));
     return 0;
 }
 
 extern "C" int ll_spin_resolve(ll_spin *h)
 {
-    if (!h) return api_error("ll_spin_resolve", "null handle");
-    SC(hipSetDevice(h->prm.device));
-    SC(hipStreamSynchronize(h->stream));
+    if (!h) return set_err("ll_spin_resolve", "null handle");
+    HC(hipSetDevice(h->prm.device));
+    HC(hipStreamSynchronize(h->stream));
     int n_amb = 0;
-    SC(hipMemcpy(&n_amb, h->d.n_ambig, sizeof(int), hipMemcpyDeviceToHost));
+    HC(hipMemcpy(&n_amb, h->d.n_ambig, sizeof(int), hipMemcpyDeviceToHost));
     if (n_amb == 0) return 0;
-    if (n_amb > h->d.ambig_cap) return api_error("ll_spin_resolve", "more points near an atanf / atan2f decision than the list holds");
+    if (n_amb > h->d.ambig_cap) return set_err("ll_spin_resolve", "more points near an atanf / atan2f decision than the list holds");
     // the listed points and their device decisions come back in one copy, the host decisions go out in one copy
     spin_launch_ambig(h->d, n_amb, false, h->stream);
-    SC(hipGetLastError());
+    HC(hipGetLastError());
     std::vector<float4> p(n_amb);
     std::vector<int> sid_d(n_amb), sid(n_amb);
     std::vector<float> ori_d(n_amb), ori(n_amb);
-    SC(hipMemcpyAsync(p.data(), h->d.ambig_p, n_amb * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
-    SC(hipMemcpyAsync(sid_d.data(), h->d.ambig_sid, n_amb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    SC(hipMemcpyAsync(ori_d.data(), h->d.ambig_ori, n_amb * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    SC(hipStreamSynchronize(h->stream));
+    HC(hipMemcpyAsync(p.data(), h->d.ambig_p, n_amb * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+    HC(hipMemcpyAsync(sid_d.data(), h->d.ambig_sid, n_amb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HC(hipMemcpyAsync(ori_d.data(), h->d.ambig_ori, n_amb * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HC(hipStreamSynchronize(h->stream));
     bool changed = false;
     for (int k = 0; k < n_amb; k++) {
         // the same decisions as spin_assign_kernel, with the host libm
@@ -263,23 +234,23 @@ extern "C" int ll_spin_resolve(ll_spin *h)
         changed |= sid[k] != sid_d[k] || memcmp(&ori[k], &ori_d[k], sizeof(float)) != 0;
     }
     if (changed) {
-        SC(hipMemcpyAsync(h->d.ambig_sid, sid.data(), n_amb * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        SC(hipMemcpyAsync(h->d.ambig_ori, ori.data(), n_amb * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HC(hipMemcpyAsync(h->d.ambig_sid, sid.data(), n_amb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HC(hipMemcpyAsync(h->d.ambig_ori, ori.data(), n_amb * sizeof(float), hipMemcpyHostToDevice, h->stream));
         spin_launch_ambig(h->d, n_amb, true, h->stream);
         if (spin_run_rest(h, h->last_batch)) return -1;
-        SC(hipStreamSynchronize(h->stream));
+        HC(hipStreamSynchronize(h->stream));
     }
     return n_amb;
 }
 
 extern "C" int ll_spin_counts(ll_spin *h, int32_t n_scans, int32_t *counts, int32_t *status)
 {
-    if (!h || !counts) return api_error("ll_spin_counts", "null argument");
-    if (n_scans < 1 || n_scans > h->prm.max_scans) return api_error("ll_spin_counts", "n_scans out of range");
-    SC(hipSetDevice(h->prm.device));
-    SC(hipStreamSynchronize(h->stream));
+    if (!h || !counts) return set_err("ll_spin_counts", "null argument");
+    if (n_scans < 1 || n_scans > h->prm.max_scans) return set_err("ll_spin_counts", "n_scans out of range");
+    HC(hipSetDevice(h->prm.device));
+    HC(hipStreamSynchronize(h->stream));
     std::vector<int> c((size_t)n_scans * SPIN_NCNT);
-    SC(hipMemcpy(c.data(), h->d.cnt, c.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HC(hipMemcpy(c.data(), h->d.cnt, c.size() * sizeof(int), hipMemcpyDeviceToHost));
     for (int b = 0; b < n_scans; b++) {
         const int *cb = &c[(size_t)b * SPIN_NCNT];
         for (int k = 0; k < 5; k++) counts[5 * b + k] = cb[k];
@@ -290,14 +261,14 @@ extern "C" int ll_spin_counts(ll_spin *h, int32_t n_scans, int32_t *counts, int3
 
 extern "C" int ll_spin_cloud(ll_spin *h, int32_t scan, int32_t which, float *xyzi, int32_t *idx, int32_t *n)
 {
-    if (!h || !n) return api_error("ll_spin_cloud", "null argument");
-    if (scan < 0 || scan >= h->prm.max_scans) return api_error("ll_spin_cloud", "scan out of range");
-    if (which < LL_SPIN_FULL || which > LL_SPIN_LESS_FLAT_PRE) return api_error("ll_spin_cloud", "unknown cloud");
-    if (which == LL_SPIN_LESS_FLAT && idx) return api_error("ll_spin_cloud", "the less-flat cloud (voxel centroids) has no index");
-    SC(hipSetDevice(h->prm.device));
-    SC(hipStreamSynchronize(h->stream));
+    if (!h || !n) return set_err("ll_spin_cloud", "null argument");
+    if (scan < 0 || scan >= h->prm.max_scans) return set_err("ll_spin_cloud", "scan out of range");
+    if (which < LL_SPIN_FULL || which > LL_SPIN_LESS_FLAT_PRE) return set_err("ll_spin_cloud", "unknown cloud");
+    if (which == LL_SPIN_LESS_FLAT && idx) return set_err("ll_spin_cloud", "the less-flat cloud (voxel centroids) has no index");
+    HC(hipSetDevice(h->prm.device));
+    HC(hipStreamSynchronize(h->stream));
     int c[SPIN_NCNT];
-    SC(hipMemcpy(c, h->d.cnt + (size_t)scan * SPIN_NCNT, sizeof(c), hipMemcpyDeviceToHost));
+    HC(hipMemcpy(c, h->d.cnt + (size_t)scan * SPIN_NCNT, sizeof(c), hipMemcpyDeviceToHost));
     static const int slot[6] = {SPIN_C_FULL, SPIN_C_SHARP, SPIN_C_LESS_SHARP, SPIN_C_FLAT, SPIN_C_LESS_FLAT, SPIN_C_LF_PRE};
     const int m = c[slot[which]];
     *n = m;
@@ -305,21 +276,21 @@ extern "C" int ll_spin_cloud(ll_spin *h, int32_t scan, int32_t which, float *xyz
     if (m <= 0) return 0;
     const float4 *full = h->d.full + base;
     if (which == LL_SPIN_FULL) {
-        if (xyzi) SC(hipMemcpy(xyzi, full, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost));
-        if (idx) SC(hipMemcpy(idx, h->d.full_src + base, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+        if (xyzi) HC(hipMemcpy(xyzi, full, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost));
+        if (idx) HC(hipMemcpy(idx, h->d.full_src + base, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
         return 0;
     }
     if (which == LL_SPIN_LESS_FLAT) {
-        if (xyzi) SC(hipMemcpy(xyzi, h->d.less_flat + base, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost));
+        if (xyzi) HC(hipMemcpy(xyzi, h->d.less_flat + base, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost));
         return 0;
     }
     const int *src = which == LL_SPIN_SHARP ? h->d.sharp : which == LL_SPIN_LESS_SHARP ? h->d.less_sharp : which == LL_SPIN_FLAT ? h->d.flat : h->d.lf_pos;
     std::vector<int> pos(m);
-    SC(hipMemcpy(pos.data(), src + base, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+    HC(hipMemcpy(pos.data(), src + base, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
     if (idx) memcpy(idx, pos.data(), (size_t)m * sizeof(int));
     if (xyzi) {
         std::vector<float4> f(c[SPIN_C_FULL]);
-        SC(hipMemcpy(f.data(), full, f.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        HC(hipMemcpy(f.data(), full, f.size() * sizeof(float4), hipMemcpyDeviceToHost));
         for (int k = 0; k < m; k++) memcpy(xyzi + 4 * (size_t)k, &f[pos[k]], sizeof(float4));
     }
     return 0;
@@ -327,12 +298,12 @@ extern "C" int ll_spin_cloud(ll_spin *h, int32_t scan, int32_t which, float *xyz
 
 extern "C" int ll_spin_lines(ll_spin *h, int32_t scan, int32_t *line_start, int32_t *line_n)
 {
-    if (!h || !line_start || !line_n) return api_error("ll_spin_lines", "null argument");
-    if (scan < 0 || scan >= h->prm.max_scans) return api_error("ll_spin_lines", "scan out of range");
-    SC(hipSetDevice(h->prm.device));
-    SC(hipStreamSynchronize(h->stream));
+    if (!h || !line_start || !line_n) return set_err("ll_spin_lines", "null argument");
+    if (scan < 0 || scan >= h->prm.max_scans) return set_err("ll_spin_lines", "scan out of range");
+    HC(hipSetDevice(h->prm.device));
+    HC(hipStreamSynchronize(h->stream));
     int off[SPIN_MAX_LINES + 1];
-    SC(hipMemcpy(off, h->d.line_off + (size_t)scan * (SPIN_MAX_LINES + 1), sizeof(off), hipMemcpyDeviceToHost));
+    HC(hipMemcpy(off, h->d.line_off + (size_t)scan * (SPIN_MAX_LINES + 1), sizeof(off), hipMemcpyDeviceToHost));
     for (int l = 0; l < h->prm.scan_line; l++) {
         line_start[l] = off[l];
         line_n[l] = off[l + 1] - off[l];
@@ -342,7 +313,7 @@ extern "C" int ll_spin_lines(ll_spin *h, int32_t scan, int32_t *line_start, int3
 
 extern "C" int ll_spin_extract(ll_spin *h, const float *xyzi, int32_t n)
 {
-    if (!h) return api_error("ll_spin_extract", "null handle");
+    if (!h) return set_err("ll_spin_extract", "null handle");
     const int32_t np = n;
     if (ll_spin_upload(h, 0, 1, xyzi, &np, n) || ll_spin_extract_batch(h, 1) || ll_spin_resolve(h) < 0) return -1;
     int32_t counts[5], status = 0;
@@ -366,20 +337,20 @@ void spin_view(const ll_spin *h, SpinView *v)
 
 int spin_handoff(ll_spin *h, int n_scans, SpinView *v)
 {
-    if (n_scans < 1 || n_scans > h->prm.max_scans) return api_error("ll_spin (hand-off)", "n_scans out of range");
-    SC(hipSetDevice(h->prm.device));
+    if (n_scans < 1 || n_scans > h->prm.max_scans) return set_err("ll_spin (hand-off)", "n_scans out of range");
+    HC(hipSetDevice(h->prm.device));
     const size_t S = h->prm.max_scans;
     if (!h->pack) {
-        if (dm(&h->pack, S * h->pack_stride) || dm(&h->pack_nc, S) || dm(&h->pack_ns, S)) return -1;
-        for (auto &e : h->ev_pack) SC(hipEventCreate(&e));
+        if (dmalloc(&h->pack, S * h->pack_stride) || dmalloc(&h->pack_nc, S) || dmalloc(&h->pack_ns, S)) return -1;
+        for (auto &e : h->ev_pack) HC(hipEventCreate(&e));
     }
     // On the handle's own stream: behind the extraction that wrote the lists, and ahead of the event every consumer waits for.  Nothing
     // is zeroed: the kernel writes both counts of every slot it hands over, and no consumer reads a cloud beyond its count.
     if (h->packed_n < n_scans) {
-        SC(hipEventRecord(h->ev_pack[0], h->stream));
+        HC(hipEventRecord(h->ev_pack[0], h->stream));
         spin_launch_pack(h->d, h->d.less_sharp, SPIN_C_LESS_SHARP, h->pack, h->pack_stride, h->pack_nc, h->pack_ns, n_scans, h->stream);
-        SC(hipEventRecord(h->ev_pack[1], h->stream));
-        SC(hipGetLastError());
+        HC(hipEventRecord(h->ev_pack[1], h->stream));
+        HC(hipGetLastError());
         h->packed_n = n_scans;
     }
     spin_view(h, v);
@@ -392,8 +363,8 @@ int spin_handoff(ll_spin *h, int n_scans, SpinView *v)
 
 int spin_device_cloud(ll_spin *h, int n_scans, int which, const float4 **src, int *stride, int *counts)
 {
-    if (n_scans < 1 || n_scans > h->prm.max_scans) return api_error("ll_spin (hand-off)", "n_scans out of range");
-    SC(hipSetDevice(h->prm.device));
+    if (n_scans < 1 || n_scans > h->prm.max_scans) return set_err("ll_spin (hand-off)", "n_scans out of range");
+    HC(hipSetDevice(h->prm.device));
     const size_t S = h->prm.max_scans;
     static const int slot[5] = {SPIN_C_FULL, SPIN_C_SHARP, SPIN_C_LESS_SHARP, SPIN_C_FLAT, SPIN_C_LESS_FLAT};
     if (which == LL_SPIN_FULL || which == LL_SPIN_LESS_FLAT) {
@@ -401,17 +372,17 @@ int spin_device_cloud(ll_spin *h, int n_scans, int which, const float4 **src, in
         *stride = h->d.stride;
     } else {
         if (!h->pack_x) {
-            if (dm(&h->pack_x, S * h->pack_stride) || dm(&h->pack_xn, S)) return -1;
+            if (dmalloc(&h->pack_x, S * h->pack_stride) || dmalloc(&h->pack_xn, S)) return -1;
         }
         const int *list = which == LL_SPIN_SHARP ? h->d.sharp : which == LL_SPIN_LESS_SHARP ? h->d.less_sharp : h->d.flat;
         spin_launch_pack(h->d, list, slot[which], h->pack_x, h->pack_stride, h->pack_xn, nullptr, n_scans, h->stream);
-        SC(hipGetLastError());
+        HC(hipGetLastError());
         *src = h->pack_x;
         *stride = h->pack_stride;
     }
-    SC(hipStreamSynchronize(h->stream));
+    HC(hipStreamSynchronize(h->stream));
     std::vector<int> c((size_t)n_scans * SPIN_NCNT);
-    SC(hipMemcpy(c.data(), h->d.cnt, c.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HC(hipMemcpy(c.data(), h->d.cnt, c.size() * sizeof(int), hipMemcpyDeviceToHost));
     for (int b = 0; b < n_scans; b++) {
         const int m = c[(size_t)b * SPIN_NCNT + slot[which]];
         counts[b] = m < *stride ? m : *stride;
@@ -423,20 +394,20 @@ int spin_device_cloud(ll_spin *h, int n_scans, int which, const float4 **src, in
 
 extern "C" int ll_spin_kernel_times(ll_spin *h, float ms[6])
 {
-    if (!h || !ms) return api_error("ll_spin_kernel_times", "null argument");
-    SC(hipSetDevice(h->prm.device));
-    SC(hipEventSynchronize(h->ev[7]));
-    SC(hipEventElapsedTime(&ms[0], h->ev[0], h->ev[1]));
-    for (int k = 1; k < 6; k++) SC(hipEventElapsedTime(&ms[k], h->ev[k + 1], h->ev[k + 2]));
+    if (!h || !ms) return set_err("ll_spin_kernel_times", "null argument");
+    HC(hipSetDevice(h->prm.device));
+    HC(hipEventSynchronize(h->ev[7]));
+    HC(hipEventElapsedTime(&ms[0], h->ev[0], h->ev[1]));
+    for (int k = 1; k < 6; k++) HC(hipEventElapsedTime(&ms[k], h->ev[k + 1], h->ev[k + 2]));
     return 0;
 }
 
 extern "C" int ll_spin_handoff_time(ll_spin *h, float *ms)
 {
-    if (!h || !ms) return api_error("ll_spin_handoff_time", "null argument");
-    if (!h->ev_pack[1]) return api_error("ll_spin_handoff_time", "nothing has been handed over yet");
-    SC(hipSetDevice(h->prm.device));
-    SC(hipEventSynchronize(h->ev_pack[1]));
-    SC(hipEventElapsedTime(ms, h->ev_pack[0], h->ev_pack[1]));
+    if (!h || !ms) return set_err("ll_spin_handoff_time", "null argument");
+    if (!h->ev_pack[1]) return set_err("ll_spin_handoff_time", "nothing has been handed over yet");
+    HC(hipSetDevice(h->prm.device));
+    HC(hipEventSynchronize(h->ev_pack[1]));
+    HC(hipEventElapsedTime(ms, h->ev_pack[0], h->ev_pack[1]));
     return 0;
 }

@@ -6,7 +6,7 @@
 
 for one scan registered against the corner + surface maps, with the uniform grid geometry of the device maps
 (origin = minimum corner of the finite map points, cubic cells of the library's default size: 1.45 m corner, 0.6 m
-surface -- loam_livox_amd/csrc/ll_api.hip ll_map_upload).  Queries are the oracle's features of the scan transformed
+surface -- loam_livox_amd/csrc/ll_api_map.hip ll_map_upload).  Queries are the oracle's features of the scan transformed
 with the given pose (the first ICP iteration's query positions; later iterations move them by centimetres).
 """
 from __future__ import annotations

@@ -2,7 +2,7 @@
 
 bench.py runs batches of 256 24 000-point scans against the 5 M-point map with the library's DEFAULT switches: for batches of
 more than 16 scans that is the query sort + the tile search (ll_knn_tile.h) in every ICP iteration and the one-workgroup
-plane-table solver -- a path the small parity batches (B = 1 ... 4, where ll_api.hip switches the tile search off) never reach --
+plane-table solver -- a path the small parity batches (B = 1 ... 4, where ll_api_reg.hip switches the tile search off) never reach --
 and it keeps three batches in flight on three extractor handles / registrars / stream sets that share one map.
 
   (a) B = 32 slots, default switches, slots filled from the four scans the REFERENCE'S OWN build registered

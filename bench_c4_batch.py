@@ -15,7 +15,13 @@ ends in a device synchronise.  Prints one JSON line per S: aggregate frames/s of
 host time per phase and the number of sequences whose poses differ in any bit between the routes (must be 0; for lockstep_batched:
 from either other route).
 
+--cell-maps measures what C4 hands over at its end, the two cell maps of every sequence: one_by_one runs Laser_mapping(keep_cell_maps=True),
+lockstep_batched runs Laser_mapping_batch(batched_history=True, cell_maps=True), both with their sync() inside the timed region, and
+lockstep_batched_plain is lockstep_batched without cell maps from the same call.  The line then also reports the number of
+(sequence, kind) cell-map dumps that differ in any bit between the two routes that keep them (must be 0).
+
   python bench_c4_batch.py [--sequences 1,8,64] [--frames 200] [--distinct-frames 100] [--out profiles/bench_c4_batch.json]
+  python bench_c4_batch.py --cell-maps --sequences 1,8,64 --out profiles/bench_c4_batch_cell_maps.json
   python bench_c4_batch.py --routes lockstep_batched --sequences 8 --frames 12 --repeats 1   # one route alone, e.g. under a kernel trace"""
 import argparse
 import json
@@ -67,11 +73,15 @@ def main():
     ap.add_argument("--refresh-threads", type=int, default=0, help="0 = Laser_mapping_batch's default")
     ap.add_argument("--workers", type=int, default=8, help="processes that generate the synthetic scans")
     ap.add_argument("--routes", default="one_by_one,lockstep,lockstep_batched", help="the routes to run (all three for the JSON line of record)")
+    ap.add_argument("--cell-maps", action="store_true", help="keep every sequence's two cell maps: one_by_one, lockstep_batched and lockstep_batched_plain")
+    ap.add_argument("--cell-map-points", type=int, default=1 << 19, help="with --cell-maps: cell_map_max_points of both routes (the maps grow from it)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     S_list = [int(x) for x in args.sequences.split(",")]
     routes = args.routes.split(",")
-    assert routes and set(routes) <= {"one_by_one", "lockstep", "lockstep_batched"}, "--routes: one_by_one, lockstep, lockstep_batched"
+    if args.cell_maps:  # (the threaded lockstep route keeps no cell maps; the plain batched loop joins the line of record)
+        routes = [r for r in routes if r != "lockstep"] + (["lockstep_batched_plain"] if "lockstep_batched" in routes and "one_by_one" in routes else [])
+    assert routes and set(routes) <= {"one_by_one", "lockstep", "lockstep_batched", "lockstep_batched_plain"}, "--routes: one_by_one, lockstep, lockstep_batched"
     F, D, N = args.frames, args.distinct_frames, args.scan_points
     assert D >= F or (D % 50 == 0 and D >= 100), "--distinct-frames must be a multiple of 50 and at least 100"
     n_gen = min(F, D + 3)
@@ -90,8 +100,12 @@ def main():
                     ceres_max_iterations=20, max_allow_incre_R=20.0, max_allow_incre_T=0.3, minimum_icp_R_diff=1e-3, minimum_icp_T_diff=1e-4)
     lines = []
     for S in S_list:
+        def dumps_of(cell_map):
+            """both dumps of one sequence as bytes"""
+            return [b"".join(np.ascontiguousarray(a).tobytes() for a in cell_map(kind).dump()) for kind in (0, 1)]
+
         def one_by_one(frames):
-            lms = [Laser_mapping(scan_points=N, **args_map) for _ in range(S)]
+            lms = [Laser_mapping(scan_points=N, keep_cell_maps=args.cell_maps, cell_map_max_points=args.cell_map_points, **args_map) for _ in range(S)]
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             poses, accepted = [], 0
@@ -102,17 +116,21 @@ def main():
                     accepted += lm.process_new_scan(frame_scan(seqs[s], k, D), next_xyzi=nxt)
                     ps.append(lm.pose.copy())
                 poses.append(np.stack(ps))
+                lm.sync()  # (every frame is in the cell maps: inside the timed region)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             stage = np.sum([lm.stage_s for lm in lms], axis=0)
+            dumps = [dumps_of(lm.history.cell_map) for lm in lms] if args.cell_maps else None
             for lm in lms:
                 lm.close()
-            return dt, poses, accepted, stage
+            return dt, poses, accepted, stage, None, dumps
 
-        def lockstep(frames, batched_history=False):
+        def lockstep(frames, batched_history=False, cell_maps=False):
             kw = dict(refresh_threads=args.refresh_threads) if args.refresh_threads else {}
             if batched_history:
                 kw["batched_history"] = True
+            if cell_maps:
+                kw.update(cell_maps=True, cell_map_max_points=args.cell_map_points)
             lb = Laser_mapping_batch(S, scan_points=N, **kw, **args_map)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -122,13 +140,17 @@ def main():
                 accepted += int((out == 1).sum())
                 for s in range(S):
                     poses[s].append(lb.poses[s].copy())
+            if cell_maps:
+                lb.sync()  # (the stores are in order, ready to be handed over: inside the timed region)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             stage, threads = lb.stage_s.copy(), lb.refresh_threads
+            dumps = [dumps_of(lambda kind, s=s: lb.cell_map(s, kind)) for s in range(S)] if cell_maps else None
             lb.close()
-            return dt, [np.stack(p) for p in poses], accepted, stage, threads
+            return dt, [np.stack(p) for p in poses], accepted, stage, threads, dumps
 
-        run = {"one_by_one": one_by_one, "lockstep": lockstep, "lockstep_batched": lambda frames: lockstep(frames, True)}
+        run = {"one_by_one": one_by_one, "lockstep": lockstep, "lockstep_batched": lambda frames: lockstep(frames, True, args.cell_maps),
+               "lockstep_batched_plain": lambda frames: lockstep(frames, True)}
         for r in routes:
             run[r](min(6, F))  # warm-up: code objects load lazily, the ICP kernels first run on frame 3
         times, last = {r: [] for r in routes}, {}
@@ -147,7 +169,7 @@ def main():
         def wall(st):
             return {"extract_register": round(1e3 * float(st[0]) / F, 4), "history_add_and_refresh": round(1e3 * float(st[4]) / F, 4)}
 
-        line = {"metric": "frames_per_s", "sequences": S, "frames_per_sequence": F, "scan_points": N}
+        line = {"metric": "frames_per_s", "sequences": S, "frames_per_sequence": F, "scan_points": N, "cell_maps": bool(args.cell_maps)}
         if "one_by_one" in routes:
             line["one_by_one"] = dict(rate("one_by_one"), ms_per_frame_by_stage=dict(zip(("extract_register", "history_add", "match_buffer_refresh"),
                                                                                        [round(1e3 * float(v) / n, 4) for v in last["one_by_one"][3][:3]])))
@@ -166,7 +188,15 @@ def main():
                 line["lockstep_batched_over_lockstep"] = round(min(times["lockstep"]) / min(times["lockstep_batched"]), 3)
             if "one_by_one" in routes:
                 line["lockstep_batched_over_one_by_one"] = round(min(times["one_by_one"]) / min(times["lockstep_batched"]), 3)
-            others = [r for r in ("one_by_one", "lockstep") if r in routes]
+            if "lockstep_batched_plain" in routes:  # the same loop without cell maps, from the same call
+                line["lockstep_batched_plain"] = rate("lockstep_batched_plain")
+                line["cell_maps_time_factor_lockstep_batched"] = round(min(times["lockstep_batched"]) / min(times["lockstep_batched_plain"]), 3)
+            if args.cell_maps and "one_by_one" in routes:
+                a, b = last["one_by_one"][5], last["lockstep_batched"][5]
+                line["cell_map_dumps_differing"] = sum(a[s][kind] != b[s][kind] for s in range(S) for kind in (0, 1))
+                line["cell_map_dumps_compared"] = 2 * S
+                line["cell_map_dump_bytes"] = sum(len(x) for d in b for x in d)
+            others = [r for r in ("one_by_one", "lockstep", "lockstep_batched_plain") if r in routes]
             if others:  # sequences whose poses differ in any bit from EITHER other route
                 line["lockstep_batched_sequences_with_differing_poses"] = sum(
                     1 if any(not np.array_equal(last["lockstep_batched"][1][s].view(np.uint64), last[r][1][s].view(np.uint64)) for r in others) else 0

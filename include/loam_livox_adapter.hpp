@@ -644,6 +644,43 @@ class History_batch {
     int n_sequences() const { return n_; }
     ll_history_batch *handle() { return h_; }
 
+    // m_pt_cell_map_corners / m_pt_cell_map_planes of every slot (laser_mapping.hpp:274-275, 617-624): from here on every active slot
+    // of add() appends its filtered frame to its two cell maps, pushed or not.  An add costs the new points; the stored points are put
+    // in order by the first read after it (cell_map_stats / cell_map_dump / cell_map_device_view, or sync_cell_maps()).
+    void enable_cell_maps(int64_t initial_points_per_map, float cell_resolution = 1.0f, int threshold_cell_revisit = 5000)
+    {
+        check(ll_history_batch_enable_cell_maps(h_, initial_points_per_map, cell_resolution, threshold_cell_revisit), "ll_history_batch_enable_cell_maps");
+    }
+    void sync_cell_maps() { check(ll_history_batch_sync_cell_maps(h_), "ll_history_batch_sync_cell_maps"); }
+    void cell_map_stats(int sequence, int kind, int64_t *n_cells, int64_t *n_points, int32_t *frame_idx = nullptr)
+    {
+        check(ll_history_batch_cell_map_stats(h_, sequence, kind, n_cells, n_points, frame_idx), "ll_history_batch_cell_map_stats");
+    }
+    // the layouts of ll_cellmap_dump: xyzi [n_points][4], cell_ijk [n_cells][3], cell_start [n_cells + 1], cell_last_update [n_cells]
+    void cell_map_dump(int sequence, int kind, std::vector<float> &xyzi, std::vector<int32_t> &cell_ijk, std::vector<int32_t> &cell_start,
+                       std::vector<int32_t> &cell_last_update)
+    {
+        int64_t nc = 0, np = 0;
+        cell_map_stats(sequence, kind, &nc, &np);
+        xyzi.assign((size_t)(np > 0 ? np : 1) * 4, 0.0f);
+        cell_ijk.assign((size_t)(nc > 0 ? nc : 1) * 3, 0);
+        cell_start.assign((size_t)nc + 1, 0);
+        cell_last_update.assign((size_t)(nc > 0 ? nc : 1), 0);
+        check(ll_history_batch_cell_map_dump(h_, sequence, kind, xyzi.data(), np > 0 ? np : 1, cell_ijk.data(), cell_start.data(),
+                                             cell_last_update.data(), nc > 0 ? nc : 1),
+              "ll_history_batch_cell_map_dump");
+        xyzi.resize((size_t)np * 4);
+        cell_ijk.resize((size_t)nc * 3);
+        cell_last_update.resize((size_t)nc);
+    }
+    // device pointers to the slot's stored points ({x, y, z, 0}) and their 64-bit cell keys: valid until the next add()
+    void cell_map_device_view(int sequence, int kind, const float **dev_xyz0, const uint64_t **dev_point_keys, int64_t *n_points,
+                              int64_t *n_cells = nullptr)
+    {
+        check(ll_history_batch_cell_map_device_view(h_, sequence, kind, dev_xyz0, dev_point_keys, n_points, n_cells),
+              "ll_history_batch_cell_map_device_view");
+    }
+
    private:
     ll_history_batch *h_ = nullptr;
     int n_ = 0;

@@ -406,7 +406,7 @@ int ll_history_map_cloud_device(ll_history *h, int32_t kind, const float **dev_x
  * n_sequences * maximum_history_size * max_points_per_frame >= 2^31 (the sorts index with 32 bits).
  * The search grids of one refresh share pooled storage that lives as long as any snapshot built in it is published or pinned
  * by a registration in flight: a registration enqueued before a refresh and collected after it reads the old snapshots.
- * ll_map_to_f16 refuses such a snapshot.  There are no cell maps on this handle. */
+ * ll_map_to_f16 refuses such a snapshot.  Cell maps per slot: ll_history_batch_enable_cell_maps below. */
 typedef struct ll_history_batch ll_history_batch;
 int ll_history_batch_create(int32_t device, int32_t n_sequences, int32_t maximum_history_size, int32_t max_points_per_frame,
                             float line_res, float plane_res, ll_history_batch **out);
@@ -420,6 +420,33 @@ int ll_history_batch_refresh(ll_history_batch *h, ll_map *const *maps, const int
                              int64_t *n_map_surf);
 int32_t ll_history_batch_size(const ll_history_batch *h, int32_t sequence);
 int64_t ll_history_batch_map_cloud(ll_history_batch *h, int32_t sequence, int32_t kind, float *xyzi, int64_t capacity_points);
+/* The two cell maps of every slot (the sub-map a sequence hands over at its end, laser_mapping.hpp:274-275, 1492-1493).  Per slot the
+ * semantics are those of ll_history_enable_cell_map: once enabled, every ACTIVE slot of ll_history_batch_add_voxel / _add_fe appends its
+ * map-frame, voxel-filtered frame to that slot's corner and surface cell map, whether or not the add-frame rule pushes the frame; an
+ * inactive slot's maps and their frame counters stay as they were.  Per map the rules are ll_cellmap_append's: cell index and key,
+ * non-finite or out-of-range points dropped, a hit on a cell that was not updated for threshold_cell_revisit appends drops the cell's
+ * stored points first, the frame counter moves by 1 per append (by 2 while the map has no cells), also for an empty cloud.
+ * The cost differs: an add appends through one fixed chain of launches over all slots whose work is that of the NEW points and of the
+ * cell tables -- no kernel of an add reads, sorts or moves the stored points.  The stored points are put in order, (cell key, insertion
+ * order) per slot with the points of reset cells gone, when somebody reads: ll_history_batch_cell_map_stats / _dump / _device_view or
+ * ll_history_batch_sync_cell_maps materialise all slots at once if an add came since the last time, and cost nothing otherwise.
+ * The stores grow geometrically from n_sequences * initial_points_per_map points per kind.
+ * Outputs have the layouts of ll_cellmap_stats / ll_cellmap_dump / ll_cellmap_device_view; a device view is valid until the next add.
+ * Refused before anything is enqueued, with the handle still usable: a null handle, a second enable, cell_resolution <= 0,
+ * initial_points_per_map < max_points_per_frame, a read before the enable, a sequence or kind out of range, buffers too small, and a
+ * store that would pass 2^31 points per kind (at the enable, and at an add by the sizes of the incoming frames).
+ * ll_history_batch_cell_map_work is a test tap: out[0] points appended since the enable; out[1] points that went through a sort or a
+ * gather INSIDE add calls; out[2] materialisations run; out[3] kernel launches and library calls of the cell-map part of the last add. */
+int ll_history_batch_enable_cell_maps(ll_history_batch *h, int64_t initial_points_per_map, float cell_resolution,
+                                      int32_t threshold_cell_revisit);
+int ll_history_batch_sync_cell_maps(ll_history_batch *h);
+int ll_history_batch_cell_map_stats(ll_history_batch *h, int32_t sequence, int32_t kind, int64_t *n_cells, int64_t *n_points,
+                                    int32_t *frame_idx);
+int ll_history_batch_cell_map_dump(ll_history_batch *h, int32_t sequence, int32_t kind, float *xyzi, int64_t capacity_points,
+                                   int32_t *cell_ijk, int32_t *cell_start, int32_t *cell_last_update, int64_t capacity_cells);
+int ll_history_batch_cell_map_device_view(ll_history_batch *h, int32_t sequence, int32_t kind, const float **dev_xyz0,
+                                          const uint64_t **dev_point_keys, int64_t *n_points, int64_t *n_cells);
+int ll_history_batch_cell_map_work(ll_history_batch *h, int64_t out[4]);
 /* Host arithmetic only (no device needed): the geometry ll_map_upload and both refreshes give the search grid over the bounding
  * box {min x, y, z, max x, y, z} of a cloud's finite points (min > max: no finite point) with cells of cell_size metres.  The
  * cell grows by 1.5 x until the dense table has at most 2^27 cells. */

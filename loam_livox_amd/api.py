@@ -497,6 +497,71 @@ class History_buffer_batch:
         return out
 
 
+    def enable_cell_maps(self, initial_points_per_map: int = 1 << 20, cell_resolution: float = 1.0, threshold_cell_revisit: int = 5000) -> None:
+        """the two cell maps of every slot (laser_mapping.hpp:274-275, 617-624): fed by every active slot of add_voxel / add_fe, put in
+        order when read; the stores grow from n_sequences * initial_points_per_map points per kind"""
+        check(self.L.ll_history_batch_enable_cell_maps(self.h, int(initial_points_per_map), cell_resolution, int(threshold_cell_revisit)),
+              "ll_history_batch_enable_cell_maps")
+        self._cell_resolution = cell_resolution
+
+    def sync_cell_maps(self) -> None:
+        """put the stored points of all slots in order now (every reader does so itself when an add came since the last time)"""
+        check(self.L.ll_history_batch_sync_cell_maps(self.h), "ll_history_batch_sync_cell_maps")
+
+    def cell_map(self, sequence: int, kind: int) -> "Cell_map_slot":
+        return Cell_map_slot(self, int(sequence), int(kind))
+
+    def cell_map_work(self) -> np.ndarray:
+        """test tap (ll_history_batch_cell_map_work): points appended, points sorted or gathered inside adds, materialisations, launches of
+        the cell-map part of the last add"""
+        out = np.zeros(4, np.int64)
+        check(self.L.ll_history_batch_cell_map_work(self.h, ptr(out)), "ll_history_batch_cell_map_work")
+        return out
+
+
+class Cell_map_slot:
+    """One cell map of one slot of a History_buffer_batch, read the way a Cell_map is: stats(), dump() and device_view(device) have
+    Cell_map's return shapes, so what gathers a Cell_map (multigpu.gather_cell_maps) takes a slot's view unchanged."""
+
+    def __init__(self, batch: "History_buffer_batch", sequence: int, kind: int):
+        self.batch, self.sequence, self.kind = batch, sequence, kind
+        self.resolution = getattr(batch, "_cell_resolution", None)
+
+    def stats(self):
+        """(cells, points, m_current_frame_idx)"""
+        b = self.batch
+        nc, npts, fr = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        check(b.L.ll_history_batch_cell_map_stats(b.h, self.sequence, self.kind, C.byref(nc), C.byref(npts), C.byref(fr)),
+              "ll_history_batch_cell_map_stats")
+        return nc.value, npts.value, fr.value
+
+    def dump(self):
+        """(xyz [n,3] in (cell, insertion) order, cell indices [c,3], first point of each cell [c+1], last-update frame [c])"""
+        b = self.batch
+        nc, npts, _ = self.stats()
+        xyzi = np.zeros((max(npts, 1), 4), np.float32)
+        ijk = np.zeros((max(nc, 1), 3), np.int32)
+        start = np.zeros(nc + 1, np.int32)
+        last = np.zeros(max(nc, 1), np.int32)
+        check(b.L.ll_history_batch_cell_map_dump(b.h, self.sequence, self.kind, ptr(xyzi), xyzi.shape[0], ptr(ijk), ptr(start), ptr(last),
+                                                 ijk.shape[0]), "ll_history_batch_cell_map_dump")
+        return xyzi[:npts, :3].copy(), ijk[:nc].copy(), start, last[:nc].copy()
+
+    def device_view(self, device: int = 0):
+        """(points (n, 4) float32, cell keys (n,) int64) as torch DEVICE tensors, copied device-to-device out of the handle's store
+        (which the next add writes behind and may move)"""
+        import torch
+        b = self.batch
+        p, k, n, nc = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(0)
+        check(b.L.ll_history_batch_cell_map_device_view(b.h, self.sequence, self.kind, C.byref(p), C.byref(k), C.byref(n), C.byref(nc)),
+              "ll_history_batch_cell_map_device_view")
+        if n.value == 0:
+            return torch.zeros((0, 4), dtype=torch.float32, device=f"cuda:{device}"), torch.zeros(0, dtype=torch.int64, device=f"cuda:{device}")
+        pts = torch.as_tensor(_DeviceView(p.value, n.value), device=f"cuda:{device}").clone()
+        keys = torch.as_tensor(_DeviceView64(k.value, n.value), device=f"cuda:{device}").clone()
+        return pts, keys
+
+
 def map_grid_geometry(bbox_min_max, cell_size: float):
     """ll_map_grid_geometry (host arithmetic): ((nx, ny, nz), cell, slack) of the search grid over a bounding box"""
     bb = np.ascontiguousarray(bbox_min_max, np.float32).reshape(6)

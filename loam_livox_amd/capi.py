@@ -124,6 +124,12 @@ SYMBOLS = {
     "ll_history_batch_refresh": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "ll_history_batch_size": (_i32, [_vp, _i32]),
     "ll_history_batch_map_cloud": (_i64, [_vp, _i32, _i32, _vp, _i64]),
+    "ll_history_batch_enable_cell_maps": (_i32, [_vp, _i64, C.c_float, _i32]),
+    "ll_history_batch_sync_cell_maps": (_i32, [_vp]),
+    "ll_history_batch_cell_map_stats": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "ll_history_batch_cell_map_dump": (_i32, [_vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64]),
+    "ll_history_batch_cell_map_device_view": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ll_history_batch_cell_map_work": (_i32, [_vp, _vp]),
     "ll_map_grid_geometry": (_i32, [_vp, _f, _vp, _vp, _vp]),
     "ll_cellmap_create": (_i32, [_i32, _i64, C.c_float, _i32, _vp]),
     "ll_cellmap_destroy": (None, [_vp]),

@@ -4,6 +4,10 @@
 // refresh live in ONE pooled pair of buffers, an arena.  Every MapSnap built in an arena holds a reference to it, so the immutable
 // snapshot contract of ll_map carries over: an arena is taken for the next refresh only when nothing but the handle's pool refers
 // to it -- no snapshot built in it is published by a map or pinned by a registration any more.
+//
+// The handle can keep the two cell maps of every slot as well (ll_history_batch_enable_cell_maps): every active slot of an add
+// appends its filtered frame to them, through one more fixed chain whose work is that of the new points and the cell tables
+// (ll_cellmap_batch_kernels.hip); the stored points are put in order when somebody reads.
 #include "ll_api_internal.h"
 
 struct HbArena {
@@ -47,6 +51,14 @@ struct ll_history_batch {
     char *tmp = nullptr;
     size_t cap_n = 0, cap_cells = 0, cap_tmp = 0;
     std::vector<std::shared_ptr<HbArena>> arenas;
+    // the cell maps of all slots, one deferred store per kind (ll_history_batch_enable_cell_maps)
+    bool cm_on = false, cm_dirty = false;    // dirty: an add came after the last materialisation
+    CbDev cm[2]{};
+    std::vector<int> cm_frame[2];            // [S] m_current_frame_idx of every map
+    std::vector<int> cm_coff[2], cm_poff[2]; // [S + 1] host copies: first cell / first stored point of every slot
+    CbSlot *hp_cm_tab = nullptr;             // pinned [2][S]
+    int *hp_cm = nullptr;                    // pinned: filtered counts [2][S], coff [2][S + 1], poff [2][S + 1], counts [2][4]
+    int64_t cm_work[4] = {0, 0, 0, 0};       // ll_history_batch_cell_map_work
 };
 
 // grow-only device buffer, half again as large as asked when it has to move
@@ -61,6 +73,16 @@ static int hb_grow(T **p, size_t *cap, size_t need)
     HC(hipMalloc((void **)p, want * sizeof(T)));
     *cap = want;
     return 0;
+}
+
+static void hb_cells_free(CbDev &m)
+{
+    void *ptrs[] = {m.pts,   m.pts2, m.pkey,  m.pkey2, m.pslot, m.pslot2, m.pep,    m.pep2,  m.ckey,  m.ckey2, m.cslot, m.cslot2, m.clast,
+                    m.clast2, m.cep, m.cep2,  m.coff,  m.coff2, m.poff,   m.cstart, m.akey,  m.akey2, m.aslot, m.aslot2, m.aflag, m.arank,
+                    m.mkey,  m.mkey2, m.mval, m.mval2, m.mslot, m.mslot2, m.tmp,    m.counts, m.tab};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    memset(&m, 0, sizeof(m));
 }
 
 static int history_batch_create_impl(ll_history_batch *h)
@@ -117,7 +139,8 @@ extern "C" void ll_history_batch_destroy(ll_history_batch *h)
                    h->d_nvalid, h->keys, h->keys2, h->vals, h->vals2, h->counts, h->tmp};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    void *host[] = {h->hp_add, h->hp_cnt, h->hp_ref, h->hp_mm_init, h->hp_mm, h->hp_grid, h->hp_nvalid};
+    for (int k = 0; k < 2; k++) hb_cells_free(h->cm[k]);
+    void *host[] = {h->hp_add, h->hp_cnt, h->hp_ref, h->hp_mm_init, h->hp_mm, h->hp_grid, h->hp_nvalid, h->hp_cm_tab, h->hp_cm};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
     h->arenas.clear();  // (an arena still referenced by a published or pinned snapshot dies with that snapshot)
@@ -161,6 +184,186 @@ extern "C" int32_t ll_history_batch_size(const ll_history_batch *h, int32_t sequ
     return (h && sequence >= 0 && sequence < h->S) ? h->size[sequence] : -1;
 }
 
+
+// ================================================================================================ the cell maps of the slots
+static const long long kCbLimit = 0x7fffffffLL;  // a store holds fewer than 2^31 points per kind (the sorts index with 32 bits)
+
+// a device array of `count` entries that keeps its first `keep`
+template <typename T>
+static int hb_cells_move(ll_history_batch *h, T **p, size_t count, size_t keep)
+{
+    T *q = nullptr;
+    HC(hipMalloc((void **)&q, (count > 0 ? count : 1) * sizeof(T)));
+    if (*p && keep > 0) {
+        hipError_t e = hipMemcpyAsync(q, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(q);
+            return set_err("ll_history_batch (cell maps)", hipGetErrorString(e));
+        }
+    }
+    if (*p) (void)hipFree(*p);
+    *p = q;
+    return 0;
+}
+
+// Room for `need` logged points: twice the capacity when they would not fit -- the only time stored points are copied outside a
+// materialisation.  A capacity is raised only after every array of its group has moved, so a failure leaves the store consistent.
+static int hb_cells_reserve_log(ll_history_batch *h, CbDev &m, long long need)
+{
+    if (need <= (long long)m.cap) return 0;
+    long long want = 2LL * (long long)m.cap;
+    want = want < need ? need : want;
+    want = want < kCbLimit ? want : kCbLimit;
+    const size_t n = (size_t)want, keep = (size_t)m.n_log;
+    if (hb_cells_move(h, &m.pts, n, keep) || hb_cells_move(h, &m.pkey, n, keep) || hb_cells_move(h, &m.pslot, n, keep) ||
+        hb_cells_move(h, &m.pep, n, keep) || hb_cells_move(h, &m.pts2, n, 0) || hb_cells_move(h, &m.pkey2, n, 0) ||
+        hb_cells_move(h, &m.pslot2, n, 0) || hb_cells_move(h, &m.pep2, n, 0))
+        return -1;
+    m.cap = n;
+    return 0;
+}
+
+static int hb_cells_reserve_table(ll_history_batch *h, CbDev &m, long long need)
+{
+    if (need <= (long long)m.ccap) return 0;
+    long long want = 2LL * (long long)m.ccap;
+    want = want < need ? need : want;
+    const size_t n = (size_t)want, keep = (size_t)m.n_cells;
+    if (hb_cells_move(h, &m.ckey, n, keep) || hb_cells_move(h, &m.cslot, n, keep) || hb_cells_move(h, &m.clast, n, keep) ||
+        hb_cells_move(h, &m.cep, n, keep) || hb_cells_move(h, &m.ckey2, n, 0) || hb_cells_move(h, &m.cslot2, n, 0) ||
+        hb_cells_move(h, &m.clast2, n, 0) || hb_cells_move(h, &m.cep2, n, 0) || hb_cells_move(h, &m.cstart, n + (size_t)m.S + 1, 0))
+        return -1;
+    HC(hipMemset(m.cstart, 0, (n + (size_t)m.S + 1) * sizeof(int)));  // (rebuilt by the next materialisation)
+    HC(hipDeviceSynchronize());
+    m.ccap = n;
+    return 0;
+}
+
+static int hb_cells_reserve_tmp(ll_history_batch *h, CbDev &m, long long n)
+{
+    size_t bytes = 0;
+    const char *err = nullptr;
+    if (cb_tmp_bytes(n, &bytes, &err)) return set_err("ll_history_batch (cell maps)", err);
+    if (bytes <= m.tmp_bytes) return 0;
+    char *p = (char *)m.tmp;
+    if (hb_cells_move(h, &p, bytes + bytes / 2, 0)) return -1;
+    m.tmp = p;
+    m.tmp_bytes = bytes + bytes / 2;
+    return 0;
+}
+
+// before an add enqueues anything: the store stays below 2^31 points per kind even if the VoxelGrid drops nothing
+static int hb_cells_room(const char *where, ll_history_batch *h, const int32_t *active, const int *in_n)
+{
+    for (int k = 0; k < 2; k++) {
+        long long bound = h->cm[k].n_log;
+        for (int s = 0; s < h->S; s++)
+            if (!active || active[s]) bound += in_n[k * h->S + s] > 0 ? in_n[k * h->S + s] : 0;
+        if (bound >= kCbLimit) return set_err(where, "the cell maps would pass 2^31 stored points per kind");
+    }
+    return 0;
+}
+
+// The cell-map part of an add: the filtered frames of the working slots (h->vf[k].out, their sizes in hp_cm) behind the logs of the
+// two kinds.  One chain per kind, one wait for both.
+static int hb_cells_append(const char *where, ll_history_batch *h)
+{
+    const int S = h->S;
+    long long n_new[2] = {0, 0};
+    int max_n[2] = {0, 0}, launches = 0;
+    for (int k = 0; k < 2; k++) {
+        CbSlot *tab = h->hp_cm_tab + (size_t)k * S;
+        for (int s = 0; s < S; s++) {
+            memset(&tab[s], 0, sizeof(CbSlot));
+            if (!h->hp_add[s].work) continue;
+            int n = h->hp_cm[(size_t)k * S + s];
+            n = n < 0 ? 0 : (n < h->max_pts ? n : h->max_pts);
+            tab[s].off = h->cm[k].n_log + n_new[k];
+            tab[s].n = n;
+            tab[s].frame = h->cm_frame[k][s];
+            tab[s].active = 1;
+            n_new[k] += n;
+            max_n[k] = n > max_n[k] ? n : max_n[k];
+        }
+    }
+    for (int k = 0; k < 2; k++) {
+        CbDev &m = h->cm[k];
+        if (n_new[k] == 0) continue;
+        if (m.n_log + n_new[k] >= kCbLimit) return set_err(where, "the cell maps would pass 2^31 stored points per kind");
+        if (hb_cells_reserve_log(h, m, m.n_log + n_new[k]) || hb_cells_reserve_table(h, m, (long long)m.n_cells + n_new[k]) ||
+            hb_cells_reserve_tmp(h, m, n_new[k]))
+            return -1;
+        if ((long long)m.acap < n_new[k]) {
+            const size_t n = (size_t)(n_new[k] + n_new[k] / 2);
+            if (hb_cells_move(h, &m.akey, n, 0) || hb_cells_move(h, &m.akey2, n, 0) || hb_cells_move(h, &m.aslot, n, 0) ||
+                hb_cells_move(h, &m.aslot2, n, 0) || hb_cells_move(h, &m.aflag, n, 0) || hb_cells_move(h, &m.arank, n, 0))
+                return -1;
+            m.acap = n;
+        }
+    }
+    int *h_coff = h->hp_cm + (size_t)2 * S, *h_counts = h->hp_cm + (size_t)2 * S + 4 * ((size_t)S + 1);
+    const char *err = nullptr;
+    for (int k = 0; k < 2; k++) {
+        CbDev &m = h->cm[k];
+        if (n_new[k] == 0) continue;
+        HC(hipMemcpyAsync(m.tab, h->hp_cm_tab + (size_t)k * S, (size_t)S * sizeof(CbSlot), hipMemcpyHostToDevice, h->stream));
+        if (cb_append(m, h->vf[k].out, h->max_pts, max_n[k], n_new[k], h->stream, &launches, &err)) return set_err(where, err);
+        HC(hipMemcpyAsync(h_counts + 4 * k, m.counts, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HC(hipMemcpyAsync(h_coff + (size_t)k * (S + 1), m.coff, (size_t)(S + 1) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
+    HC(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 2; k++) {
+        CbDev &m = h->cm[k];
+        for (int s = 0; s < S; s++)  // (the cell counts at the call decide the step of the frame counter)
+            if (h->hp_add[s].work) h->cm_frame[k][s] += cb_frame_step(h->cm_coff[k][s + 1] == h->cm_coff[k][s]);
+        if (n_new[k] == 0) continue;
+        m.n_cells = h_counts[4 * k + 1];
+        for (int s = 0; s <= S; s++) h->cm_coff[k][s] = h_coff[(size_t)k * (S + 1) + s];
+        h->cm_work[0] += n_new[k];
+        h->cm_work[1] += n_new[k];  // (the candidates' keys: two sorts over the new points, nothing else is sorted or gathered here)
+    }
+    h->cm_work[3] = launches;
+    h->cm_dirty = true;
+    return 0;
+}
+
+// put the stores of both kinds in order (a read after an add); nothing to do when no add came since the last time
+static int hb_cells_materialise(const char *where, ll_history_batch *h)
+{
+    if (!h->cm_dirty) return 0;
+    const int S = h->S;
+    HC(hipSetDevice(h->device));
+    for (int k = 0; k < 2; k++) {
+        CbDev &m = h->cm[k];
+        if (m.n_log <= 0) continue;
+        if (hb_cells_reserve_tmp(h, m, m.n_log)) return -1;
+        if ((long long)m.mcap < m.n_log) {
+            const size_t n = m.cap;  // (the log's capacity: grows as rarely as the log does)
+            if (hb_cells_move(h, &m.mkey, n, 0) || hb_cells_move(h, &m.mkey2, n, 0) || hb_cells_move(h, &m.mval, n, 0) ||
+                hb_cells_move(h, &m.mval2, n, 0) || hb_cells_move(h, &m.mslot, n, 0) || hb_cells_move(h, &m.mslot2, n, 0))
+                return -1;
+            m.mcap = n;
+        }
+    }
+    int *h_poff = h->hp_cm + (size_t)2 * S + 2 * ((size_t)S + 1), launches = 0;
+    const char *err = nullptr;
+    for (int k = 0; k < 2; k++) {
+        CbDev &m = h->cm[k];
+        if (cb_materialise(m, h->stream, &launches, &err)) return set_err(where, err);
+        HC(hipMemcpyAsync(h_poff + (size_t)k * (S + 1), m.poff, (size_t)(S + 1) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
+    HC(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 2; k++) {
+        for (int s = 0; s <= S; s++) h->cm_poff[k][s] = h_poff[(size_t)k * (S + 1) + s];
+        h->cm[k].n_log = h->cm_poff[k][S];  // the ordered store replaces the log: later adds write behind it
+    }
+    h->cm_dirty = false;
+    h->cm_work[2]++;
+    return 0;
+}
+
+
 // slots 0 .. S-1 of a device-resident producer
 static int history_batch_add_common(const char *where, ll_history_batch *h, const FeatView &v, const int32_t *active, const double *poses7,
                                     const double *gate_poses7, double t_step, double angle_step, int32_t *added)
@@ -179,23 +382,28 @@ static int history_batch_add_common(const char *where, ll_history_batch *h, cons
             return set_err(where, "frame exceeds max_points_per_frame");
     }
     // the add-frame rule per slot (history_add_frame): host arithmetic on the gate poses
-    int n_push = 0, max_in[2] = {0, 0};
+    // With cell maps every active slot goes through the transform and the VoxelGrid, pushed or not (laser_mapping.hpp:1492-1493 feeds
+    // the cell maps with every registered frame); only the scatter into the ring is left to the rule.
+    if (h->cm_on && hb_cells_room(where, h, active, in_n)) return -1;
+    int n_work = 0, max_in[2] = {0, 0};
     for (int s = 0; s < S; s++) {
         HbAddSlot &a = h->hp_add[s];
         memset(&a, 0, sizeof(a));
         if (active && !active[s]) continue;
         const double *pose = poses7 + 7 * (size_t)s, *gp = gate_poses7 ? gate_poses7 + 7 * (size_t)s : pose;
-        if (!history_add_frame(gp, &h->last_q[4 * (size_t)s], &h->last_t[3 * (size_t)s], h->size[s], h->max_hist, t_step, angle_step)) continue;
+        const bool push = history_add_frame(gp, &h->last_q[4 * (size_t)s], &h->last_t[3 * (size_t)s], h->size[s], h->max_hist, t_step, angle_step);
+        if (!push && !h->cm_on) continue;
         for (int i = 0; i < 7; i++) a.pose[i] = pose[i];
         a.work = 1;
+        a.push = push ? 1 : 0;
         a.ring = (h->head[s] + h->size[s]) % h->slots;
-        n_push++;
+        n_work++;
         for (int k = 0; k < 2; k++) {
             const int n = in_n[k * S + s] > 0 ? in_n[k * S + s] : 0;
             max_in[k] = n > max_in[k] ? n : max_in[k];
         }
     }
-    if (n_push == 0) return 0;
+    if (n_work == 0) return 0;
     HC(hipMemcpyAsync(h->d_add, h->hp_add, (size_t)S * sizeof(HbAddSlot), hipMemcpyHostToDevice, h->stream));
     launch_hb_transform(v.corner, v.n_corner, v.stride_c, v.surf, v.n_surf, v.stride_s, h->d_add, S, h->max_pts, h->d_xf, h->d_nxf, h->stream);  // :1421-1431
     const char *err = nullptr;
@@ -209,10 +417,12 @@ static int history_batch_add_common(const char *where, ll_history_batch *h, cons
     HC(hipGetLastError());
     int *out_n = h->hp_cnt + 2 * S;
     HC(hipMemcpyAsync(out_n, h->d_cnt, (size_t)2 * S * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (h->cm_on)
+        for (int k = 0; k < 2; k++) HC(hipMemcpyAsync(h->hp_cm + (size_t)k * S, h->vf[k].n_out, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HC(hipStreamSynchronize(h->stream));
     for (int s = 0; s < S; s++) {
         const HbAddSlot &a = h->hp_add[s];
-        if (!a.work) continue;
+        if (!a.push) continue;
         const double *gp = gate_poses7 ? gate_poses7 + 7 * (size_t)s : poses7 + 7 * (size_t)s;
         for (int k = 0; k < 2; k++) h->count[k][(size_t)s * h->slots + a.ring] = out_n[k * S + s];
         for (int i = 0; i < 4; i++) h->last_q[4 * (size_t)s + i] = gp[i];  // :1450-1451
@@ -223,6 +433,7 @@ static int history_batch_add_common(const char *where, ll_history_batch *h, cons
         }
         if (added) added[s] = 1;
     }
+    if (h->cm_on) return hb_cells_append(where, h);
     return 0;
 }
 
@@ -421,4 +632,138 @@ extern "C" int64_t ll_history_batch_map_cloud(ll_history_batch *h, int32_t seque
     if (n > 0 && hipMemcpy(xyzi, h->d_map + ((size_t)kind * h->S + sequence) * h->cstride, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess)
         return set_err("ll_history_batch_map_cloud", "copy failed");
     return n;
+}
+
+static int hb_cells_enable_impl(ll_history_batch *h, int64_t initial_points_per_map, float cell_resolution, int32_t threshold)
+{
+    const size_t S = (size_t)h->S;
+    HC(hipHostMalloc((void **)&h->hp_cm_tab, 2 * S * sizeof(CbSlot), hipHostMallocDefault));
+    HC(hipHostMalloc((void **)&h->hp_cm, (2 * S + 4 * (S + 1) + 8) * sizeof(int), hipHostMallocDefault));
+    for (int k = 0; k < 2; k++) {
+        CbDev &m = h->cm[k];
+        m.S = h->S;
+        m.geom = cell_geom(cell_resolution);  // laser_mapping.hpp:620-624: set_resolution( m_pt_cell_resolution ), m_minimum_revisit_threshold
+        m.threshold = threshold;
+        DM(m.coff, S + 1);
+        DM(m.coff2, S + 1);
+        DM(m.poff, S + 1);
+        DM(m.counts, 4);
+        DM(m.tab, S);
+        HC(hipMemset(m.coff, 0, (S + 1) * sizeof(int)));
+        HC(hipMemset(m.poff, 0, (S + 1) * sizeof(int)));
+        HC(hipMemset(m.counts, 0, 4 * sizeof(int)));
+        if (hb_cells_reserve_log(h, m, (long long)(S * (size_t)initial_points_per_map)) || hb_cells_reserve_table(h, m, (long long)h->max_pts)) return -1;
+        h->cm_frame[k].assign(S, 0);
+        h->cm_coff[k].assign(S + 1, 0);
+        h->cm_poff[k].assign(S + 1, 0);
+    }
+    HC(hipDeviceSynchronize());  // (null-stream memsets are not ordered with the handle's non-blocking stream)
+    return 0;
+}
+
+extern "C" int ll_history_batch_enable_cell_maps(ll_history_batch *h, int64_t initial_points_per_map, float cell_resolution,
+                                                 int32_t threshold_cell_revisit)
+{
+    static const char *where = "ll_history_batch_enable_cell_maps";
+    if (!h) return set_err(where, "null argument");
+    if (h->cm_on) return set_err(where, "already enabled");
+    if (!(cell_resolution > 0.f)) return set_err(where, "cell_resolution must be positive");
+    if (initial_points_per_map < h->max_pts) return set_err(where, "initial_points_per_map below max_points_per_frame");
+    if ((double)initial_points_per_map * (double)h->S >= 2147483647.0)
+        return set_err(where, "n_sequences * initial_points_per_map must stay below 2^31 stored points per kind");
+    HC(hipSetDevice(h->device));
+    HC(hipStreamSynchronize(h->stream));
+    if (hb_cells_enable_impl(h, initial_points_per_map, cell_resolution, threshold_cell_revisit)) {  // all or nothing
+        const std::string keep = g_err;
+        for (int k = 0; k < 2; k++) hb_cells_free(h->cm[k]);
+        if (h->hp_cm_tab) (void)hipHostFree(h->hp_cm_tab);
+        if (h->hp_cm) (void)hipHostFree(h->hp_cm);
+        h->hp_cm_tab = nullptr;
+        h->hp_cm = nullptr;
+        g_err = keep;
+        return -1;
+    }
+    h->cm_on = true;
+    return 0;
+}
+
+// what every reader checks first; 0 with the stores in order
+static int hb_cells_reader(const char *where, ll_history_batch *h, int32_t sequence, int32_t kind)
+{
+    if (!h) return set_err(where, "null argument");
+    if (!h->cm_on) return set_err(where, "cell maps are not enabled (ll_history_batch_enable_cell_maps)");
+    if (sequence < 0 || sequence >= h->S) return set_err(where, "sequence out of range");
+    if (kind < 0 || kind > 1) return set_err(where, "kind out of range");
+    return hb_cells_materialise(where, h);
+}
+
+extern "C" int ll_history_batch_sync_cell_maps(ll_history_batch *h)
+{
+    return hb_cells_reader("ll_history_batch_sync_cell_maps", h, 0, 0);
+}
+
+extern "C" int ll_history_batch_cell_map_stats(ll_history_batch *h, int32_t sequence, int32_t kind, int64_t *n_cells, int64_t *n_points,
+                                               int32_t *frame_idx)
+{
+    if (hb_cells_reader("ll_history_batch_cell_map_stats", h, sequence, kind)) return -1;
+    if (n_cells) *n_cells = h->cm_coff[kind][sequence + 1] - h->cm_coff[kind][sequence];
+    if (n_points) *n_points = h->cm_poff[kind][sequence + 1] - h->cm_poff[kind][sequence];
+    if (frame_idx) *frame_idx = h->cm_frame[kind][sequence];
+    return 0;
+}
+
+extern "C" int ll_history_batch_cell_map_dump(ll_history_batch *h, int32_t sequence, int32_t kind, float *xyzi, int64_t capacity_points,
+                                              int32_t *cell_ijk, int32_t *cell_start, int32_t *cell_last_update, int64_t capacity_cells)
+{
+    static const char *where = "ll_history_batch_cell_map_dump";
+    if (!h) return set_err(where, "null argument");
+    if (h->cm_on && sequence >= 0 && sequence < h->S && kind >= 0 && kind <= 1 && !h->cm_dirty) {  // (sizes known: refuse short buffers before any work)
+        const int np = h->cm_poff[kind][sequence + 1] - h->cm_poff[kind][sequence], nc = h->cm_coff[kind][sequence + 1] - h->cm_coff[kind][sequence];
+        if ((xyzi && capacity_points < np) || ((cell_ijk || cell_start || cell_last_update) && capacity_cells < nc)) return set_err(where, "buffer too small");
+    }
+    if (hb_cells_reader(where, h, sequence, kind)) return -1;
+    const CbDev &m = h->cm[kind];
+    const int p0 = h->cm_poff[kind][sequence], c0 = h->cm_coff[kind][sequence];
+    const int np = h->cm_poff[kind][sequence + 1] - p0, nc = h->cm_coff[kind][sequence + 1] - c0;
+    if ((xyzi && capacity_points < np) || ((cell_ijk || cell_start || cell_last_update) && capacity_cells < nc)) return set_err(where, "buffer too small");
+    if (xyzi && np > 0) HC(hipMemcpy(xyzi, m.pts + p0, (size_t)np * sizeof(float4), hipMemcpyDeviceToHost));
+    if (cell_start) {
+        if (nc > 0)
+            HC(hipMemcpy(cell_start, m.cstart + c0 + sequence, (size_t)(nc + 1) * sizeof(int), hipMemcpyDeviceToHost));
+        else
+            cell_start[0] = 0;
+    }
+    if (cell_last_update && nc > 0) HC(hipMemcpy(cell_last_update, m.clast + c0, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
+    if (cell_ijk && nc > 0) {
+        std::vector<unsigned long long> keys(nc);
+        HC(hipMemcpy(keys.data(), m.ckey + c0, (size_t)nc * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (int i = 0; i < nc; i++) cell_unpack(keys[i], cell_ijk + 3 * (size_t)i);
+    }
+    return 0;
+}
+
+// One slot's map where it lies, in the layout of ll_cellmap_device_view.  Valid until the next add on this handle (which writes behind
+// the store and may move it); the handle's stream has been drained.
+extern "C" int ll_history_batch_cell_map_device_view(ll_history_batch *h, int32_t sequence, int32_t kind, const float **dev_xyz0,
+                                                     const uint64_t **dev_point_keys, int64_t *n_points, int64_t *n_cells)
+{
+    static const char *where = "ll_history_batch_cell_map_device_view";
+    if (!h || !dev_xyz0 || !dev_point_keys || !n_points) return set_err(where, "null argument");
+    if (hb_cells_reader(where, h, sequence, kind)) return -1;
+    const CbDev &m = h->cm[kind];
+    const int p0 = h->cm_poff[kind][sequence];
+    *dev_xyz0 = (const float *)(m.pts + p0);
+    *dev_point_keys = (const uint64_t *)(m.pkey + p0);
+    *n_points = h->cm_poff[kind][sequence + 1] - p0;
+    if (n_cells) *n_cells = h->cm_coff[kind][sequence + 1] - h->cm_coff[kind][sequence];
+    return 0;
+}
+
+extern "C" int ll_history_batch_cell_map_work(ll_history_batch *h, int64_t out[4])
+{
+    static const char *where = "ll_history_batch_cell_map_work";
+    if (!h || !out) return set_err(where, "null argument");
+    if (!h->cm_on) return set_err(where, "cell maps are not enabled (ll_history_batch_enable_cell_maps)");
+    for (int i = 0; i < 4; i++) out[i] = h->cm_work[i];
+    return 0;
 }

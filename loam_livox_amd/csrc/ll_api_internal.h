@@ -24,6 +24,7 @@
 #include "ll_voxel.h"
 #include "ll_spin.h"
 #include "ll_history_batch.h"
+#include "ll_cellmap_batch.h"
 
 using namespace ll;
 

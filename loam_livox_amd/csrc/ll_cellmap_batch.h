@@ -1,0 +1,71 @@
+// ll_cellmap_batch.h -- device side of the cell maps of the batched match buffer (ll_history_batch_enable_cell_maps,
+// ll_cellmap_batch_kernels.hip).  One CbDev per kind (corner, surface) holds the maps of all S slots:
+//   the log      points in arrival order: {x, y, z, 0}, cell key, slot, and the epoch of the point's cell when it went in.  Its
+//                first n_store entries are the store the last materialisation left, ordered by (slot, cell key, insertion).
+//   the table    the occupied cells of all slots, ordered by (slot, cell key): key, slot, last-update stamp, epoch;
+//                slot s owns [coff[s], coff[s + 1]).
+// An append classifies the new points, stamps and resets the cells they hit, merges the new cells into the table and writes the
+// points behind the log: work for the new points and the table, none for the stored points.  A materialisation drops the dead
+// points, orders the rest and rebuilds what a reader of one slot needs (poff, cstart).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ll_cellmap_batch_core.h"
+
+namespace ll {
+
+// one slot of an append
+struct CbSlot {
+    long long off;  // first log position of the slot's points
+    int n;          // its points in the source stack
+    int frame;      // the map's frame counter at the call
+    int active;
+    int pad;
+};
+
+struct CbDev {
+    int S;
+    CellGeom geom;
+    int threshold;
+    // log (cap entries each; the *2 arrays are the targets of the next materialisation)
+    float4 *pts, *pts2;
+    unsigned long long *pkey, *pkey2;
+    int *pslot, *pslot2, *pep, *pep2;
+    size_t cap;
+    long long n_log;
+    // cell table (ccap entries each; the *2 arrays are the targets of the next merge)
+    unsigned long long *ckey, *ckey2;
+    int *cslot, *cslot2, *clast, *clast2, *cep, *cep2;
+    size_t ccap;
+    int n_cells;
+    int *coff, *coff2;  // [S + 1]
+    int *poff;          // [S + 1] first point of every slot in the materialised store
+    int *cstart;        // [ccap + S + 1]: slot s's n_cells(s) + 1 local first-point indices start at coff[s] + s
+    // scratch of an append (acap entries)
+    unsigned long long *akey, *akey2;
+    int *aslot, *aslot2;
+    unsigned int *aflag, *arank;
+    size_t acap;
+    // scratch of a materialisation (mcap entries)
+    unsigned long long *mkey, *mkey2;
+    int *mval, *mval2, *mslot, *mslot2;
+    size_t mcap;
+    void *tmp;
+    size_t tmp_bytes;
+    int *counts;  // [4]: new cells of the last append, cells after it
+    CbSlot *tab;  // [S]
+};
+
+// temporary storage the hipcub calls of an append of n_new points / a materialisation of n_log points need
+int cb_tmp_bytes(long long n, size_t *bytes, const char **err);
+// The append chain of one kind: src [S][src_stride] holds the slots' clouds, m.tab (already on the device) their sizes, log offsets
+// and frame counters; max_n bounds tab[s].n and n_new is their sum over the active slots.  Needs n_log + n_new <= cap,
+// n_cells + n_new <= ccap, n_new <= acap.  Swaps the table arrays; the new cell count is in counts[1], the new coff on the device.
+// *launches += kernel launches and library calls enqueued.
+int cb_append(CbDev &m, const float4 *src, int src_stride, int max_n, long long n_new, hipStream_t s, int *launches, const char **err);
+// The materialise chain of one kind over the n_log logged points (needs n_log <= mcap): swaps the log arrays; the ordered store's
+// size is poff[S] on the device.
+int cb_materialise(CbDev &m, hipStream_t s, int *launches, const char **err);
+
+}  // namespace ll

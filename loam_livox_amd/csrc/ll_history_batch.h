@@ -12,8 +12,10 @@ namespace ll {
 // one slot of an add: the pose its two clouds are moved with and the ring slot the filtered frame goes to
 struct HbAddSlot {
     double pose[7];
-    int work;             // 0: the slot is idle, or its frame is not pushed (nothing is read, nothing is written)
+    int work;             // 0: the slot is idle, or its frame is neither pushed nor wanted by the cell maps (nothing is read, nothing is written)
     int ring;             // ring slot of the frame (0 .. maximum_history_size)
+    int push;             // the filtered frame goes into the ring (without cell maps: wherever work is set)
+    int pad;
 };
 
 // one frame of one kind of one slot in a refresh's concatenation

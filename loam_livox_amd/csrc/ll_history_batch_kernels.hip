@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void hb_scatter_kernel(const float4 *out_c, co
     const int s = blockIdx.y, kind = blockIdx.z;
     const int i = blockIdx.x * 256 + threadIdx.x;
     int n = 0;
-    if (tab[s].work) {
+    if (tab[s].push) {
         n = kind ? n_out_s[s] : n_out_c[s];
         n = n < 0 ? 0 : n;
         n = n < max_pts ? n : max_pts;

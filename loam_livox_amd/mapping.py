@@ -290,9 +290,16 @@ class Laser_mapping_batch:
 
     batched_history=True keeps all histories in ONE History_buffer_batch: the slots a step accepted go through one add and one
     refresh, whose launches and host waits do not grow with n_sequences (no thread pool, no per-sequence handles; refresh_threads is
-    ignored).  Same bits per sequence; histories[s] is then a view of slot s that offers len() and map_cloud(kind)."""
+    ignored).  Same bits per sequence; histories[s] is then a view of slot s that offers len() and map_cloud(kind).
 
-    def __init__(self, n_sequences: int, refresh_threads: int | None = None, batched_history: bool = False, **kw):
+    cell_maps=True (with batched_history=True only) keeps the two cell maps of every sequence on the History_buffer_batch -- the
+    sub-map a sequence hands over at its end, what Laser_mapping(keep_cell_maps=True) keeps for one sequence -- under
+    cell_map_max_points (the points per map the store starts with, 2^18 unless given; it grows), cell_resolution and threshold_cell_revisit.  Every
+    accepted frame is appended; poses and results do not change by a bit.  sync() puts the stores in order, cell_map(s, kind) reads
+    one (stats(), dump(), device_view(device) as api.Cell_map has them).  keep_cell_maps itself stays refused: it names
+    Laser_mapping's per-sequence maps and their service thread."""
+
+    def __init__(self, n_sequences: int, refresh_threads: int | None = None, batched_history: bool = False, cell_maps: bool = False, **kw):
         import inspect
         sig = inspect.signature(Laser_mapping.__init__)
         unknown = set(kw) - set(sig.parameters)
@@ -309,7 +316,9 @@ class Laser_mapping_batch:
         if a["loop_closure_if_enable"]:
             raise ValueError("loop_closure_if_enable must be 0 in the batched loop")
         if a["keep_cell_maps"]:
-            raise ValueError("keep_cell_maps is not offered by the batched loop")
+            raise ValueError("keep_cell_maps is not offered by the batched loop (cell_maps=True keeps them on the batched history)")
+        if cell_maps and not batched_history:
+            raise ValueError("cell_maps=True needs batched_history=True: the cell maps live on the History_buffer_batch")
         if refresh_threads is None:
             refresh_threads = min(4, n_sequences)
         if not 1 <= int(refresh_threads) <= 16:
@@ -321,10 +330,14 @@ class Laser_mapping_batch:
         self.reg = Point_cloud_registration(max_scans=S, max_features=scan_points, device=device)
         self.vox = (VoxelGrid(scan_points, S, device=device), VoxelGrid(scan_points, S, device=device))
         self.maps = [Map_buffer(device=device) for _ in range(S)]
-        self.batched_history = bool(batched_history)
+        self.batched_history, self.cell_maps = bool(batched_history), bool(cell_maps)
         if self.batched_history:
             self.history_batch = History_buffer_batch(S, a["maximum_history_size"], scan_points, a["line_res"], a["plane_res"], device=device)
             self.histories = [_History_slot(self.history_batch, s) for s in range(S)]
+            if cell_maps:  # laser_mapping.hpp:620-624
+                # the stores grow: they start at the points per map the caller names, a quarter of a million otherwise
+                first = max(int(kw.get("cell_map_max_points", 1 << 18)), int(scan_points))
+                self.history_batch.enable_cell_maps(first, a["cell_resolution"], a["threshold_cell_revisit"])
         else:
             self.history_batch = None
             self.histories = [History_buffer(a["maximum_history_size"], scan_points, a["line_res"], a["plane_res"], device=device) for _ in range(S)]
@@ -357,6 +370,16 @@ class Laser_mapping_batch:
             self._pool = None
         for h in [self.fe, self.reg, self.vox[0], self.vox[1]] + self.maps + ([self.history_batch] if self.batched_history else self.histories):
             h.close()
+
+    def sync(self) -> None:
+        """every accepted frame is in the cell maps and their stores are in order (cell_maps=True; otherwise nothing to wait for)"""
+        if self.cell_maps:
+            self.history_batch.sync_cell_maps()
+
+    def cell_map(self, sequence: int, kind: int):
+        if not self.cell_maps:
+            raise ValueError("no cell maps: create the loop with batched_history=True, cell_maps=True")
+        return self.history_batch.cell_map(sequence, kind)
 
     def _upload(self, scans, stamps, active):
         S = self.n_sequences

@@ -20,8 +20,14 @@ lockstep_batched runs Laser_mapping_batch(batched_history=True, cell_maps=True),
 lockstep_batched_plain is lockstep_batched without cell maps from the same call.  The line then also reports the number of
 (sequence, kind) cell-map dumps that differ in any bit between the two routes that keep them (must be 0).
 
+--cell-matching measures the cell ("cube") matching mode: one_by_one runs S Laser_mapping(matching_mode=1) loops, lockstep_batched runs
+Laser_mapping_batch(batched_history=True, cell_maps=True, cell_matching=True); both register every frame against the cells of their
+own map around the current pose (--fov, --search-range).  The line also reports the wall time of the refresh phase per step (for
+one_by_one: summed over the S sequences) and the number of sequences whose poses differ in any bit (must be 0).
+
   python bench_c4_batch.py [--sequences 1,8,64] [--frames 200] [--distinct-frames 100] [--out profiles/bench_c4_batch.json]
   python bench_c4_batch.py --cell-maps --sequences 1,8,64 --out profiles/bench_c4_batch_cell_maps.json
+  python bench_c4_batch.py --cell-matching --sequences 1,8,64 --out profiles/bench_c4_batch_cell_matching.json
   python bench_c4_batch.py --routes lockstep_batched --sequences 8 --frames 12 --repeats 1   # one route alone, e.g. under a kernel trace"""
 import argparse
 import json
@@ -75,12 +81,19 @@ def main():
     ap.add_argument("--routes", default="one_by_one,lockstep,lockstep_batched", help="the routes to run (all three for the JSON line of record)")
     ap.add_argument("--cell-maps", action="store_true", help="keep every sequence's two cell maps: one_by_one, lockstep_batched and lockstep_batched_plain")
     ap.add_argument("--cell-map-points", type=int, default=1 << 19, help="with --cell-maps: cell_map_max_points of both routes (the maps grow from it)")
+    ap.add_argument("--cell-matching", action="store_true", help="the cell matching mode: one_by_one (matching_mode=1) and lockstep_batched (cell_matching=True)")
+    ap.add_argument("--fov", type=float, default=30.0, help="with --cell-matching: maximum_in_fov_angle")
+    ap.add_argument("--search-range", type=float, default=100.0, help="with --cell-matching: maximum_search_range_corner and _surface")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    assert not (args.cell_maps and args.cell_matching), "--cell-maps and --cell-matching are separate measurements"
     S_list = [int(x) for x in args.sequences.split(",")]
     routes = args.routes.split(",")
     if args.cell_maps:  # (the threaded lockstep route keeps no cell maps; the plain batched loop joins the line of record)
         routes = [r for r in routes if r != "lockstep"] + (["lockstep_batched_plain"] if "lockstep_batched" in routes and "one_by_one" in routes else [])
+    if args.cell_matching:  # (the threaded lockstep route has no cell mode; the plain batched loop would not match against cells)
+        assert "lockstep_batched_plain" not in routes, "--cell-matching: routes one_by_one and lockstep_batched"
+        routes = [r for r in routes if r != "lockstep"]
     assert routes and set(routes) <= {"one_by_one", "lockstep", "lockstep_batched", "lockstep_batched_plain"}, "--routes: one_by_one, lockstep, lockstep_batched"
     F, D, N = args.frames, args.distinct_frames, args.scan_points
     assert D >= F or (D % 50 == 0 and D >= 100), "--distinct-frames must be a multiple of 50 and at least 100"
@@ -98,6 +111,8 @@ def main():
     from loam_livox_amd.mapping import Laser_mapping, Laser_mapping_batch
     args_map = dict(maximum_history_size=args.history, init_accumulate_frames=2, line_res=0.1, plane_res=0.15, icp_max_iterations=10,
                     ceres_max_iterations=20, max_allow_incre_R=20.0, max_allow_incre_T=0.3, minimum_icp_R_diff=1e-3, minimum_icp_T_diff=1e-4)
+    cell_mode = dict(maximum_search_range_corner=args.search_range, maximum_search_range_surface=args.search_range, maximum_in_fov_angle=args.fov,
+                     cell_map_max_points=args.cell_map_points) if args.cell_matching else {}
     lines = []
     for S in S_list:
         def dumps_of(cell_map):
@@ -105,7 +120,10 @@ def main():
             return [b"".join(np.ascontiguousarray(a).tobytes() for a in cell_map(kind).dump()) for kind in (0, 1)]
 
         def one_by_one(frames):
-            lms = [Laser_mapping(scan_points=N, keep_cell_maps=args.cell_maps, cell_map_max_points=args.cell_map_points, **args_map) for _ in range(S)]
+            if args.cell_matching:
+                lms = [Laser_mapping(scan_points=N, matching_mode=1, **cell_mode, **args_map) for _ in range(S)]
+            else:
+                lms = [Laser_mapping(scan_points=N, keep_cell_maps=args.cell_maps, cell_map_max_points=args.cell_map_points, **args_map) for _ in range(S)]
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             poses, accepted = [], 0
@@ -123,12 +141,14 @@ def main():
             dumps = [dumps_of(lm.history.cell_map) for lm in lms] if args.cell_maps else None
             for lm in lms:
                 lm.close()
-            return dt, poses, accepted, stage, None, dumps
+            return dt, poses, accepted, stage, None, dumps, [tuple(lm.map_sizes) for lm in lms]
 
-        def lockstep(frames, batched_history=False, cell_maps=False):
+        def lockstep(frames, batched_history=False, cell_maps=False, cell_matching=False):
             kw = dict(refresh_threads=args.refresh_threads) if args.refresh_threads else {}
             if batched_history:
                 kw["batched_history"] = True
+            if cell_matching:
+                kw.update(cell_maps=True, cell_matching=True, **cell_mode)
             if cell_maps:
                 kw.update(cell_maps=True, cell_map_max_points=args.cell_map_points)
             lb = Laser_mapping_batch(S, scan_points=N, **kw, **args_map)
@@ -144,12 +164,12 @@ def main():
                 lb.sync()  # (the stores are in order, ready to be handed over: inside the timed region)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            stage, threads = lb.stage_s.copy(), lb.refresh_threads
+            stage, threads, sizes = lb.stage_s.copy(), lb.refresh_threads, [tuple(x) for x in lb.map_sizes]
             dumps = [dumps_of(lambda kind, s=s: lb.cell_map(s, kind)) for s in range(S)] if cell_maps else None
             lb.close()
-            return dt, [np.stack(p) for p in poses], accepted, stage, threads, dumps
+            return dt, [np.stack(p) for p in poses], accepted, stage, threads, dumps, sizes
 
-        run = {"one_by_one": one_by_one, "lockstep": lockstep, "lockstep_batched": lambda frames: lockstep(frames, True, args.cell_maps),
+        run = {"one_by_one": one_by_one, "lockstep": lockstep, "lockstep_batched": lambda frames: lockstep(frames, True, args.cell_maps, args.cell_matching),
                "lockstep_batched_plain": lambda frames: lockstep(frames, True)}
         for r in routes:
             run[r](min(6, F))  # warm-up: code objects load lazily, the ICP kernels first run on frame 3
@@ -170,6 +190,14 @@ def main():
             return {"extract_register": round(1e3 * float(st[0]) / F, 4), "history_add_and_refresh": round(1e3 * float(st[4]) / F, 4)}
 
         line = {"metric": "frames_per_s", "sequences": S, "frames_per_sequence": F, "scan_points": N, "cell_maps": bool(args.cell_maps)}
+        if args.cell_matching:
+            line.update(cell_matching=True, maximum_in_fov_angle=args.fov, maximum_search_range=args.search_range)
+            if "one_by_one" in routes:
+                line["refresh_ms_per_step_one_by_one"] = round(1e3 * float(last["one_by_one"][3][2]) / F, 4)
+                line["match_buffer_points_last_frame_one_by_one"] = [int(x) for x in np.sum(last["one_by_one"][6], axis=0)]
+            if "lockstep_batched" in routes:
+                line["refresh_ms_per_step_lockstep_batched"] = round(1e3 * float(last["lockstep_batched"][3][2]) / F, 4)
+                line["match_buffer_points_last_frame"] = [int(x) for x in np.sum(last["lockstep_batched"][6], axis=0)]
         if "one_by_one" in routes:
             line["one_by_one"] = dict(rate("one_by_one"), ms_per_frame_by_stage=dict(zip(("extract_register", "history_add", "match_buffer_refresh"),
                                                                                        [round(1e3 * float(v) / n, 4) for v in last["one_by_one"][3][:3]])))

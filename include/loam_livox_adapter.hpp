@@ -631,6 +631,18 @@ class History_batch {
     {
         check(ll_history_batch_refresh(h_, maps, active, n_corner, n_surf), "ll_history_batch_refresh");
     }
+    // update_buff_for_matching() with m_matching_mode == 1 for every active slot, at poses [n_sequences][7]: the cells of the slot's cell
+    // maps in range and in the field of view, each through the VoxelGrid (and replaced by its leaves with m_down_sample_replace),
+    // concatenated, filtered, published into maps[s].  Needs enable_cell_maps().
+    void refresh_cells(ll_map *const *maps, const double *poses, const int32_t *active = nullptr, float m_maximum_search_range_corner = 100.0f,
+                       float m_maximum_search_range_surface = 100.0f, float m_maximum_in_fov_angle = 30.0f, int m_down_sample_replace = 1,
+                       int64_t *n_corner = nullptr, int64_t *n_surf = nullptr)
+    {
+        check(ll_history_batch_refresh_cells(h_, maps, active, poses, m_maximum_search_range_corner, m_maximum_search_range_surface,
+                                             m_maximum_in_fov_angle, m_down_sample_replace, n_corner, n_surf),
+              "ll_history_batch_refresh_cells");
+    }
+    void cell_match_work(int64_t out[8]) { check(ll_history_batch_cell_match_work(h_, out), "ll_history_batch_cell_match_work"); }
     template <class Cloud>
     void map_cloud(int sequence, int kind, Cloud &out)
     {

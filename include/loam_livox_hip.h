@@ -447,6 +447,37 @@ int ll_history_batch_cell_map_dump(ll_history_batch *h, int32_t sequence, int32_
 int ll_history_batch_cell_map_device_view(ll_history_batch *h, int32_t sequence, int32_t kind, const float **dev_xyz0,
                                           const uint64_t **dev_point_keys, int64_t *n_points, int64_t *n_cells);
 int ll_history_batch_cell_map_work(ll_history_batch *h, int64_t out[4]);
+/* The cell ("cube") matching mode for all slots: update_buff_for_matching with m_matching_mode == 1 (laser_mapping.hpp:471-513,
+ * 533-546), per slot what ll_history_refresh_cells does for one sequence.  Needs ll_history_batch_enable_cell_maps.  For every ACTIVE
+ * slot s: the cells of its two cell maps whose centre lies within maximum_search_range_corner / _surface of the translation of
+ * poses7[s] and inside maximum_in_fov_angle (>= 360: no field-of-view test) of its rotation are selected; every selected cell goes
+ * through the VoxelGrid (leaf line_res / plane_res) on its own; the leaves are concatenated in cell-key order, filtered once more
+ * and published as the search grids of maps[s], as ll_history_batch_refresh publishes its concatenations.  With down_sample_replace
+ * != 0 the leaves replace the points of their cell (the last-update stamps stay).  ll_history_batch_map_cloud then returns the
+ * cell-mode buffer; an inactive slot keeps its maps, its buffer and its stored points.
+ * Cost: per kind one chain of launches over all slots that selects in the cell tables, streams the log once for the live points of
+ * the selected cells, moves those candidates' (key, position) pairs to the front and sorts them -- padded to the log's length, as
+ * the sort's size must be known on the host without a wait, so the sort is as long as the log; no stored point is read or moved by
+ * it.  A replace gives the selected cells a new epoch and writes their leaves behind the log, after the new maps are published, so
+ * dead entries accumulate: the handle materialises by itself after a refresh that leaves more dead entries than live
+ * ones, which keeps  log entries <= 2 * live entries + the entries of one step.  Host waits per refresh: one for the leaf counts of
+ * both kinds and the two of ll_history_batch_refresh's second half (plus one when it compacts, and one per growth of a store).
+ * Refused before anything is changed, with the handle still usable: null handle, maps or poses7, cell maps not enabled, a negative
+ * range, a leaf so small that a cell spans more than 1020 leaves, a null map in an active slot, a map on another device or twice,
+ * and a slot whose selected cells hold more leaves than its match buffer (maximum_history_size * max_points_per_frame points): the
+ * error names slot, size and capacity.  Any later failure up to the publication of the maps (an allocation, a device error) also
+ * leaves the stored points and epochs as they were: the replace is enqueued only after the maps are published.  A failure after
+ * the publication (the launch of the replace, a compaction) returns -1 with the new maps in place; the replace is then applied for
+ * none, one or both kinds, each kind whole, and the stores stay readable.
+ * ll_history_batch_cell_match_work is a test tap: out[0] enqueues (launches, library calls, copies) of the cell-mode part of the last
+ * refresh, the replace included, out[1] the host waits of the refresh proper including the second half's (a compaction or a growth
+ * of a store waits on top and is not counted), out[2] compactions so far, out[3] / out[4] log entries and live entries
+ * of the corner stores after the last refresh, out[5] / out[6] of the surface stores, out[7] candidates of the last refresh. */
+int ll_history_batch_refresh_cells(ll_history_batch *h, ll_map *const *maps, const int32_t *active, const double *poses7,
+                                   float maximum_search_range_corner, float maximum_search_range_surface,
+                                   float maximum_in_fov_angle, int32_t down_sample_replace,
+                                   int64_t *n_map_corner, int64_t *n_map_surf);
+int ll_history_batch_cell_match_work(ll_history_batch *h, int64_t out[8]);
 /* Host arithmetic only (no device needed): the geometry ll_map_upload and both refreshes give the search grid over the bounding
  * box {min x, y, z, max x, y, z} of a cloud's finite points (min > max: no finite point) with cells of cell_size metres.  The
  * cell grows by 1.5 x until the dense table has at most 2^27 cells. */

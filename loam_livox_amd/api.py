@@ -484,6 +484,29 @@ class History_buffer_batch:
         check(self.L.ll_history_batch_refresh(self.h, arr, ptr(act), ptr(nc), ptr(ns)), "ll_history_batch_refresh")
         return nc, ns
 
+    def refresh_cells(self, maps, poses, active=None, maximum_search_range_corner: float = 100.0, maximum_search_range_surface: float = 100.0,
+                      maximum_in_fov_angle: float = 30.0, down_sample_replace: int = 1):
+        """update_buff_for_matching in the cell mode (m_matching_mode == 1) for every active slot, at poses [S][7]: the cells in range
+        and in the field of view, each through the VoxelGrid (and replaced by its leaves with down_sample_replace), concatenated,
+        filtered, published into maps[s].  Needs enable_cell_maps.  Returns (n_corner [S], n_surf [S])."""
+        S = self.n_sequences
+        if len(maps) != S:
+            raise ValueError(f"{len(maps)} maps for {S} sequences")
+        act = None if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.int32).reshape(S)
+        poses = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(S, 7)
+        arr = (C.c_void_p * S)(*[None if m is None else m.h for m in maps])
+        nc, ns = np.zeros(S, np.int64), np.zeros(S, np.int64)
+        check(self.L.ll_history_batch_refresh_cells(self.h, arr, ptr(act), ptr(poses), maximum_search_range_corner, maximum_search_range_surface,
+                                                    maximum_in_fov_angle, int(down_sample_replace), ptr(nc), ptr(ns)), "ll_history_batch_refresh_cells")
+        return nc, ns
+
+    def cell_match_work(self) -> np.ndarray:
+        """test tap (ll_history_batch_cell_match_work): enqueues and host waits of the last refresh_cells, compactions so far, log and live
+        entries of the corner and of the surface stores, candidates of the last refresh"""
+        out = np.zeros(8, np.int64)
+        check(self.L.ll_history_batch_cell_match_work(self.h, ptr(out)), "ll_history_batch_cell_match_work")
+        return out
+
     def size(self, sequence: int) -> int:
         return int(self.L.ll_history_batch_size(self.h, sequence))
 

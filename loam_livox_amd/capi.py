@@ -130,6 +130,8 @@ SYMBOLS = {
     "ll_history_batch_cell_map_dump": (_i32, [_vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64]),
     "ll_history_batch_cell_map_device_view": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ll_history_batch_cell_map_work": (_i32, [_vp, _vp]),
+    "ll_history_batch_refresh_cells": (_i32, [_vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, _vp, _vp]),
+    "ll_history_batch_cell_match_work": (_i32, [_vp, _vp]),
     "ll_map_grid_geometry": (_i32, [_vp, _f, _vp, _vp, _vp]),
     "ll_cellmap_create": (_i32, [_i32, _i64, C.c_float, _i32, _vp]),
     "ll_cellmap_destroy": (None, [_vp]),

@@ -9,6 +9,7 @@
 // appends its filtered frame to them, through one more fixed chain whose work is that of the new points and the cell tables
 // (ll_cellmap_batch_kernels.hip); the stored points are put in order when somebody reads.
 #include "ll_api_internal.h"
+#include "ll_cellmatch_batch.h"
 
 struct HbArena {
     int device = 0;
@@ -59,6 +60,11 @@ struct ll_history_batch {
     CbSlot *hp_cm_tab = nullptr;             // pinned [2][S]
     int *hp_cm = nullptr;                    // pinned: filtered counts [2][S], coff [2][S + 1], poff [2][S + 1], counts [2][4]
     int64_t cm_work[4] = {0, 0, 0, 0};       // ll_history_batch_cell_map_work
+    // the cell-mode refresh (ll_history_batch_refresh_cells): scratch per kind, the slots' poses, the drained counts
+    CmbDev cq[2]{};
+    CmbSlot *hp_cq_tab = nullptr, *d_cq_tab = nullptr;  // [S]
+    int *hp_cq = nullptr;                    // pinned [2][S + 4]: first leaf of every slot, leaves, candidates, live entries
+    int64_t cq_work[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // ll_history_batch_cell_match_work
 };
 
 // grow-only device buffer, half again as large as asked when it has to move
@@ -83,6 +89,14 @@ static void hb_cells_free(CbDev &m)
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     memset(&m, 0, sizeof(m));
+}
+
+static void hb_cellmatch_free(CmbDev &q)
+{
+    void *ptrs[] = {q.csel, q.cflag, q.crank, q.ccell, q.key, q.key2, q.val, q.val2, q.hflag, q.hrank, q.head, q.leaf, q.leaf_cell, q.out, q.tmp};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    memset(&q, 0, sizeof(q));
 }
 
 static int history_batch_create_impl(ll_history_batch *h)
@@ -140,7 +154,9 @@ extern "C" void ll_history_batch_destroy(ll_history_batch *h)
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (int k = 0; k < 2; k++) hb_cells_free(h->cm[k]);
-    void *host[] = {h->hp_add, h->hp_cnt, h->hp_ref, h->hp_mm_init, h->hp_mm, h->hp_grid, h->hp_nvalid, h->hp_cm_tab, h->hp_cm};
+    for (int k = 0; k < 2; k++) hb_cellmatch_free(h->cq[k]);
+    if (h->d_cq_tab) (void)hipFree(h->d_cq_tab);
+    void *host[] = {h->hp_add, h->hp_cnt, h->hp_ref, h->hp_mm_init, h->hp_mm, h->hp_grid, h->hp_nvalid, h->hp_cm_tab, h->hp_cm, h->hp_cq_tab, h->hp_cq};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
     h->arenas.clear();  // (an arena still referenced by a published or pinned snapshot dies with that snapshot)
@@ -457,14 +473,11 @@ extern "C" int ll_history_batch_add_fe(ll_history_batch *h, ll_fe *fe, const int
     return history_batch_add_common(where, h, feat_view(fe), active, poses7, gate_poses7, history_add_t_step, history_add_angle_step, added);
 }
 
-extern "C" int ll_history_batch_refresh(ll_history_batch *h, ll_map *const *maps, const int32_t *active, int64_t *n_map_corner,
-                                        int64_t *n_map_surf)
+// what a refresh checks before it touches anything: a map of the handle's device in every active slot, none of them twice
+static int hb_check_maps(const char *where, const ll_history_batch *h, ll_map *const *maps, const int32_t *active, bool *any)
 {
-    static const char *where = "ll_history_batch_refresh";
-    if (!h || !maps) return set_err(where, "null argument");
-    const int S = h->S;
     std::vector<const ll_map *> seen;
-    for (int s = 0; s < S; s++) {
+    for (int s = 0; s < h->S; s++) {
         if (active && !active[s]) continue;
         if (!maps[s]) return set_err(where, "null map in an active slot");
         if (maps[s]->device != h->device) return set_err(where, "map lives on another device");
@@ -472,14 +485,31 @@ extern "C" int ll_history_batch_refresh(ll_history_batch *h, ll_map *const *maps
     }
     std::sort(seen.begin(), seen.end());
     if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return set_err(where, "the same map in two active slots");
-    auto sizes_out = [&]() {
-        for (int s = 0; s < S; s++) {
-            if (n_map_corner) n_map_corner[s] = h->n_map[0][s];
-            if (n_map_surf) n_map_surf[s] = h->n_map[1][s];
-        }
-    };
-    if (seen.empty()) {
-        sizes_out();
+    *any = !seen.empty();
+    return 0;
+}
+
+static void hb_sizes_out(const ll_history_batch *h, int64_t *n_map_corner, int64_t *n_map_surf)
+{
+    for (int s = 0; s < h->S; s++) {
+        if (n_map_corner) n_map_corner[s] = h->n_map[0][s];
+        if (n_map_surf) n_map_surf[s] = h->n_map[1][s];
+    }
+}
+
+static int hb_refresh_second_half(const char *where, ll_history_batch *h, ll_map *const *maps, const int max_cat[2], const int cat_stride[2],
+                                  int64_t *n_map_corner, int64_t *n_map_surf);
+
+extern "C" int ll_history_batch_refresh(ll_history_batch *h, ll_map *const *maps, const int32_t *active, int64_t *n_map_corner,
+                                        int64_t *n_map_surf)
+{
+    static const char *where = "ll_history_batch_refresh";
+    if (!h || !maps) return set_err(where, "null argument");
+    const int S = h->S;
+    bool any = false;
+    if (hb_check_maps(where, h, maps, active, &any)) return -1;
+    if (!any) {
+        hb_sizes_out(h, n_map_corner, n_map_surf);
         return 0;
     }
     HC(hipSetDevice(h->device));
@@ -519,8 +549,19 @@ extern "C" int ll_history_batch_refresh(ll_history_batch *h, ll_map *const *maps
     }
     HC(hipMemcpyAsync(h->d_ref, h->hp_ref, h->ref_seg_off + (size_t)n_seg * sizeof(HbSeg), hipMemcpyHostToDevice, h->stream));
     HC(hipMemcpyAsync(h->d_mm, h->hp_mm_init, (size_t)2 * S * 8 * sizeof(unsigned int), hipMemcpyHostToDevice, h->stream));
-    const int *d_active = (const int *)h->d_ref, *d_ncat = d_active + S;
     launch_hb_gather_frames(h->frames[0], h->frames[1], (const HbSeg *)(h->d_ref + h->ref_seg_off), n_seg, h->max_pts, h->d_concat, h->stream);
+    return hb_refresh_second_half(where, h, maps, max_cat, cat_stride, n_map_corner, n_map_surf);
+}
+
+// The second half of a refresh, shared by the history mode and the cell mode: the VoxelGrid over the concatenations
+// (laser_mapping.hpp:533-537; h->d_concat holds them per kind as [S][cat_stride[kind]], the tables of the call are on their way to
+// h->d_ref), then the search grids of all active slots in one arena, published into maps[s].  Two host waits.
+static int hb_refresh_second_half(const char *where, ll_history_batch *h, ll_map *const *maps, const int max_cat[2], const int cat_stride[2],
+                                  int64_t *n_map_corner, int64_t *n_map_surf)
+{
+    const int S = h->S;
+    const int *t_active = (const int *)h->hp_ref;
+    const int *d_active = (const int *)h->d_ref, *d_ncat = d_active + S;
     const char *err = nullptr;
     for (int k = 0; k < 2; k++) {
         const float leaf[3] = {h->res[k], h->res[k], h->res[k]};
@@ -618,7 +659,7 @@ extern "C" int ll_history_batch_refresh(ll_history_batch *h, ll_map *const *maps
         (void)map_publish(maps[s], k, sn);
         h->n_map[k][s] = t.n;
     }
-    sizes_out();
+    hb_sizes_out(h, n_map_corner, n_map_surf);
     return 0;
 }
 
@@ -765,5 +806,165 @@ extern "C" int ll_history_batch_cell_map_work(ll_history_batch *h, int64_t out[4
     if (!h || !out) return set_err(where, "null argument");
     if (!h->cm_on) return set_err(where, "cell maps are not enabled (ll_history_batch_enable_cell_maps)");
     for (int i = 0; i < 4; i++) out[i] = h->cm_work[i];
+    return 0;
+}
+
+
+// ================================================================================================ the cell-mode refresh
+// scratch of one kind for a store of n_log logged points and n_cells table entries (the stream is idle)
+static int hb_cellmatch_reserve(ll_history_batch *h, CmbDev &q, long long n_log, int n_cells)
+{
+    if (!q.out) DM(q.out, (size_t)h->S + 4);
+    if ((long long)q.ncap < n_log) {
+        const size_t n = (size_t)(n_log + n_log / 2 + 16);
+        if (hb_cells_move(h, &q.cflag, n, 0) || hb_cells_move(h, &q.crank, n, 0) || hb_cells_move(h, &q.ccell, n, 0) || hb_cells_move(h, &q.key, n, 0) ||
+            hb_cells_move(h, &q.key2, n, 0) || hb_cells_move(h, &q.val, n, 0) || hb_cells_move(h, &q.val2, n, 0) || hb_cells_move(h, &q.hflag, n, 0) ||
+            hb_cells_move(h, &q.hrank, n, 0) || hb_cells_move(h, &q.head, n, 0) || hb_cells_move(h, &q.leaf, n, 0) || hb_cells_move(h, &q.leaf_cell, n, 0))
+            return -1;
+        q.ncap = n;
+    }
+    if (q.ccap < (size_t)n_cells) {
+        const size_t n = (size_t)n_cells + (size_t)n_cells / 2 + 16;
+        if (hb_cells_move(h, &q.csel, n, 0)) return -1;
+        q.ccap = n;
+    }
+    size_t bytes = 0;
+    const char *err = nullptr;
+    if (cmb_tmp_bytes(n_log, &bytes, &err)) return set_err("ll_history_batch_refresh_cells", err);
+    if (bytes > q.tmp_bytes) {
+        char *p = (char *)q.tmp;
+        if (hb_cells_move(h, &p, bytes + bytes / 2, 0)) return -1;
+        q.tmp = p;
+        q.tmp_bytes = bytes + bytes / 2;
+    }
+    return 0;
+}
+
+// update_buff_for_matching with m_matching_mode == 1 (laser_mapping.hpp:471-546) for all slots: per kind one chain over the deferred
+// store (ll_cellmatch_batch_kernels.hip), one drain for the leaf counts of both kinds, the checks, then the scatter into the
+// concatenation buffers, the replace, and the second half of ll_history_batch_refresh.
+extern "C" int ll_history_batch_refresh_cells(ll_history_batch *h, ll_map *const *maps, const int32_t *active, const double *poses7,
+                                              float maximum_search_range_corner, float maximum_search_range_surface,
+                                              float maximum_in_fov_angle, int32_t down_sample_replace, int64_t *n_map_corner,
+                                              int64_t *n_map_surf)
+{
+    static const char *where = "ll_history_batch_refresh_cells";
+    if (!h || !maps) return set_err(where, "null argument");
+    if (!h->cm_on) return set_err(where, "cell maps are not enabled (ll_history_batch_enable_cell_maps)");
+    if (!poses7) return set_err(where, "null argument (poses7)");
+    const float range[2] = {maximum_search_range_corner, maximum_search_range_surface};
+    if (!(range[0] >= 0.f) || !(range[1] >= 0.f)) return set_err(where, "a search range must not be negative");
+    for (int k = 0; k < 2; k++)
+        if (!cmb_leaf_fits(h->cm[k].geom, h->res[k]))
+            return set_err(where, "leaf size too small for the cell size (more than 1020 leaves across one cell)");
+    const int S = h->S;
+    bool any = false;
+    if (hb_check_maps(where, h, maps, active, &any)) return -1;
+    if (!any) {
+        hb_sizes_out(h, n_map_corner, n_map_surf);
+        return 0;
+    }
+    HC(hipSetDevice(h->device));
+    if (!h->hp_cq) {
+        HC(hipHostMalloc((void **)&h->hp_cq_tab, (size_t)S * sizeof(CmbSlot), hipHostMallocDefault));
+        HC(hipHostMalloc((void **)&h->hp_cq, 2 * ((size_t)S + 4) * sizeof(int), hipHostMallocDefault));
+        DM(h->d_cq_tab, (size_t)S);
+    }
+    int *t_active = (int *)h->hp_ref, *t_ncat = t_active + S;
+    for (int s = 0; s < S; s++) {
+        CmbSlot &t = h->hp_cq_tab[s];
+        memset(&t, 0, sizeof(t));
+        t.active = t_active[s] = (!active || active[s]) ? 1 : 0;
+        for (int i = 0; t.active && i < 7; i++) t.pose[i] = poses7[7 * (size_t)s + i];
+    }
+    bool run[2];
+    for (int k = 0; k < 2; k++) {
+        run[k] = h->cm[k].n_log > 0 && h->cm[k].n_cells > 0;
+        if (run[k] && hb_cellmatch_reserve(h, h->cq[k], h->cm[k].n_log, h->cm[k].n_cells)) return -1;
+    }
+    // ---- per kind: select, candidates, per-cell VoxelGrid, counts; one copy each, one drain for both
+    int enq = 0, waits = 0;
+    const char *err = nullptr;
+    memset(h->hp_cq, 0, 2 * ((size_t)S + 4) * sizeof(int));
+    HC(hipMemcpyAsync(h->d_cq_tab, h->hp_cq_tab, (size_t)S * sizeof(CmbSlot), hipMemcpyHostToDevice, h->stream));
+    enq++;
+    for (int k = 0; k < 2; k++) {
+        if (!run[k]) continue;
+        if (cmb_query(h->cm[k], h->cq[k], h->d_cq_tab, range[k], maximum_in_fov_angle, h->res[k], h->stream, &enq, &err)) return set_err(where, err);
+        HC(hipMemcpyAsync(h->hp_cq + (size_t)k * (S + 4), h->cq[k].out, ((size_t)S + 3) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        enq++;
+    }
+    HC(hipStreamSynchronize(h->stream));
+    waits++;
+    // ---- the checks, before anything is changed
+    int max_cat[2] = {0, 0}, n_leaves[2] = {0, 0};
+    long long n_cand[2] = {0, 0}, n_live[2] = {0, 0};
+    for (int k = 0; k < 2; k++) {
+        const int *loff = h->hp_cq + (size_t)k * (S + 4);
+        n_leaves[k] = loff[S];
+        n_cand[k] = loff[S + 1];
+        n_live[k] = loff[S + 2];
+        for (int s = 0; s < S; s++) {
+            const int n = loff[s + 1] - loff[s];
+            if (n < 0 || (!t_active[s] && n != 0)) return set_err(where, "leaf counts out of range");
+            if ((size_t)n > h->cstride) {
+                char msg[200];
+                snprintf(msg, sizeof(msg), "the cells selected for slot %d hold %d %s leaves, the match buffer of a slot holds %zu points "
+                         "(maximum_history_size * max_points_per_frame)", s, n, k ? "surface" : "corner", h->cstride);
+                return set_err(where, msg);
+            }
+            t_ncat[k * S + s] = n;
+            max_cat[k] = n > max_cat[k] ? n : max_cat[k];
+        }
+        if (down_sample_replace && h->cm[k].n_log + n_leaves[k] >= kCbLimit) return set_err(where, "the cell maps would pass 2^31 stored points per kind");
+    }
+    if (down_sample_replace)
+        for (int k = 0; k < 2; k++)
+            if (n_leaves[k] > 0 && hb_cells_reserve_log(h, h->cm[k], h->cm[k].n_log + n_leaves[k])) return -1;
+    const int cat_stride[2] = {max_cat[0] > 0 ? max_cat[0] : 1, max_cat[1] > 0 ? max_cat[1] : 1};
+    // ---- the leaves into the concatenations (:496-512)
+    HC(hipMemcpyAsync(h->d_ref, h->hp_ref, h->ref_seg_off, hipMemcpyHostToDevice, h->stream));
+    HC(hipMemcpyAsync(h->d_mm, h->hp_mm_init, (size_t)2 * S * 8 * sizeof(unsigned int), hipMemcpyHostToDevice, h->stream));
+    enq += 2;
+    for (int k = 0; k < 2; k++)
+        if (run[k] && cmb_scatter(h->cm[k], h->cq[k], n_leaves[k], h->d_concat + (size_t)k * S * h->cstride, cat_stride[k], h->stream, &enq, &err))
+            return set_err(where, err);
+    // The stores are still as they were: a second half that fails (an allocation, a size out of range) leaves no replace behind.
+    if (hb_refresh_second_half(where, h, maps, max_cat, cat_stride, n_map_corner, n_map_surf)) return -1;
+    waits += 2;
+    // ---- the replace (:492-495), once the maps are published; the second half uses none of the chain's scratch
+    for (int k = 0; k < 2; k++) {
+        if (!run[k] || !down_sample_replace || n_leaves[k] <= 0) continue;
+        if (cmb_replace(h->cm[k], h->cq[k], n_leaves[k], h->stream, &enq, &err)) return set_err(where, err);
+        n_live[k] += n_leaves[k] - n_cand[k];
+        h->cm_dirty = true;  // (dead entries in the log: a reader puts the stores in order first)
+    }
+    h->cq_work[0] = enq;
+    h->cq_work[1] = waits;
+    h->cq_work[7] = n_cand[0] + n_cand[1];
+    for (int k = 0; k < 2; k++) {
+        h->cq_work[3 + 2 * k] = h->cm[k].n_log;
+        h->cq_work[4 + 2 * k] = run[k] ? n_live[k] : 0;
+    }
+    // ---- the handle puts the stores in order by itself once the dead entries outnumber the live ones
+    if (h->cm_dirty && ((run[0] && cmb_compact_now(h->cm[0].n_log, n_live[0])) || (run[1] && cmb_compact_now(h->cm[1].n_log, n_live[1])))) {
+        if (hb_cells_materialise(where, h)) return -1;
+        h->cq_work[2]++;
+        for (int k = 0; k < 2; k++) h->cq_work[3 + 2 * k] = h->cq_work[4 + 2 * k] = h->cm[k].n_log;
+    }
+    return 0;
+}
+
+// Test tap of the cell-mode refresh: [0] enqueues (launches, library calls, copies) of the cell-mode part of the last refresh, the
+// replace included, ll_history_batch_refresh's second half not, [1] the host waits of the refresh proper, second half included --
+// a compaction or a growth of the log waits on top and is not counted here, [2] compactions so far (each costs a materialisation
+// and its wait), [3] / [4] log entries and live entries of the corner stores after the last
+// refresh, [5] / [6] of the surface stores, [7] candidates of the last refresh, both kinds.
+extern "C" int ll_history_batch_cell_match_work(ll_history_batch *h, int64_t out[8])
+{
+    static const char *where = "ll_history_batch_cell_match_work";
+    if (!h || !out) return set_err(where, "null argument");
+    if (!h->cm_on) return set_err(where, "cell maps are not enabled (ll_history_batch_enable_cell_maps)");
+    for (int i = 0; i < 8; i++) out[i] = h->cq_work[i];
     return 0;
 }

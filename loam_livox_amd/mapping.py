@@ -285,8 +285,8 @@ class Laser_mapping_batch:
 
     Per sequence this is Laser_mapping._process_new_scan line for line -- the frame index handed to the gate, the gate pose of the
     add rule, the repeat of an aborted grouped solve on one workgroup -- and gives the same bits as a Laser_mapping run alone on that
-    sequence.  Takes the arguments of Laser_mapping; Livox scans in history mode only: lidar_type other than "livox", matching_mode,
-    loop_closure_if_enable and keep_cell_maps raise ValueError.
+    sequence.  Takes the arguments of Laser_mapping; Livox scans only, in history mode unless cell_matching=True (below): lidar_type
+    other than "livox", matching_mode, loop_closure_if_enable and keep_cell_maps raise ValueError.
 
     batched_history=True keeps all histories in ONE History_buffer_batch: the slots a step accepted go through one add and one
     refresh, whose launches and host waits do not grow with n_sequences (no thread pool, no per-sequence handles; refresh_threads is
@@ -297,9 +297,15 @@ class Laser_mapping_batch:
     cell_map_max_points (the points per map the store starts with, 2^18 unless given; it grows), cell_resolution and threshold_cell_revisit.  Every
     accepted frame is appended; poses and results do not change by a bit.  sync() puts the stores in order, cell_map(s, kind) reads
     one (stats(), dump(), device_view(device) as api.Cell_map has them).  keep_cell_maps itself stays refused: it names
-    Laser_mapping's per-sequence maps and their service thread."""
+    Laser_mapping's per-sequence maps and their service thread.
 
-    def __init__(self, n_sequences: int, refresh_threads: int | None = None, batched_history: bool = False, cell_maps: bool = False, **kw):
+    cell_matching=True (with cell_maps=True only) registers against those cell maps: the step's one refresh becomes one refresh_cells
+    at the accepted slots' new poses -- the cells within maximum_search_range_corner / _surface and maximum_in_fov_angle, each through
+    the VoxelGrid, replaced by their leaves with down_sample_replace -- which is Laser_mapping(matching_mode=1) per sequence, bit for
+    bit.  matching_mode itself stays refused: it names Laser_mapping's per-sequence route."""
+
+    def __init__(self, n_sequences: int, refresh_threads: int | None = None, batched_history: bool = False, cell_maps: bool = False,
+                 cell_matching: bool = False, **kw):
         import inspect
         sig = inspect.signature(Laser_mapping.__init__)
         unknown = set(kw) - set(sig.parameters)
@@ -312,13 +318,16 @@ class Laser_mapping_batch:
         if a["lidar_type"] != "livox":
             raise ValueError(f'lidar_type "{a["lidar_type"]}": the batched loop takes Livox scans only')
         if a["matching_mode"]:
-            raise ValueError("matching_mode must be 0: the batched loop matches against the history buffers only")
+            raise ValueError("matching_mode is not offered by the batched loop (cell_maps=True, cell_matching=True matches against the cell "
+                             "maps on the batched history)")
         if a["loop_closure_if_enable"]:
             raise ValueError("loop_closure_if_enable must be 0 in the batched loop")
         if a["keep_cell_maps"]:
             raise ValueError("keep_cell_maps is not offered by the batched loop (cell_maps=True keeps them on the batched history)")
         if cell_maps and not batched_history:
             raise ValueError("cell_maps=True needs batched_history=True: the cell maps live on the History_buffer_batch")
+        if cell_matching and not cell_maps:
+            raise ValueError("cell_matching=True needs cell_maps=True: the cell mode matches against the cell maps of the History_buffer_batch")
         if refresh_threads is None:
             refresh_threads = min(4, n_sequences)
         if not 1 <= int(refresh_threads) <= 16:
@@ -330,7 +339,9 @@ class Laser_mapping_batch:
         self.reg = Point_cloud_registration(max_scans=S, max_features=scan_points, device=device)
         self.vox = (VoxelGrid(scan_points, S, device=device), VoxelGrid(scan_points, S, device=device))
         self.maps = [Map_buffer(device=device) for _ in range(S)]
-        self.batched_history, self.cell_maps = bool(batched_history), bool(cell_maps)
+        self.batched_history, self.cell_maps, self.cell_matching = bool(batched_history), bool(cell_maps), bool(cell_matching)
+        self.m_maximum_search_range = (a["maximum_search_range_corner"], a["maximum_search_range_surface"])
+        self.m_maximum_in_fov_angle, self.m_down_sample_replace = a["maximum_in_fov_angle"], a["down_sample_replace"]
         if self.batched_history:
             self.history_batch = History_buffer_batch(S, a["maximum_history_size"], scan_points, a["line_res"], a["plane_res"], device=device)
             self.histories = [_History_slot(self.history_batch, s) for s in range(S)]
@@ -427,7 +438,12 @@ class Laser_mapping_batch:
         else:
             hb.add_fe(self.fe, new, gate, on, self.history_add_t_step, self.history_add_angle_step)
         t1 = time.perf_counter()
-        nc, ns = hb.refresh([self.maps[s] if on[s] else None for s in range(S)], on)
+        maps = [self.maps[s] if on[s] else None for s in range(S)]
+        if self.cell_matching:  # update_buff_for_matching with m_matching_mode == 1, at the poses the step just accepted
+            nc, ns = hb.refresh_cells(maps, new, on, self.m_maximum_search_range[0], self.m_maximum_search_range[1], self.m_maximum_in_fov_angle,
+                                      self.m_down_sample_replace)
+        else:
+            nc, ns = hb.refresh(maps, on)
         t2 = time.perf_counter()
         k = max(len(jobs), 1)
         return [(s, (int(nc[s]), int(ns[s])), (t1 - t0) / k, (t2 - t1) / k) for s, _, _ in jobs]

@@ -2,7 +2,6 @@
 bound; null arguments are refused without a device; Laser_mapping_batch(batched_history=True) keeps every sequence's books right
 (against stubbed device handles); the grid geometry both grid builds share equals a plain restatement; the adapter demo compiles."""
 import ctypes as C
-import math
 import os
 import re
 import subprocess
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 from loam_livox_amd import capi, mapping
+from tests.placement import plain_geometry  # (the numpy restatement of map_grid_geometry)
 from tests.test_multimap_host import _Stubs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,23 +172,6 @@ def test_default_mode_is_unchanged(monkeypatch):
 
 
 # ---- the grid geometry --------------------------------------------------------------------------------------------------------------------
-def plain_geometry(mm, cell):
-    """map_grid_geometry restated: float32 where the library computes in float, double where it computes in double"""
-    f = np.float32
-    mm = [f(x) for x in mm]
-    if not (mm[0] <= mm[3]):
-        mm = [f(0)] * 6
-    h = f(cell)
-    while True:
-        dims = [math.floor(float(f(mm[3 + d] - mm[d])) / float(h)) + 1 for d in range(3)]
-        if float(dims[0]) * dims[1] * dims[2] <= float(1 << 27):
-            break
-        h = f(h * f(1.5))
-    ext = f(max(abs(x) for x in mm) + max(f(mm[3 + d] - mm[d]) for d in range(3)))
-    slack = f(f(f(1e-3) * h) + f(f(2e-6) * ext))
-    return tuple(int(d) for d in dims), h, slack
-
-
 def test_grid_geometry_equals_a_plain_restatement():
     from loam_livox_amd.api import map_grid_geometry
     rng = np.random.default_rng(5)

@@ -25,9 +25,18 @@ Laser_mapping_batch(batched_history=True, cell_maps=True, cell_matching=True); b
 own map around the current pose (--fov, --search-range).  The line also reports the wall time of the refresh phase per step (for
 one_by_one: summed over the S sequences) and the number of sequences whose poses differ in any bit (must be 0).
 
+--full-maps [--key-frames] measures the map a user of offline map building receives, the un-filtered full cloud of every accepted scan
+(m_pt_cell_map_full), and with --key-frames the key frames and the loop detector on top of it: one_by_one runs S
+Laser_mapping(loop_closure_if_enable=1) loops (without --key-frames their key-frame length lies beyond the run), lockstep_batched runs
+Laser_mapping_batch(batched_history=True, full_maps=True[, key_frames=True]).  Both routes read every sequence's full map once, at the
+end, inside the timed region.  The line reports frames/s of both, the wall time of the full-map phase per step (for one_by_one: summed
+over the S sequences), the number of sequences whose full-map dumps differ in any bit and, with --key-frames, whose key-frame states,
+images or detector logs differ (both must be 0).
+
   python bench_c4_batch.py [--sequences 1,8,64] [--frames 200] [--distinct-frames 100] [--out profiles/bench_c4_batch.json]
   python bench_c4_batch.py --cell-maps --sequences 1,8,64 --out profiles/bench_c4_batch_cell_maps.json
   python bench_c4_batch.py --cell-matching --sequences 1,8,64 --out profiles/bench_c4_batch_cell_matching.json
+  python bench_c4_batch.py --full-maps [--key-frames] --sequences 1,8,64 --frames 100 --out profiles/bench_c4_batch_full_maps.json
   python bench_c4_batch.py --routes lockstep_batched --sequences 8 --frames 12 --repeats 1   # one route alone, e.g. under a kernel trace"""
 import argparse
 import json
@@ -68,6 +77,98 @@ def frame_scan(scans, k, D):
     return scans[k]
 
 
+def keyframes_digest(kf):
+    """everything the two routes must agree on about one sequence's key frames: the lists, every processed key frame's cell set, images
+    and ratios, the detector's log and its loops"""
+    def flat(rec):
+        return [(k, np.asarray(rec[k]).tobytes()) for k in sorted(rec)]
+    return [kf.state(), [(sorted(k.m_set_cell), k.m_ending_frame_idx, [(n, np.asarray(k.analysis[n]).tobytes()) for n in sorted(k.analysis)])
+                         for k in kf.keyframe_vec], [flat(r) for r in kf.log], [flat(r) for r in kf.loops]]
+
+
+def full_maps_line(args, S, seqs, routes, args_map):
+    """--full-maps: one JSON line for S sequences"""
+    import torch
+    from loam_livox_amd.mapping import Laser_mapping, Laser_mapping_batch
+    F, D, N = args.frames, args.distinct_frames, args.scan_points
+    kf_scans = args.keyframe_scans if args.key_frames else F + 1000
+    closure = dict(scans_of_each_keyframe=kf_scans, scans_between_two_keyframe=max(1, kf_scans // 3), minimum_keyframe_differen=2,
+                   map_alignment_maximum_icp_iteration=2, max_points=1 << 19)
+
+    def dump_of(cell_map):
+        return b"".join(np.ascontiguousarray(a).tobytes() for a in cell_map.dump())
+
+    def one_by_one(frames):
+        lms = [Laser_mapping(scan_points=N, loop_closure_if_enable=1, loop_closure=closure, **args_map) for _ in range(S)]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        poses, dumps, accepted = [], [], 0
+        for s, lm in enumerate(lms):
+            ps = []
+            for k in range(frames):
+                nxt = frame_scan(seqs[s], k + 1, D) if k + 1 < frames else None
+                accepted += lm.process_new_scan(frame_scan(seqs[s], k, D), next_xyzi=nxt)
+                ps.append(lm.pose.copy())
+            poses.append(np.stack(ps))
+            dumps.append(dump_of(lm.keyframes.m_pt_cell_map_full))  # (the map is read once, at the end: inside the timed region)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        out = dict(dt=dt, poses=poses, accepted=accepted, dumps=dumps, full_s=sum(lm.full_map_s for lm in lms),
+                   keyframes=[keyframes_digest(lm.keyframes) for lm in lms] if args.key_frames else None,
+                   n_keyframes=sum(len(lm.keyframes.keyframe_vec) for lm in lms))
+        for lm in lms:
+            lm.close()
+        return out
+
+    def lockstep_batched(frames):
+        lb = Laser_mapping_batch(S, scan_points=N, batched_history=True, full_maps=True, key_frames=args.key_frames, loop_closure=closure, **args_map)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        poses, accepted = [[] for _ in range(S)], 0
+        for k in range(frames):
+            out = lb.process_new_scans([frame_scan(seqs[s], k, D) for s in range(S)])
+            accepted += int((out == 1).sum())
+            for s in range(S):
+                poses[s].append(lb.poses[s].copy())
+        dumps = [dump_of(lb.full_map(s)) for s in range(S)]
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        out = dict(dt=dt, poses=[np.stack(p) for p in poses], accepted=accepted, dumps=dumps, full_s=lb.full_map_s,
+                   keyframes=[keyframes_digest(k) for k in lb.keyframes] if args.key_frames else None,
+                   n_keyframes=sum(len(k.keyframe_vec) for k in lb.keyframes) if args.key_frames else 0,
+                   work=lb.history_batch.full_map_work().tolist(), stored_points=sum(lb.full_map(s).stats()[1] for s in range(S)))
+        lb.close()
+        return out
+
+    run = {"one_by_one": one_by_one, "lockstep_batched": lockstep_batched}
+    assert set(routes) <= set(run), "--full-maps: routes one_by_one and lockstep_batched"
+    for r in routes:
+        run[r](min(6, F))  # warm-up
+    times, last = {r: [] for r in routes}, {}
+    for _ in range(args.repeats):
+        for r in routes:
+            last[r] = run[r](F)
+            times[r].append(last[r]["dt"])
+    n = S * F
+    line = {"metric": "frames_per_s", "sequences": S, "frames_per_sequence": F, "scan_points": N, "full_maps": True, "key_frames": bool(args.key_frames)}
+    for r in routes:
+        line[r] = {"frames_per_s": round(n / min(times[r]), 1), "all_repeats": [round(n / t, 1) for t in times[r]], "accepted": last[r]["accepted"],
+                   "full_map_phase_ms_per_step": round(1e3 * last[r]["full_s"] / F, 4), "key_frames_processed": last[r]["n_keyframes"]}
+    if "lockstep_batched" in routes:
+        b = last["lockstep_batched"]
+        line["full_map_work_last_append"] = b["work"]
+        line["full_map_points_stored"] = int(b["stored_points"])
+        line["full_map_dump_bytes"] = sum(len(x) for x in b["dumps"])
+    if len(routes) == 2:
+        a, b = last["one_by_one"], last["lockstep_batched"]
+        line["lockstep_batched_over_one_by_one"] = round(min(times["one_by_one"]) / min(times["lockstep_batched"]), 3)
+        line["sequences_with_differing_poses"] = sum(0 if np.array_equal(a["poses"][s].view(np.uint64), b["poses"][s].view(np.uint64)) else 1 for s in range(S))
+        line["sequences_with_differing_full_map_dumps"] = sum(a["dumps"][s] != b["dumps"][s] for s in range(S))
+        if args.key_frames:
+            line["sequences_with_differing_key_frames"] = sum(a["keyframes"][s] != b["keyframes"][s] for s in range(S))
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sequences", default="1,8,64")
@@ -84,15 +185,22 @@ def main():
     ap.add_argument("--cell-matching", action="store_true", help="the cell matching mode: one_by_one (matching_mode=1) and lockstep_batched (cell_matching=True)")
     ap.add_argument("--fov", type=float, default=30.0, help="with --cell-matching: maximum_in_fov_angle")
     ap.add_argument("--search-range", type=float, default=100.0, help="with --cell-matching: maximum_search_range_corner and _surface")
+    ap.add_argument("--full-maps", action="store_true", help="keep every sequence's full-cloud map: one_by_one (loop_closure_if_enable=1) and lockstep_batched")
+    ap.add_argument("--key-frames", action="store_true", help="with --full-maps: the key frames and the loop detector on top of the full maps")
+    ap.add_argument("--keyframe-scans", type=int, default=30, help="with --key-frames: scans_of_each_keyframe (a new key frame opens every third of it)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert not (args.cell_maps and args.cell_matching), "--cell-maps and --cell-matching are separate measurements"
+    assert not (args.full_maps and (args.cell_maps or args.cell_matching)), "--full-maps is a measurement of its own"
+    assert args.full_maps or not args.key_frames, "--key-frames needs --full-maps"
     S_list = [int(x) for x in args.sequences.split(",")]
     routes = args.routes.split(",")
     if args.cell_maps:  # (the threaded lockstep route keeps no cell maps; the plain batched loop joins the line of record)
         routes = [r for r in routes if r != "lockstep"] + (["lockstep_batched_plain"] if "lockstep_batched" in routes and "one_by_one" in routes else [])
     if args.cell_matching:  # (the threaded lockstep route has no cell mode; the plain batched loop would not match against cells)
         assert "lockstep_batched_plain" not in routes, "--cell-matching: routes one_by_one and lockstep_batched"
+        routes = [r for r in routes if r != "lockstep"]
+    if args.full_maps:  # (the threaded lockstep route keeps no full maps)
         routes = [r for r in routes if r != "lockstep"]
     assert routes and set(routes) <= {"one_by_one", "lockstep", "lockstep_batched", "lockstep_batched_plain"}, "--routes: one_by_one, lockstep, lockstep_batched"
     F, D, N = args.frames, args.distinct_frames, args.scan_points
@@ -114,7 +222,11 @@ def main():
     cell_mode = dict(maximum_search_range_corner=args.search_range, maximum_search_range_surface=args.search_range, maximum_in_fov_angle=args.fov,
                      cell_map_max_points=args.cell_map_points) if args.cell_matching else {}
     lines = []
-    for S in S_list:
+    for S in S_list if args.full_maps else []:
+        line = full_maps_line(args, S, seqs, routes, args_map)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    for S in [] if args.full_maps else S_list:
         def dumps_of(cell_map):
             """both dumps of one sequence as bytes"""
             return [b"".join(np.ascontiguousarray(a).tobytes() for a in cell_map(kind).dump()) for kind in (0, 1)]

@@ -478,6 +478,35 @@ int ll_history_batch_refresh_cells(ll_history_batch *h, ll_map *const *maps, con
                                    float maximum_in_fov_angle, int32_t down_sample_replace,
                                    int64_t *n_map_corner, int64_t *n_map_surf);
 int ll_history_batch_cell_match_work(ll_history_batch *h, int64_t out[8]);
+/* The full-cloud map of every slot: m_pt_cell_map_full (laser_mapping.hpp:1442, 1527), the un-filtered cloud of every accepted scan
+ * in the map frame, which the key frames and the loop detector are built on (:1524-1562).  Independent of
+ * ll_history_batch_enable_cell_maps: either, both or neither may be on.  Once enabled, kind 2 is valid for
+ * ll_history_batch_cell_map_stats / _dump / _device_view: a read of kind 2 materialises the full store only, reads of kinds 0 and 1 and
+ * the cell-mode refresh (its compaction included) never touch it, and ll_history_batch_sync_cell_maps orders whatever is enabled.
+ * ll_history_batch_append_full_fe is ll_cellmap_append_touched for all ACTIVE slots at once: slot s takes the extractor's full
+ * selection of scan s (ll_fe_select_batch), moves it with poses7[s] (pointAssociateToMap: double arithmetic, float store), appends
+ * it under ll_cellmap_append's rules -- a point with a non-finite coordinate is dropped, the frame counter moves by 1 (by 2 while
+ * the map has no cells), also for an empty selection -- and lists the cells that received at least min_points of THIS scan's stored
+ * points (every cell that received one when the map had no cells at the call; points in a cell the same append reset count), in
+ * ascending cell order.  n_touched[s] is the length of slot s's list; the lists stay on the handle until the next such call, and an
+ * inactive slot keeps its map, its counter and its list.  ll_history_batch_full_touched reads one: *n cells, and with cell_ijk their
+ * {i, j, k} (capacity_cells >= *n).
+ * Cost: one gather launch, the append chain of the cell maps and five enqueues for the touched cells -- a counter per table entry
+ * over the step's new log entries, a flag against the slot's threshold, a scan, a compaction; no kernel of the call reads, sorts or
+ * moves a stored point.  The host waits three times (selection sizes, tables, lists); enqueues and waits do not depend on
+ * n_sequences or on the number of active slots.  A growth of the store waits on top.
+ * Refused before anything is enqueued, with the handle still usable: a null handle, extractor, poses7 or n_touched, a call before the
+ * enable, a second enable, an extractor on another device or with fewer slots than n_sequences, a full selection larger than
+ * max_points_per_frame, min_points < 1, and a store that would pass 2^31 points.
+ * ll_history_batch_full_map_work is a test tap: out[0] enqueues (launches, library calls, copies) of the last append call, out[1] its
+ * host waits, out[2] stored points that went through a sort or a gather inside append calls (nothing adds to it), out[3]
+ * materialisations of the full store. */
+int ll_history_batch_enable_full_maps(ll_history_batch *h, int64_t initial_points_per_map, float cell_resolution,
+                                      int32_t threshold_cell_revisit);
+int ll_history_batch_append_full_fe(ll_history_batch *h, ll_fe *fe, const int32_t *active, const double *poses7, int32_t min_points,
+                                    int64_t *n_touched);
+int ll_history_batch_full_touched(ll_history_batch *h, int32_t sequence, int32_t *cell_ijk, int64_t capacity_cells, int64_t *n);
+int ll_history_batch_full_map_work(ll_history_batch *h, int64_t out[4]);
 /* Host arithmetic only (no device needed): the geometry ll_map_upload and both refreshes give the search grid over the bounding
  * box {min x, y, z, max x, y, z} of a cloud's finite points (min > max: no finite point) with cells of cell_size metres.  The
  * cell grows by 1.5 x until the dense table has at most 2^27 cells. */

@@ -541,6 +541,49 @@ class History_buffer_batch:
         check(self.L.ll_history_batch_cell_map_work(self.h, ptr(out)), "ll_history_batch_cell_map_work")
         return out
 
+    def enable_full_maps(self, initial_points_per_map: int = 1 << 20, cell_resolution: float = 1.0, threshold_cell_revisit: int = 5000) -> None:
+        """the full-cloud map of every slot (m_pt_cell_map_full, laser_mapping.hpp:1442, 1527), independent of enable_cell_maps: fed by
+        append_full, read as cell_map(s, 2) / full_map(s); the store grows from n_sequences * initial_points_per_map points"""
+        check(self.L.ll_history_batch_enable_full_maps(self.h, int(initial_points_per_map), cell_resolution, int(threshold_cell_revisit)),
+              "ll_history_batch_enable_full_maps")
+        self._full_resolution = cell_resolution
+        self._full_min_points = None
+
+    def append_full(self, fe: "Livox_laser", poses, active=None, min_points: int = 3, lists: bool = True):
+        """every active slot appends the full selection of scan s of the extractor, moved with poses[s], to its full-cloud map; returns
+        per slot the cells [n, 3] its last appended scan touched (Cell_map.append_cloud_touched's list; an inactive slot keeps its own),
+        with lists=False only their numbers [S] (full_touched(s) reads a list later)"""
+        S = self.n_sequences
+        act = None if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.int32).reshape(S)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(S, 7)
+        n = np.zeros(S, np.int64)
+        check(self.L.ll_history_batch_append_full_fe(self.h, fe.h, ptr(act), ptr(poses), int(min_points), ptr(n)), "ll_history_batch_append_full_fe")
+        self._full_min_points = int(min_points)
+        if not lists:
+            return n
+        return [self.full_touched(s, int(n[s])) for s in range(S)]
+
+    def full_touched(self, sequence: int, n: int | None = None) -> np.ndarray:
+        """the cells [n, 3] the last scan appended to slot `sequence`'s full-cloud map touched, in ascending cell order"""
+        if n is None:
+            c = C.c_int64(0)
+            check(self.L.ll_history_batch_full_touched(self.h, int(sequence), None, 0, C.byref(c)), "ll_history_batch_full_touched")
+            n = c.value
+        ijk = np.zeros((max(1, n), 3), np.int32)
+        c = C.c_int64(0)
+        check(self.L.ll_history_batch_full_touched(self.h, int(sequence), ptr(ijk), ijk.shape[0], C.byref(c)), "ll_history_batch_full_touched")
+        return ijk[:c.value].copy()
+
+    def full_map(self, sequence: int) -> "Full_map_slot":
+        return Full_map_slot(self, int(sequence))
+
+    def full_map_work(self) -> np.ndarray:
+        """test tap (ll_history_batch_full_map_work): enqueues and host waits of the last append_full, stored points sorted or gathered
+        inside append_full calls, materialisations of the full store"""
+        out = np.zeros(4, np.int64)
+        check(self.L.ll_history_batch_full_map_work(self.h, ptr(out)), "ll_history_batch_full_map_work")
+        return out
+
 
 class Cell_map_slot:
     """One cell map of one slot of a History_buffer_batch, read the way a Cell_map is: stats(), dump() and device_view(device) have
@@ -548,7 +591,7 @@ class Cell_map_slot:
 
     def __init__(self, batch: "History_buffer_batch", sequence: int, kind: int):
         self.batch, self.sequence, self.kind = batch, sequence, kind
-        self.resolution = getattr(batch, "_cell_resolution", None)
+        self.resolution = getattr(batch, "_full_resolution" if kind == 2 else "_cell_resolution", None)
 
     def stats(self):
         """(cells, points, m_current_frame_idx)"""
@@ -583,6 +626,26 @@ class Cell_map_slot:
         pts = torch.as_tensor(_DeviceView(p.value, n.value), device=f"cuda:{device}").clone()
         keys = torch.as_tensor(_DeviceView64(k.value, n.value), device=f"cuda:{device}").clone()
         return pts, keys
+
+
+class Full_map_slot(Cell_map_slot):
+    """The full-cloud map of one slot of a History_buffer_batch (kind 2), in the place of the Cell_map a Keyframe_assembly owns:
+    stats() and dump() read the slot; append_cloud_touched does NOT append -- the step's one append_full has done that for all slots --
+    it answers with the list that append left for this slot; close() leaves the batch alone."""
+
+    def __init__(self, batch: "History_buffer_batch", sequence: int):
+        super().__init__(batch, sequence, 2)
+
+    def append_cloud_touched(self, cloud=None, min_points: int = 3) -> np.ndarray:
+        used = getattr(self.batch, "_full_min_points", None)
+        if used is None:
+            raise ValueError("no append_full on the batch yet: there is no list to answer with")
+        if int(min_points) != used:
+            raise ValueError(f"the batch's append_full listed the cells with min_points={used}, not {min_points}")
+        return self.batch.full_touched(self.sequence)
+
+    def close(self):
+        pass
 
 
 def map_grid_geometry(bbox_min_max, cell_size: float):

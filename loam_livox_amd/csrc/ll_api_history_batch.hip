@@ -8,8 +8,13 @@
 // The handle can keep the two cell maps of every slot as well (ll_history_batch_enable_cell_maps): every active slot of an add
 // appends its filtered frame to them, through one more fixed chain whose work is that of the new points and the cell tables
 // (ll_cellmap_batch_kernels.hip); the stored points are put in order when somebody reads.
+//
+// Independently of those it can keep the full-cloud map of every slot (ll_history_batch_enable_full_maps): a third store of the same
+// kind, fed by ll_history_batch_append_full_fe with the extractor's full selections and reporting the cells each scan touched
+// (ll_fullmap_batch_kernels.hip).  Nothing of an add or of a refresh reads it.
 #include "ll_api_internal.h"
 #include "ll_cellmatch_batch.h"
+#include "ll_fullmap_batch.h"
 
 struct HbArena {
     int device = 0;
@@ -54,9 +59,9 @@ struct ll_history_batch {
     std::vector<std::shared_ptr<HbArena>> arenas;
     // the cell maps of all slots, one deferred store per kind (ll_history_batch_enable_cell_maps)
     bool cm_on = false, cm_dirty = false;    // dirty: an add came after the last materialisation
-    CbDev cm[2]{};
-    std::vector<int> cm_frame[2];            // [S] m_current_frame_idx of every map
-    std::vector<int> cm_coff[2], cm_poff[2]; // [S + 1] host copies: first cell / first stored point of every slot
+    CbDev cm[3]{};                           // corner, surface; [2]: the full-cloud store (ll_history_batch_enable_full_maps)
+    std::vector<int> cm_frame[3];            // [S] m_current_frame_idx of every map
+    std::vector<int> cm_coff[3], cm_poff[3]; // [S + 1] host copies: first cell / first stored point of every slot
     CbSlot *hp_cm_tab = nullptr;             // pinned [2][S]
     int *hp_cm = nullptr;                    // pinned: filtered counts [2][S], coff [2][S + 1], poff [2][S + 1], counts [2][4]
     int64_t cm_work[4] = {0, 0, 0, 0};       // ll_history_batch_cell_map_work
@@ -65,6 +70,16 @@ struct ll_history_batch {
     CmbSlot *hp_cq_tab = nullptr, *d_cq_tab = nullptr;  // [S]
     int *hp_cq = nullptr;                    // pinned [2][S + 4]: first leaf of every slot, leaves, candidates, live entries
     int64_t cq_work[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // ll_history_batch_cell_match_work
+    // the full-cloud maps of all slots: cm[2] and what an append needs on top of it (ll_history_batch_enable_full_maps)
+    bool fm_on = false, fm_dirty = false;
+    FbDev fm{};
+    CbSlot *hp_fm_tab = nullptr;             // pinned [S]
+    FbSlot *hp_fb_tab = nullptr;             // pinned [S]
+    int *hp_fm = nullptr;                    // pinned: full-selection sizes [S], coff [S + 1], poff [S + 1], counts [4], toff [S + 1]
+    int *hp_fm_cells = nullptr;              // pinned [fm_cells_cap][3]: the touched cells of the last append on their way to the lists
+    size_t fm_cells_cap = 0;
+    std::vector<std::vector<int32_t>> fm_touched;  // [S] the {i, j, k} of the cells the slot's last appended scan touched
+    int64_t fm_work[4] = {0, 0, 0, 0};       // ll_history_batch_full_map_work
 };
 
 // grow-only device buffer, half again as large as asked when it has to move
@@ -89,6 +104,24 @@ static void hb_cells_free(CbDev &m)
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     memset(&m, 0, sizeof(m));
+}
+
+static void hb_full_free(ll_history_batch *h)
+{
+    FbDev &t = h->fm;
+    void *ptrs[] = {t.xf, t.tab, t.cnt, t.flag, t.rank, t.cells, t.toff, t.tmp};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    memset(&t, 0, sizeof(t));
+    hb_cells_free(h->cm[2]);
+    void *host[] = {h->hp_fm_tab, h->hp_fb_tab, h->hp_fm, h->hp_fm_cells};
+    for (void *p : host)
+        if (p) (void)hipHostFree(p);
+    h->hp_fm_tab = nullptr;
+    h->hp_fb_tab = nullptr;
+    h->hp_fm = nullptr;
+    h->hp_fm_cells = nullptr;
+    h->fm_cells_cap = 0;
 }
 
 static void hb_cellmatch_free(CmbDev &q)
@@ -154,6 +187,7 @@ extern "C" void ll_history_batch_destroy(ll_history_batch *h)
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (int k = 0; k < 2; k++) hb_cells_free(h->cm[k]);
+    hb_full_free(h);
     for (int k = 0; k < 2; k++) hb_cellmatch_free(h->cq[k]);
     if (h->d_cq_tab) (void)hipFree(h->d_cq_tab);
     void *host[] = {h->hp_add, h->hp_cnt, h->hp_ref, h->hp_mm_init, h->hp_mm, h->hp_grid, h->hp_nvalid, h->hp_cm_tab, h->hp_cm, h->hp_cq_tab, h->hp_cq};
@@ -344,13 +378,12 @@ static int hb_cells_append(const char *where, ll_history_batch *h)
     return 0;
 }
 
-// put the stores of both kinds in order (a read after an add); nothing to do when no add came since the last time
-static int hb_cells_materialise(const char *where, ll_history_batch *h)
+// put the stores of the kinds k0 .. k1 - 1 in order; h_poff: pinned, S + 1 entries per kind
+static int hb_stores_materialise(const char *where, ll_history_batch *h, int k0, int k1, int *h_poff)
 {
-    if (!h->cm_dirty) return 0;
     const int S = h->S;
     HC(hipSetDevice(h->device));
-    for (int k = 0; k < 2; k++) {
+    for (int k = k0; k < k1; k++) {
         CbDev &m = h->cm[k];
         if (m.n_log <= 0) continue;
         if (hb_cells_reserve_tmp(h, m, m.n_log)) return -1;
@@ -362,20 +395,38 @@ static int hb_cells_materialise(const char *where, ll_history_batch *h)
             m.mcap = n;
         }
     }
-    int *h_poff = h->hp_cm + (size_t)2 * S + 2 * ((size_t)S + 1), launches = 0;
+    int launches = 0;
     const char *err = nullptr;
-    for (int k = 0; k < 2; k++) {
+    for (int k = k0; k < k1; k++) {
         CbDev &m = h->cm[k];
         if (cb_materialise(m, h->stream, &launches, &err)) return set_err(where, err);
-        HC(hipMemcpyAsync(h_poff + (size_t)k * (S + 1), m.poff, (size_t)(S + 1) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HC(hipMemcpyAsync(h_poff + (size_t)(k - k0) * (S + 1), m.poff, (size_t)(S + 1) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     }
     HC(hipStreamSynchronize(h->stream));
-    for (int k = 0; k < 2; k++) {
-        for (int s = 0; s <= S; s++) h->cm_poff[k][s] = h_poff[(size_t)k * (S + 1) + s];
+    for (int k = k0; k < k1; k++) {
+        for (int s = 0; s <= S; s++) h->cm_poff[k][s] = h_poff[(size_t)(k - k0) * (S + 1) + s];
         h->cm[k].n_log = h->cm_poff[k][S];  // the ordered store replaces the log: later adds write behind it
     }
+    return 0;
+}
+
+// put the stores of both feature kinds in order (a read after an add); nothing to do when no add came since the last time
+static int hb_cells_materialise(const char *where, ll_history_batch *h)
+{
+    if (!h->cm_dirty) return 0;
+    if (hb_stores_materialise(where, h, 0, 2, h->hp_cm + (size_t)2 * h->S + 2 * ((size_t)h->S + 1))) return -1;
     h->cm_dirty = false;
     h->cm_work[2]++;
+    return 0;
+}
+
+// the same for the full-cloud store alone: a read of kind 2 never orders the feature stores, and the other way round
+static int hb_full_materialise(const char *where, ll_history_batch *h)
+{
+    if (!h->fm_dirty) return 0;
+    if (hb_stores_materialise(where, h, 2, 3, h->hp_fm + (size_t)h->S + ((size_t)h->S + 1))) return -1;
+    h->fm_dirty = false;
+    h->fm_work[3]++;
     return 0;
 }
 
@@ -732,6 +783,10 @@ extern "C" int ll_history_batch_enable_cell_maps(ll_history_batch *h, int64_t in
 static int hb_cells_reader(const char *where, ll_history_batch *h, int32_t sequence, int32_t kind)
 {
     if (!h) return set_err(where, "null argument");
+    if (kind == 2 && h->fm_on) {  // the full-cloud store, on its own
+        if (sequence < 0 || sequence >= h->S) return set_err(where, "sequence out of range");
+        return hb_full_materialise(where, h);
+    }
     if (!h->cm_on) return set_err(where, "cell maps are not enabled (ll_history_batch_enable_cell_maps)");
     if (sequence < 0 || sequence >= h->S) return set_err(where, "sequence out of range");
     if (kind < 0 || kind > 1) return set_err(where, "kind out of range");
@@ -740,7 +795,12 @@ static int hb_cells_reader(const char *where, ll_history_batch *h, int32_t seque
 
 extern "C" int ll_history_batch_sync_cell_maps(ll_history_batch *h)
 {
-    return hb_cells_reader("ll_history_batch_sync_cell_maps", h, 0, 0);
+    static const char *where = "ll_history_batch_sync_cell_maps";
+    if (h && h->fm_on) {  // whatever is enabled
+        if (h->cm_on && hb_cells_materialise(where, h)) return -1;
+        return hb_full_materialise(where, h);
+    }
+    return hb_cells_reader(where, h, 0, 0);
 }
 
 extern "C" int ll_history_batch_cell_map_stats(ll_history_batch *h, int32_t sequence, int32_t kind, int64_t *n_cells, int64_t *n_points,
@@ -758,7 +818,8 @@ extern "C" int ll_history_batch_cell_map_dump(ll_history_batch *h, int32_t seque
 {
     static const char *where = "ll_history_batch_cell_map_dump";
     if (!h) return set_err(where, "null argument");
-    if (h->cm_on && sequence >= 0 && sequence < h->S && kind >= 0 && kind <= 1 && !h->cm_dirty) {  // (sizes known: refuse short buffers before any work)
+    if (sequence >= 0 && sequence < h->S && ((kind == 2 && h->fm_on && !h->fm_dirty) || (h->cm_on && kind >= 0 && kind <= 1 && !h->cm_dirty))) {
+        // (sizes known: refuse short buffers before any work)
         const int np = h->cm_poff[kind][sequence + 1] - h->cm_poff[kind][sequence], nc = h->cm_coff[kind][sequence + 1] - h->cm_coff[kind][sequence];
         if ((xyzi && capacity_points < np) || ((cell_ijk || cell_start || cell_last_update) && capacity_cells < nc)) return set_err(where, "buffer too small");
     }
@@ -806,6 +867,228 @@ extern "C" int ll_history_batch_cell_map_work(ll_history_batch *h, int64_t out[4
     if (!h || !out) return set_err(where, "null argument");
     if (!h->cm_on) return set_err(where, "cell maps are not enabled (ll_history_batch_enable_cell_maps)");
     for (int i = 0; i < 4; i++) out[i] = h->cm_work[i];
+    return 0;
+}
+
+
+// ================================================================================================ the full-cloud maps of the slots
+static int hb_full_enable_impl(ll_history_batch *h, int64_t initial_points_per_map, float cell_resolution, int32_t threshold)
+{
+    const size_t S = (size_t)h->S;
+    HC(hipHostMalloc((void **)&h->hp_fm_tab, S * sizeof(CbSlot), hipHostMallocDefault));
+    HC(hipHostMalloc((void **)&h->hp_fb_tab, S * sizeof(FbSlot), hipHostMallocDefault));
+    HC(hipHostMalloc((void **)&h->hp_fm, (S + 3 * (S + 1) + 4) * sizeof(int), hipHostMallocDefault));
+    h->fm_cells_cap = 4096;
+    HC(hipHostMalloc((void **)&h->hp_fm_cells, h->fm_cells_cap * 3 * sizeof(int), hipHostMallocDefault));
+    CbDev &m = h->cm[2];
+    m.S = h->S;
+    m.geom = cell_geom(cell_resolution);  // laser_mapping.hpp:616-617: m_pt_cell_map_full has the feature maps' resolution and threshold
+    m.threshold = threshold;
+    DM(m.coff, S + 1);
+    DM(m.coff2, S + 1);
+    DM(m.poff, S + 1);
+    DM(m.counts, 4);
+    DM(m.tab, S);
+    HC(hipMemset(m.coff, 0, (S + 1) * sizeof(int)));
+    HC(hipMemset(m.poff, 0, (S + 1) * sizeof(int)));
+    HC(hipMemset(m.counts, 0, 4 * sizeof(int)));
+    if (hb_cells_reserve_log(h, m, (long long)(S * (size_t)initial_points_per_map)) || hb_cells_reserve_table(h, m, (long long)h->max_pts)) return -1;
+    FbDev &t = h->fm;
+    DM(t.xf, S * (size_t)h->max_pts);
+    DM(t.tab, S);
+    DM(t.toff, S + 1);
+    HC(hipMemset(t.toff, 0, (S + 1) * sizeof(int)));
+    h->cm_frame[2].assign(S, 0);
+    h->cm_coff[2].assign(S + 1, 0);
+    h->cm_poff[2].assign(S + 1, 0);
+    h->fm_touched.assign(S, std::vector<int32_t>());
+    HC(hipDeviceSynchronize());  // (null-stream memsets are not ordered with the handle's non-blocking stream)
+    return 0;
+}
+
+extern "C" int ll_history_batch_enable_full_maps(ll_history_batch *h, int64_t initial_points_per_map, float cell_resolution,
+                                                 int32_t threshold_cell_revisit)
+{
+    static const char *where = "ll_history_batch_enable_full_maps";
+    if (!h) return set_err(where, "null argument");
+    if (h->fm_on) return set_err(where, "already enabled");
+    if (!(cell_resolution > 0.f)) return set_err(where, "cell_resolution must be positive");
+    if (initial_points_per_map < h->max_pts) return set_err(where, "initial_points_per_map below max_points_per_frame");
+    if ((double)initial_points_per_map * (double)h->S >= 2147483647.0)
+        return set_err(where, "n_sequences * initial_points_per_map must stay below 2^31 stored points");
+    HC(hipSetDevice(h->device));
+    HC(hipStreamSynchronize(h->stream));
+    if (hb_full_enable_impl(h, initial_points_per_map, cell_resolution, threshold_cell_revisit)) {  // all or nothing
+        const std::string keep = g_err;
+        hb_full_free(h);
+        g_err = keep;
+        return -1;
+    }
+    h->fm_on = true;
+    return 0;
+}
+
+// the scratch of the touched chain follows the cell table's capacity (the stream is idle)
+static int hb_full_reserve_scratch(ll_history_batch *h, long long n_upper)
+{
+    FbDev &t = h->fm;
+    const size_t want = h->cm[2].ccap;
+    if (t.tcap < want) {
+        if (hb_cells_move(h, &t.cnt, want, 0) || hb_cells_move(h, &t.flag, want, 0) || hb_cells_move(h, &t.rank, want, 0) ||
+            hb_cells_move(h, &t.cells, 3 * want, 0))
+            return -1;
+        t.tcap = want;
+    }
+    size_t bytes = 0;
+    const char *err = nullptr;
+    if (fb_tmp_bytes(n_upper, &bytes, &err)) return set_err("ll_history_batch_append_full_fe", err);
+    if (bytes > t.tmp_bytes) {
+        char *p = (char *)t.tmp;
+        if (hb_cells_move(h, &p, bytes + bytes / 2, 0)) return -1;
+        t.tmp = p;
+        t.tmp_bytes = bytes + bytes / 2;
+    }
+    return 0;
+}
+
+// laser_mapping.hpp:1442 + 1527 for all active slots: the scan's full cloud (the extractor's full selection) into the map frame with
+// the slot's pose and behind the full-cloud store, and per slot the cells the scan touched.  One gather, the append chain of
+// ll_cellmap_batch_kernels.hip, the touched chain; the host waits for the selection sizes, for the tables of the append, and for
+// the touched cells themselves.  A growth of the store waits on top, as it does for the feature stores.
+extern "C" int ll_history_batch_append_full_fe(ll_history_batch *h, ll_fe *fe, const int32_t *active, const double *poses7, int32_t min_points,
+                                               int64_t *n_touched)
+{
+    static const char *where = "ll_history_batch_append_full_fe";
+    if (!h || !fe || !poses7 || !n_touched) return set_err(where, "null argument");
+    if (!h->fm_on) return set_err(where, "full maps are not enabled (ll_history_batch_enable_full_maps)");
+    if (fe->prm.device != h->device) return set_err(where, "extractor lives on another device");
+    if (fe->prm.max_scans < h->S) return set_err(where, "the extractor holds fewer scans than n_sequences");
+    if (min_points < 1) return set_err(where, "min_points must be at least 1");
+    const int S = h->S;
+    CbDev &m = h->cm[2];
+    FbDev &t = h->fm;
+    HC(hipSetDevice(h->device));
+    int enq = 0, waits = 0;
+    int *in_n = h->hp_fm, *h_coff = in_n + S, *h_counts = h_coff + 2 * ((size_t)S + 1), *h_toff = h_counts + 4;
+    HC(hipMemcpyAsync(in_n, fe->dev.n_full, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, fe->stream));  // (behind the selection)
+    HC(hipStreamSynchronize(fe->stream));
+    enq++;
+    waits++;
+    // ---- the checks: nothing is enqueued on the handle's stream and nothing is changed before they have passed
+    long long n_new = 0;
+    int max_n = 0;
+    for (int s = 0; s < S; s++) {
+        if (active && !active[s]) continue;
+        if (in_n[s] > h->max_pts || in_n[s] > fe->dev.stride) return set_err(where, "full selection exceeds max_points_per_frame");
+        const int n = in_n[s] > 0 ? in_n[s] : 0;
+        n_new += n;
+        max_n = n > max_n ? n : max_n;
+    }
+    if (m.n_log + n_new >= kCbLimit) return set_err(where, "the full maps would pass 2^31 stored points");
+    const long long n_upper = (long long)m.n_cells + n_new;  // bound of the cell table after the merge
+    if (n_upper >= kCbLimit) return set_err(where, "the full maps would pass 2^31 cells");
+    if (n_new > 0) {
+        if (hb_cells_reserve_log(h, m, m.n_log + n_new) || hb_cells_reserve_table(h, m, n_upper) || hb_cells_reserve_tmp(h, m, n_new) ||
+            hb_full_reserve_scratch(h, n_upper))
+            return -1;
+        if ((long long)m.acap < n_new) {
+            const size_t n = (size_t)(n_new + n_new / 2);
+            if (hb_cells_move(h, &m.akey, n, 0) || hb_cells_move(h, &m.akey2, n, 0) || hb_cells_move(h, &m.aslot, n, 0) ||
+                hb_cells_move(h, &m.aslot2, n, 0) || hb_cells_move(h, &m.aflag, n, 0) || hb_cells_move(h, &m.arank, n, 0))
+                return -1;
+            m.acap = n;
+        }
+    }
+    // ---- the tables of the call
+    long long off = m.n_log;
+    for (int s = 0; s < S; s++) {
+        CbSlot &c = h->hp_fm_tab[s];
+        FbSlot &f = h->hp_fb_tab[s];
+        memset(&c, 0, sizeof(c));
+        memset(&f, 0, sizeof(f));
+        if (active && !active[s]) continue;
+        const int n = in_n[s] > 0 ? in_n[s] : 0;
+        c.off = off;
+        c.n = f.n = n;
+        c.frame = h->cm_frame[2][s];
+        c.active = f.active = 1;
+        f.need = fb_need(h->cm_coff[2][s + 1] == h->cm_coff[2][s], min_points);
+        for (int i = 0; i < 7; i++) f.pose[i] = poses7[7 * (size_t)s + i];
+        off += n;
+    }
+    int total = 0;
+    if (n_new > 0) {
+        const char *err = nullptr;
+        HC(hipMemcpyAsync(m.tab, h->hp_fm_tab, (size_t)S * sizeof(CbSlot), hipMemcpyHostToDevice, h->stream));
+        HC(hipMemcpyAsync(t.tab, h->hp_fb_tab, (size_t)S * sizeof(FbSlot), hipMemcpyHostToDevice, h->stream));
+        enq += 2;
+        if (fb_gather(t, fe->dev.xyzi, fe->dev.full_idx, fe->dev.stride, S, h->max_pts, max_n, h->stream, &enq, &err)) return set_err(where, err);
+        if (cb_append(m, t.xf, h->max_pts, max_n, n_new, h->stream, &enq, &err)) return set_err(where, err);
+        if (fb_touched_chain(m, t, max_n, (int)n_upper, h->stream, &enq, &err)) return set_err(where, err);
+        HC(hipMemcpyAsync(h_counts, m.counts, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HC(hipMemcpyAsync(h_coff, m.coff, (size_t)(S + 1) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HC(hipMemcpyAsync(h_toff, t.toff, (size_t)(S + 1) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        enq += 3;
+        HC(hipStreamSynchronize(h->stream));
+        waits++;
+        total = h_toff[S];
+        if (total < 0 || total > h_counts[1] || h_counts[1] > n_upper) return set_err(where, "touched-cell counts out of range");
+        if ((size_t)total > h->fm_cells_cap) {  // (the stream is idle)
+            const size_t want = (size_t)total + (size_t)total / 2;
+            int *p = nullptr;
+            HC(hipHostMalloc((void **)&p, want * 3 * sizeof(int), hipHostMallocDefault));
+            (void)hipHostFree(h->hp_fm_cells);
+            h->hp_fm_cells = p;
+            h->fm_cells_cap = want;
+        }
+        // the lists themselves; the copy and its wait are there for every call that appended, so that their number does not depend on the data
+        HC(hipMemcpyAsync(h->hp_fm_cells, t.cells, (size_t)(total > 0 ? total : 1) * 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        enq++;
+        HC(hipStreamSynchronize(h->stream));
+        waits++;
+    }
+    for (int s = 0; s < S; s++) {
+        if (active && !active[s]) continue;  // (an inactive slot keeps its map, its counter and its list)
+        h->cm_frame[2][s] += cb_frame_step(h->cm_coff[2][s + 1] == h->cm_coff[2][s]);  // (the cell counts at the call)
+        std::vector<int32_t> &list = h->fm_touched[s];
+        list.clear();
+        if (n_new > 0) list.assign(h->hp_fm_cells + 3 * (size_t)h_toff[s], h->hp_fm_cells + 3 * (size_t)h_toff[s + 1]);
+    }
+    if (n_new > 0) {
+        m.n_cells = h_counts[1];
+        for (int s = 0; s <= S; s++) h->cm_coff[2][s] = h_coff[s];
+        h->fm_dirty = true;
+    }
+    for (int s = 0; s < S; s++) n_touched[s] = (int64_t)(h->fm_touched[s].size() / 3);
+    h->fm_work[0] = enq;
+    h->fm_work[1] = waits;
+    return 0;
+}
+
+extern "C" int ll_history_batch_full_touched(ll_history_batch *h, int32_t sequence, int32_t *cell_ijk, int64_t capacity_cells, int64_t *n)
+{
+    static const char *where = "ll_history_batch_full_touched";
+    if (!h || !n) return set_err(where, "null argument");
+    if (!h->fm_on) return set_err(where, "full maps are not enabled (ll_history_batch_enable_full_maps)");
+    if (sequence < 0 || sequence >= h->S) return set_err(where, "sequence out of range");
+    const std::vector<int32_t> &list = h->fm_touched[sequence];
+    *n = (int64_t)(list.size() / 3);
+    if (!cell_ijk) return 0;
+    if (capacity_cells < *n) return set_err(where, "buffer too small");
+    if (!list.empty()) memcpy(cell_ijk, list.data(), list.size() * sizeof(int32_t));
+    return 0;
+}
+
+// Test tap of the full-cloud maps: [0] enqueues (launches, library calls, copies) of the last ll_history_batch_append_full_fe, [1] its
+// host waits (a growth of the store waits on top and is not counted), [2] stored points that went through a sort or a gather inside
+// append calls so far -- no kernel of an append takes a stored point, so nothing ever adds to it: the number is there to be
+// asserted -- [3] materialisations of the full store so far.
+extern "C" int ll_history_batch_full_map_work(ll_history_batch *h, int64_t out[4])
+{
+    static const char *where = "ll_history_batch_full_map_work";
+    if (!h || !out) return set_err(where, "null argument");
+    if (!h->fm_on) return set_err(where, "full maps are not enabled (ll_history_batch_enable_full_maps)");
+    for (int i = 0; i < 4; i++) out[i] = h->fm_work[i];
     return 0;
 }
 

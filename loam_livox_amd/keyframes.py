@@ -84,7 +84,9 @@ class Keyframe_assembly:
         # parameter names and defaults: laser_mapping.hpp:698-710 (loop_closure/*), :686-687 (mapping/pt_cell_resolution, threshold_cell_revisit)
         self.device = device
         self.m_pt_cell_resolution = cell_resolution
-        # (full_cell_map: anything with append_cloud_touched / dump / close -- tests drive the bookkeeping without a device)
+        # (full_cell_map: anything with append_cloud_touched / dump / close -- tests drive the bookkeeping without a device, and the
+        #  lock-step loop hands in api.Full_map_slot, slot s of the batched full-cloud store: its append_cloud_touched answers with the
+        #  cells the step's one batched append listed for the slot, so add_scan is given an empty cloud there)
         self.m_pt_cell_map_full = full_cell_map if full_cell_map is not None else \
             Cell_map(max_points, cell_resolution, threshold_cell_revisit, device=device)   # :616-617
         self.m_para_scans_of_each_keyframe = scans_of_each_keyframe

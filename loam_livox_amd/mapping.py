@@ -90,6 +90,7 @@ class Laser_mapping:
         # and the front half of loop detection (keyframes.py; laser_mapping.hpp:626, 1524-1562, 919-1060)
         self.keyframes = None
         self.loops = []
+        self.full_map_s = 0.0  # cumulative wall time of the full-map and key-frame part of the frames (part of stage_s[1])
         if loop_closure_if_enable:
             from .keyframes import Keyframe_assembly
             self.keyframes = Keyframe_assembly(device=device, cell_resolution=cell_resolution, threshold_cell_revisit=threshold_cell_revisit,
@@ -208,7 +209,9 @@ class Laser_mapping:
             self.history.add_fe(fe, 0, pc[0], self.history_add_t_step, self.history_add_angle_step)
         self.pose = pc[0].copy()  # :1496-1500
         if self.keyframes is not None:
+            tk = time.perf_counter()
             self._keyframe_step(np.asarray(xyzi, np.float32)[fe.get_features(0.0, 1.0)["full_idx"]])  # /pc2_full of this scan
+            self.full_map_s += time.perf_counter() - tk
         t2 = time.perf_counter()
         if self.m_matching_mode:  # update_buff_for_matching (service thread in the node), synchronous here
             self.map_sizes = self.history.refresh_cells(self.map, self.pose, self.m_maximum_search_range[0], self.m_maximum_search_range[1],
@@ -302,10 +305,21 @@ class Laser_mapping_batch:
     cell_matching=True (with cell_maps=True only) registers against those cell maps: the step's one refresh becomes one refresh_cells
     at the accepted slots' new poses -- the cells within maximum_search_range_corner / _surface and maximum_in_fov_angle, each through
     the VoxelGrid, replaced by their leaves with down_sample_replace -- which is Laser_mapping(matching_mode=1) per sequence, bit for
-    bit.  matching_mode itself stays refused: it names Laser_mapping's per-sequence route."""
+    bit.  matching_mode itself stays refused: it names Laser_mapping's per-sequence route.
+
+    full_maps=True (with batched_history=True only) keeps the full-cloud map of every sequence -- m_pt_cell_map_full, the un-filtered
+    cloud of every accepted scan in the map frame (laser_mapping.hpp:1442, 1527), what Laser_mapping(loop_closure_if_enable=1) keeps
+    for one sequence -- on the History_buffer_batch: one append_full per step for the accepted slots at their new poses, after the
+    add.  The store starts at loop_closure["max_points"] points per map (2^18 unless given; it grows) under cell_resolution and
+    threshold_cell_revisit; full_map(s) reads slot s (stats(), dump()).  key_frames=True (with full_maps=True only) also owns one
+    keyframes.Keyframe_assembly per sequence, built with the rest of loop_closure, on top of its slot: per accepted slot add_scan with
+    the new pose and the slot's frame index after the increment, then process_waiting, as Laser_mapping._keyframe_step does;
+    keyframes[s] and loops[s] are those of Laser_mapping run alone on sequence s.  Nothing of the registration reads the full maps:
+    poses and reports do not change by a bit.  loop_closure_if_enable itself stays refused: it names Laser_mapping's per-sequence
+    map."""
 
     def __init__(self, n_sequences: int, refresh_threads: int | None = None, batched_history: bool = False, cell_maps: bool = False,
-                 cell_matching: bool = False, **kw):
+                 cell_matching: bool = False, full_maps: bool = False, key_frames: bool = False, **kw):
         import inspect
         sig = inspect.signature(Laser_mapping.__init__)
         unknown = set(kw) - set(sig.parameters)
@@ -328,6 +342,10 @@ class Laser_mapping_batch:
             raise ValueError("cell_maps=True needs batched_history=True: the cell maps live on the History_buffer_batch")
         if cell_matching and not cell_maps:
             raise ValueError("cell_matching=True needs cell_maps=True: the cell mode matches against the cell maps of the History_buffer_batch")
+        if full_maps and not batched_history:
+            raise ValueError("full_maps=True needs batched_history=True: the full-cloud maps live on the History_buffer_batch")
+        if key_frames and not full_maps:
+            raise ValueError("key_frames=True needs full_maps=True: a key frame is a set of cells of the sequence's full-cloud map")
         if refresh_threads is None:
             refresh_threads = min(4, n_sequences)
         if not 1 <= int(refresh_threads) <= 16:
@@ -340,6 +358,9 @@ class Laser_mapping_batch:
         self.vox = (VoxelGrid(scan_points, S, device=device), VoxelGrid(scan_points, S, device=device))
         self.maps = [Map_buffer(device=device) for _ in range(S)]
         self.batched_history, self.cell_maps, self.cell_matching = bool(batched_history), bool(cell_maps), bool(cell_matching)
+        self.full_maps, self.key_frames = bool(full_maps), bool(key_frames)
+        self.keyframes, self.loops = None, None
+        self.full_map_s = 0.0  # cumulative wall time of the full-map phase (append_full, and the key-frame steps with key_frames)
         self.m_maximum_search_range = (a["maximum_search_range_corner"], a["maximum_search_range_surface"])
         self.m_maximum_in_fov_angle, self.m_down_sample_replace = a["maximum_in_fov_angle"], a["down_sample_replace"]
         if self.batched_history:
@@ -349,6 +370,16 @@ class Laser_mapping_batch:
                 # the stores grow: they start at the points per map the caller names, a quarter of a million otherwise
                 first = max(int(kw.get("cell_map_max_points", 1 << 18)), int(scan_points))
                 self.history_batch.enable_cell_maps(first, a["cell_resolution"], a["threshold_cell_revisit"])
+            if full_maps:  # laser_mapping.hpp:616-617, 626
+                lc = dict(a["loop_closure"] or {})
+                first = max(int(lc.pop("max_points", 1 << 18)), int(scan_points))
+                self.history_batch.enable_full_maps(first, a["cell_resolution"], a["threshold_cell_revisit"])
+                if key_frames:
+                    from .keyframes import Keyframe_assembly
+                    self.keyframes = [Keyframe_assembly(device=device, cell_resolution=a["cell_resolution"],
+                                                        threshold_cell_revisit=a["threshold_cell_revisit"],
+                                                        full_cell_map=self.history_batch.full_map(s), **lc) for s in range(S)]
+                    self.loops = [[] for _ in range(S)]
         else:
             self.history_batch = None
             self.histories = [History_buffer(a["maximum_history_size"], scan_points, a["line_res"], a["plane_res"], device=device) for _ in range(S)]
@@ -379,6 +410,8 @@ class Laser_mapping_batch:
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
+        for kf in self.keyframes or []:
+            kf.close()
         for h in [self.fe, self.reg, self.vox[0], self.vox[1]] + self.maps + ([self.history_batch] if self.batched_history else self.histories):
             h.close()
 
@@ -391,6 +424,25 @@ class Laser_mapping_batch:
         if not self.cell_maps:
             raise ValueError("no cell maps: create the loop with batched_history=True, cell_maps=True")
         return self.history_batch.cell_map(sequence, kind)
+
+    def full_map(self, sequence: int):
+        if not self.full_maps:
+            raise ValueError("no full maps: create the loop with batched_history=True, full_maps=True")
+        return self.history_batch.full_map(sequence)
+
+    def _full_step(self, jobs, on, new) -> None:
+        """laser_mapping.hpp:1442 + 1524-1562 for the accepted slots: their scans' full clouds into the full-cloud maps in one append,
+        then per slot the key-frame bookkeeping on the cells that scan touched"""
+        import time
+        t0 = time.perf_counter()
+        self.history_batch.append_full(self.fe, new, on, 3, lists=False)  # (a key frame reads its slot's list through its view)
+        if self.key_frames:
+            none = np.zeros((0, 4), np.float32)  # (the slot view answers with the append's list; the cloud itself stays on the device)
+            for s, _, pose_new in jobs:
+                kf = self.keyframes[s]
+                kf.add_scan(none, pose_new, int(self.frame_index[s]))
+                self.loops[s] += kf.process_waiting()
+        self.full_map_s += time.perf_counter() - t0
 
     def _upload(self, scans, stamps, active):
         S = self.n_sequences
@@ -438,6 +490,10 @@ class Laser_mapping_batch:
         else:
             hb.add_fe(self.fe, new, gate, on, self.history_add_t_step, self.history_add_angle_step)
         t1 = time.perf_counter()
+        t_full = self.full_map_s
+        if self.full_maps:
+            self._full_step(jobs, on, new)
+        t_full = self.full_map_s - t_full  # (its own figure: neither the add's nor the refresh's)
         maps = [self.maps[s] if on[s] else None for s in range(S)]
         if self.cell_matching:  # update_buff_for_matching with m_matching_mode == 1, at the poses the step just accepted
             nc, ns = hb.refresh_cells(maps, new, on, self.m_maximum_search_range[0], self.m_maximum_search_range[1], self.m_maximum_in_fov_angle,
@@ -446,7 +502,7 @@ class Laser_mapping_batch:
             nc, ns = hb.refresh(maps, on)
         t2 = time.perf_counter()
         k = max(len(jobs), 1)
-        return [(s, (int(nc[s]), int(ns[s])), (t1 - t0) / k, (t2 - t1) / k) for s, _, _ in jobs]
+        return [(s, (int(nc[s]), int(ns[s])), (t1 - t0) / k, (t2 - t1 - t_full) / k) for s, _, _ in jobs]
 
     def process_new_scans(self, scans, time_stamps=None) -> np.ndarray:
         """One step of every sequence: scans[s] is sequence s's next scan, or None when it has none this step.  Returns an int array:

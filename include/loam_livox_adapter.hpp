@@ -745,7 +745,27 @@ class Points_cloud_map {
     }
     // The reference's cells live on the heap and the map grows without bound (:619-672); the device map has a capacity: raise it, content,
     // revisit stamps and frame counter kept (no-op when not larger).
-    void reserve(int64_t max_points) { check(ll_cellmap_reserve(h_, max_points), "ll_cellmap_reserve"); }
+    void reserve(int64_t max_points)
+    {
+        check(ll_cellmap_reserve(h_, max_points), "ll_cellmap_reserve");
+        if (max_points > capacity_) capacity_ = max_points;  // (reserve_for doubles from the capacity the map really has)
+    }
+    // Maps_keyframe's view of the shared cells (:1243-1261: a key frame holds pointers to the map's cells and reads them as they are
+    // now): the cells of this map named in `cells` -- a set: order and repeats do not matter, cells the map does not hold are skipped --
+    // copied on the device into dst, a map of the same resolution on the same device.  dst's previous content goes and its capacity
+    // grows when the selection does not fit; it ends as a fresh map after one append_cloud of the selected points, every point in
+    // the cell it had here.  Returns the cells found; *n_points: the points copied.
+    int64_t extract_cells(const std::vector<std::array<int, 3>> &cells, Points_cloud_map &dst, int64_t *n_points = nullptr)
+    {
+        std::vector<int32_t> ijk(cells.size() * 3);
+        for (size_t i = 0; i < cells.size(); i++)
+            for (int d = 0; d < 3; d++) ijk[3 * i + d] = (int32_t)cells[i][(size_t)d];
+        int64_t n_found = 0, n_pts = 0;
+        check(ll_cellmap_extract_cells(h_, ijk.empty() ? nullptr : ijk.data(), (int64_t)cells.size(), dst.h_, &n_found, &n_pts), "ll_cellmap_extract_cells");
+        if (n_pts > dst.capacity_) dst.capacity_ = n_pts;
+        if (n_points) *n_points = n_pts;
+        return n_found;
+    }
     // the stored points ({x, y, z, 0}, ordered by (cell, insertion)) and the 64-bit cell key of every point where they lie on the device;
     // valid until the next call that changes the map
     void device_view(const float **dev_xyz0, const uint64_t **dev_point_keys, int64_t *n_points, int64_t *n_cells = nullptr)
@@ -759,10 +779,7 @@ class Points_cloud_map {
         check(ll_cellmap_stats(h_, nullptr, &n_pts, nullptr), "ll_cellmap_stats");
         if (cap <= 0) cap = 1;
         while (cap < n_pts + (int64_t)n_more) cap *= 2;
-        if (cap != capacity_) {
-            reserve(cap);
-            capacity_ = cap;
-        }
+        if (cap != capacity_) reserve(cap);
     }
     // find_cells_in_radius( centre, radius ) (:761-788) followed by what service_pub_surround_pts does with the cells
     // (laser_mapping.hpp:1172-1187): every cell's cloud through pcl::VoxelGrid( leaf ) on its own, concatenated in ascending cell order;

@@ -558,6 +558,32 @@ int ll_cellmap_dump(ll_cellmap *c, float *xyzi, int64_t capacity_points, int32_t
  * 64-bit cell key of every point.  Valid until the next call that changes this map.  Input of the multi-GPU gather of cell maps
  * (BASELINE config C4; laser_mapping.hpp:274-275, 1492-1493). */
 int ll_cellmap_device_view(ll_cellmap *c, const float **dev_xyz0, const uint64_t **dev_point_keys, int64_t *n_points, int64_t *n_cells);
+/* The cells of `src` named in cell_ijk[n_list][3], copied into `dst` on the device (Maps_keyframe's view of the shared cells,
+ * cell_map_keyframe.hpp:1243-1261: a key frame holds pointers to the map's cells and reads them as they are now).
+ *   The list is a SET: its order does not matter and a cell named twice is copied once.  A cell that src does not hold is skipped
+ *   and not counted in *n_cells_found; so is an index outside +-2^20 on any axis (the packed cell key cannot represent it).
+ *   n_list == 0 is legal, cell_ijk may then be NULL.
+ *   dst ends with exactly the selected cells in ascending cell order, each cell's points in src's stored (insertion) order, and
+ *   every point under the cell key it had in src: the key is copied, not recomputed from the coordinates.  That is the order in
+ *   which an append of the selected points to an empty map stores them, the order determine_feature's float sums run in.
+ *   When at least one point is copied, dst's bookkeeping is that of a freshly created map after one ll_cellmap_append of those
+ *   points: frame index 2 (the reference's double increment on an empty map), every cell_last_update 0,
+ *   cell_start[n_cells] == n_points.  When nothing is copied dst is empty with frame index 0.  The previous content of dst and
+ *   the result of its last query are discarded in both cases; its revisit threshold stays its own.
+ *   dst's capacity is raised (as by ll_cellmap_reserve) when the selection does not fit, before anything in dst is overwritten.
+ *   The call fails, with ll_last_error() set and dst left as it was, when src == dst, when the two are on different devices or
+ *   have different resolutions (the keys would mean different cubes), for a NULL handle (or a NULL list with n_list > 0), a
+ *   negative n_list, and when dst is a history-owned handle (ll_history_cell_map).  src may be one: the call then waits for the
+ *   frames handed over so far, like every ll_cellmap_* call on such a handle.
+ *   src is not modified.  The call uses src's scratch between queries -- the sort-key arrays of the per-cell VoxelGrid, the head
+ *   flags and the scan's temporary storage -- and not the filtered cloud: a following ll_cellmap_result still returns the last
+ *   query's cloud.
+ *   A map whose cells were replaced by ll_cellmap_query_filter(..., down_sample_replace = 1) stores centroids, each under its
+ *   cell's key.  Extraction keeps them in that cell, where appending their coordinates again could bin a centroid that sits on
+ *   a face into the neighbour.  A key frame is a set of cells, so extraction is the faithful form.
+ * Either count may be NULL. */
+int ll_cellmap_extract_cells(ll_cellmap *src, const int32_t *cell_ijk, int64_t n_list, ll_cellmap *dst, int64_t *n_cells_found,
+                             int64_t *n_points);
 
 /* Points_cloud_cell::determine_feature( if_recompute = 1 ) for every cell (cell_map_keyframe.hpp:436-473 with get_mean
  * :225-237, get_covmat :280-315, covmat_eig_decompose :239-249; SURVEY 8(f) row 4, first half): float sums and second

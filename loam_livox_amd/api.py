@@ -720,6 +720,21 @@ class Cell_map:
         cloud = capi.as_f32(cloud, 4)
         check(self.L.ll_cellmap_append(self.h, ptr(cloud), cloud.shape[0]), "ll_cellmap_append")
 
+    def extract_cells(self, cell_ijk, dst: "Cell_map"):
+        """The cells of this map named in cell_ijk [n, 3], copied on the device into dst (another Cell_map of the same resolution on the
+        same device, whose previous content goes and whose capacity grows when the selection does not fit): a key frame's view of the
+        shared cells (Maps_keyframe::add_cells keeps pointers to the map's cells and reads them as they are now,
+        cell_map_keyframe.hpp:1243-1261).  The list is a set -- order and repeats do not matter, cells the map does not hold are skipped;
+        dst ends with the selected cells in cell order, every point in its stored order under the key it had here, and the
+        bookkeeping of a fresh map after one append of those points (include/loam_livox_hip.h, ll_cellmap_extract_cells).  Returns
+        (cells found, points)."""
+        ijk = np.ascontiguousarray(cell_ijk, np.int32).reshape(-1, 3)
+        nc, npts = C.c_int64(0), C.c_int64(0)
+        check(self.L.ll_cellmap_extract_cells(self.h, ptr(ijk) if len(ijk) else None, len(ijk), dst.h, C.byref(nc), C.byref(npts)),
+              "ll_cellmap_extract_cells")
+        dst.max_points = max(dst.max_points, npts.value)
+        return nc.value, npts.value
+
     def append_cloud_touched(self, cloud, min_points: int = 3) -> np.ndarray:
         """append_cloud( pts, &cell_vec ) (cell_map_keyframe.hpp:619-672): the append, and the indices [n,3] of the cells that received
         at least min_points of this cloud's points (every touched cell on an empty map)."""

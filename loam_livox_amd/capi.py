@@ -141,6 +141,7 @@ SYMBOLS = {
     "ll_cellmap_destroy": (None, [_vp]),
     "ll_cellmap_reserve": (_i32, [_vp, _i64]),
     "ll_cellmap_device_view": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "ll_cellmap_extract_cells": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "ll_cellmap_append": (_i32, [_vp, _vp, _i32]),
     "ll_cellmap_append_touched": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, C.POINTER(_i64)]),
     "ll_cellmap_query_filter": (_i32, [_vp, _vp, C.c_float, C.c_float, C.c_float, _i32, _vp, _vp]),

@@ -10,6 +10,7 @@ void ll::cellmap_release(ll_cellmap *c)
     if (c->d_pose) (void)hipFree(c->d_pose);
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->d_kf) (void)hipFree(c->d_kf);
+    if (c->d_list) (void)hipFree(c->d_list);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -39,16 +40,12 @@ extern "C" int ll_cellmap_create(int32_t device, int64_t max_points, float resol
 
 extern "C" void ll_cellmap_destroy(ll_cellmap *c) { cellmap_release(c); }
 
-// Points_cloud_map grows on the heap without bound (CMK:619-672); the device map has a capacity: raise it, content kept.
-extern "C" int ll_cellmap_reserve(ll_cellmap *c, int64_t max_points)
+// capacity -> max_points (larger than the present one), content kept; the staging buffer follows
+static int cellmap_make_room(ll_cellmap *c, int64_t max_points, const char *where)
 {
-    if (!c) return set_err("ll_cellmap_reserve", "null argument");
-    if (cellmap_settle(c)) return -1;
-    if (max_points < 1 || max_points >= 0x3fffffffLL) return set_err("ll_cellmap_reserve", "max_points out of range");
-    if (max_points <= c->dev.cap) return 0;
     HC(hipSetDevice(c->device));
     const char *err = nullptr;
-    if (cellmap_grow(c->dev, (int)max_points, c->stream, &err)) return set_err("ll_cellmap_reserve", err ? err : "allocation failed");
+    if (cellmap_grow(c->dev, (int)max_points, c->stream, &err)) return set_err(where, err ? err : "allocation failed");
     float4 *d_new = nullptr;
     HC(hipMalloc((void **)&d_new, (size_t)max_points * sizeof(float4)));
     if (c->d_in) (void)hipFree(c->d_in);
@@ -58,6 +55,16 @@ extern "C" int ll_cellmap_reserve(ll_cellmap *c, int64_t max_points)
         c->d_stats = nullptr;
     }
     return 0;
+}
+
+// Points_cloud_map grows on the heap without bound (CMK:619-672); the device map has a capacity: raise it, content kept.
+extern "C" int ll_cellmap_reserve(ll_cellmap *c, int64_t max_points)
+{
+    if (!c) return set_err("ll_cellmap_reserve", "null argument");
+    if (cellmap_settle(c)) return -1;
+    if (max_points < 1 || max_points >= 0x3fffffffLL) return set_err("ll_cellmap_reserve", "max_points out of range");
+    if (max_points <= c->dev.cap) return 0;
+    return cellmap_make_room(c, max_points, "ll_cellmap_reserve");
 }
 
 extern "C" int ll_cellmap_append(ll_cellmap *c, const float *xyzi, int32_t n)
@@ -257,5 +264,42 @@ extern "C" int ll_cellmap_device_view(ll_cellmap *c, const float **dev_xyz0, con
     *dev_point_keys = (const uint64_t *)c->dev.pkey;
     *n_points = c->dev.n_pts;
     if (n_cells) *n_cells = c->dev.n_cells;
+    return 0;
+}
+
+// A key frame's view of the shared cells (CMK:1243-1261): the cells of src named in the list, copied into dst where they lie
+// (ll_cellmap_extract_kernels.hip).  Every refusal comes before the first launch; the one host wait before the points move returns
+// {cells found, points}, which size dst and become its host mirrors.  The work runs on src's stream: dst's is idle between calls.
+extern "C" int ll_cellmap_extract_cells(ll_cellmap *src, const int32_t *cell_ijk, int64_t n_list, ll_cellmap *dst, int64_t *n_cells_found,
+                                        int64_t *n_points)
+{
+    const char *fn = "ll_cellmap_extract_cells";
+    if (!src || !dst || (n_list > 0 && !cell_ijk)) return set_err(fn, "null argument");
+    if (src == dst) return set_err(fn, "source and destination are the same map");
+    if (dst->owner) return set_err(fn, "the destination is owned by a history");
+    if (n_list < 0 || n_list >= 0x3fffffffLL) return set_err(fn, "n_list out of range");
+    if (src->device != dst->device) return set_err(fn, "source and destination are on different devices");
+    if (src->dev.resolution != dst->dev.resolution) return set_err(fn, "source and destination have different resolutions");
+    if (cellmap_settle(src)) return -1;
+    HC(hipSetDevice(src->device));
+    if (n_list > src->list_cap) {
+        int *d_new = nullptr;
+        HC(hipMalloc((void **)&d_new, (size_t)n_list * 3 * sizeof(int)));
+        if (src->d_list) (void)hipFree(src->d_list);
+        src->d_list = d_new;
+        src->list_cap = n_list;
+    }
+    if (n_list > 0) HC(hipMemcpyAsync(src->d_list, cell_ijk, (size_t)n_list * 3 * sizeof(int), hipMemcpyHostToDevice, src->stream));
+    const char *err = nullptr;
+    if (cellmap_extract_mark(src->dev, src->d_list, (int)n_list, src->stream, &err)) return set_err(fn, err);
+    unsigned long long totals = 0;
+    HC(hipMemcpyAsync(&totals, src->dev.skey2 + src->dev.n_cells, sizeof(totals), hipMemcpyDeviceToHost, src->stream));
+    HC(hipStreamSynchronize(src->stream));
+    const int found = (int)(totals >> 32), points = (int)(totals & 0xffffffffu);
+    if (points > dst->dev.cap && cellmap_make_room(dst, points, fn)) return -1;
+    if (cellmap_extract_cells(src->dev, dst->dev, found, points, src->stream, &err)) return set_err(fn, err);
+    HC(hipStreamSynchronize(src->stream));
+    if (n_cells_found) *n_cells_found = found;
+    if (n_points) *n_points = points;
     return 0;
 }

@@ -160,6 +160,8 @@ struct ll_cellmap {
     double *d_pose = nullptr;
     CellStats *d_stats = nullptr;  // allocated by the first ll_cellmap_features / ll_cellmap_keyframe_images
     KfOut *d_kf = nullptr;
+    int *d_list = nullptr;    // staging of a cell list (ll_cellmap_extract_cells), list_cap x {i, j, k}
+    int64_t list_cap = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------- history

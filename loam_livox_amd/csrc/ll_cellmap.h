@@ -45,6 +45,13 @@ int cellmap_touch_counts(CellMapDev &m, int n_before, int n_appended, hipStream_
 int cellmap_query_filter(CellMapDev &m, const double *d_pose, float radius, float max_fov_deg, float leaf, int replace, hipStream_t s,
                          const char **err);
 
+// A set of cells of src copied into dst (ll_cellmap_extract_kernels.hip), in two halves around the caller's one host wait:
+// the cells named in d_ijk[n_list][3] (device) marked and scanned in src's scratch (skey, skey2, tmp) -> src.skey2[src.n_cells] =
+// (cells found << 32 | points) on the device; ...
+int cellmap_extract_mark(CellMapDev &src, const int *d_ijk, int n_list, hipStream_t s, const char **err);
+// ... then, with those two totals read back and dst.cap >= n_points: cell table and points into dst (also uses src.flag)
+int cellmap_extract_cells(CellMapDev &src, CellMapDev &dst, int n_found, int n_points, hipStream_t s, const char **err);
+
 // result block of cellmap_keyframe_images (device memory)
 struct KfOut {
     float img[4][LL_KF_RES * LL_KF_RES];  // m_feature_img_line, _plane, _line_roi, _plane_roi ([phi][theta], blurred)

@@ -15,8 +15,8 @@ The pose graph, the map refinement and every file dump behind that point (:1069-
 
 A key frame is a SET OF CELLS of the full cell map, not a copy: the reference's key frames hold shared pointers to the map's cells, so
 what a key frame is analysed with is whatever those cells contain when it is processed (earlier and later scans included).  Here a key
-frame keeps the cell indices; `materialize` reads those cells out of the device-resident full map into a cell map of its own, in the
-map's (cell, insertion) order, which is the order determine_feature's float sums run in.
+frame keeps the cell indices; `materialize` copies those cells out of the device-resident full map into a cell map of its own
+(ll_cellmap_extract_cells, on the device), in the map's (cell, insertion) order, which is the order determine_feature's float sums run in.
 
 Memory (the shipped loop_closure settings keep a few hundred key frames before any pair is old enough to be compared,
 minimum_keyframe_differen = 200): a processed key frame keeps its direction images, its cell set and the compacted points it was analysed
@@ -153,6 +153,18 @@ class Keyframe_assembly:
 
     # ---- the key frame's view of the shared cells ------------------------------------------------------------------------------------
     def materialize(self, kf: Maps_keyframe) -> Cell_map:
+        """the key frame's cells as a cell map of their own (the caller closes it): copied on the device when the full map offers it
+        (Cell_map.extract_cells: no sort, nothing but the cell list crosses to the device), through the host otherwise (test stubs,
+        api.Full_map_slot).  Both give the same map: the cells in key order, every cell's points in the full map's stored order."""
+        full = self.m_pt_cell_map_full
+        if not hasattr(full, "extract_cells"):
+            return self._materialize_host(kf)
+        want = _unpack_cells(np.fromiter(kf.m_set_cell, np.int64, len(kf.m_set_cell)))
+        km = Cell_map(max(1024, len(want)), self.m_pt_cell_resolution, device=self.device)
+        full.extract_cells(want, km)
+        return km
+
+    def _materialize_host(self, kf: Maps_keyframe) -> Cell_map:
         xyz, ijk, start, _ = self.m_pt_cell_map_full.dump()
         want = np.fromiter(kf.m_set_cell, np.int64, len(kf.m_set_cell))
         sel = np.flatnonzero(np.isin(_pack_cells(ijk), want))
@@ -243,6 +255,12 @@ def _pack_cells(cell_ijk) -> np.ndarray:
     """(i, j, k) cell indices -> one int64 per cell (21 bits per axis, like the device's cell key)"""
     c = np.asarray(cell_ijk, np.int64).reshape(-1, 3) + (1 << 20)
     return c[:, 0] | (c[:, 1] << 21) | (c[:, 2] << 42)
+
+
+def _unpack_cells(packed) -> np.ndarray:
+    """_pack_cells' int64 form -> (i, j, k) int32 [n, 3]"""
+    p = np.asarray(packed, np.int64).reshape(-1)
+    return (np.stack([p, p >> 21, p >> 42], axis=1) & 0x1fffff).astype(np.int32) - (1 << 20)
 
 
 def _close(cm) -> None:

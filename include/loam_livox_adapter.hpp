@@ -692,6 +692,36 @@ class History_batch {
         check(ll_history_batch_cell_map_device_view(h_, sequence, kind, dev_xyz0, dev_point_keys, n_points, n_cells),
               "ll_history_batch_cell_map_device_view");
     }
+    // Maps_keyframe's view of the shared cells (cell_map_keyframe.hpp:1243-1261) for several slots in one call: request r copies the
+    // cells of slot sequences[r]'s map of `kind` (0 corner, 1 surface; 2 the full-cloud map of ll_history_batch_enable_full_maps) named
+    // in cells[r] into *dst[r], on the device, as Points_cloud_map::extract_cells does out of a map of the slot's own.  A slot and a
+    // destination appear at most once per call; enqueues and host waits do not depend on the number of requests.  Returns, per
+    // request, the cells found; n_points (when given): the points copied.
+    // Map: Points_cloud_map (defined below).
+    template <class Map>
+    std::vector<int64_t> extract_cells(int kind, const std::vector<int> &sequences, const std::vector<std::vector<std::array<int, 3>>> &cells,
+                                       const std::vector<Map *> &dst, std::vector<int64_t> *n_points = nullptr)
+    {
+        const size_t R = sequences.size();
+        if (cells.size() != R || dst.size() != R) throw std::invalid_argument("History_batch::extract_cells: one cell list and one destination per sequence");
+        std::vector<int32_t> seq(sequences.begin(), sequences.end()), ijk;
+        std::vector<int64_t> off(R + 1, 0), n_found(R > 0 ? R : 1, 0), n_pts(R > 0 ? R : 1, 0);
+        std::vector<ll_cellmap *> maps(R > 0 ? R : 1, nullptr);
+        for (size_t r = 0; r < R; r++) {
+            for (const std::array<int, 3> &c : cells[r])
+                for (int d = 0; d < 3; d++) ijk.push_back((int32_t)c[(size_t)d]);
+            off[r + 1] = off[r] + (int64_t)cells[r].size();
+            maps[r] = dst[r] ? dst[r]->handle() : nullptr;
+        }
+        check(ll_history_batch_extract_cells(h_, kind, (int32_t)R, seq.data(), off.data(), ijk.empty() ? nullptr : ijk.data(), maps.data(), n_found.data(),
+                                             n_pts.data()),
+              "ll_history_batch_extract_cells");
+        for (size_t r = 0; r < R; r++) dst[r]->holds_at_least(n_pts[r]);
+        n_found.resize(R);
+        n_pts.resize(R);
+        if (n_points) *n_points = n_pts;
+        return n_found;
+    }
 
    private:
     ll_history_batch *h_ = nullptr;
@@ -822,6 +852,11 @@ class Points_cloud_map {
         return s;
     }
     ll_cellmap *handle() { return h_; }
+    // the library raised the capacity itself (History_batch::extract_cells into this map): reserve_for doubles from what the map has
+    void holds_at_least(int64_t n_points)
+    {
+        if (n_points > capacity_) capacity_ = n_points;
+    }
 
    private:
     ll_cellmap *h_ = nullptr;

@@ -584,6 +584,32 @@ int ll_cellmap_device_view(ll_cellmap *c, const float **dev_xyz0, const uint64_t
  * Either count may be NULL. */
 int ll_cellmap_extract_cells(ll_cellmap *src, const int32_t *cell_ijk, int64_t n_list, ll_cellmap *dst, int64_t *n_cells_found,
                              int64_t *n_points);
+/* The same out of the batched store, for several slots in one call: the key frames that lock-step sequences close in the same
+ * step.  Request r (0 <= r < n_requests, 1 <= n_requests <= n_sequences) names slot sequences[r], the cells
+ * cell_ijk[list_offsets[r] .. list_offsets[r + 1]) ({i, j, k} triples, counted in cells) and the destination dst[r]; a slot and a
+ * destination appear at most once per call.  kind 0 / 1 read the feature cell maps (ll_history_batch_enable_cell_maps), kind 2
+ * the full-cloud maps (ll_history_batch_enable_full_maps).
+ *   Every dst[r] ends as ll_cellmap_extract_cells( the slot's map, its list, dst[r] ) would leave it: the selected cells in key
+ *   order, every point in stored order under the key it had, frame index 2 and every stamp 0 -- or empty with frame index 0 --
+ *   and no query result.  A list is a set: order and repeats do not matter, cells the SLOT does not hold (other slots may) and
+ *   indices beyond +-2^20 are skipped and not counted.  n_cells_found[r] / n_points[r] are the request's totals.
+ *   Cost: the store is first put in order as by every reader (at most one materialisation, with its own wait); then one copy of
+ *   the requests and lists, a memset, a mark launch over the list entries, ONE scan over the cell table, a totals launch and one
+ *   copy back, on which the host waits; one copy of the destinations' addresses, a table launch and a gather launch with one
+ *   lane per copied point, and a final wait: nine enqueues and two waits whatever n_requests is.  Nothing is sorted and nothing
+ *   of the store is written; the store, its host mirrors, the touched lists and the frame counters are unchanged.
+ *   Every destination that needs room is grown (as by ll_cellmap_reserve, content kept) before any destination is overwritten:
+ *   when a growth fails no destination has changed.
+ *   Refused before anything is enqueued, all destinations as they were: a null handle, sequences, list_offsets, dst, dst[r] or
+ *   count array (or a null cell_ijk with a non-empty list), n_requests outside 1 .. n_sequences, a sequence out of range or named
+ *   twice, a destination named twice, owned by a history, on another device or of another resolution than the kind was enabled
+ *   with, list_offsets that are negative or descend, lists of 2^30 / 3 cells or more in all, a kind that is not enabled.
+ * ll_history_batch_extract_work is a test tap: out[0] enqueues and out[1] host waits of the last call behind the store's being put
+ * in order, out[2] stored points sorted or moved by such calls (nothing adds to it), out[3] materialisations such calls caused. */
+int ll_history_batch_extract_cells(ll_history_batch *h, int32_t kind, int32_t n_requests, const int32_t *sequences,
+                                   const int64_t *list_offsets, const int32_t *cell_ijk, ll_cellmap *const *dst, int64_t *n_cells_found,
+                                   int64_t *n_points);
+int ll_history_batch_extract_work(ll_history_batch *h, int64_t out[4]);
 
 /* Points_cloud_cell::determine_feature( if_recompute = 1 ) for every cell (cell_map_keyframe.hpp:436-473 with get_mean
  * :225-237, get_covmat :280-315, covmat_eig_decompose :239-249; SURVEY 8(f) row 4, first half): float sums and second

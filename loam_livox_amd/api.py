@@ -577,6 +577,34 @@ class History_buffer_batch:
     def full_map(self, sequence: int) -> "Full_map_slot":
         return Full_map_slot(self, int(sequence))
 
+    def extract_cells(self, kind: int, sequences, cell_lists, dsts):
+        """Key frames' views of the shared cells for several slots in one call (include/loam_livox_hip.h,
+        ll_history_batch_extract_cells): request r copies the cells of slot sequences[r]'s map of `kind` (0 corner, 1 surface, 2 full
+        cloud) named in cell_lists[r] [n, 3] into the Cell_map dsts[r], on the device, as Cell_map.extract_cells would out of a map
+        of the slot's own.  A slot and a destination appear at most once.  Returns [(cells found, points)] per request."""
+        R = len(sequences)
+        if len(cell_lists) != R or len(dsts) != R:
+            raise ValueError(f"{R} sequences, {len(cell_lists)} cell lists, {len(dsts)} destinations")
+        seq = np.ascontiguousarray(sequences, np.int32).reshape(R)
+        lists = [np.ascontiguousarray(c, np.int32).reshape(-1, 3) for c in cell_lists]
+        off = np.zeros(R + 1, np.int64)
+        off[1:] = np.cumsum([len(c) for c in lists])
+        ijk = np.ascontiguousarray(np.concatenate(lists)) if R and off[-1] else None
+        arr = (C.c_void_p * max(R, 1))(*[d.h for d in dsts])
+        nc, npts = np.zeros(max(R, 1), np.int64), np.zeros(max(R, 1), np.int64)
+        check(self.L.ll_history_batch_extract_cells(self.h, int(kind), R, ptr(seq), ptr(off), ptr(ijk), arr, ptr(nc), ptr(npts)),
+              "ll_history_batch_extract_cells")
+        for d, n in zip(dsts, npts):
+            d.max_points = max(d.max_points, int(n))
+        return [(int(a), int(b)) for a, b in zip(nc[:R], npts[:R])]
+
+    def extract_work(self) -> np.ndarray:
+        """test tap (ll_history_batch_extract_work): enqueues and host waits of the last extract_cells, stored points sorted or moved
+        by extractions (stays 0), materialisations extractions caused"""
+        out = np.zeros(4, np.int64)
+        check(self.L.ll_history_batch_extract_work(self.h, ptr(out)), "ll_history_batch_extract_work")
+        return out
+
     def full_map_work(self) -> np.ndarray:
         """test tap (ll_history_batch_full_map_work): enqueues and host waits of the last append_full, stored points sorted or gathered
         inside append_full calls, materialisations of the full store"""
@@ -626,6 +654,11 @@ class Cell_map_slot:
         pts = torch.as_tensor(_DeviceView(p.value, n.value), device=f"cuda:{device}").clone()
         keys = torch.as_tensor(_DeviceView64(k.value, n.value), device=f"cuda:{device}").clone()
         return pts, keys
+
+    def extract_cells_into(self, cell_ijk, dst: "Cell_map"):
+        """Cell_map.extract_cells for this slot: the one-request form of History_buffer_batch.extract_cells.  (Not named extract_cells:
+        a consumer that holds many slots batches its requests; Keyframe_assembly.materialize falls back to this.)"""
+        return self.batch.extract_cells(self.kind, [self.sequence], [cell_ijk], [dst])[0]
 
 
 class Full_map_slot(Cell_map_slot):

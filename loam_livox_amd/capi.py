@@ -136,6 +136,8 @@ SYMBOLS = {
     "ll_history_batch_append_full_fe": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
     "ll_history_batch_full_touched": (_i32, [_vp, _i32, _vp, _i64, _vp]),
     "ll_history_batch_full_map_work": (_i32, [_vp, _vp]),
+    "ll_history_batch_extract_cells": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ll_history_batch_extract_work": (_i32, [_vp, _vp]),
     "ll_map_grid_geometry": (_i32, [_vp, _f, _vp, _vp, _vp]),
     "ll_cellmap_create": (_i32, [_i32, _i64, C.c_float, _i32, _vp]),
     "ll_cellmap_destroy": (None, [_vp]),

@@ -41,7 +41,7 @@ extern "C" int ll_cellmap_create(int32_t device, int64_t max_points, float resol
 extern "C" void ll_cellmap_destroy(ll_cellmap *c) { cellmap_release(c); }
 
 // capacity -> max_points (larger than the present one), content kept; the staging buffer follows
-static int cellmap_make_room(ll_cellmap *c, int64_t max_points, const char *where)
+int ll::cellmap_make_room(ll_cellmap *c, int64_t max_points, const char *where)
 {
     HC(hipSetDevice(c->device));
     const char *err = nullptr;

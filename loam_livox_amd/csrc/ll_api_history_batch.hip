@@ -12,6 +12,9 @@
 // Independently of those it can keep the full-cloud map of every slot (ll_history_batch_enable_full_maps): a third store of the same
 // kind, fed by ll_history_batch_append_full_fe with the extractor's full selections and reporting the cells each scan touched
 // (ll_fullmap_batch_kernels.hip).  Nothing of an add or of a refresh reads it.
+//
+// Chosen cells of any of the three stores leave it on the device, for several slots in one call (ll_history_batch_extract_cells,
+// ll_cellmap_batch_extract_kernels.hip): the key frames the sequences close in the same step, each into a cell map of its own.
 #include "ll_api_internal.h"
 #include "ll_cellmatch_batch.h"
 #include "ll_fullmap_batch.h"
@@ -80,6 +83,13 @@ struct ll_history_batch {
     size_t fm_cells_cap = 0;
     std::vector<std::vector<int32_t>> fm_touched;  // [S] the {i, j, k} of the cells the slot's last appended scan touched
     int64_t fm_work[4] = {0, 0, 0, 0};       // ll_history_batch_full_map_work
+    // cells of several slots into cell maps (ll_history_batch_extract_cells): the staged requests and lists, the totals, the destinations
+    float cm_res[3] = {0.f, 0.f, 0.f};       // the cell resolution every kind was enabled with
+    int *hp_cx_in = nullptr, *d_cx_in = nullptr;
+    size_t cx_in_cap = 0;                    // ints
+    int *hp_cx_out = nullptr, *d_cx_out = nullptr;      // [4 S + 2]
+    CxbDst *hp_cx_dst = nullptr, *d_cx_dst = nullptr;   // [S]
+    int64_t cx_work[4] = {0, 0, 0, 0};       // ll_history_batch_extract_work
 };
 
 // grow-only device buffer, half again as large as asked when it has to move
@@ -190,6 +200,12 @@ extern "C" void ll_history_batch_destroy(ll_history_batch *h)
     hb_full_free(h);
     for (int k = 0; k < 2; k++) hb_cellmatch_free(h->cq[k]);
     if (h->d_cq_tab) (void)hipFree(h->d_cq_tab);
+    void *cx_dev[] = {h->d_cx_in, h->d_cx_out, h->d_cx_dst};
+    for (void *p : cx_dev)
+        if (p) (void)hipFree(p);
+    void *cx_host[] = {h->hp_cx_in, h->hp_cx_out, h->hp_cx_dst};
+    for (void *p : cx_host)
+        if (p) (void)hipHostFree(p);
     void *host[] = {h->hp_add, h->hp_cnt, h->hp_ref, h->hp_mm_init, h->hp_mm, h->hp_grid, h->hp_nvalid, h->hp_cm_tab, h->hp_cm, h->hp_cq_tab, h->hp_cq};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
@@ -776,6 +792,7 @@ extern "C" int ll_history_batch_enable_cell_maps(ll_history_batch *h, int64_t in
         return -1;
     }
     h->cm_on = true;
+    h->cm_res[0] = h->cm_res[1] = cell_resolution;
     return 0;
 }
 
@@ -925,6 +942,7 @@ extern "C" int ll_history_batch_enable_full_maps(ll_history_batch *h, int64_t in
         return -1;
     }
     h->fm_on = true;
+    h->cm_res[2] = cell_resolution;
     return 0;
 }
 
@@ -1089,6 +1107,164 @@ extern "C" int ll_history_batch_full_map_work(ll_history_batch *h, int64_t out[4
     if (!h || !out) return set_err(where, "null argument");
     if (!h->fm_on) return set_err(where, "full maps are not enabled (ll_history_batch_enable_full_maps)");
     for (int i = 0; i < 4; i++) out[i] = h->fm_work[i];
+    return 0;
+}
+
+
+// ================================================================================================ cells of the slots into cell maps
+// the staging of a call and the scratch of its chain (the stream is idle: the store has just been put in order)
+static int hb_extract_reserve(const char *where, ll_history_batch *h, CbDev &m, size_t n_in)
+{
+    const size_t S = (size_t)h->S;
+    if (!h->hp_cx_out) HC(hipHostMalloc((void **)&h->hp_cx_out, (4 * S + 2) * sizeof(int), hipHostMallocDefault));
+    if (!h->hp_cx_dst) HC(hipHostMalloc((void **)&h->hp_cx_dst, S * sizeof(CxbDst), hipHostMallocDefault));
+    if (!h->d_cx_out) DM(h->d_cx_out, 4 * S + 2);
+    if (!h->d_cx_dst) DM(h->d_cx_dst, S);
+    if (n_in > h->cx_in_cap) {
+        const size_t want = n_in + n_in / 2 + 64;
+        int *hp = nullptr, *d = nullptr;
+        HC(hipHostMalloc((void **)&hp, want * sizeof(int), hipHostMallocDefault));
+        if (hipMalloc((void **)&d, want * sizeof(int)) != hipSuccess) {
+            (void)hipHostFree(hp);
+            return set_err(where, "allocation failed");
+        }
+        if (h->hp_cx_in) (void)hipHostFree(h->hp_cx_in);
+        if (h->d_cx_in) (void)hipFree(h->d_cx_in);
+        h->hp_cx_in = hp;
+        h->d_cx_in = d;
+        h->cx_in_cap = want;
+    }
+    if (m.mcap < (size_t)m.n_cells + 1) {  // (a store that was never materialised, or one whose every point opened a cell)
+        const size_t n = m.cap > (size_t)m.n_cells + 1 ? m.cap : (size_t)m.n_cells + 1;
+        if (hb_cells_move(h, &m.mkey, n, 0) || hb_cells_move(h, &m.mkey2, n, 0) || hb_cells_move(h, &m.mval, n, 0) ||
+            hb_cells_move(h, &m.mval2, n, 0) || hb_cells_move(h, &m.mslot, n, 0) || hb_cells_move(h, &m.mslot2, n, 0))
+            return -1;
+        m.mcap = n;
+    }
+    size_t bytes = 0;
+    const char *err = nullptr;
+    if (cxb_tmp_bytes(m.n_cells, &bytes, &err)) return set_err(where, err);
+    if (bytes > m.tmp_bytes) {
+        char *p = (char *)m.tmp;
+        if (hb_cells_move(h, &p, bytes + bytes / 2, 0)) return -1;
+        m.tmp = p;
+        m.tmp_bytes = bytes + bytes / 2;
+    }
+    return 0;
+}
+
+// Key frames' views of the shared cells (CMK:1243-1261) for several slots at once: request r copies the cells of slot sequences[r]'s
+// map of `kind` named in cell_ijk[list_offsets[r] .. list_offsets[r + 1]) into dst[r], where they lie (ll_cellmap_batch_extract_kernels.hip).
+// Every refusal comes before anything is enqueued; the store is put in order as every reader does; then one fixed chain, one wait
+// for the totals -- which size the destinations: all that need room grow before any is overwritten -- and a final wait.
+extern "C" int ll_history_batch_extract_cells(ll_history_batch *h, int32_t kind, int32_t n_requests, const int32_t *sequences,
+                                              const int64_t *list_offsets, const int32_t *cell_ijk, ll_cellmap *const *dst, int64_t *n_cells_found,
+                                              int64_t *n_points)
+{
+    static const char *where = "ll_history_batch_extract_cells";
+    if (!h) return set_err(where, "null argument");
+    if (kind == 2) {
+        if (!h->fm_on) return set_err(where, "full maps are not enabled (ll_history_batch_enable_full_maps)");
+    } else if (kind == 0 || kind == 1) {
+        if (!h->cm_on) return set_err(where, "cell maps are not enabled (ll_history_batch_enable_cell_maps)");
+    } else {
+        return set_err(where, "kind out of range");
+    }
+    const int S = h->S, R = n_requests;
+    if (R < 1 || R > S) return set_err(where, "n_requests must lie in 1 .. n_sequences");
+    if (!sequences || !list_offsets || !dst || !n_cells_found || !n_points) return set_err(where, "null argument");
+    if (list_offsets[0] < 0) return set_err(where, "list_offsets must not be negative");
+    for (int r = 0; r < R; r++)
+        if (list_offsets[r + 1] < list_offsets[r]) return set_err(where, "list_offsets must not descend");
+    const int64_t n_list64 = list_offsets[R] - list_offsets[0];
+    if (n_list64 >= 0x3fffffffLL / 3) return set_err(where, "the cell lists are too long");
+    if (n_list64 > 0 && !cell_ijk) return set_err(where, "null argument");
+    std::vector<char> named((size_t)S, 0);
+    for (int r = 0; r < R; r++) {
+        const int s = sequences[r];
+        if (s < 0 || s >= S) return set_err(where, "sequence out of range");
+        if (named[s]) return set_err(where, "a sequence is named twice");
+        named[s] = 1;
+        const ll_cellmap *d = dst[r];
+        if (!d) return set_err(where, "null argument");
+        for (int o = 0; o < r; o++)
+            if (dst[o] == d) return set_err(where, "a destination is named twice");
+        if (d->owner) return set_err(where, "a destination is owned by a history");
+        if (d->device != h->device) return set_err(where, "a destination is on another device");
+        if (d->dev.resolution != h->cm_res[kind]) return set_err(where, "a destination has another resolution than the store");
+    }
+    HC(hipSetDevice(h->device));
+    const int64_t mats = kind == 2 ? h->fm_work[3] : h->cm_work[2];
+    if (hb_cells_reader(where, h, sequences[0], kind)) return -1;  // at most one materialisation, with its own wait
+    h->cx_work[3] += (kind == 2 ? h->fm_work[3] : h->cm_work[2]) - mats;
+    CbDev &m = h->cm[kind];
+    const int n_list = (int)n_list64;
+    const size_t n_in = (size_t)3 * R + 1 + (size_t)3 * n_list;
+    if (hb_extract_reserve(where, h, m, n_in)) return -1;
+    // ---- the requests in ascending slot order: the order of the table, and so of the scan
+    std::vector<int> order((size_t)R);
+    for (int r = 0; r < R; r++) order[r] = r;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return sequences[a] < sequences[b]; });
+    int *in = h->hp_cx_in;
+    for (int r = 0; r <= R; r++) in[r] = (int)(list_offsets[r] - list_offsets[0]);
+    for (int r = 0; r < R; r++) in[R + 1 + r] = sequences[r];
+    for (int q = 0; q < R; q++) in[2 * R + 1 + q] = sequences[order[q]];
+    if (n_list > 0) memcpy(in + 3 * R + 1, cell_ijk + 3 * (size_t)list_offsets[0], (size_t)3 * n_list * sizeof(int));
+    int enq = 0, waits = 0;
+    const char *err = nullptr;
+    HC(hipMemcpyAsync(h->d_cx_in, in, n_in * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (cxb_mark(m, h->d_cx_in, R, n_list, h->d_cx_out, h->stream, &enq, &err)) return set_err(where, err);
+    HC(hipMemcpyAsync(h->hp_cx_out, h->d_cx_out, ((size_t)4 * R + 2) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    enq += 2;
+    HC(hipStreamSynchronize(h->stream));  // the only wait before points move
+    waits++;
+    const int *found = h->hp_cx_out, *points = found + R, *qrank = points + R, *qpos = qrank + R + 1;
+    const int n_found = qrank[R], n_pts = qpos[R];
+    for (int q = 0; q < R; q++) {
+        const int s = sequences[order[q]];
+        if (found[q] < 0 || points[q] < found[q] || found[q] > h->cm_coff[kind][s + 1] - h->cm_coff[kind][s] ||
+            points[q] > h->cm_poff[kind][s + 1] - h->cm_poff[kind][s] || points[q] >= 0x3fffffff)
+            return set_err(where, "cell selection out of range");
+    }
+    // ---- every destination that needs room grows (content kept) before any is overwritten: a failure here leaves all as they were
+    for (int q = 0; q < R; q++) {
+        ll_cellmap *d = dst[order[q]];
+        if (points[q] > d->dev.cap && cellmap_make_room(d, points[q], where)) return -1;
+    }
+    for (int q = 0; q < R; q++) {
+        const CellMapDev &d = dst[order[q]]->dev;
+        h->hp_cx_dst[q] = CxbDst{d.ckey, d.cstart, d.clast, d.pts, d.pkey};
+    }
+    HC(hipMemcpyAsync(h->d_cx_dst, h->hp_cx_dst, (size_t)R * sizeof(CxbDst), hipMemcpyHostToDevice, h->stream));
+    enq++;
+    if (cxb_extract(m, h->d_cx_in, R, h->d_cx_out, h->d_cx_dst, n_found, n_pts, h->stream, &enq, &err)) return set_err(where, err);
+    HC(hipStreamSynchronize(h->stream));  // the destinations are readable from their own streams
+    waits++;
+    for (int q = 0; q < R; q++) {
+        const int r = order[q];
+        CellMapDev &d = dst[r]->dev;
+        d.n_pts = points[q];
+        d.n_cells = points[q] > 0 ? found[q] : 0;
+        d.frame = points[q] > 0 ? 2 : 0;  // the double increment of an append on an empty map (cellmap_append)
+        d.n_filt = d.n_sel = 0;
+        n_cells_found[r] = found[q];
+        n_points[r] = points[q];
+    }
+    h->cx_work[0] = enq;
+    h->cx_work[1] = waits;
+    return 0;
+}
+
+// Test tap of the extraction: [0] enqueues (launches, library calls, copies) of the last ll_history_batch_extract_cells behind the
+// store's being put in order, [1] its host waits (a materialisation and a growth of a destination wait on top), [2] stored points
+// sorted or moved by extraction calls so far -- the chain copies points out and never touches the store, so nothing ever adds to it:
+// the number is there to be asserted -- [3] materialisations extraction calls caused so far.
+extern "C" int ll_history_batch_extract_work(ll_history_batch *h, int64_t out[4])
+{
+    static const char *where = "ll_history_batch_extract_work";
+    if (!h || !out) return set_err(where, "null argument");
+    if (!h->cm_on && !h->fm_on) return set_err(where, "neither cell maps nor full maps are enabled");
+    for (int i = 0; i < 4; i++) out[i] = h->cx_work[i];
     return 0;
 }
 

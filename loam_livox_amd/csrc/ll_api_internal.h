@@ -245,6 +245,7 @@ int map_rebuild(ll_map *m, int kind, const float *d_raw, int stride, int64_t n, 
                 int64_t *generation = nullptr);
 // ll_api_cellmap.hip
 void cellmap_release(ll_cellmap *c);
+int cellmap_make_room(ll_cellmap *c, int64_t max_points, const char *where);
 // ll_api_history.hip
 int history_cells_drain(ll_history *h);
 float match_cell_size(int kind, float leaf);

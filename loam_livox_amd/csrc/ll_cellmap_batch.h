@@ -68,4 +68,24 @@ int cb_append(CbDev &m, const float4 *src, int src_stride, int max_n, long long 
 // size is poff[S] on the device.
 int cb_materialise(CbDev &m, hipStream_t s, int *launches, const char **err);
 
+// ---- chosen cells of several slots into one cell map each (ll_cellmap_batch_extract_kernels.hip) -------------------------------
+// where one request's cells and points go: the live arrays of its destination cell map
+struct CxbDst {
+    unsigned long long *ckey;
+    int *cstart, *clast;
+    float4 *pts;
+    unsigned long long *pkey;
+};
+// temporary storage the scan over n_cells + 1 words needs
+int cxb_tmp_bytes(int n_cells, size_t *bytes, const char **err);
+// First half, over a store in materialised order (m.n_log = its points; needs n_cells + 1 <= mcap and cxb_tmp_bytes <= tmp_bytes).
+// d_in (device ints): list_off [n_req + 1] and slot [n_req] in the caller's order, the requested slots in ascending order [n_req],
+// then the concatenated lists, n_list x {i, j, k}.  d_out (device ints, 4 n_req + 2): cells found [n_req], points [n_req], first
+// global rank [n_req + 1], first global output position [n_req + 1], all in ascending slot order.  Writes mkey, mkey2, tmp.
+int cxb_mark(CbDev &m, const int *d_in, int n_req, int n_list, int *d_out, hipStream_t s, int *launches, const char **err);
+// Second half, with d_out read back and every destination large enough: d_dst [n_req] in ascending slot order; n_found and n_points
+// are the totals over all requests.  Writes mval, mval2 and the destinations' arrays; nothing of the store.
+int cxb_extract(CbDev &m, const int *d_in, int n_req, const int *d_out, const CxbDst *d_dst, int n_found, int n_points, hipStream_t s, int *launches,
+                const char **err);
+
 }  // namespace ll

@@ -110,6 +110,7 @@ class Keyframe_assembly:
         self.loops = []                 # detected loops: dict(his, last, inlier_threshold, icp_q, icp_t)
         self.if_end = False
         self.log = []                   # one record per compared pair (what the node writes to loop_closure.log)
+        self._prefetched = None         # (key frame, its cell map) handed over in advance (prefetch)
 
     def state(self) -> str:
         """the lists as tests/verbatim_build.py's harness prints them: open key frames frames:cells, waiting ones frames:cells:ending-index"""
@@ -152,17 +153,37 @@ class Keyframe_assembly:
         return cell_vec
 
     # ---- the key frame's view of the shared cells ------------------------------------------------------------------------------------
+    def prefetch(self, kf: Maps_keyframe, cell_map) -> None:
+        """hand over, in advance, the cell map materialize( kf ) is to return: an owner of many assemblies extracts the key frames they
+        close in the same step in one call (History_buffer_batch.extract_cells).  Consumed by the next materialize of that key frame."""
+        self._prefetched = (kf, cell_map)
+
+    def wanted_cells(self, kf: Maps_keyframe) -> np.ndarray:
+        """the key frame's cells as {i, j, k} [n, 3]"""
+        return _unpack_cells(np.fromiter(kf.m_set_cell, np.int64, len(kf.m_set_cell)))
+
     def materialize(self, kf: Maps_keyframe) -> Cell_map:
-        """the key frame's cells as a cell map of their own (the caller closes it): copied on the device when the full map offers it
-        (Cell_map.extract_cells: no sort, nothing but the cell list crosses to the device), through the host otherwise (test stubs,
-        api.Full_map_slot).  Both give the same map: the cells in key order, every cell's points in the full map's stored order."""
+        """the key frame's cells as a cell map of their own (the caller closes it): the one handed over in advance for this key frame
+        (prefetch), else copied on the device when the full map offers it (Cell_map.extract_cells, or a batch slot's
+        extract_cells_into: no sort, nothing but the cell list crosses to the device), through the host otherwise (test stubs).  All
+        give the same map: the cells in key order, every cell's points in the full map's stored order."""
+        ready, self._prefetched = self._prefetched, None
+        if ready is not None:
+            if ready[0] is kf:
+                return ready[1]
+            _close(ready[1])
         full = self.m_pt_cell_map_full
-        if not hasattr(full, "extract_cells"):
+        route = getattr(full, "extract_cells", None) or getattr(full, "extract_cells_into", None)
+        if route is None:
             return self._materialize_host(kf)
-        want = _unpack_cells(np.fromiter(kf.m_set_cell, np.int64, len(kf.m_set_cell)))
-        km = Cell_map(max(1024, len(want)), self.m_pt_cell_resolution, device=self.device)
-        full.extract_cells(want, km)
+        want = self.wanted_cells(kf)
+        km = self.new_keyframe_map(len(want))
+        route(want, km)
         return km
+
+    def new_keyframe_map(self, n_cells: int) -> Cell_map:
+        """an empty cell map for a key frame of n_cells cells to be extracted into (it grows to the points the cells hold)"""
+        return Cell_map(max(1024, n_cells), self.m_pt_cell_resolution, device=self.device)
 
     def _materialize_host(self, kf: Maps_keyframe) -> Cell_map:
         xyz, ijk, start, _ = self.m_pt_cell_map_full.dump()
@@ -187,11 +208,13 @@ class Keyframe_assembly:
         return self._cell_map_from_points(kf.points) if kf.points is not None else self.materialize(kf)
 
     # ---- laser_mapping.hpp:919-1060 --------------------------------------------------------------------------------------------------
-    def process_waiting(self):
-        """Every waiting key frame through one pass of service_loop_detection's loop body.  Returns the loops found in this call."""
+    def process_waiting(self, limit: int | None = None):
+        """Every waiting key frame (the first `limit` of them, when given) through one pass of service_loop_detection's loop body.
+        Returns the loops found in this call."""
         found = []
         avail_ratio_plane, avail_ratio_line = self.avail_ratio_plane, self.avail_ratio_line   # :887-888
-        while self.m_keyframe_need_precession_list and not self.if_end:
+        while self.m_keyframe_need_precession_list and not self.if_end and (limit is None or limit > 0):
+            limit = None if limit is None else limit - 1
             last = self.m_keyframe_need_precession_list.popleft()
             cm = self.materialize(last)                     # update_features_of_each_cells + analyze read the cells as they are now
             last.analysis = cm.keyframe_images()

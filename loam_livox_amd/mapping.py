@@ -313,7 +313,8 @@ class Laser_mapping_batch:
     add.  The store starts at loop_closure["max_points"] points per map (2^18 unless given; it grows) under cell_resolution and
     threshold_cell_revisit; full_map(s) reads slot s (stats(), dump()).  key_frames=True (with full_maps=True only) also owns one
     keyframes.Keyframe_assembly per sequence, built with the rest of loop_closure, on top of its slot: per accepted slot add_scan with
-    the new pose and the slot's frame index after the increment, then process_waiting, as Laser_mapping._keyframe_step does;
+    the new pose and the slot's frame index after the increment, as Laser_mapping._keyframe_step does; then the key frames the slots
+    closed leave the store in one History_buffer_batch.extract_cells and every slot runs its process_waiting on the map handed to it;
     keyframes[s] and loops[s] are those of Laser_mapping run alone on sequence s.  Nothing of the registration reads the full maps:
     poses and reports do not change by a bit.  loop_closure_if_enable itself stays refused: it names Laser_mapping's per-sequence
     map."""
@@ -439,10 +440,39 @@ class Laser_mapping_batch:
         if self.key_frames:
             none = np.zeros((0, 4), np.float32)  # (the slot view answers with the append's list; the cloud itself stays on the device)
             for s, _, pose_new in jobs:
-                kf = self.keyframes[s]
-                kf.add_scan(none, pose_new, int(self.frame_index[s]))
-                self.loops[s] += kf.process_waiting()
+                self.keyframes[s].add_scan(none, pose_new, int(self.frame_index[s]))
+            self._process_keyframes([s for s, _, _ in jobs])
         self.full_map_s += time.perf_counter() - t0
+
+    def _process_keyframes(self, slots) -> None:
+        """The waiting key frames of the step's slots, a round at a time: the first waiting key frame of every slot is extracted from
+        the full-cloud store in ONE call, handed to its assembly, and processed.  No append happens between the extraction and the
+        processing, so the cells are read as they are now (cell_map_keyframe.hpp:1243-1261), as by the assembly's own route.  A
+        slot with nothing waiting still gets its process_waiting, as before."""
+        def waiting(ka):
+            todo = getattr(ka, "m_keyframe_need_precession_list", None)
+            return len(todo) if todo and not ka.if_end else 0
+        first = True
+        while True:
+            todo = [(s, self.keyframes[s]) for s in slots if waiting(self.keyframes[s])]
+            if not todo and not first:
+                return
+            if todo:
+                fronts = [ka.m_keyframe_need_precession_list[0] for _, ka in todo]
+                wants = [ka.wanted_cells(kf) for (_, ka), kf in zip(todo, fronts)]
+                dsts = [ka.new_keyframe_map(len(w)) for (_, ka), w in zip(todo, wants)]
+                try:
+                    self.history_batch.extract_cells(2, [s for s, _ in todo], wants, dsts)
+                except Exception:
+                    for km in dsts:
+                        km.close()
+                    raise
+                for (_, ka), kf, km in zip(todo, fronts, dsts):
+                    ka.prefetch(kf, km)
+            for s in (slots if first else [s for s, _ in todo]):
+                ka = self.keyframes[s]
+                self.loops[s] += ka.process_waiting(limit=1) if waiting(ka) > 1 else ka.process_waiting()
+            first = False
 
     def _upload(self, scans, stamps, active):
         S = self.n_sequences

@@ -905,11 +905,16 @@ __device__ __forceinline__ void load_blk(const RegDev &rd, size_t sb, const doub
 //      order; no flag array in LDS);
 //   2. every active plane block's triple (rd.nn) goes into an LDS hash table of 8192 16-byte slots: the key is claimed with a
 //      64-bit compare-and-swap on {p0, p1} and a 32-bit one on p2 -- whoever loses either moves on to the next slot, nobody
-//      ever waits for another lane -- and the slot index is parked in rd.blk_id;
-//   3. the occupied slots are numbered densely (prefix sum in slot order), one thread per slot gathers the three map points
-//      and computes {n', c} with block_plane() -- the arithmetic reg_build_kernel used per block -- into the scan's table in
-//      HBM (rd.pl_tab); blocks that found no slot within PT_MAX_PROBE probes get a private entry at the top of the table;
-//   4. rd.blk_id[p] <- dense id; the first PT_TCAP (4864) table entries are copied into LDS, where the hash table was;
+//      ever waits for another lane -- and the slot index stays in the thread's registers (a thread owns at most 48 blocks: 24
+//      registers of two 16-bit slots, indexed by the trip number, which is a constant once the selects are unrolled);
+//   3. the occupied slots are numbered densely (prefix sum in slot order); rd.blk_id[p] <- dense id of the block's slot, straight
+//      from the registers (stores only); blocks that found no slot within PT_MAX_PROBE probes get a private entry at the top of
+//      the table in HBM;
+//   4. thread t pulls the triples of the ids t, t + 512, ... (at most 16) into registers -- the last reads of the hash table --
+//      and, after one barrier, gathers their map points and computes {n', c} with block_plane() -- the arithmetic reg_build_kernel
+//      used per block -- straight into the LDS entry of every id below PT_TCAP (4864), where the hash table was, and into the
+//      scan's table in HBM (rd.pl_tab), which the slow evaluation form, the inlier phase and plane_table_reload read: nothing
+//      is stored to HBM only to be loaded back;
 //   5. a cost evaluation streams 18 bytes per block (the fp32 feature point straight from the extractor's cloud + the 16-bit
 //      id) instead of 48 and reads the plane from LDS (ids beyond the LDS part: one 32-byte gather from the table in L2);
 //      whatever LDS the table leaves free caches the first records {f, id} of the scan across the evaluations of a solve.
@@ -922,8 +927,9 @@ __device__ __forceinline__ void load_blk(const RegDev &rd, size_t sb, const doub
 #define LL_LINE_CACHE_MAX 1024        // line blocks of a scan kept in LDS (one workgroup per scan; a group member keeps its first round)
 #define PT_EMPTY_A 0xffffffffffffffffull
 #define PT_EMPTY_B 0xffffffffu
-#define PT_PRIVATE 0xffffu   // rd.blk_id between the two passes: no slot found, the block gets a private table entry
+#define PT_PRIVATE 0xffffu   // a block's slot between the two passes: no slot found, the block gets a private table entry
 #define PT_INACTIVE 0xfffeu  // ... not an active plane block
+#define PT_NTRIP (FAST_MAX_BLOCKS / RS_THREADS / 8)  // trips of eight rounds a compact scan has at most (6)
 
 struct PtSlot {
     unsigned long long a;  // (p0 << 32) | p1
@@ -1031,6 +1037,12 @@ __device__ __noinline__ unsigned long long census_and_plane_table(const RegDev &
     // ---- census (PCR:325,425) of all blocks + pass 1 of the own plane blocks: triples -> hash slots -----------------------
     unsigned long long act = 0;
     int na = 0, nca = 0, nsa = 0;
+    // hash slot (or PT_PRIVATE / PT_INACTIVE) of every own plane block, two per register: a trip's eight (grouped: one) in
+    // hreg[4 * trip ...] (grouped: half `trip & 1` of hreg[trip / 2])
+    constexpr int NHREG = GROUPED ? PT_NTRIP / 2 : PT_NTRIP * 4;
+    unsigned int hreg[NHREG];
+#pragma unroll
+    for (int i = 0; i < NHREG; i++) hreg[i] = PT_INACTIVE | (PT_INACTIVE << 16);
     for (int k0 = 0; k0 * RS_THREADS < totp; k0 += 8) {
         LL_T0(t_trip);
         unsigned char fl8[8];
@@ -1072,13 +1084,19 @@ __device__ __noinline__ unsigned long long census_and_plane_table(const RegDev &
                 h8[GROUPED ? 0 : u] = h;
             }
         }
-        // the slot indices leave together at the end of the trip: a store between the inserts makes the wait for the next
-        // flag byte a wait for that store (the counters are imprecise behind divergent code), one HBM round trip per block
+        // the slot indices stay in registers until pass 2 (no store between the inserts: the wait for the next flag byte would
+        // become a wait for that store, one HBM round trip per block).  `k0 >> 3 == t` is uniform and t a constant after
+        // unrolling, so hreg[] is never indexed at run time and stays out of scratch.
 #pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int j = tid + (k0 + u) * RS_THREADS;
-            if ((!GROUPED || u == g) && j < nS) gstore_u16(ids + j, (unsigned short)h8[GROUPED ? 0 : u]);
-        }
+        for (int t = 0; t < PT_NTRIP; t++)
+            if ((k0 >> 3) == t) {
+                if constexpr (GROUPED) {
+                    hreg[t / 2] = (t & 1) ? ((hreg[t / 2] & 0xffffu) | (h8[0] << 16)) : ((hreg[t / 2] & 0xffff0000u) | h8[0]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++) hreg[4 * t + i] = h8[2 * i] | (h8[2 * i + 1] << 16);
+                }
+            }
 #ifdef LL_SOLVE_TIMING
         LL_TACC(11, t_ins);
 #endif
@@ -1145,70 +1163,52 @@ __device__ __noinline__ unsigned long long census_and_plane_table(const RegDev &
     }
     __syncthreads();
     LL_TACC(13, t_cmp);
-    LL_T0(t_pl);
-    // ---- plane constants -> the table in HBM: thread t computes ids t, t + 512, ... (four triples' gathers in flight) ------
+    LL_T0(t_p2);
     int4 *tabG = pt_table_global(rd, b, g, GROUPED);
     double pose_last[7];
 #pragma unroll
     for (int i = 0; i < 7; i++) pose_last[i] = gload_f64(st->pose_last + i);
-    for (int i0 = tid; i0 < T; i0 += 4 * RS_THREADS) {
-        f4 m[4][3];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int id = i0 + u * RS_THREADS;
-            const unsigned int sl = slot_of_id[id < T ? id : i0];
-            const unsigned long long sa = ht[sl].a;
-            const unsigned int sb2 = ht[sl].b;
-            m[u][0] = gload_pt(map_pts + (unsigned int)(sa >> 32));
-            m[u][1] = gload_pt(map_pts + (unsigned int)sa);
-            m[u][2] = gload_pt(map_pts + sb2);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int id = i0 + u * RS_THREADS;
-            const double pa[3] = {(double)m[u][0].x, (double)m[u][0].y, (double)m[u][0].z};
-            const double pb[3] = {(double)m[u][1].x, (double)m[u][1].y, (double)m[u][1].z};
-            const double pc[3] = {(double)m[u][2].x, (double)m[u][2].y, (double)m[u][2].z};
-            double a_out[3] = {0.0, 0.0, 0.0}, v_out[3] = {0.0, 0.0, 0.0};
-            (void)block_plane(pose_last, pa, pb, pc, a_out, v_out);  // degenerate triples never reach the table (build_one clears their flag)
-            {  // the table holds the SCALED plane {m = |n'| n', beta = |n'| c} (ll_reg_core.h plane_scale)
-                double m_[3], beta_;
-                plane_scale(v_out, a_out[0], m_, &beta_);
-                v_out[0] = m_[0], v_out[1] = m_[1], v_out[2] = m_[2], a_out[0] = beta_;
-            }
-            if (id < T) {
-                gstore_i4(tabG + 2 * id, make_int4(__double2loint(v_out[0]), __double2hiint(v_out[0]), __double2loint(v_out[1]), __double2hiint(v_out[1])));
-                gstore_i4(tabG + 2 * id + 1, make_int4(__double2loint(v_out[2]), __double2hiint(v_out[2]), __double2loint(a_out[0]), __double2hiint(a_out[0])));
-            }
-        }
-    }
-    LL_TACC(14, t_pl);
-    LL_T0(t_p2);
-    // ---- pass 2: slot -> dense id (nothing but arithmetic and LDS reads between the loads and the stores of a trip) ---------
+    // ---- pass 2: slot (registers) -> dense id (LDS) -> rd.blk_id: stores only -----------------------------------------------
     const int region = GROUPED ? rd.tab_cap / LL_GRP : rd.tab_cap;
-    for (int k0 = 0; k0 < kp; k0 += 8) {
-        unsigned short h8[8];
+    if constexpr (GROUPED) {  // one block per trip: p0 + trip * GS (kp <= PT_NTRIP)
+        unsigned int id8[PT_NTRIP];
 #pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int p = p0 + (k0 + u) * GS;
-            h8[u] = gload_u16(ids + (p < nS ? p : 0));
-        }
-        unsigned int id8[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const unsigned int h = h8[u];
+        for (int u = 0; u < PT_NTRIP; u++) {
+            const unsigned int h = (hreg[u / 2] >> ((u & 1) * 16)) & 0xffffu;
             const unsigned int sid = ht[h < PT_SLOTS ? h : 0u].id;
             id8[u] = h < PT_SLOTS ? sid : (h == PT_PRIVATE ? PT_PRIVATE : 0u);
         }
 #pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int p = p0 + (k0 + u) * GS;
+        for (int u = 0; u < PT_NTRIP; u++) {
+            const int p = p0 + u * GS;
             if (p < nS) gstore_u16(ids + p, (unsigned short)id8[u]);
+        }
+    } else {
+        for (int k0 = 0; k0 < kp; k0 += 8) {
+            unsigned int w4[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int t = 0; t < PT_NTRIP; t++)
+                if ((k0 >> 3) == t) {
+#pragma unroll
+                    for (int i = 0; i < 4; i++) w4[i] = hreg[4 * t + i];
+                }
+            unsigned int id8[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const unsigned int h = (w4[u >> 1] >> ((u & 1) * 16)) & 0xffffu;
+                const unsigned int sid = ht[h < PT_SLOTS ? h : 0u].id;
+                id8[u] = h < PT_SLOTS ? sid : (h == PT_PRIVATE ? PT_PRIVATE : 0u);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int p = p0 + (k0 + u) * GS;
+                if (p < nS) gstore_u16(ids + p, (unsigned short)id8[u]);
+            }
         }
     }
     if (sh.pt_priv > 0) {  // (uniform; rare: the hash table was too crowded around some triples -- those blocks get entries of
-        int npriv = 0;     //  their own at the top of the table region, numbered per thread and then across the workgroup)
-        for (int k = 0; k < kp; k++) {
+        int npriv = 0;     //  their own at the top of the table region, numbered per thread and then across the workgroup;
+        for (int k = 0; k < kp; k++) {  // they live in HBM only)
             const int p = p0 + k * GS;
             if (p < nS && gload_u16(ids + p) == PT_PRIVATE) npriv++;
         }
@@ -1236,24 +1236,28 @@ __device__ __noinline__ unsigned long long census_and_plane_table(const RegDev &
             gstore_u16(ids + p, (unsigned short)id);
         }
     }
-    __threadfence_block();
-    __syncthreads();  // the hash table is dead, the table in HBM complete
-    // ---- the first PT_TCAP entries -> LDS; the rest of s_raw caches records ----------------------------------------------
+    LL_TACC(15, t_p2);
+    LL_T0(t_pl);
+    // ---- the triples of the thread's ids t, t + 512, ... -> registers (the last readers of the hash table and the id -> slot
+    //      map: after the barrier the planes overwrite them) ---------------------------------------------------------------------
+    constexpr int IPT = PT_SLOTS / RS_THREADS;  // ids per thread at most
+    const int Tu = __builtin_amdgcn_readfirstlane(T);
+    unsigned long long ta[IPT];
+    unsigned int tb[IPT];
+#pragma unroll
+    for (int i = 0; i < IPT; i++) ta[i] = 0ull, tb[i] = 0u;
+#pragma unroll
+    for (int q = 0; q < IPT / 4; q++)
+        if (q * 4 * RS_THREADS < Tu) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int id = tid + (4 * q + u) * RS_THREADS;
+                const unsigned int sl = slot_of_id[id < T ? id : 0] & (PT_SLOTS - 1);
+                ta[4 * q + u] = ht[sl].a;
+                tb[4 * q + u] = ht[sl].b;
+            }
+        }
     const int Tl = T < PT_TCAP ? T : PT_TCAP;
-    int4 *s_tab = (int4 *)s_raw;
-    for (int e0 = tid; e0 < 2 * Tl; e0 += 8 * RS_THREADS) {
-        int4 v8[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int e = e0 + u * RS_THREADS;
-            v8[u] = gload_i4(tabG + (e < 2 * Tl ? e : e0));
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int e = e0 + u * RS_THREADS;
-            if (e < 2 * Tl) lds_store_i4(s_tab + e, v8[u]);
-        }
-    }
     if (tid == 0) {
         // (T beyond the LDS part, or private entries: the evaluation takes its slower form, solver_eval3)
         // Line blocks (64 B each: sensor point + a', v' in fp64) are few in a Q-full scan and half of a voxel-filtered one; they are
@@ -1274,8 +1278,61 @@ __device__ __noinline__ unsigned long long census_and_plane_table(const RegDev &
         sh.pt_kc = kc < kp ? kc : kp;
         sh.pt_nl = nl;
     }
-    __syncthreads();
-    LL_TACC(15, t_p2);
+    __syncthreads();  // the hash table is dead
+    // ---- plane constants: ids below PT_TCAP straight into their LDS entries, every id into the table in HBM (which the slow
+    //      evaluation form, the inlier phase and plane_table_reload read; nobody waits for these stores).  Four triples' gathers
+    //      in flight -------------------------------------------------------------------------------------------------------------
+    int4 *s_tab = (int4 *)s_raw;
+#pragma unroll 1  // (one copy of the plane arithmetic: the selects below cost a few moves per trip)
+    for (int q = 0; q * 4 * RS_THREADS < Tu; q++) {
+        unsigned long long a4[4] = {0ull, 0ull, 0ull, 0ull};
+        unsigned int b4[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int t = 0; t < IPT / 4; t++)
+            if (q == t) {
+#pragma unroll
+                for (int u = 0; u < 4; u++) a4[u] = ta[4 * t + u], b4[u] = tb[4 * t + u];
+            }
+        const int i0 = tid + q * 4 * RS_THREADS;
+        if (i0 < T) {
+            f4 m[4][3];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int id = i0 + u * RS_THREADS;
+                const unsigned long long sa = id < T ? a4[u] : a4[0];
+                const unsigned int sb2 = id < T ? b4[u] : b4[0];
+                m[u][0] = gload_pt(map_pts + (unsigned int)(sa >> 32));
+                m[u][1] = gload_pt(map_pts + (unsigned int)sa);
+                m[u][2] = gload_pt(map_pts + sb2);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int id = i0 + u * RS_THREADS;
+                const double pa[3] = {(double)m[u][0].x, (double)m[u][0].y, (double)m[u][0].z};
+                const double pb[3] = {(double)m[u][1].x, (double)m[u][1].y, (double)m[u][1].z};
+                const double pc[3] = {(double)m[u][2].x, (double)m[u][2].y, (double)m[u][2].z};
+                double a_out[3] = {0.0, 0.0, 0.0}, v_out[3] = {0.0, 0.0, 0.0};
+                (void)block_plane(pose_last, pa, pb, pc, a_out, v_out);  // degenerate triples never reach the table (build_one clears their flag)
+                {  // the table holds the SCALED plane {m = |n'| n', beta = |n'| c} (ll_reg_core.h plane_scale)
+                    double m_[3], beta_;
+                    plane_scale(v_out, a_out[0], m_, &beta_);
+                    v_out[0] = m_[0], v_out[1] = m_[1], v_out[2] = m_[2], a_out[0] = beta_;
+                }
+                const int4 ob = make_int4(__double2loint(v_out[0]), __double2hiint(v_out[0]), __double2loint(v_out[1]), __double2hiint(v_out[1]));
+                const int4 oc = make_int4(__double2loint(v_out[2]), __double2hiint(v_out[2]), __double2loint(a_out[0]), __double2hiint(a_out[0]));
+                if (id < Tl) {
+                    lds_store_i4(s_tab + 2 * id, ob);
+                    lds_store_i4(s_tab + 2 * id + 1, oc);
+                }
+                if (id < T) {
+                    gstore_i4(tabG + 2 * id, ob);
+                    gstore_i4(tabG + 2 * id + 1, oc);
+                }
+            }
+        }
+    }
+    __syncthreads();  // the LDS part of the table is complete
+    LL_TACC(14, t_pl);
     LL_TACC(8, t_tab);
     return act;
 }

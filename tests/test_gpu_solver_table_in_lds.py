@@ -1,0 +1,212 @@
+"""-m gpu: the Mid-40 solver's plane table, built straight into LDS (ll_reg_kernels.hip census_and_plane_table): the hash slots of
+a thread's blocks wait in registers between the two passes, the triples of its ids are pulled into registers before the planes
+overwrite the hash table.  Shapes at which that can go wrong -- block counts on either side of one round (512), one trip of eight
+rounds (4096) and one trip plus one block, a last trip of nothing but flag-cleared blocks, more distinct triples than the LDS part
+of the table holds -- in the three forms the table is built in: a group of eight workgroups per scan (batches of up to 16 scans with a
+scan of 6000 features or more), one workgroup per scan with the groups switched off, and one workgroup per scan as batches of more
+than 16 scans run it (the headline's dispatch).  Every result is compared with the oracle (the tolerances of tests/test_gpu_reg.py)
+and with the same scans on the general solver path, which keeps {n', c} with every block and builds no table (pose 1e-12)."""
+import numpy as np
+import pytest
+
+from loam_livox_amd import synth
+from loam_livox_amd.api import Map_buffer, Point_cloud_registration
+from oracle import orc
+from tests.conftest import oracle_features
+
+pytestmark = pytest.mark.gpu
+POSE_TOL_M, POSE_TOL_RAD = 1e-4, 1e-4   # BASELINE.json north_star (tests/test_gpu_reg.py)
+ORACLE_TOL = 1e-7                       # "what we actually expect from identical algorithms in fp64" (tests/test_gpu_reg.py)
+GENERAL_TOL = 1e-12                     # plane table against per-block constants: the same numbers summed in another grouping
+ICP, CERES = 4, 20
+COUNTS = (1, 511, 512, 513, 4095, 4097)   # surface features: either side of one round, of one trip (8 rounds), one trip + one block (8 * 512 + 1)
+PT_TCAP = 4864                          # table entries the LDS part holds (ll_reg_kernels.hip)
+
+
+def set_params(reg, icp=ICP):
+    p = reg.params
+    p.icp_max_iterations, p.ceres_max_iterations, p.force_all_iterations = icp, CERES, 1
+    p.para_max_angular_rate, p.para_max_speed, p.max_final_cost = 20.0, 0.3, 100.0
+    p.current_frame_index, p.mapping_init_accumulate_frames = 100, 50
+    return p
+
+
+class Case:
+    """one scan's features, its start pose and the oracle's answer (computed once, never changed)"""
+
+    def __init__(self, name, fc, fs, pose, tree_c, tree_s, icp=ICP):
+        self.name, self.fc, self.fs, self.pose = name, np.ascontiguousarray(fc), np.ascontiguousarray(fs), pose.copy()
+        prm = orc.RegParams.defaults(icp_iters=icp, ceres_iters=CERES, force_all=1)
+        self.ret, self.pc, _, self.rep = orc.reg_solve(tree_c, tree_s, self.fc, self.fs, prm, pose, pose)
+
+
+def spread(fs, n):
+    """n features spread evenly over the scan (the geometry stays that of the whole scan)"""
+    return fs[np.linspace(0, len(fs) - 1, n).astype(np.int64)]
+
+
+@pytest.fixture(scope="module")
+def rooms(gpu_lib):
+    """a 40 k-point map of the synthetic rooms, one scan, and the scan thinned to the block counts under test"""
+    world, corner, surf = synth.make_maps(40_000)
+    tree_c, tree_s = orc.KdTree(corner), orc.KdTree(surf)
+    m = Map_buffer()
+    m.setInputCloud(Map_buffer.CORNER, corner)
+    m.setInputCloud(Map_buffer.SURF, surf)
+    sc = synth.make_scan(world, 0)
+    _, _, _, _, fc, fs = oracle_features(sc)
+    assert len(fs) > 8192 and len(fc) + len(fs) >= 6000   # the whole scan alone makes a batch of up to 16 take the grouped form
+    cases = {"full": Case("full", fc, fs, sc.pose_init, tree_c, tree_s)}
+    for n in COUNTS:
+        cases[n] = Case(str(n), fc, spread(fs, n), sc.pose_init, tree_c, tree_s)
+    # an inactive tail: one full trip of 4096 good blocks, then 2000 features half a kilometre above the map -- no neighbours inside
+    # the search radius, so every block of the last trip (rounds 8 - 11; a group member's second block) has its flag cleared
+    far = spread(fs, 2000).copy()
+    far[:, 2] += 500.0
+    cases["tail"] = Case("tail", fc, np.concatenate([spread(fs, 4096), far]), sc.pose_init, tree_c, tree_s)
+    assert cases["tail"].rep.surf_avail <= 4096
+    yield dict(map=m, cases=cases)
+    m.close()
+
+
+@pytest.fixture(scope="module")
+def noise(gpu_lib, rooms):
+    """the same scan against a uniform random cloud: nearly every surface query has a neighbour triple of its own, so the scan has more
+    distinct triples than the LDS part of the table holds (the construction of test_plane_table_agrees_with_per_block_records)"""
+    full = rooms["cases"]["full"]
+    rng = np.random.default_rng(5)
+    q = synth.transform_points(full.pose, full.fs[:, :3])
+    lo, hi = q.min(0) - 1.0, q.max(0) + 1.0
+    corner = rng.uniform(lo, hi, (60000, 3)).astype(np.float32)
+    surf = rng.uniform(lo, hi, (400000, 3)).astype(np.float32)
+    tree_c, tree_s = orc.KdTree(corner), orc.KdTree(surf)
+    m = Map_buffer()
+    m.setInputCloud(Map_buffer.CORNER, corner)
+    m.setInputCloud(Map_buffer.SURF, surf)
+    cases = {"full": Case("noise-full", full.fc, full.fs, full.pose, tree_c, tree_s, icp=2),
+             4097: Case("noise-4097", full.fc, spread(full.fs, 4097), full.pose, tree_c, tree_s, icp=2)}
+    yield dict(map=m, cases=cases, tree_s=tree_s)
+    m.close()
+
+
+def run(m, cases, general=False, groups=True, icp=ICP, debug=False):
+    reg = Point_cloud_registration(max_scans=len(cases), max_features=24000)
+    reg.set_debug(debug, force_general_solver=general, no_solver_groups=not groups, no_small_solver=True)
+    set_params(reg, icp)
+    pl = np.stack([c.pose for c in cases])
+    res, pc, _, reps = reg.solve_batch(m, [c.fc for c in cases], [c.fs for c in cases], pl, pl)
+    return reg, res, pc, reps
+
+
+def check_against_oracle_and_general(tag, cases, res, pc, reps, gen):
+    """gen: name -> pose of the same scan on the general path.  Prints every figure before it asserts."""
+    fig = []
+    for i, c in enumerate(cases):
+        dt, dr = synth.pose_error(pc[i], c.pc)
+        gt, gr = synth.pose_error(pc[i], gen[c.name])
+        fig.append((c.name, dt, dr, gt, gr))
+        print(f"{tag} scan {c.name:>10}: vs oracle {dt:.2e} m {dr:.2e} rad; vs general path {gt:.2e} m {gr:.2e} rad; blocks {reps[i].n_blocks_last}")
+    for i, c in enumerate(cases):
+        _, dt, dr, gt, gr = fig[i]
+        g, o = reps[i], c.rep
+        assert res[i] == c.ret and np.all(np.isfinite(pc[i])), c.name
+        assert dt <= POSE_TOL_M and dr <= POSE_TOL_RAD and dt < ORACLE_TOL and dr < ORACLE_TOL, (c.name, dt, dr)
+        assert g.icp_iterations == o.icp_iterations and g.n_blocks_last == o.n_blocks_last, c.name
+        assert g.corner_avail == o.corner_avail and g.surf_avail == o.surf_avail and g.lm_iterations_total == o.lm_iterations_total, c.name
+        assert np.isclose(g.final_cost, o.final_cost, rtol=1e-8) and np.isclose(g.initial_cost, o.initial_cost, rtol=1e-8), c.name
+        assert np.isclose(g.inlier_threshold, o.inlier_threshold, rtol=1e-8), c.name
+        assert gt < GENERAL_TOL and gr < GENERAL_TOL, (c.name, gt, gr)
+
+
+def batches_of_3(cs):
+    # every batch of three holds a scan of 6000 features or more (the grouped form) and scans of different counts
+    return [[cs["full"], cs[1], cs[511]], [cs[512], cs["full"], cs[513]], [cs[4095], cs[4097], cs["tail"]]]
+
+
+def batch_of_17(cs):
+    order = ["full", 1, 511, 512, 513, 4095, 4097, "tail"]
+    return [cs[order[i % len(order)]] for i in range(17)]
+
+
+@pytest.fixture(scope="module")
+def rooms_general(rooms):
+    """every scan once on the general path (per-block constants, no table): name -> pose"""
+    cases = batch_of_17(rooms["cases"])
+    reg, res, pc, _ = run(rooms["map"], cases, general=True)
+    reg.close()
+    return {c.name: pc[i].copy() for i, c in enumerate(cases)}
+
+
+@pytest.mark.parametrize("groups", [True, False])
+def test_block_counts_around_the_loop_edges_batches_of_three(rooms, rooms_general, groups):
+    """B = 3: the default (a group of 8 workgroups per scan: GROUPED, one block per trip and member) and with the groups off (one workgroup
+    per scan, eight blocks per trip).  The last batch ends in the scan whose last trip is all flag-cleared blocks."""
+    for k, cases in enumerate(batches_of_3(rooms["cases"])):
+        reg, res, pc, reps = run(rooms["map"], cases, groups=groups)
+        reg.close()
+        check_against_oracle_and_general(f"B=3 groups={groups} batch {k}", cases, res, pc, reps, rooms_general)
+
+
+def test_block_counts_around_the_loop_edges_batch_of_17(rooms, rooms_general):
+    """B = 17: more than 16 scans, the one-workgroup-per-scan dispatch of the headline; a scan's answer does not depend on its slot."""
+    cases = batch_of_17(rooms["cases"])
+    reg, res, pc, reps = run(rooms["map"], cases)
+    reg.close()
+    check_against_oracle_and_general("B=17", cases, res, pc, reps, rooms_general)
+    for i in range(8, 17):
+        assert np.array_equal(pc[i], pc[i - 8])
+
+
+@pytest.mark.parametrize("form", ["grouped", "single", "b17"])
+def test_more_distinct_triples_than_the_lds_part_holds(noise, form):
+    """Against a random cloud the scan's active blocks carry more than PT_TCAP distinct triples: ids beyond the LDS part are read from the
+    table in HBM by the slow evaluation form, which must see the same planes.  (Counted here from the neighbour lists of the last ICP
+    iteration: the blocks found, less every query that repeats another query's triple, is a lower bound of the distinct active triples.)"""
+    cs = noise["cases"]
+    cases = {"grouped": [cs["full"], cs[4097], cs["full"]], "single": [cs["full"], cs[4097], cs["full"]],
+             "b17": [cs["full"] if i % 3 else cs[4097] for i in range(17)]}[form]
+    distinct = [cs["full"], cs[4097]]
+    reg_g, _, pc_g, _ = run(noise["map"], distinct, general=True, icp=2)
+    reg_g.close()
+    gen = {c.name: pc_g[i].copy() for i, c in enumerate(distinct)}
+    reg = Point_cloud_registration(max_scans=len(cases), max_features=24000)
+    reg.set_debug(True, no_solver_groups=(form == "single"), no_small_solver=True)
+    reg.set_debug_knn_iteration(1)
+    set_params(reg, 2)
+    pl = np.stack([c.pose for c in cases])
+    res, pc, _, reps = reg.solve_batch(noise["map"], [c.fc for c in cases], [c.fs for c in cases], pl, pl)
+    i_full = [i for i, c in enumerate(cases) if c.name == "noise-full"][0]
+    full = cases[i_full]
+    _, _, si, _ = reg.debug_knn(i_full, len(full.fc), len(full.fs))
+    reg.close()
+    triples = si[:, [0, 2, 4]]
+    repeats = len(triples) - len(np.unique(triples, axis=0))
+    print(f"{form}: surface blocks found {reps[i_full].surf_avail}, queries repeating a triple {repeats}")
+    assert reps[i_full].surf_avail - repeats > PT_TCAP
+    check_against_oracle_and_general(f"overflow {form}", cases, res, pc, reps, gen)
+
+
+def test_run_to_run_and_three_registrars_in_flight(rooms):
+    """The same batch twice on one handle, and on three registrars enqueued before any is collected: bit-equal poses (a scan's answer does not
+    depend on which dense id a triple gets, nor on what else runs on the device)."""
+    cs = rooms["cases"]
+    for cases in (batches_of_3(cs)[2], batch_of_17(cs)):
+        n = len(cases)
+        pl = np.stack([c.pose for c in cases])
+        regs = []
+        for _ in range(3):
+            reg = Point_cloud_registration(max_scans=n, max_features=24000)
+            reg.set_debug(False, no_small_solver=True)
+            set_params(reg)
+            reg.upload_features([c.fc for c in cases], [c.fs for c in cases])
+            regs.append(reg)
+        for reg in regs:
+            reg.enqueue_uploaded(rooms["map"], n, pl, pl)
+        outs = [reg.collect(n) for reg in regs]
+        regs[0].enqueue_uploaded(rooms["map"], n, pl, pl)
+        outs.append(regs[0].collect(n))
+        for reg in regs:
+            reg.close()
+        for o in outs[1:]:
+            assert np.array_equal(o[0], outs[0][0]) and np.array_equal(o[1], outs[0][1])
+        assert np.all(np.isfinite(outs[0][1]))

@@ -15,15 +15,6 @@
 
 namespace ll {
 
-// one slot of an append
-struct CbSlot {
-    long long off;  // first log position of the slot's points
-    int n;          // its points in the source stack
-    int frame;      // the map's frame counter at the call
-    int active;
-    int pad;
-};
-
 struct CbDev {
     int S;
     CellGeom geom;
@@ -57,6 +48,44 @@ struct CbDev {
     CbSlot *tab;  // [S]
 };
 
+// what the host halves of the units built on this store share: *err (which has to be in scope) and -1 on a HIP error; the blocks of
+// 256 threads for n items.  ll_history_batch_kernels.hip and ll_cellmap_extract_kernels.hip do not include this header and keep theirs.
+#define CBCHK(x)                              \
+    do {                                      \
+        hipError_t e_ = (x);                  \
+        if (e_ != hipSuccess) {               \
+            *err = hipGetErrorString(e_);     \
+            return -1;                        \
+        }                                     \
+    } while (0)
+static inline unsigned int cb_blocks(long long n) { return (unsigned int)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1); }
+
+// ---- the arrays of a CbDev, named once per capacity group.  f(array, entries, keep) returns non-zero to stop; `keep` marks the
+// arrays whose content has to survive a move (the *2 targets and all scratch are rewritten before they are read).  Whoever sizes a
+// group sets its capacity after every array of it has gone through.
+template <typename F> static inline int cb_each_log(CbDev &m, size_t n, F f)  // cap
+{
+    return f(m.pts, n, true) || f(m.pkey, n, true) || f(m.pslot, n, true) || f(m.pep, n, true) || f(m.pts2, n, false) || f(m.pkey2, n, false) ||
+           f(m.pslot2, n, false) || f(m.pep2, n, false);
+}
+template <typename F> static inline int cb_each_table(CbDev &m, size_t n, F f)  // ccap
+{
+    return f(m.ckey, n, true) || f(m.cslot, n, true) || f(m.clast, n, true) || f(m.cep, n, true) || f(m.ckey2, n, false) || f(m.cslot2, n, false) ||
+           f(m.clast2, n, false) || f(m.cep2, n, false) || f(m.cstart, n + (size_t)m.S + 1, false);
+}
+template <typename F> static inline int cb_each_append(CbDev &m, size_t n, F f)  // acap
+{
+    return f(m.akey, n, false) || f(m.akey2, n, false) || f(m.aslot, n, false) || f(m.aslot2, n, false) || f(m.aflag, n, false) || f(m.arank, n, false);
+}
+template <typename F> static inline int cb_each_mat(CbDev &m, size_t n, F f)  // mcap
+{
+    return f(m.mkey, n, false) || f(m.mkey2, n, false) || f(m.mval, n, false) || f(m.mval2, n, false) || f(m.mslot, n, false) || f(m.mslot2, n, false);
+}
+template <typename F> static inline int cb_each_fixed(CbDev &m, F f)  // sized by S alone
+{
+    return f(m.coff, (size_t)m.S + 1, false) || f(m.coff2, (size_t)m.S + 1, false) || f(m.poff, (size_t)m.S + 1, false) || f(m.counts, (size_t)4, false) ||
+           f(m.tab, (size_t)m.S, false);
+}
 // temporary storage the hipcub calls of an append of n_new points / a materialisation of n_log points need
 int cb_tmp_bytes(long long n, size_t *bytes, const char **err);
 // The append chain of one kind: src [S][src_stride] holds the slots' clouds, m.tab (already on the device) their sizes, log offsets
@@ -79,9 +108,7 @@ struct CxbDst {
 // temporary storage the scan over n_cells + 1 words needs
 int cxb_tmp_bytes(int n_cells, size_t *bytes, const char **err);
 // First half, over a store in materialised order (m.n_log = its points; needs n_cells + 1 <= mcap and cxb_tmp_bytes <= tmp_bytes).
-// d_in (device ints): list_off [n_req + 1] and slot [n_req] in the caller's order, the requested slots in ascending order [n_req],
-// then the concatenated lists, n_list x {i, j, k}.  d_out (device ints, 4 n_req + 2): cells found [n_req], points [n_req], first
-// global rank [n_req + 1], first global output position [n_req + 1], all in ascending slot order.  Writes mkey, mkey2, tmp.
+// d_in and d_out are device ints in the layouts ll_cellmap_batch_extract_core.h names (cxb_stage, cxb_out).  Writes mkey, mkey2, tmp.
 int cxb_mark(CbDev &m, const int *d_in, int n_req, int n_list, int *d_out, hipStream_t s, int *launches, const char **err);
 // Second half, with d_out read back and every destination large enough: d_dst [n_req] in ascending slot order; n_found and n_points
 // are the totals over all requests.  Writes mval, mval2 and the destinations' arrays; nothing of the store.

@@ -90,4 +90,45 @@ LL_HD int cb_find(const unsigned long long *ckey, int first, int last, unsigned 
     return (p < last && ckey[p] == k) ? p : -1;
 }
 
+// ---- host decisions of an append, shared by the API (ll_api_history_batch_stores.hip) and the test-only CPU drivers (tests/cellmap_batch_rig.h)
+// one slot of an append
+struct CbSlot {
+    long long off;  // first log position of the slot's points
+    int n;          // its points in the source stack
+    int frame;      // the map's frame counter at the call
+    int active;
+    int pad;
+};
+
+// The slot table of an append: the working slots' clouds behind the n_log logged points, in slot order.  n_of(s): the slot's points,
+// negative for a slot that sits the call out.  Returns the new points; *max_n: the largest cloud.
+template <typename N>
+inline long long cb_fill_slots(CbSlot *tab, int S, N n_of, const int *frame, long long n_log, int *max_n)
+{
+    long long n_new = 0;
+    *max_n = 0;
+    for (int s = 0; s < S; s++) {
+        tab[s] = CbSlot{0, 0, 0, 0, 0};
+        const int n = n_of(s);
+        if (n < 0) continue;
+        tab[s].off = n_log + n_new;
+        tab[s].n = n;
+        tab[s].frame = frame[s];
+        tab[s].active = 1;
+        n_new += n;
+        *max_n = n > *max_n ? n : *max_n;
+    }
+    return n_new;
+}
+
+// After an append: the cell counts at the call (coff, S + 1 host entries) decide the step of every working slot's frame counter;
+// then coff takes the offsets the chain left (new_coff; null when nothing was appended).
+template <typename W>
+inline void cb_after_append(int *frame, int *coff, int S, W worked, const int *new_coff)
+{
+    for (int s = 0; s < S; s++)
+        if (worked(s)) frame[s] += cb_frame_step(coff[s + 1] == coff[s]);
+    for (int s = 0; new_coff && s <= S; s++) coff[s] = new_coff[s];
+}
+
 }  // namespace ll

@@ -33,17 +33,6 @@ namespace ll {
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
-#define CXBCHK(x)                             \
-    do {                                      \
-        hipError_t e_ = (x);                  \
-        if (e_ != hipSuccess) {               \
-            *err = hipGetErrorString(e_);     \
-            return -1;                        \
-        }                                     \
-    } while (0)
-
-static inline unsigned int cxb_blocks(long long n) { return (unsigned int)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1); }
-
 __global__ __launch_bounds__(256) void cxb_mark_kernel(const int *ijk, int n_list, const int *list_off, const int *seq, int n_req, const u64 *ckey,
                                                        const int *coff, const int *cstart, u64 *mark)
 {
@@ -131,7 +120,7 @@ int cxb_tmp_bytes(int n_cells, size_t *bytes, const char **err)
 {
     size_t need = 0;
     u64 *w = nullptr;
-    CXBCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, w, w, n_cells + 1));
+    CBCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, w, w, n_cells + 1));
     *bytes = need + 16;
     return 0;
 }
@@ -143,19 +132,19 @@ int cxb_mark(CbDev &m, const int *d_in, int n_req, int n_list, int *d_out, hipSt
         *err = "cell-map scratch too small for the extraction";
         return -1;
     }
-    const int *list_off = d_in, *seq = d_in + n_req + 1, *qslot = seq + n_req, *ijk = qslot + n_req;
-    CXBCHK(hipMemsetAsync(m.mkey, 0, (size_t)(nc + 1) * sizeof(u64), s));
-    hipLaunchKernelGGL(cxb_mark_kernel, dim3(cxb_blocks(n_list)), dim3(256), 0, s, ijk, n_list, list_off, seq, n_req, m.ckey, m.coff, m.cstart, m.mkey);
+    const CxbIn t = cxb_in(d_in, n_req);
+    CBCHK(hipMemsetAsync(m.mkey, 0, (size_t)(nc + 1) * sizeof(u64), s));
+    hipLaunchKernelGGL(cxb_mark_kernel, dim3(cb_blocks(n_list)), dim3(256), 0, s, t.ijk, n_list, t.list_off, t.seq, n_req, m.ckey, m.coff, m.cstart, m.mkey);
     size_t need = 0;
-    CXBCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, m.mkey, m.mkey2, nc + 1));
+    CBCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, m.mkey, m.mkey2, nc + 1));
     if (need > m.tmp_bytes) {
         *err = "cell-map scratch too small for the scan";
         return -1;
     }
     size_t tb = m.tmp_bytes;
-    CXBCHK(hipcub::DeviceScan::ExclusiveSum(m.tmp, tb, m.mkey, m.mkey2, nc + 1, s));
-    hipLaunchKernelGGL(cxb_totals_kernel, dim3(cxb_blocks(n_req + 1)), dim3(256), 0, s, m.mkey2, m.coff, qslot, n_req, nc, d_out);
-    CXBCHK(hipGetLastError());
+    CBCHK(hipcub::DeviceScan::ExclusiveSum(m.tmp, tb, m.mkey, m.mkey2, nc + 1, s));
+    hipLaunchKernelGGL(cxb_totals_kernel, dim3(cb_blocks(n_req + 1)), dim3(256), 0, s, m.mkey2, m.coff, t.qslot, n_req, nc, d_out);
+    CBCHK(hipGetLastError());
     *launches += 4;
     return 0;
 }
@@ -167,12 +156,12 @@ int cxb_extract(CbDev &m, const int *d_in, int n_req, const int *d_out, const Cx
         *err = "cell selection out of range";
         return -1;
     }
-    const int *qslot = d_in + 2 * (size_t)n_req + 1;
-    hipLaunchKernelGGL(cxb_table_kernel, dim3(cxb_blocks((long long)m.n_cells + n_req + 1)), dim3(256), 0, s, m.mkey, m.mkey2, m.ckey, m.cslot, m.cstart,
+    const int *qslot = cxb_in(d_in, n_req).qslot;
+    hipLaunchKernelGGL(cxb_table_kernel, dim3(cb_blocks((long long)m.n_cells + n_req + 1)), dim3(256), 0, s, m.mkey, m.mkey2, m.ckey, m.cslot, m.cstart,
                        m.poff, m.n_cells, qslot, n_req, d_out, d_dst, m.mval, m.mval2);
-    hipLaunchKernelGGL(cxb_gather_kernel, dim3(cxb_blocks(n_points)), dim3(256), 0, s, m.pts, m.pkey, m.mval, m.mval2, d_out, n_req, n_found, n_points,
+    hipLaunchKernelGGL(cxb_gather_kernel, dim3(cb_blocks(n_points)), dim3(256), 0, s, m.pts, m.pkey, m.mval, m.mval2, d_out, n_req, n_found, n_points,
                        d_dst);
-    CXBCHK(hipGetLastError());
+    CBCHK(hipGetLastError());
     *launches += 2;
     return 0;
 }

@@ -20,16 +20,6 @@ namespace ll {
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
-#define CBCHK(x)                              \
-    do {                                      \
-        hipError_t e_ = (x);                  \
-        if (e_ != hipSuccess) {               \
-            *err = hipGetErrorString(e_);     \
-            return -1;                        \
-        }                                     \
-    } while (0)
-
-static inline unsigned int cb_blocks(long long n) { return (unsigned int)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1); }
 static inline int cb_slot_bits(int S)  // the slot field holds 0 .. S (S: "no slot", sorts behind every slot)
 {
     int b = 1;

@@ -20,17 +20,6 @@ namespace ll {
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
-#define CMBCHK(x)                             \
-    do {                                      \
-        hipError_t e_ = (x);                  \
-        if (e_ != hipSuccess) {               \
-            *err = hipGetErrorString(e_);     \
-            return -1;                        \
-        }                                     \
-    } while (0)
-
-static inline unsigned int cmb_blocks(long long n) { return (unsigned int)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1); }
-
 struct alignas(16) CmbU64x2 {
     u64 a, b;
 };
@@ -199,9 +188,9 @@ int cmb_tmp_bytes(long long n, size_t *bytes, const char **err)
     int *v = nullptr;
     u32 *f = nullptr;
     const int nn = (int)(n > 0 ? n : 1);
-    CMBCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, k, k, v, v, nn, 0, 64));
-    CMBCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, k, k, nn));
-    CMBCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, f, f, nn));
+    CBCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, k, k, v, v, nn, 0, 64));
+    CBCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, k, k, nn));
+    CBCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, f, f, nn));
     *bytes = (t1 > t2 ? (t1 > t3 ? t1 : t3) : (t2 > t3 ? t2 : t3)) + 16;
     return 0;
 }
@@ -221,23 +210,23 @@ int cmb_query(const CbDev &m, CmbDev &q, const CmbSlot *d_tab, float radius, flo
     const float inv_leaf = 1.0f / leaf;
     int bits = 30;
     while (bits < 64 && (cmb_key_none(nc) >> bits) != 0ull) bits++;
-    hipLaunchKernelGGL(cmb_select_kernel, dim3(cmb_blocks(nc)), dim3(256), 0, s, m.ckey, m.cslot, nc, m.geom, d_tab, radius, (double)max_fov_deg, q.csel);
-    hipLaunchKernelGGL(cmb_candidates_kernel, dim3(cmb_blocks(((long long)n + 1) / 2)), dim3(256), 0, s, m.pkey, m.pslot, m.pep, n, S, m.ckey, m.cep,
+    hipLaunchKernelGGL(cmb_select_kernel, dim3(cb_blocks(nc)), dim3(256), 0, s, m.ckey, m.cslot, nc, m.geom, d_tab, radius, (double)max_fov_deg, q.csel);
+    hipLaunchKernelGGL(cmb_candidates_kernel, dim3(cb_blocks(((long long)n + 1) / 2)), dim3(256), 0, s, m.pkey, m.pslot, m.pep, n, S, m.ckey, m.cep,
                        m.coff, q.csel, q.cflag, q.ccell);
     size_t tb = q.tmp_bytes;
-    CMBCHK(hipcub::DeviceScan::ExclusiveSum(q.tmp, tb, q.cflag, q.crank, n, s));
-    hipLaunchKernelGGL(cmb_compact_kernel, dim3(cmb_blocks(n)), dim3(256), 0, s, m.pts, m.pkey, q.cflag, q.crank, q.ccell, n, nc, m.geom, inv_leaf, q.key,
+    CBCHK(hipcub::DeviceScan::ExclusiveSum(q.tmp, tb, q.cflag, q.crank, n, s));
+    hipLaunchKernelGGL(cmb_compact_kernel, dim3(cb_blocks(n)), dim3(256), 0, s, m.pts, m.pkey, q.cflag, q.crank, q.ccell, n, nc, m.geom, inv_leaf, q.key,
                        q.val);
     tb = q.tmp_bytes;
-    CMBCHK(hipcub::DeviceRadixSort::SortPairs(q.tmp, tb, q.key, q.key2, q.val, q.val2, n, 0, bits, s));
-    hipLaunchKernelGGL(cmb_head_kernel, dim3(cmb_blocks(n)), dim3(256), 0, s, q.key2, q.cflag, q.crank, n, q.hflag);
+    CBCHK(hipcub::DeviceRadixSort::SortPairs(q.tmp, tb, q.key, q.key2, q.val, q.val2, n, 0, bits, s));
+    hipLaunchKernelGGL(cmb_head_kernel, dim3(cb_blocks(n)), dim3(256), 0, s, q.key2, q.cflag, q.crank, n, q.hflag);
     tb = q.tmp_bytes;
-    CMBCHK(hipcub::DeviceScan::ExclusiveSum(q.tmp, tb, q.hflag, q.hrank, n, s));
-    hipLaunchKernelGGL(cmb_head_pos_kernel, dim3(cmb_blocks(n)), dim3(256), 0, s, q.hflag, q.hrank, q.cflag, q.crank, n, q.head);
-    hipLaunchKernelGGL(cmb_centroid_kernel, dim3(cmb_blocks(n)), dim3(256), 0, s, m.pts, q.key2, q.val2, q.head, q.hflag, q.hrank, q.cflag, q.crank, n,
+    CBCHK(hipcub::DeviceScan::ExclusiveSum(q.tmp, tb, q.hflag, q.hrank, n, s));
+    hipLaunchKernelGGL(cmb_head_pos_kernel, dim3(cb_blocks(n)), dim3(256), 0, s, q.hflag, q.hrank, q.cflag, q.crank, n, q.head);
+    hipLaunchKernelGGL(cmb_centroid_kernel, dim3(cb_blocks(n)), dim3(256), 0, s, m.pts, q.key2, q.val2, q.head, q.hflag, q.hrank, q.cflag, q.crank, n,
                        q.leaf, q.leaf_cell);
-    hipLaunchKernelGGL(cmb_counts_kernel, dim3(cmb_blocks(S + 3)), dim3(256), 0, s, q.key2, q.hflag, q.hrank, q.cflag, q.crank, n, m.coff, S, q.out);
-    CMBCHK(hipGetLastError());
+    hipLaunchKernelGGL(cmb_counts_kernel, dim3(cb_blocks(S + 3)), dim3(256), 0, s, q.key2, q.hflag, q.hrank, q.cflag, q.crank, n, m.coff, S, q.out);
+    CBCHK(hipGetLastError());
     *launches += 10;
     return 0;
 }
@@ -245,8 +234,8 @@ int cmb_query(const CbDev &m, CmbDev &q, const CmbSlot *d_tab, float radius, flo
 int cmb_scatter(const CbDev &m, const CmbDev &q, int n_leaves, float4 *concat, int stride, hipStream_t s, int *launches, const char **err)
 {
     if (n_leaves <= 0) return 0;
-    hipLaunchKernelGGL(cmb_scatter_kernel, dim3(cmb_blocks(n_leaves)), dim3(256), 0, s, q.leaf, q.leaf_cell, m.cslot, q.out, n_leaves, concat, stride);
-    CMBCHK(hipGetLastError());
+    hipLaunchKernelGGL(cmb_scatter_kernel, dim3(cb_blocks(n_leaves)), dim3(256), 0, s, q.leaf, q.leaf_cell, m.cslot, q.out, n_leaves, concat, stride);
+    CBCHK(hipGetLastError());
     *launches += 1;
     return 0;
 }
@@ -258,10 +247,10 @@ int cmb_replace(CbDev &m, const CmbDev &q, int n_leaves, hipStream_t s, int *lau
         *err = "cell-map store too small for the replace";
         return -1;
     }
-    hipLaunchKernelGGL(cmb_append_leaves_kernel, dim3(cmb_blocks(n_leaves)), dim3(256), 0, s, q.leaf, q.leaf_cell, n_leaves, m.ckey, m.cslot, m.cep,
+    hipLaunchKernelGGL(cmb_append_leaves_kernel, dim3(cb_blocks(n_leaves)), dim3(256), 0, s, q.leaf, q.leaf_cell, n_leaves, m.ckey, m.cslot, m.cep,
                        m.n_log, m.pts, m.pkey, m.pslot, m.pep);
-    hipLaunchKernelGGL(cmb_bump_kernel, dim3(cmb_blocks(m.n_cells)), dim3(256), 0, s, q.csel, m.n_cells, m.cep);
-    CMBCHK(hipGetLastError());
+    hipLaunchKernelGGL(cmb_bump_kernel, dim3(cb_blocks(m.n_cells)), dim3(256), 0, s, q.csel, m.n_cells, m.cep);
+    CBCHK(hipGetLastError());
     *launches += 2;
     m.n_log += n_leaves;
     return 0;

@@ -16,15 +16,6 @@
 
 namespace ll {
 
-// one slot of an append_full call
-struct FbSlot {
-    double pose[7];  // {qx, qy, qz, qw, tx, ty, tz} of the scan
-    int n;           // points of the slot's full selection (0 for an inactive slot)
-    int active;
-    int need;        // fb_need: points of this cloud a cell needs to be listed
-    int pad;
-};
-
 struct FbDev {
     float4 *xf;  // [S][max_points_per_frame] the gathered clouds in the map frame
     FbSlot *tab;  // [S]

@@ -23,4 +23,33 @@ LL_HD int fb_need(bool was_empty, int min_points) { return was_empty ? 1 : min_p
 
 LL_HD bool fb_touched(int count, int need) { return count >= need; }
 
+// ---- host decisions of an append_full call, shared by the API and the test-only CPU driver
+// one slot of an append_full call
+struct FbSlot {
+    double pose[7];  // {qx, qy, qz, qw, tx, ty, tz} of the scan
+    int n;           // points of the slot's full selection (0 for an inactive slot)
+    int active;
+    int need;        // fb_need: points of this cloud a cell needs to be listed
+    int pad;
+};
+
+// cb_fill_slots for the full-cloud store, and beside it the gather's and the touched chain's table: the slot's pose and the points a
+// cell needs, from the cell counts at the call (coff, S + 1 host entries)
+template <typename N>
+inline long long fb_fill_slots(CbSlot *ctab, FbSlot *ftab, int S, N n_of, const int *frame, const int *coff, int min_points, const double *poses7,
+                               long long n_log, int *max_n)
+{
+    const long long n_new = cb_fill_slots(ctab, S, n_of, frame, n_log, max_n);
+    for (int s = 0; s < S; s++) {
+        FbSlot &f = ftab[s];
+        f = FbSlot{{0, 0, 0, 0, 0, 0, 0}, 0, 0, 0, 0};
+        if (!ctab[s].active) continue;
+        f.n = ctab[s].n;
+        f.active = 1;
+        f.need = fb_need(coff[s + 1] == coff[s], min_points);
+        for (int i = 0; i < 7; i++) f.pose[i] = poses7[7 * (size_t)s + i];
+    }
+    return n_new;
+}
+
 }  // namespace ll

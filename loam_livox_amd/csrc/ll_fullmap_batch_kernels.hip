@@ -18,17 +18,6 @@ namespace ll {
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
-#define FBCHK(x)                              \
-    do {                                      \
-        hipError_t e_ = (x);                  \
-        if (e_ != hipSuccess) {               \
-            *err = hipGetErrorString(e_);     \
-            return -1;                        \
-        }                                     \
-    } while (0)
-
-static inline unsigned int fb_blocks(long long n) { return (unsigned int)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1); }
-
 // grid (chunks of 256 points, slots), one lane per point: 16-byte loads and stores, the index gather is the only irregular access.
 // The arithmetic is cloud_transform_kernel's and hb_transform_kernel's: point_to_map in double, stored as float.
 __global__ __launch_bounds__(256) void fb_gather_kernel(const float4 *xyzi, const int *full_idx, int stride, const FbSlot *tab, int max_pts, float4 *xf)
@@ -125,7 +114,7 @@ int fb_tmp_bytes(long long n, size_t *bytes, const char **err)
 {
     size_t t = 0;
     u32 *f = nullptr;
-    FBCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t, f, f, (int)(n > 0 ? n : 1)));
+    CBCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t, f, f, (int)(n > 0 ? n : 1)));
     *bytes = t + 16;
     return 0;
 }
@@ -135,7 +124,7 @@ int fb_gather(const FbDev &t, const float4 *xyzi, const int *full_idx, int strid
 {
     if (max_n <= 0) return 0;
     hipLaunchKernelGGL(fb_gather_kernel, dim3((max_n + 255) / 256, S), dim3(256), 0, s, xyzi, full_idx, stride, t.tab, max_pts, t.xf);
-    FBCHK(hipGetLastError());
+    CBCHK(hipGetLastError());
     *launches += 1;
     return 0;
 }
@@ -148,14 +137,14 @@ int fb_touched_chain(const CbDev &m, FbDev &t, int max_n, int n_upper, hipStream
         return -1;
     }
     const int S = m.S;
-    FBCHK(hipMemsetAsync(t.cnt, 0, (size_t)n_upper * sizeof(int), s));
+    CBCHK(hipMemsetAsync(t.cnt, 0, (size_t)n_upper * sizeof(int), s));
     hipLaunchKernelGGL(fb_count_kernel, dim3((max_n + 255) / 256, S), dim3(256), 0, s, m.tab, m.pkey, m.ckey, m.coff, t.cnt);
-    hipLaunchKernelGGL(fb_flag_kernel, dim3(fb_blocks(n_upper)), dim3(256), 0, s, t.cnt, m.cslot, m.counts, n_upper, t.tab, S, t.flag);
+    hipLaunchKernelGGL(fb_flag_kernel, dim3(cb_blocks(n_upper)), dim3(256), 0, s, t.cnt, m.cslot, m.counts, n_upper, t.tab, S, t.flag);
     size_t tb = t.tmp_bytes;
-    FBCHK(hipcub::DeviceScan::ExclusiveSum(t.tmp, tb, t.flag, t.rank, n_upper, s));
-    hipLaunchKernelGGL(fb_compact_kernel, dim3(fb_blocks((long long)n_upper + S + 1)), dim3(256), 0, s, m.ckey, m.coff, t.flag, t.rank, n_upper, S, t.cells,
+    CBCHK(hipcub::DeviceScan::ExclusiveSum(t.tmp, tb, t.flag, t.rank, n_upper, s));
+    hipLaunchKernelGGL(fb_compact_kernel, dim3(cb_blocks((long long)n_upper + S + 1)), dim3(256), 0, s, m.ckey, m.coff, t.flag, t.rank, n_upper, S, t.cells,
                        t.toff);
-    FBCHK(hipGetLastError());
+    CBCHK(hipGetLastError());
     *launches += 5;
     return 0;
 }

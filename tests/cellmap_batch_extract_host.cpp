@@ -1,7 +1,7 @@
 // Test-only: ll_history_batch_extract_cells' launch chain on the CPU (tests/test_cellmap_batch_extract_host.py).  The kernels of
 // ll_cellmap_batch_extract_kernels.hip and of ll_cellmap_batch_kernels.hip themselves, compiled against tests/cellmap_batch_shim and
-// driven the way ll_api_history_batch.hip drives them: appends and materialisations build the store of S slots; an extraction stages
-// the requests in ascending slot order, runs cxb_mark, reads the totals, gives every request a destination with room for exactly
+// driven the way ll_api_history_batch_extract.hip drives them: appends and materialisations build the store of S slots
+// (tests/cellmap_batch_rig.h); an extraction stages the requests with cxb_stage, runs cxb_mark, reads the totals, gives every request a destination with room for exactly
 // its points, and runs cxb_extract.  Also built as it stands with -fsanitize=address,undefined: every buffer is freed at the end.
 //
 //   cellmap_batch_extract_host IN OUT
@@ -18,9 +18,8 @@
 #include <hip/hip_runtime.h>
 #include "../loam_livox_amd/csrc/ll_cellmap_batch_kernels.hip"
 #include "../loam_livox_amd/csrc/ll_cellmap_batch_extract_kernels.hip"
-#include <stdio.h>
-#include <stdlib.h>
-using namespace ll;
+#include "cellmap_batch_rig.h"
+using namespace rig;
 static const size_t GUARD = 64;
 // what the call changes of a destination cell map: its live arrays and host mirrors
 struct Dst {
@@ -29,12 +28,6 @@ struct Dst {
     unsigned long long *pkey, *ckey;
     int *cstart, *clast;
 };
-static std::vector<void *> g_owned;
-template <typename T> static void al(T *&p, size_t n)
-{
-    p = (T *)calloc(n + 8, sizeof(T));
-    g_owned.push_back(p);
-}
 template <typename T> static void alg(T *&p, size_t n)
 {
     p = (T *)malloc((n + GUARD) * sizeof(T));
@@ -47,11 +40,6 @@ template <typename T> static bool guard_ok(const T *p, size_t n)
         if (b[i] != 0xAB) return false;
     return true;
 }
-static void put_i(FILE *f, int v) { fwrite(&v, 4, 1, f); }
-static void rd(void *p, size_t size, size_t n, FILE *f)
-{
-    if (n && fread(p, size, n, f) != n) exit(3);
-}
 int main(int argc, char **argv)
 {
     if (argc != 3) return 2;
@@ -60,42 +48,19 @@ int main(int argc, char **argv)
     int S; float res;
     rd(&S, 4, 1, in); rd(&res, 4, 1, in);
     if (S < 1 || S > 64) return 2;
-    const size_t CAP = 20000, MAXP = 1200;
-    CbDev m; memset(&m, 0, sizeof(m));
-    m.S = S; m.geom = cell_geom(res); m.threshold = 1 << 30;
-    al(m.pts, CAP); al(m.pts2, CAP); al(m.pkey, CAP); al(m.pkey2, CAP); al(m.pslot, CAP); al(m.pslot2, CAP); al(m.pep, CAP); al(m.pep2, CAP); m.cap = CAP;
-    al(m.ckey, CAP); al(m.ckey2, CAP); al(m.cslot, CAP); al(m.cslot2, CAP); al(m.clast, CAP); al(m.clast2, CAP); al(m.cep, CAP); al(m.cep2, CAP); m.ccap = CAP;
-    al(m.coff, S + 1); al(m.coff2, S + 1); al(m.poff, S + 1); al(m.cstart, CAP + S + 1);
-    al(m.akey, CAP); al(m.akey2, CAP); al(m.aslot, CAP); al(m.aslot2, CAP); al(m.aflag, CAP); al(m.arank, CAP); m.acap = CAP;
-    al(m.mkey, CAP); al(m.mkey2, CAP); al(m.mval, CAP); al(m.mval2, CAP); al(m.mslot, CAP); al(m.mslot2, CAP); m.mcap = CAP;
-    char *tmp; al(tmp, 64); m.tmp = tmp; m.tmp_bytes = 64; al(m.counts, 4); al(m.tab, S);
-    std::vector<int> frame(S, 0);
-    float4 *src; al(src, S * MAXP);
-    int launches = 0, rc = 0, op; const char *err = nullptr;
+    Store st(S, res, 1 << 30, 20000, 1200);
+    CbDev &m = st.m;
+    int &launches = st.launches;
+    int rc = 0, op; const char *err = nullptr;
     bool ordered = true;
     while (rc == 0 && fread(&op, 4, 1, in) == 1) {
         if (op == 1) {
-            long long n_new = 0; int max_n = 0;
-            std::vector<int> act(S, 0), ncb(S);
-            for (int s = 0; s < S; s++) {
-                ncb[s] = m.coff[s + 1] - m.coff[s];
-                int n; rd(&n, 4, 1, in);
-                memset(&m.tab[s], 0, sizeof(CbSlot));
-                if (n < 0) continue;
-                if ((size_t)n > MAXP) return 2;
-                for (int i = 0; i < n; i++) { float p[3]; rd(p, 4, 3, in); src[s * MAXP + i] = make_float4(p[0], p[1], p[2], 7.f); }
-                m.tab[s].off = m.n_log + n_new; m.tab[s].n = n; m.tab[s].frame = frame[s]; m.tab[s].active = 1; act[s] = 1;
-                n_new += n; max_n = n > max_n ? n : max_n;
-            }
-            if (n_new > 0) {
-                if (cb_append(m, src, (int)MAXP, max_n, n_new, nullptr, &launches, &err)) { printf("append: %s\n", err); rc = 1; break; }
-                m.n_cells = m.counts[1];
-                ordered = false;
-            }
-            for (int s = 0; s < S; s++) if (act[s]) frame[s] += cb_frame_step(ncb[s] == 0);
+            st.read_clouds(in);
+            const long long n_new = st.append();
+            if (n_new < 0) { rc = 1; break; }
+            if (n_new > 0) ordered = false;
         } else if (op == 2) {
-            if (cb_materialise(m, nullptr, &launches, &err)) { printf("mat: %s\n", err); rc = 1; break; }
-            m.n_log = m.poff[S];
+            if (st.materialise()) { rc = 1; break; }
             ordered = true;
         } else if (op == 4) {
             if (!ordered) { rc = 6; break; }
@@ -113,22 +78,18 @@ int main(int argc, char **argv)
             if (R < 1 || R > S) return 2;
             std::vector<int> seq(R), off(R + 1);
             rd(seq.data(), 4, R, in); rd(off.data(), 4, R + 1, in);
+            if (off[0] != 0) return 2;  // (the lists start at the first triple of the operation)
             const int n_list = off[R];
-            std::vector<int> order(R);
-            for (int r = 0; r < R; r++) order[r] = r;
-            std::sort(order.begin(), order.end(), [&](int a, int b) { return seq[a] < seq[b]; });
-            const size_t n_in = (size_t)3 * R + 1 + (size_t)3 * n_list;
-            int *d_in = (int *)malloc((n_in + 1) * sizeof(int)), *d_out = (int *)malloc(((size_t)4 * R + 2) * sizeof(int));
-            for (int r = 0; r <= R; r++) d_in[r] = off[r];
-            for (int r = 0; r < R; r++) d_in[R + 1 + r] = seq[r];
-            for (int q = 0; q < R; q++) d_in[2 * R + 1 + q] = seq[order[q]];
-            rd(d_in + 3 * R + 1, 4, (size_t)3 * n_list, in);
+            std::vector<int> order(R), ijk((size_t)3 * n_list + 1), d_in(cxb_in_ints(R, n_list)), d_out(cxb_out_ints(R));
+            rd(ijk.data(), 4, (size_t)3 * n_list, in);
+            cxb_stage(d_in.data(), order.data(), R, seq.data(), off.data(), ijk.data());
             std::vector<Dst> dst(R);
             std::vector<CxbDst> tab(R);
             bool made = false;
-            if (cxb_mark(m, d_in, R, n_list, d_out, nullptr, &launches, &err)) { printf("mark: %s\n", err); rc = 1; }
+            if (cxb_mark(m, d_in.data(), R, n_list, d_out.data(), nullptr, &launches, &err)) { printf("mark: %s\n", err); rc = 1; }
             if (rc == 0) {
-                const int *found = d_out, *points = d_out + R, *qrank = points + R, *qpos = qrank + R + 1;
+                const CxbOut o = cxb_out(d_out.data(), R);
+                const int *found = o.found, *points = o.points;
                 for (int q = 0; q < R; q++) {
                     Dst &d = dst[order[q]]; memset(&d, 0, sizeof(d));
                     d.cap = points[q] > 0 ? points[q] : 1; d.frame = 5; d.n_pts = 3; d.n_cells = 2; d.n_filt = 1; d.n_sel = 1;  // (a used map)
@@ -136,7 +97,7 @@ int main(int argc, char **argv)
                     tab[q] = CxbDst{d.ckey, d.cstart, d.clast, d.pts, d.pkey};
                 }
                 made = true;
-                if (cxb_extract(m, d_in, R, d_out, tab.data(), qrank[R], qpos[R], nullptr, &launches, &err)) { printf("extract: %s\n", err); rc = 1; }
+                if (cxb_extract(m, d_in.data(), R, d_out.data(), tab.data(), o.qrank[R], o.qpos[R], nullptr, &launches, &err)) { printf("extract: %s\n", err); rc = 1; }
                 for (int q = 0; q < R && rc == 0; q++) {
                     Dst &d = dst[order[q]];
                     if (!guard_ok(d.pts, points[q]) || !guard_ok(d.pkey, points[q]) || !guard_ok(d.ckey, found[q]) || !guard_ok(d.cstart, found[q] + 1) ||
@@ -160,12 +121,10 @@ int main(int argc, char **argv)
             }
             if (made)
                 for (int r = 0; r < R; r++) { free(dst[r].pts); free(dst[r].pkey); free(dst[r].ckey); free(dst[r].cstart); free(dst[r].clast); }
-            free(d_in); free(d_out);
         } else {
             rc = 2;
         }
     }
-    for (void *p : g_owned) free(p);
     fclose(in);
     fclose(out);
     return rc ? rc : (launches > 0 ? 0 : 5);

@@ -1,16 +1,9 @@
 // Test-only: the launch chains of the batched cell maps -- cb_append and cb_materialise of ll_cellmap_batch_kernels.hip, the kernels
-// themselves, not a restatement -- compiled for the CPU against tests/cellmap_batch_shim and driven the way ll_api_history_batch.hip
-// drives them (slot table, frame counters and cell counts on the host).  Same IN / OUT files as tests/cellmap_batch_host.cpp.
+// themselves, not a restatement -- compiled for the CPU against tests/cellmap_batch_shim and driven through tests/cellmap_batch_rig.h:
+// the host functions ll_api_history_batch_stores.hip drives them with.  Same IN / OUT files as tests/cellmap_batch_host.cpp.
 #include "../loam_livox_amd/csrc/ll_cellmap_batch_kernels.hip"
-#include <stdio.h>
-#include <stdlib.h>
-using namespace ll;
-template <typename T> static void al(T *&p, size_t n) { p = (T *)calloc(n + 8, sizeof(T)); }
-static void put_i(FILE *f, int v) { fwrite(&v, 4, 1, f); }
-static void rd(void *p, size_t size, size_t n, FILE *f)
-{
-    if (fread(p, size, n, f) != n) exit(3);
-}
+#include "cellmap_batch_rig.h"
+using namespace rig;
 int main(int argc, char **argv)
 {
     if (argc != 3) return 2;
@@ -18,49 +11,19 @@ int main(int argc, char **argv)
     if (!in || !out) return 2;
     int S, T, thr; float res;
     rd(&S, 4, 1, in); rd(&T, 4, 1, in); rd(&thr, 4, 1, in); rd(&res, 4, 1, in);
-    const size_t CAP = 20000, MAXP = 400;
-    CbDev m; memset(&m, 0, sizeof(m));
-    m.S = S; m.geom = cell_geom(res); m.threshold = thr;
-    al(m.pts, CAP); al(m.pts2, CAP); al(m.pkey, CAP); al(m.pkey2, CAP); al(m.pslot, CAP); al(m.pslot2, CAP); al(m.pep, CAP); al(m.pep2, CAP); m.cap = CAP;
-    al(m.ckey, CAP); al(m.ckey2, CAP); al(m.cslot, CAP); al(m.cslot2, CAP); al(m.clast, CAP); al(m.clast2, CAP); al(m.cep, CAP); al(m.cep2, CAP); m.ccap = CAP;
-    al(m.coff, S + 1); al(m.coff2, S + 1); al(m.poff, S + 1); al(m.cstart, CAP + S + 1);
-    al(m.akey, CAP); al(m.akey2, CAP); al(m.aslot, CAP); al(m.aslot2, CAP); al(m.aflag, CAP); al(m.arank, CAP); m.acap = CAP;
-    al(m.mkey, CAP); al(m.mkey2, CAP); al(m.mval, CAP); al(m.mval2, CAP); al(m.mslot, CAP); al(m.mslot2, CAP); m.mcap = CAP;
-    m.tmp = malloc(64); m.tmp_bytes = 64; al(m.counts, 4); al(m.tab, S);
-    std::vector<int> frame(S, 0);
-    float4 *src; al(src, S * MAXP);
-    int mats = 0, launches = 0; const char *err = nullptr;
+    Store st(S, res, thr, 20000, 400);
+    int mats = 0;
     for (int t = 0; t < T; t++) {
         int read; rd(&read, 4, 1, in);
-        long long n_new = 0; int max_n = 0;
-        std::vector<int> act(S, 0), ncb(S);
-        for (int s = 0; s < S; s++) {
-            ncb[s] = m.coff[s + 1] - m.coff[s];
-            int n; rd(&n, 4, 1, in);
-            memset(&m.tab[s], 0, sizeof(CbSlot));
-            if (n < 0) continue;
-            for (int i = 0; i < n; i++) { float p[3]; rd(p, 4, 3, in); src[s * MAXP + i] = make_float4(p[0], p[1], p[2], 7.f); }
-            m.tab[s].off = m.n_log + n_new; m.tab[s].n = n; m.tab[s].frame = frame[s]; m.tab[s].active = 1; act[s] = 1;
-            n_new += n; max_n = n > max_n ? n : max_n;
-        }
-        if (n_new > 0) {
-            if (cb_append(m, src, MAXP, max_n, n_new, nullptr, &launches, &err)) { printf("append: %s\n", err); return 1; }
-            m.n_cells = m.counts[1];
-        }
-        for (int s = 0; s < S; s++) if (act[s]) frame[s] += cb_frame_step(ncb[s] == 0);
+        st.read_clouds(in);
+        if (st.append() < 0) return 1;
         if (!read) continue;
-        if (cb_materialise(m, nullptr, &launches, &err)) { printf("mat: %s\n", err); return 1; }
-        m.n_log = m.poff[S]; mats++;
-        for (int s = 0; s < S; s++) {
-            const int c0 = m.coff[s], nc = m.coff[s + 1] - c0, p0 = m.poff[s], np = m.poff[s + 1] - p0;
-            put_i(out, frame[s]); put_i(out, nc); put_i(out, np);
-            for (int c = 0; c < nc; c++) { int k[3]; cell_unpack(m.ckey[c0 + c], k); fwrite(k, 4, 3, out); }
-            for (int c = 0; c <= nc; c++) put_i(out, nc > 0 ? m.cstart[c0 + s + c] : 0);
-            for (int c = 0; c < nc; c++) put_i(out, m.clast[c0 + c]);
-            for (int i = 0; i < np; i++) fwrite(&m.pts[p0 + i].x, 4, 3, out);
-        }
+        if (st.materialise()) return 1;
+        mats++;
+        st.dump(out);
     }
     put_i(out, mats);
+    fclose(in);
     fclose(out);
-    return launches > 0 ? 0 : 5;
+    return st.launches > 0 ? 0 : 5;
 }

@@ -71,9 +71,9 @@ static int reg_create_impl(int32_t device, int32_t max_scans, int32_t max_featur
     DM(d.blk_flag0, B * d.cap);
     DM(d.work_search, B * d.cap);
     DM(d.work_build, B * d.cap);
-    d.n_chunks = (int)((F + 255) / 256);  // must match RQ_THREADS in ll_reg_kernels.hip
+    d.n_chunks = (int)((F + 255) / 256);  // must match RQ_THREADS in ll_reg_query_kernels.hip
     DM(d.work_cnt, B * 4);
-    DM(d.work_off, 3 * 2049);  // 3 prefix tables x (RL_MAX_SEG + 1), ll_reg_kernels.hip
+    DM(d.work_off, 3 * 2049);  // 3 prefix tables x (RL_MAX_SEG + 1), ll_reg_query_kernels.hip
     DM(d.grp_ctl, 2 * B + 1);
     DM(d.solve_order, B);
     DM(d.grp_part, B * 2 * LL_GRP * 28);
@@ -386,7 +386,7 @@ static int reg_enqueue(const char *where, ll_reg *r, const ll_map *map, int n_sc
     if (r->rc.knn_tile == 2 && max_ns > LL_KNN_TILE_SEG) r->rc.knn_tile = 1;
     if (r->rc.knn_tile == 2) r->rc.knn_reuse = 0;
     // Small batches leave most of the chip idle with one workgroup per scan: spread each scan's cost evaluations over a
-    // group of LL_GRP workgroups (ll_reg_kernels.hip, group_*).  Compact scans only; the others run on the group's first.
+    // group of LL_GRP workgroups (ll_reg_solve_fast.h, group_*).  Compact scans only; the others run on the group's first.
     // A scan whose records (nearly) fit one CU's LDS cache gains nothing from it and pays ~3.5 us per exchange: voxel-filtered
     // clouds of a few thousand features (the mapping loop, Q-pipe) stay on one workgroup.
     r->rc.solve_group = (r->rc.solve_group == 1 || n_scans > LL_GRP_MAX_SCANS || r->rc.if_motion_deblur || r->rc.force_general ||

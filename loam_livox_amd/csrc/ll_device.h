@@ -126,7 +126,7 @@ struct RegConst {
     int knn_reuse;       // exact neighbour reuse across ICP iterations (ll_knn_core.h)
     int knn_reuse_from;  // first ICP iteration that tries it (iteration 1 usually moves the queries too far)
     int check_line_pca, check_plane_pca;  // K7 (PCR:46,48)
-    int solve_group;     // workgroups per scan of the compact solver (1, or LL_GRP for small batches: ll_reg_kernels.hip, group_*)
+    int solve_group;     // workgroups per scan of the compact solver (1, or LL_GRP for small batches: ll_reg_solve_fast.h, group_*)
     int xch_epoch;       // ... number of this solver launch within its registration, from 1 (tags of the exchange granules, group_reduce)
     int test_group_abort; // test switch: the grouped solver behaves as if its first barrier had timed out
     int knn_coop;        // corner searches by whole wavefronts where a launch has few of them (ll_knn_coop.h); 0 = A/B switch off
@@ -156,7 +156,7 @@ struct RegDev {
     // residual blocks, slot layout per scan: [0, cap_c) corner queries, [cap_c, cap_c + cap_s) surface queries
     int cap_c, cap_s, cap;        // cap = cap_c + cap_s
     float4 *blk_f;                // [B][cap]  f.xyz (sensor frame), w = motion-blur ratio s
-    double *blk_av;               // [B][6 * cap] per scan {a0, v0}[cap], {v1, v2}[cap], {a1, a2}[cap] (16-byte pairs; ll_reg_kernels.hip av_load), frame of pose_last
+    double *blk_av;               // [B][6 * cap] per scan {a0, v0}[cap], {v1, v2}[cap], {a1, a2}[cap] (16-byte pairs; ll_reg_query.h av_load), frame of pose_last
     // round-3 compact path (solve_fast3): the plane constants {n', c} are stored once per DISTINCT neighbour triple of a scan
     // (a scan's ~17 k plane blocks share 2.4 - 4.6 k triples), built by the solver itself at the start of every launch
     unsigned short *blk_id;       // [B][cap_s] plane id of every surface block (relative to its solver workgroup's table region)

@@ -282,7 +282,7 @@ void reg_knn_tile_kernel(RegDev rd, RegConst rc, Grid gs, int iter, int surf_blo
     if (done || (i & ~63) >= nS) return;  // (whole wavefronts)
     const size_t sb = (size_t)b * rd.cap;
     const bool valid = i < nS;
-    const bool compact = !rc.force_general && (nS + RS_THREADS - 1) / RS_THREADS * RS_THREADS + nC <= LL_TABLE_MAX_BLOCKS;  // scan_is_compact
+    const bool compact = !rc.force_general && padded_block_count(nC, nS) <= LL_TABLE_MAX_BLOCKS;  // scan_is_compact
 #ifdef LL_TILE_TIMING
     // instrumented build: wall clocks of this wavefront per phase, added to the scan's RegState::dbg_cycles by lane 0 --
     // 0 tile_query, 1 round set-up, 2 staging, 3 offers, 4 winners + finish test, 5 query position (order + transform), 6 sum of tile

@@ -1,5 +1,5 @@
 // ll_reg_core.h -- per-thread arithmetic of the scan-to-map registrar shared by the HIP kernels
-// (ll_reg_kernels.hip) and tests/hostcheck: pose algebra, residual-block construction, per-block
+// (ll_reg_*_kernels.hip) and tests/hostcheck: pose algebra, residual-block construction, per-block
 // cost / gradient / Gauss-Newton accumulation, and the Levenberg-Marquardt step controller that replaces the
 // ceres::Solve calls of hku-mars/loam_livox source/point_cloud_registration.hpp:474,508.
 //
@@ -1204,7 +1204,7 @@ LL_LM_FN int lm_init(LmCtl &c, const double e[LL_NACC], int n_active)
 }
 
 // ---- lm_update, in the pieces the device needs: the three-sample fit of a line search (lm_quintic_min_step) is the one part of
-// the controller with parallel work in it, and the solver runs it on the controller's whole wavefront (ll_reg_kernels.hip
+// the controller with parallel work in it, and the solver runs it on the controller's whole wavefront (ll_reg_solve_common.h
 // lm_quintic_min_step_wave) between lm_update_pre and lm_update_post.  lm_update below is the same code in one call.
 
 // the part of lm_update behind the line search: e is the evaluation that stands (at c.cand)

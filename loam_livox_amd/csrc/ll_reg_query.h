@@ -1,4 +1,5 @@
-// ll_reg_query.h -- per-query device helpers of the registrar shared by its kernel files (ll_reg_kernels.hip, ll_knn_kernels.hip):
+// ll_reg_query.h -- per-query device helpers of the registrar shared by its kernel files (ll_reg_query_kernels.hip, ll_knn_kernels.hip;
+// the solver units include it for the address-space loads, padded_block_count and scan_is_compact):
 // pose transform of a feature (pointAssociateToMap, point_cloud_registration.hpp:622-661), storing a search result and its reuse
 // record, the per-lane and per-wavefront search of one query slot, and the residual-block constants of one slot
 // (point_cloud_registration.hpp:259-323, 357-423).  Device only.
@@ -120,9 +121,13 @@ __device__ __forceinline__ void av_load(const double *av, int cap, int slot, boo
 // only decides their flags): planes padded to whole 512-thread rounds + lines within LL_TABLE_MAX_BLOCKS -- 120 rounds, the 128-bit
 // activity mask of solve_big (ll_reg_big_path.h) and the 16-bit plane ids.  Within FAST_MAX_BLOCKS and without motion deblur a batch
 // takes solve_fast3 (64-bit masks, register tiles); launch_reg_solve decides that per batch.  Larger scans and the force_general
-// test switch: per-block constants in HBM (solve_general).
+// test switch: per-block constants in HBM (solve_general, ll_reg_solve_general.h).
 #define FAST_MAX_BLOCKS 24576
 #define LL_TABLE_MAX_BLOCKS 61440
+// blocks of a scan as the table solvers count them: the planes padded to whole rounds of a solver workgroup, then the lines
+// (scan_is_compact keeps the sum written out: it adds the lines behind the force_general test, and the per-query kernels it is
+// inlined into are scheduled differently when the whole sum moves in front)
+__host__ __device__ inline int padded_block_count(int nC, int nS) { return (nS + RS_THREADS - 1) / RS_THREADS * RS_THREADS + nC; }
 __device__ __forceinline__ bool scan_is_compact(const RegDev &rd, const RegConst &rc, int b)
 {
     const int nC = rd.n_corner[b], nS = rd.n_surf[b];

@@ -2,7 +2,7 @@
 //
 // laser_mapping.hpp:1367-1373 voxel-filters the feature clouds before every registration (input_downsample_mode, leaf 0.1 / 0.4 m) and
 // config/performance_*.yaml caps a problem at maximum_residual_blocks = 200: a registration then has a few hundred residual blocks, not
-// the 17 000 of an unfiltered Mid-40 sweep.  reg_solve_kernel (ll_reg_kernels.hip) gives every scan a 512-thread workgroup, 158 KB of LDS
+// the 17 000 of an unfiltered Mid-40 sweep.  reg_solve_kernel (ll_reg_solve_kernels.hip) gives every scan a 512-thread workgroup, 158 KB of LDS
 // and therefore a whole CU; on such a scan its eight wavefronts hold two blocks per lane, a third of the launch clears and scans fixed-size
 // tables, and a batch lasts as long as its slowest scan's Levenberg-Marquardt controller while 250 CUs idle (profiles/r04c_qpipe_*:
 // 772 us per launch of 256 scans).

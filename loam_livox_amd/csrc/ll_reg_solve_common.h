@@ -1,4 +1,4 @@
-// ll_reg_solve_common.h -- device helpers shared by the solver kernels (ll_reg_kernels.hip: one 512-thread workgroup per scan, and
+// ll_reg_solve_common.h -- device helpers shared by the solver kernels (ll_reg_solve_kernels.hip and ll_reg_maps_kernels.hip: one 512-thread workgroup per scan, and
 // ll_reg_small_kernels.hip: one wavefront / four wavefronts per small scan): the wavefront reduction of the 28 accumulators of a cost
 // evaluation, the Levenberg-Marquardt controller step with the line-search fit on the controller's whole wavefront, and the epilogue of
 // one ICP iteration (pose composition, convergence test: point_cloud_registration.hpp:509-531).  Device only.

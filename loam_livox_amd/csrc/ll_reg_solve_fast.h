@@ -1,354 +1,28 @@
-// ll_reg_kernels.hip -- HIP kernels (gfx950, wave64) of the scan-to-map registrar.
+// ll_reg_solve_fast.h -- everything solve_fast3, the Mid-40 solver, is made of (device only, no kernel, no host code).
+// Included by ll_reg_solve_kernels.hip (reg_solve_kernel; ll_reg_big_path.h and ll_reg_solve_general.h share SolveShared, the block
+// sums, plane_table_reload and HASH_EMPTY / HT_* / hash64) and by ll_reg_maps_kernels.hip (reg_solve_maps_kernel).
 //
-//   K6  reg_transform_kernel, reg_knn_kernel, reg_build_kernel (ICP iterations 0 and 1): per query: transform with the
-//                              current pose (pointAssociateToMap, point_cloud_registration.hpp:622-661), exact 5-NN on
-//                              the cell grid (:249,351), match-radius tests (:254,353), line / plane block constants
-//                              (:300-323, :416-423; ceres_icp.hpp:255-256, 328-334)
-//       reg_requery_kernel, reg_list_offsets_kernel, reg_list_kernel (ICP iteration >= 2): exact neighbour reuse -- every
-//                              query is classified against two displacement budgets (ll_knn_core.h), the few that need a
-//                              new search or a re-sort go to dense per-(scan, kind) work lists, one fused kernel searches /
-//                              re-sorts them and rebuilds their blocks
-//   K8/K9 reg_solve_kernel   : ONE workgroup per scan (a group of LL_GRP workgroups per scan for batches of <= 16 scans,
-//                              group_barrier / group_reduce below) runs what the reference does between :460 and :531:
-//                              the 2-iteration prerun solve, the loss-corrected L1 evaluation, the
-//                              std::set-deduplicated 80-th percentile inlier threshold (:153-161), the prune,
-//                              the final solve and the pose composition -- replacing ceres::Solve /
-//                              Problem::Evaluate by a 28-value (21 H + 6 g + 1 cost) workgroup reduction and a
-//                              Levenberg-Marquardt controller on lane 0.  No host round trip per iteration.
-//                              Two forms: solve_fast3 (plane table in LDS, 18 B streamed per plane block; every compact scan)
-//                              and solve_general (> 24 576 blocks or motion deblur)
-//        reg_finalize_kernel : accept / reject (:559-573)
-//        reg_merge_heads_kernel : Mid-100, the feature clouds of a sweep's heads concatenated on the device
+// ONE workgroup per scan (a group of LL_GRP workgroups per scan for batches of <= 16 scans, group_barrier / group_reduce below)
+// runs what the reference does between point_cloud_registration.hpp:460 and :531: the 2-iteration prerun solve, the loss-corrected
+// L1 evaluation, the std::set-deduplicated 80-th percentile inlier threshold (:153-161), the prune, the final solve and the pose
+// composition -- replacing ceres::Solve / Problem::Evaluate by a 28-value (21 H + 6 g + 1 cost) workgroup reduction and a
+// Levenberg-Marquardt controller on lane 0.  No host round trip per iteration.  solve_fast3 holds every scan within
+// FAST_MAX_BLOCKS without motion deblur: plane table in LDS, 18 B streamed per plane block, 64-bit activity masks and register
+// tiles.  In order: evaluation-context and timing macros, SolveShared, the group barrier and reduction, block sums, capacities,
+// inlier_threshold_regs, BlkRegs / load_blk, census_and_plane_table, plane_table_reload, solver_eval3, solver_lm3, inlier_phase3,
+// solve_fast3, and the prologue both kernels share (SolveTicket, solve_fast_ticket, solve_fast_check, solve_fast_group_fields).
 //
-// No MFMA: 6x6 systems are reduced, not multiplied.  Plane blocks live in HBM as three 16-byte planes (48 B + 1 flag per
-// block), line blocks as 65 B; every cost evaluation streams the part of them that does not fit the LDS record cache.
+// No MFMA: 6x6 systems are reduced, not multiplied.  Line blocks live in HBM as 65 B; every cost evaluation streams the part of
+// the blocks that does not fit the LDS record cache.
+#pragma once
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 
 #include "ll_reg_query.h"
 #include "ll_reg_solve_common.h"
 
 namespace ll {
 
-#define RQ_THREADS 256  // queries per requery workgroup = work-list segment size
-#define RQ_WAVES (RQ_THREADS / 64)
-#ifndef RS_PREFETCH
-#define RS_PREFETCH 2  // blocks in flight per thread in the fast-path sweep (0 = none, 1, 2)
-#endif
 #define RS_WAVES (RS_THREADS / 64)
-#define HASH_EMPTY 0xffffffffffffffffull
-
-
-#ifndef LL_REG_MAPS_TU  // (ll_reg_maps_kernels.hip compiles this file for the solver below alone: see its header)
-// ---------------------------------------------------------------------------------------------------------
-// ---------------------------------------------------------------------------------------------------------
-// Per-iteration query kernels (corner and surface queries share every launch, blockIdx.z = kind).
-//
-//   ICP iterations 0 and 1 (and every iteration when neighbour reuse is disabled):
-//       reg_transform_kernel -> reg_knn_kernel (all queries) -> reg_build_kernel (all queries)
-//   ICP iteration >= 2:
-//       reg_requery_kernel    : transform + displacement test of every query against its reuse record (ll_knn_core.h):
-//                                 stable  -> nothing to do: same neighbours, same order, same residual block;
-//                                 re-sort -> the same five neighbours re-evaluated at the new position, slot appended
-//                                            to the chunk's re-sort list;
-//                                 search  -> slot appended to the chunk's search list
-//       reg_list_kernel       : full exact search of the search list + block constants of everything searched or re-sorted
-// The two work lists are dense per scan and kind: every re-query workgroup reserves its share of the scan-and-kind's
-// segment with one atomicAdd per list (work_cnt; ~94 workgroups per counter -- a single batch-wide counter cost 280 us
-// of contention per launch), and the list kernel walks all segments as one dense index space (prefix sums of the 2 B
-// counters in LDS, binary search per entry): a small grid of full wavefronts.  Round 1 kept one list segment per
-// 256-query chunk and launched one workgroup per chunk: in the late iterations a chunk holds ~3 searches, the launch was
-// 48 k workgroups with three busy lanes each, and its ~110 us floor (186 us average) was the cost of scheduling them.
-// The order of the entries depends on the order of the atomics; every entry is processed independently, so results do not.
-
-// K6t: pose transform of every query (pointAssociateToMap, fp64 math -> fp32 store like the reference).  A
-// kernel of its own so that the double-precision sin/cos of the motion-deblur branch does not set the register
-// footprint of the k-NN kernel.
-__global__ __launch_bounds__(KB_THREADS) void reg_transform_kernel(RegDev rd, RegConst rc, int skip_kinds)
-{
-    const int b = blockIdx.y, kind = blockIdx.z;
-    if ((skip_kinds >> kind) & 1) return;  // (the tile kernel transforms its own queries)
-    const RegState *st = rd.state + b;
-    if (st->done) return;
-    const int n = kind ? rd.n_surf[b] : rd.n_corner[b];
-    const int q = blockIdx.x * KB_THREADS + threadIdx.x;
-    if (q >= n) return;
-    const int slot = (kind ? rd.cap_c : 0) + q;
-    float pw[3];
-    transform_query(st, rc, load_feature(rd, b, kind, q), pw);
-    // a13: a skipped feature is handed on as a non-finite query -- no neighbours, no block (PCR:232-238, 339-345)
-    if (subsample_skip_feature(rc.subsample_seed, kind, st->icp_iters, q, n, rc.max_blocks)) pw[0] = pw[1] = pw[2] = NAN;
-    rd.qw[(size_t)b * rd.cap + slot] = make_float4(pw[0], pw[1], pw[2], 0.f);
-}
-
-// K6a: one lane per query: exact 5-NN of the transformed point (fp32 only -> small register footprint, so
-// occupancy hides the gather latency).  Output per query: positions (cell-sorted order) of the neighbours the
-// block needs + "5 found" flag, and the reuse record for the next ICP iteration.
-#ifndef KNN_WAVES_PER_EU
-#define KNN_WAVES_PER_EU 4
-#endif
-__global__ __launch_bounds__(KB_THREADS) __attribute__((amdgpu_waves_per_eu(KNN_WAVES_PER_EU, 8)))
-void reg_knn_kernel(RegDev rd, RegConst rc, Grid gc, Grid gs, int iter, int skip_kinds)
-{
-    const int b = blockIdx.y, kind = blockIdx.z;
-    if ((skip_kinds >> kind) & 1) return;  // reg_knn_coop_kernel has them
-    const RegState *st = rd.state + b;
-    if (st->done) return;
-    const int n = kind ? rd.n_surf[b] : rd.n_corner[b];
-    const int q = blockIdx.x * KB_THREADS + threadIdx.x;
-    if (q >= n) return;
-    knn_one(rd, rc, gc, gs, b, (kind ? rd.cap_c : 0) + q, iter);
-}
-
-// K6a for small batches: one query per wavefront -- the corner queries (a few hundred per scan, a quarter of them searching
-// rings of the sparse corner map: per lane the longest dependent chain of the launch, header of ll_knn_coop.h), and the
-// surface queries too when a scan has few of them (voxel-filtered clouds against a sparse local map: the sequential mapping
-// loop, where every search walks rings).  kinds: bit k set = kind k is searched here.
-#define KC_THREADS 256
-__global__ __launch_bounds__(KC_THREADS) void reg_knn_coop_kernel(RegDev rd, RegConst rc, Grid gc, Grid gs, int iter, int kinds)
-{
-    const int b = blockIdx.y, kind = blockIdx.z;
-    if (!((kinds >> kind) & 1)) return;
-    const RegState *st = rd.state + b;
-    if (st->done) return;
-    const int q = (int)((blockIdx.x * KC_THREADS + threadIdx.x) >> 6);
-    if (q >= (kind ? rd.n_surf[b] : rd.n_corner[b])) return;  // (whole wavefronts)
-    knn_one_coop(rd, rc, gc, gs, b, (kind ? rd.cap_c : 0) + q, iter);
-}
-
-// K6r: transform + reuse test (ICP iteration >= 1)
-
-// One workgroup per chunk of RQ_PER x RQ_THREADS consecutive queries (round 3: four queries per thread -- their eight record loads
-// are in flight together, and a workgroup pays its two barriers and two list reservations once per 1024 queries instead of once per
-// 256; round 2: 73 us per B = 256 launch for 141 MB of records).  Unstable queries are appended to the dense per-(scan, kind) work
-// lists: every thread with state 1 (re-sort) or 2 (search) gets a distinct position in its list; the workgroup reserves one
-// contiguous range per list with one round of ballots per query slice, one barrier pair and two independent atomicAdds issued back
-// to back.  (Within a list the entries of a workgroup are ordered by slice, then wavefront, then lane; nothing depends on the order.)
-#define RQ_PER 4
-__global__ __launch_bounds__(RQ_THREADS) void reg_requery_kernel(RegDev rd, RegConst rc, Grid gc, Grid gs, int iter)
-{
-    const int chunk = blockIdx.x, b = blockIdx.y, kind = blockIdx.z;
-    const RegState *st = rd.state + b;
-    if (st->done) return;
-    const int n = kind ? rd.n_surf[b] : rd.n_corner[b];
-    if (chunk * RQ_PER * RQ_THREADS >= n) return;
-    const size_t sb = (size_t)b * rd.cap;
-    const int koff = kind ? rd.cap_c : 0;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __shared__ int s_cnt[2][RQ_PER * RQ_WAVES];  // [list][slice * RQ_WAVES + wave]
-    __shared__ int s_base[2];
-    float4 ft[RQ_PER], rq[RQ_PER];
-    int qq[RQ_PER];  // the query of this thread's u-th place (-1: beyond the scan's queries)
-#pragma unroll
-    for (int u = 0; u < RQ_PER; u++) {
-        const int place = (chunk * RQ_PER + u) * RQ_THREADS + tid;
-        qq[u] = place < n ? place : -1;
-    }
-#pragma unroll
-    for (int u = 0; u < RQ_PER; u++) {
-        const int qc = qq[u] >= 0 ? qq[u] : 0;
-        ft[u] = load_feature(rd, b, kind, qc);
-        rq[u] = rd.ref_q[sb + koff + qc];
-    }
-    int state[RQ_PER];  // 0 = stable or out of range, 1 = re-sorted, 2 = needs a search
-    unsigned long long m1[RQ_PER], m2[RQ_PER];
-#pragma unroll
-    for (int u = 0; u < RQ_PER; u++) {
-        const int q = qq[u];
-        const int slot = koff + q;
-        state[u] = 0;
-        if (q >= 0) {
-            float pw[3];
-            transform_query(st, rc, ft[u], pw);
-            KnnRef ref;
-            ref.qx = rq[u].x;
-            ref.qy = rq[u].y;
-            ref.qz = rq[u].z;
-            ref.m_strong = rq[u].w;
-            const float delta = knn5_ref_delta(ref, pw[0], pw[1], pw[2]);  // NaN for a non-finite query -> search
-            if (!(delta < ref.m_strong)) {  // else: same neighbours, same order: nn and the block are unchanged
-                const float2 rs = rd.ref_s[sb + slot];
-                ref.m_set = rs.y;
-                // Both kinds of work are left to the list kernel: the five gathers and the stores of a re-sort in here kept
-                // nearly every wavefront alive for three more dependent round trips (73 % of them hold at least one such lane)
-                rd.qw[sb + slot] = make_float4(pw[0], pw[1], pw[2], 0.f);
-                state[u] = (delta < ref.m_set) ? 1 : 2;
-            }
-        }
-        m1[u] = __ballot(state[u] == 1);
-        m2[u] = __ballot(state[u] == 2);
-        if (lane == 0) {
-            s_cnt[0][u * RQ_WAVES + wave] = __popcll(m1[u]);
-            s_cnt[1][u * RQ_WAVES + wave] = __popcll(m2[u]);
-        }
-    }
-    __syncthreads();
-    int off1[RQ_PER], off2[RQ_PER], tot1 = 0, tot2 = 0;
-#pragma unroll
-    for (int u = 0; u < RQ_PER; u++) {
-        off1[u] = off2[u] = 0;
-        for (int w = 0; w < RQ_WAVES; w++) {
-            const int c1 = s_cnt[0][u * RQ_WAVES + w], c2 = s_cnt[1][u * RQ_WAVES + w];
-            if (w < wave) off1[u] += c1, off2[u] += c2;
-            tot1 += c1, tot2 += c2;
-        }
-    }
-    // (offsets of slice u: everything in the slices before it, then the earlier wavefronts of its own)
-    int pre1 = 0, pre2 = 0;
-#pragma unroll
-    for (int u = 0; u < RQ_PER; u++) {
-        int s1 = 0, s2 = 0;
-        for (int w = 0; w < RQ_WAVES; w++) s1 += s_cnt[0][u * RQ_WAVES + w], s2 += s_cnt[1][u * RQ_WAVES + w];
-        off1[u] += pre1;
-        off2[u] += pre2;
-        pre1 += s1;
-        pre2 += s2;
-    }
-    int *cnt = rd.work_cnt + ((size_t)b * 2 + kind) * 2;  // [0] search, [1] re-sort
-    if (tid == 0) {
-        const int b1 = tot1 > 0 ? atomicAdd(cnt + 1, tot1) : 0;
-        const int b2 = tot2 > 0 ? atomicAdd(cnt + 0, tot2) : 0;
-        s_base[0] = b1;
-        s_base[1] = b2;
-    }
-    __syncthreads();
-    const size_t seg = sb + koff;  // the scan-and-kind's own segment of the work arrays
-    const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int u = 0; u < RQ_PER; u++) {
-        const int slot = koff + qq[u];
-        if (state[u] == 1) rd.work_build[seg + s_base[0] + off1[u] + __popcll(m1[u] & below)] = (int)sb + slot;
-        if (state[u] == 2) rd.work_search[seg + s_base[1] + off2[u] + __popcll(m2[u] & below)] = (int)sb + slot;
-    }
-}
-
-__global__ __launch_bounds__(KB_THREADS) void reg_build_kernel(RegDev rd, RegConst rc, Grid gc, Grid gs, int skip_kinds)
-{
-    const int b = blockIdx.y, kind = blockIdx.z;
-    if ((skip_kinds >> kind) & 1) return;  // (the tile kernel builds the blocks of its own slots)
-    const RegState *st = rd.state + b;
-    if (st->done) return;
-    const int n = kind ? rd.n_surf[b] : rd.n_corner[b];
-    const int q = blockIdx.x * KB_THREADS + threadIdx.x;
-    if (q >= n) return;
-    build_one(rd, rc, gc, gs, b, (kind ? rd.cap_c : 0) + q);
-}
-
-// ICP iteration >= 2: exact search of the dense search list followed at once by the block constants of the same slot
-// (the lane still holds the neighbours), then the block constants of the re-sorted slots.  Grid-stride over the lists.
-#define RL_THREADS 128
-#define RL_BLOCKS 2048  // x 128 threads; 4096 (every wavefront slot at 64 VGPRs) measured the same, the lists are bound by dependent misses
-#define RL_MAX_SEG 2048  // scan-and-kind segments of one offsets table (max_scans <= 1024); larger batches run in slices
-#define RL_LOCAL_SEG 64  // up to this many segments (32 scans) the list kernel builds the offsets itself
-// exclusive prefix sums of the per-segment list lengths (segment = scan * 2 + kind) -> work_off[list][0 .. n_seg]; one workgroup
-__global__ __launch_bounds__(1024) void reg_list_offsets_kernel(RegDev rd, int seg0, int n_seg)
-{
-    __shared__ int s_wave[3][16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int sg0 = 2 * tid, sg1 = 2 * tid + 1;  // two segments per thread (n_seg <= 2048): a scan's corner and surface segment
-    for (int w = 0; w < 3; w++) {
-        // (w = 2: the search list again with every surface segment -- odd: segment = scan * 2 + kind -- counted as empty)
-        const int c0 = sg0 < n_seg ? rd.work_cnt[(size_t)(seg0 + sg0) * 2 + (w & 1)] : 0;
-        const int c1 = (sg1 < n_seg && w < 2) ? rd.work_cnt[(size_t)(seg0 + sg1) * 2 + w] : 0;
-        int incl = c0 + c1;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int y = __shfl_up(incl, off);
-            if (lane >= off) incl += y;
-        }
-        if (lane == 63) s_wave[w][wave] = incl;
-        __syncthreads();
-        int base = 0;
-        for (int k = 0; k < wave; k++) base += s_wave[w][k];
-        const int excl = base + incl - (c0 + c1);
-        int *off_w = rd.work_off + (size_t)w * (RL_MAX_SEG + 1);
-        if (sg0 < n_seg) off_w[sg0] = excl;
-        if (sg1 < n_seg) off_w[sg1] = excl + c0;
-        if (tid == 1023) off_w[n_seg] = base + incl;  // its segments lie beyond n_seg or are the last ones: the grand total
-        __syncthreads();
-    }
-}
-
-// LOCAL: the offsets tables are built in LDS by every workgroup (small batches); a template constant so that the large-batch
-// form keeps plain global loads in its binary searches
-template <bool LOCAL>
-__global__ __launch_bounds__(RL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8))) void reg_list_kernel(RegDev rd, RegConst rc, Grid gc, Grid gs, int iter, int seg0, int n_seg)
-{
-    // The offsets table (<= 16 KB) is searched where it lies: it stays in L1 / L2, and a copy in LDS would cap the
-    // occupancy of this latency-bound kernel (16 KB per 128-thread workgroup: 36 -> 99 us per late iteration at B = 256).
-    const int tid = threadIdx.x;
-    const int stride = gridDim.x * RL_THREADS;
-    // Corner searches first, one per WAVEFRONT while there are few of them (round 3): a late iteration searches a handful of
-    // corner queries per scan, each a chain of 100+ dependent loads for a single lane -- the floor of this launch (~100 us at
-    // B = 256 for ~1.5 k of them beside 75 k surface searches of ~15 round trips each; 49 us for a single scan).
-    // With few searches altogether (a single scan, a small batch, voxel-filtered clouds) every search goes that way.
-    // Small batches (<= RL_LOCAL_SEG segments) skip the offsets kernel: every workgroup sums the few counters itself
-    // (one launch and one kernel boundary less per ICP iteration: ~6 us of a single scan's ~40 per iteration).
-    __shared__ int s_cnt[2][LOCAL ? RL_LOCAL_SEG : 1];
-    __shared__ int s_off[3][LOCAL ? RL_LOCAL_SEG + 1 : 1];
-    if (LOCAL) {
-        if (tid < n_seg) {
-            s_cnt[0][tid] = rd.work_cnt[(size_t)(seg0 + tid) * 2 + 0];
-            s_cnt[1][tid] = rd.work_cnt[(size_t)(seg0 + tid) * 2 + 1];
-        }
-        __syncthreads();
-        if (tid < 3) {  // (as reg_list_offsets_kernel: searches, re-sorts, the searches of the corner segments alone)
-            int acc = 0;
-            for (int sg = 0; sg < n_seg; sg++) {
-                s_off[tid][sg] = acc;
-                acc += tid == 2 ? ((sg & 1) ? 0 : s_cnt[0][sg]) : s_cnt[tid][sg];
-            }
-            s_off[tid][n_seg] = acc;
-        }
-        __syncthreads();
-    }
-    const int *off_s = LOCAL ? s_off[0] : rd.work_off;
-    const int *off_c = LOCAL ? s_off[2] : rd.work_off + (size_t)2 * (RL_MAX_SEG + 1);
-    const bool coop_all = rc.knn_coop && off_s[n_seg] <= LL_KNN_COOP_MAX_QUERIES;
-    const bool coop = rc.knn_coop && off_c[n_seg] <= LL_KNN_COOP_MAX_QUERIES;  // the corner ones at least
-    if (coop_all || coop) {
-        // (handed out from the LAST wavefront of the grid backwards: the per-lane lists below fill the grid from the front, so
-        // with short lists a wavefront has either a cooperative search or per-lane entries and the two chains overlap)
-        const int *off_w = coop_all ? off_s : off_c;
-        const int total_w = off_w[n_seg];
-        const int n_waves = stride >> 6;
-        for (int t = n_waves - 1 - (int)((blockIdx.x * RL_THREADS + tid) >> 6); t < total_w; t += n_waves) {
-            int lo = 0, hi = n_seg;  // largest segment with off_w[segment] <= t (in off_c the empty surface segments tie with their successor)
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (off_w[mid] <= t) lo = mid; else hi = mid;
-            }
-            const int sgg = seg0 + lo, b = sgg >> 1, kind = sgg & 1;
-            const int e = rd.work_search[(size_t)b * rd.cap + (kind ? rd.cap_c : 0) + (t - off_w[lo])];
-            const int slot = e - b * rd.cap;
-            knn_one_coop(rd, rc, gc, gs, b, slot, iter);
-            if ((tid & 63) == 0) build_one(rd, rc, gc, gs, b, slot);
-        }
-    }
-    // (one index space over both lists, so that a lane never runs a re-sort after a search, brought the floor from 113 back
-    // to 99 us but cost 25 % at the long early lists -- profiles/r02 runs U / V -- and was dropped)
-    for (int w = coop_all ? 1 : 0; w < 2; w++) {
-        const int *off = LOCAL ? s_off[w] : rd.work_off + (size_t)w * (RL_MAX_SEG + 1);
-        const int total = off[n_seg];
-        const int *list = w == 0 ? rd.work_search : rd.work_build;
-        for (int t = blockIdx.x * RL_THREADS + tid; t < total; t += stride) {
-            int lo = 0, hi = n_seg;  // largest segment with off[segment] <= t
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (off[mid] <= t) lo = mid; else hi = mid;
-            }
-            const int sgg = seg0 + lo, b = sgg >> 1, kind = sgg & 1;
-            if (w == 0 && coop && kind == 0) continue;  // done above
-            const int e = list[(size_t)b * rd.cap + (kind ? rd.cap_c : 0) + (t - off[lo])];
-            const int slot = e - b * rd.cap;
-            if (w == 0) knn_one(rd, rc, gc, gs, b, slot, iter);
-            else resort_one(rd, rc, gc, gs, b, slot, iter);
-            build_one(rd, rc, gc, gs, b, slot);
-        }
-    }
-}
-#endif  // LL_REG_MAPS_TU
-
 
 // Evaluation context as plain locals (R_inc / t_inc for the plain blocks, axis-angle for the motion-deblur ones);
 // DEBLUR is a template constant, so the unused half disappears from each kernel instantiation.
@@ -414,8 +88,6 @@ struct SolveShared {
     int xch_seq, xch_epoch;                // ... exchanges of partial sums made in this launch, and the launch's number in its registration (granule tags)
     unsigned int xch[LL_GRP][2 * LL_NACC]; // ... the members' partial sums of one exchange, as 32-bit halves
 };
-
-__device__ __forceinline__ int slot_of(int j, int nC, int cap_c) { return j < nC ? j : cap_c + (j - nC); }
 
 // ---- grouped solver (small batches) ------------------------------------------------------------------------------------
 // With one workgroup per scan a batch of B <= 16 scans keeps B of 256 CUs busy and every cost evaluation re-streams the 85 %
@@ -565,16 +237,11 @@ __device__ __forceinline__ unsigned long long hash64(unsigned long long k)
 
 
 
-// capacities shared by the solver paths (the fast paths are described further down)
+// capacities shared by the solver paths (solve_fast3 here, solve_big; the plane table is described further down)
 #define FAST_MAXK (FAST_MAX_BLOCKS / RS_THREADS)
+#define HASH_EMPTY 0xffffffffffffffffull  // empty slot of the de-duplication hash tables (here, solve_big, solve_general)
 #define HT_SIZE 16384
 #define HT_PART 6144  // keys per de-duplication round (load factor <= 0.375)
-// set de-duplication, common case: bitmap + contested-bit set + exact table of the contested keys (all inside s_table)
-#define DD_BM_WORDS 16384  // 512 Kbit
-#define DD_CB_LOG2 11
-#define DD_CB_SIZE (1 << DD_CB_LOG2)
-#define DD_EX_SIZE 4096
-#define DD_MAX_COLL 900    // contested keys beyond this (heavily duplicated input): hash every key instead
 // register-tile de-duplication (inlier_threshold_regs): 2-bit slot states, 64 KB + 32 KB, and a list of twice-contested keys
 #define DD2_WORDS 16384
 #define DD2_SLOTS (DD2_WORDS * 16)
@@ -596,13 +263,11 @@ __device__ __forceinline__ void inlier_threshold_regs(const double (&l1r)[NK], i
     const int tid = threadIdx.x;
     LL_T0(t_dd);
     // ---- std::set semantics (PCR:155-160): which values are distinct, and how many ---------------------------------
-    // Exact duplicates among the residuals are rare, so the common case is made cheap: every key sets one bit of a
-    // 512 Kbit LDS bitmap (atomicOr); only keys whose bit was already set -- true duplicates or hash collisions, a few
-    // hundred of ~17 k -- and the keys that share a bit with them go through an exact compare-and-swap table.  Heavily
-    // duplicated inputs (more than DD_MAX_COLL such keys) fall back to hashing every key, HT_PART keys per round.
+    // Exact duplicates among the residuals are rare, so the common case is made cheap (passes A - C below); heavily
+    // duplicated inputs (more than DD2_LIST twice-contested keys) fall back to hashing every key, HT_PART keys per round.
     unsigned long long first_mask = 0;  // bit k: block k of this thread is the first occurrence of its L1 value
     {
-        // Common case (round 2 form).  Three short, branch-light passes over the thread's keys instead of a
+        // Common case.  Three short, branch-light passes over the thread's keys instead of a
         // compare-and-swap probe per key (round 1: ~290 instructions per key once the compiler had unrolled the probe loop):
         //   A  every key marks a 2-bit slot state {bit 0: a key landed here, bit 1: a second key landed here} in a
         //      256 K-slot table (atomicOr): a key whose slot never gets bit 1 is distinct from every other key;
@@ -875,11 +540,8 @@ __device__ __forceinline__ void inlier_threshold_regs(const double (&l1r)[NK], i
     LL_TACC(4, t_sel);
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Fast path (<= FAST_MAX_BLOCKS residual blocks per scan, i.e. every BASELINE Mid-40 configuration): block
-// flags live in LDS, the per-block L1 values of the inlier test live in registers, the std::set
-// de-duplication runs in an LDS hash table and the rank select reads registers -- the only HBM traffic left is
-// one coalesced sweep over the block constants per cost evaluation, software-pipelined one block ahead.
+// a block's fp64 record as it lies in HBM: the line blocks (65 B) of solver_eval3, inlier_phase3 and solve_big; the plane blocks go
+// through the plane table below
 struct BlkRegs {
     float4 f;
     double a0, a1, a2, v0, v1, v2;
@@ -893,11 +555,8 @@ __device__ __forceinline__ void load_blk(const RegDev &rd, size_t sb, const doub
 }
 
 
-
-
-
 // ---------------------------------------------------------------------------------------------------------
-// Round-3 compact path (scan_is_compact(), default): PLANE TABLE.  A scan's ~17 k plane blocks are built from only 2.4 - 4.6 k
+// PLANE TABLE (every scan solve_fast3 holds).  A scan's ~17 k plane blocks are built from only 2.4 - 4.6 k
 // distinct ordered (nn0, nn2, nn4) neighbour triples (the queries of a wall patch share their nearest map points), and every
 // block with the same triple carries bit-identical {n', c} -- 32 of the 48 bytes a per-block record form re-streams on each of ~7 cost
 // evaluations.  Here the solver workgroup de-duplicates the triples itself at the start of every launch:
@@ -1490,108 +1149,6 @@ __device__ __noinline__ void solver_eval3(const RegDev &rd, int b, int nC, int n
         LL3_PIPE(false, FILL ? 0 : kc, kp)
     }
     plane_unfold2(acc);  // the factors 2 of the planes' rotation rows and columns (plane_accumulate_scaled leaves them out), before the lines are added
-#ifdef LL_EXP_MOMENT_EVAL
-    // EXPERIMENT (-DLL_EXP_MOMENT_EVAL together with -DLL_SOLVE_TIMING, never in the product library): what ONE evaluation in
-    // per-plane moment form would cost, run IN ADDITION to the real one so that control flow and evaluation count stay the same -- the
-    // difference of the evaluation phase's cycles between this build and the plain timing build is the cost of a moment-form evaluation:
-    //   (1) per block: the record (streamed again), the plane from the LDS table, the scalar residual and the Huber test (which blocks
-    //       are in the linear region) -- no accumulation;
-    //   (2) per distinct plane: the plane + ten moments {N, S1, S2} (80 B, streamed from HBM: 112 B x T does not fit LDS; the scan's unused
-    //       plane slots of blk_av stand in for the moment array) and the quadratic-region cost / gradient / Gauss-Newton terms from them.
-    // Not included (so this is a LOWER bound of the real thing): the two moment builds per launch and the per-block correction of the
-    // linear-region blocks.  The results of (1) and (2) go nowhere (a never-true test keeps them alive).
-    {
-        double xacc[LL_NACC];
-#pragma unroll
-        for (int i = 0; i < LL_NACC; i++) xacc[i] = 0.0;
-        int n_lin = 0;
-        for (int k0 = 0; k0 < kp; k0 += 8) {  // eight rounds' records in flight (the real loop keeps five)
-            float fx8[8], fy8[8], fz8[8];
-            unsigned int id8[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int pp = p0 + (k0 + u) * GS;
-                const int pc = pp < nS ? pp : 0;
-                gload_f3(feat + pc, fx8[u], fy8[u], fz8[u]);
-                id8[u] = gload_u16(ids + pc);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int k = k0 + u, pp = p0 + k * GS;
-                const unsigned int idl = id8[u] < (unsigned int)Tl ? id8[u] : 0u;
-                const int4 qb = lds_load_i4(tabL + 2 * idl), qc = lds_load_i4(tabL + 2 * idl + 1);
-                const double f[3] = {(double)fx8[u], (double)fy8[u], (double)fz8[u]};
-                const double m[3] = {__hiloint2double(qb.y, qb.x), __hiloint2double(qb.w, qb.z), __hiloint2double(qc.y, qc.x)};
-                const double beta = __hiloint2double(qc.w, qc.z);
-                const double q0 = R_[0] * f[0] + R_[1] * f[1] + R_[2] * f[2] + t_[0], q1 = R_[3] * f[0] + R_[4] * f[1] + R_[5] * f[2] + t_[1],
-                             q2 = R_[6] * f[0] + R_[7] * f[1] + R_[8] * f[2] + t_[2];
-                const double e = m[0] * q0 + m[1] * q1 + m[2] * q2 - beta;
-                if (k < kp && pp < nS && ((act >> (g + G * k)) & 1ull) && e * e > huber_a * huber_a) n_lin++;
-            }
-        }
-        const double *mom = rd.blk_av + (size_t)b * 6 * rd.cap + 2 * (size_t)rd.cap_c;  // (stand-in storage: 80 B per plane id)
-        for (int id = tid; id < sh.pt_T && id < Tl; id += RS_THREADS) {
-            const int4 qb = lds_load_i4(tabL + 2 * id), qc = lds_load_i4(tabL + 2 * id + 1);
-            const double m[3] = {__hiloint2double(qb.y, qb.x), __hiloint2double(qb.w, qb.z), __hiloint2double(qc.y, qc.x)};
-            const double beta = __hiloint2double(qc.w, qc.z);
-            double mo[10];
-#pragma unroll
-            for (int i = 0; i < 10; i += 2) {
-                const double2 v2 = gload_d2(reinterpret_cast<const double2 *>(mom + (size_t)id * 10 + i));
-                mo[i] = v2.x;
-                mo[i + 1] = v2.y;
-            }
-            // sensor-frame normal and offset, then the quadratic form in the moments (the algebra of DESIGN section 8's analysis)
-            const double ms[3] = {R_[0] * m[0] + R_[3] * m[1] + R_[6] * m[2], R_[1] * m[0] + R_[4] * m[1] + R_[7] * m[2], R_[2] * m[0] + R_[5] * m[1] + R_[8] * m[2]};
-            const double bs = m[0] * t_[0] + m[1] * t_[1] + m[2] * t_[2] - beta;
-            const double N = mo[0], S1[3] = {mo[1], mo[2], mo[3]};
-            const double S2[9] = {mo[4], mo[5], mo[6], mo[5], mo[7], mo[8], mo[6], mo[8], mo[9]};
-            double u[3];
-#pragma unroll
-            for (int i = 0; i < 3; i++) u[i] = S2[3 * i] * ms[0] + S2[3 * i + 1] * ms[1] + S2[3 * i + 2] * ms[2];
-            const double l1 = ms[0] * S1[0] + ms[1] * S1[1] + ms[2] * S1[2];
-            xacc[27] += 0.5 * (ms[0] * u[0] + ms[1] * u[1] + ms[2] * u[2] + 2.0 * bs * l1 + N * bs * bs);
-            const double w[3] = {u[0] + bs * S1[0], u[1] + bs * S1[1], u[2] + bs * S1[2]};
-            double gt[3], sx[3];
-            cross3(w, ms, gt);
-            cross3(S1, ms, sx);
-            const double gb = l1 + N * bs;
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                xacc[21 + i] += 2.0 * gt[i];
-                xacc[24 + i] += gb * ms[i];
-            }
-            // H_rr = 4 [ms]x S2 [ms]x^T, H_rt = 2 (S1 x ms) ms^T, H_tt = N ms ms^T (sensor frame; the common rotation is applied once at the end)
-            double A[9];
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-                const double row[3] = {S2[3 * r], S2[3 * r + 1], S2[3 * r + 2]};
-                double c[3];
-                cross3(row, ms, c);
-                A[3 * r] = c[0], A[3 * r + 1] = c[1], A[3 * r + 2] = c[2];
-            }
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const double col[3] = {A[c], A[3 + c], A[6 + c]};
-                double h[3];
-                cross3(ms, col, h);
-#pragma unroll
-                for (int r = 0; r <= c; r++) xacc[hidx(r, c)] += 4.0 * h[r];
-            }
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-#pragma unroll
-                for (int j = 0; j < 3; j++) {
-                    xacc[hidx(i, 3 + j)] += 2.0 * sx[i] * ms[j];
-                    if (j >= i) xacc[hidx(3 + i, 3 + j)] += N * ms[i] * ms[j];
-                }
-        }
-        double xs = (double)n_lin;
-#pragma unroll
-        for (int i = 0; i < LL_NACC; i++) xs += xacc[i];
-        if (xs == 1.2345678e300) acc[27] += xs;  // (never: keeps the experiment's arithmetic and loads alive)
-    }
-#endif
     {
         // line blocks (a few hundred per Mid-40 scan): the 65-byte fp64 form
         const size_t sb = (size_t)b * rd.cap;
@@ -1657,26 +1214,6 @@ __device__ __noinline__ void solver_eval3(const RegDev &rd, int b, int nC, int n
 #undef LL3_PLANE
 #undef LL3_USE
 #undef LL3_PIPE
-
-
-#ifndef LL_REG_MAPS_TU
-// test tap (ll_debug_quintic): the sequential and the wavefront form of the fit on n argument sets, one wavefront each
-__global__ __launch_bounds__(64) void debug_quintic_kernel(const double *args, int n, double *out_seq, double *out_wave)
-{
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= n) return;
-    const double *a = args + 10 * (size_t)i;
-    const double w = lm_quintic_min_step_wave(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], lane);
-    if (lane == 0) {
-        out_wave[i] = w;
-        out_seq[i] = lm_quintic_min_step(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9]);
-    }
-}
-void launch_debug_quintic(const double *args, int n, double *out_seq, double *out_wave, hipStream_t s)
-{
-    if (n > 0) hipLaunchKernelGGL(debug_quintic_kernel, dim3(n), dim3(64), 0, s, args, n, out_seq, out_wave);
-}
-#endif
 
 // one ceres::Solve on the plane-table layout: starts at x0, leaves the result in sh.ctl
 template <bool WANT_L1, bool GROUPED>
@@ -1871,38 +1408,41 @@ __device__ void solve_fast3(const RegDev &rd, const RegConst &rc, const f4 *map_
 #endif
 }
 
-#ifndef LL_REG_MAPS_TU
-// The Mid-40 batches: no motion deblur, every scan within FAST_MAX_BLOCKS (launch_reg_solve decides per batch from the host's feature
-// counts; everything else goes to reg_solve_big_kernel, ll_reg_big_path.h).
-// (reg_solve_maps_kernel at the end of this file repeats this kernel's prologue -- ticket, size check, group fields -- by hand: keep the two in step)
-__global__ __launch_bounds__(RS_THREADS) void reg_solve_kernel(RegDev rd, RegConst rc, const f4 *map_surf)
+// ---- the prologue of the kernels built on solve_fast3 (reg_solve_kernel, reg_solve_maps_kernel) -------------------------------------
+// Which scan this workgroup works on, and as which member: blockIdx.x, or in a grouped launch (n_scans * G workgroups) scan and rank
+// by ticket, see group_barrier.  (Returned by value: with three reference parameters reg_solve_maps_kernel's registers moved.)
+struct SolveTicket {
+    int b, g, G;  // scan, rank in its group, group size
+};
+__device__ __forceinline__ SolveTicket solve_fast_ticket(const RegDev &rd, const RegConst &rc, SolveShared &sh)
 {
-    __shared__ SolveShared sh;
-    // 152 KB: hash table -> plane table + record cache; the inlier phase's tables in between
-    __shared__ uint4 s_raw[PT_LDS_BYTES / 16];
-    int b = blockIdx.x, g = 0, G = 1;
-    if (rc.solve_group > 1) {  // grouped launch (n_scans * G workgroups): scan and rank by ticket, see group_barrier
+    SolveTicket t = {(int)blockIdx.x, 0, 1};
+    if (rc.solve_group > 1) {
         if (threadIdx.x == 0) sh.grp_seq = atomicAdd(rd.grp_ctl, 1);
         __syncthreads();
-        G = rc.solve_group;
-        b = sh.grp_seq / G;
-        g = sh.grp_seq - b * G;
+        t.G = rc.solve_group;
+        t.b = sh.grp_seq / t.G;
+        t.g = sh.grp_seq - t.b * t.G;
         __syncthreads();
     }
-    RegState *st = rd.state + b;
-    if (st->done) return;  // the same answer for every member: the epilogue that sets it runs behind the group's barriers
-    {
-        const int nS_ = rd.n_surf[b], nC_ = rd.n_corner[b];
-        if ((nS_ + RS_THREADS - 1) / RS_THREADS * RS_THREADS + nC_ > FAST_MAX_BLOCKS || !scan_is_compact(rd, rc, b)) {
-            // cannot happen (the host launches this kernel only for batches it holds): fail loudly -- rejected and reported -- instead of answering
-            if (g == 0 && threadIdx.x == 0) {
-                st->aborted = 1;
-                st->done = 1;
-                st->icp_iters += 1;
-            }
-            return;
+    return t;
+}
+// false: the scan is beyond solve_fast3.  Cannot happen (the host launches these kernels only for batches they hold): fail loudly --
+// rejected and reported -- instead of answering.
+__device__ __forceinline__ bool solve_fast_check(const RegDev &rd, const RegConst &rc, int b, int g, int nC, int nS, RegState *st)
+{
+    if (padded_block_count(nC, nS) > FAST_MAX_BLOCKS || !scan_is_compact(rd, rc, b)) {
+        if (g == 0 && threadIdx.x == 0) {
+            st->aborted = 1;
+            st->done = 1;
+            st->icp_iters += 1;
         }
+        return false;
     }
+    return true;
+}
+__device__ __forceinline__ void solve_fast_group_fields(const RegConst &rc, int g, int G, SolveShared &sh)
+{
     if (threadIdx.x == 0) {
         sh.grp_g = g;
         sh.grp_G = G;
@@ -1912,325 +1452,6 @@ __global__ __launch_bounds__(RS_THREADS) void reg_solve_kernel(RegDev rd, RegCon
         sh.grp_abort = (rc.test_group_abort && G > 1) ? 1 : 0;  // test switch: behave as if the first barrier had timed out
     }
     __syncthreads();
-    if (G > 1)
-        solve_fast3<true>(rd, rc, map_surf, b, st, sh, s_raw);
-    else
-        solve_fast3<false>(rd, rc, map_surf, b, st, sh, s_raw);
 }
-
-// ---- a map per slot (ll_reg_enqueue_fe_maps) --------------------------------------------------------------------------------------
-// Scan b is searched and solved against map_tab[2 b] (corner) / map_tab[2 b + 1] (surface).  The scan is uniform per workgroup
-// (blockIdx.y, or the solver's ticket), so a workgroup reads its two grids once through scalar loads and then runs the same
-// knn_one / build_one / solve_fast3 as the single-map kernels above.  A slot that does not run (gated, idle) has st->done set by
-// the host and zeroed table entries that nobody reads.
-__global__ __launch_bounds__(KB_THREADS) __attribute__((amdgpu_waves_per_eu(KNN_WAVES_PER_EU, 8)))
-void reg_knn_maps_kernel(RegDev rd, RegConst rc, const Grid *__restrict__ map_tab, int iter, int skip_kinds)
-{
-    const int b = blockIdx.y, kind = blockIdx.z;
-    if ((skip_kinds >> kind) & 1) return;  // reg_knn_coop_maps_kernel has them
-    const RegState *st = rd.state + b;
-    if (st->done) return;
-    const int n = kind ? rd.n_surf[b] : rd.n_corner[b];
-    const int q = blockIdx.x * KB_THREADS + threadIdx.x;
-    if (q >= n) return;
-    const Grid gc = map_tab[2 * b], gs = map_tab[2 * b + 1];
-    knn_one(rd, rc, gc, gs, b, (kind ? rd.cap_c : 0) + q, iter);
-}
-
-__global__ __launch_bounds__(KC_THREADS) void reg_knn_coop_maps_kernel(RegDev rd, RegConst rc, const Grid *__restrict__ map_tab, int iter, int kinds)
-{
-    const int b = blockIdx.y, kind = blockIdx.z;
-    if (!((kinds >> kind) & 1)) return;
-    const RegState *st = rd.state + b;
-    if (st->done) return;
-    const int q = (int)((blockIdx.x * KC_THREADS + threadIdx.x) >> 6);
-    if (q >= (kind ? rd.n_surf[b] : rd.n_corner[b])) return;  // (whole wavefronts)
-    const Grid gc = map_tab[2 * b], gs = map_tab[2 * b + 1];
-    knn_one_coop(rd, rc, gc, gs, b, (kind ? rd.cap_c : 0) + q, iter);
-}
-
-__global__ __launch_bounds__(KB_THREADS) void reg_build_maps_kernel(RegDev rd, RegConst rc, const Grid *__restrict__ map_tab)
-{
-    const int b = blockIdx.y, kind = blockIdx.z;
-    const RegState *st = rd.state + b;
-    if (st->done) return;
-    const int n = kind ? rd.n_surf[b] : rd.n_corner[b];
-    const int q = blockIdx.x * KB_THREADS + threadIdx.x;
-    if (q >= n) return;
-    const Grid gc = map_tab[2 * b], gs = map_tab[2 * b + 1];
-    build_one(rd, rc, gc, gs, b, (kind ? rd.cap_c : 0) + q);
-}
-
-#include "ll_reg_big_path.h"
-
-__global__ void reg_finalize_kernel(RegDev rd, RegConst rc, int n_scans)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= n_scans) return;
-    RegState *st = rd.state + b;
-    st->result = 1;
-    st->accepted = 1;
-    if (st->gated || st->icp_iters == 0) return;
-    st->inlier_thr = st->inlier_thr * st->final_cost / st->initial_cost;  // PCR:559
-    const float minimize_cost = (float)st->final_cost;                    // PCR:192,519
-    // (an aborted solve, or anything non-finite that reached the pose, is a rejection too: NaN compares false with both limits)
-    const bool broken = st->aborted || !((st->angular_diff - st->angular_diff) == 0.0) || !((st->final_cost - st->final_cost) == 0.0);
-    if (broken || st->angular_diff > (double)rc.para_max_angular_rate || minimize_cost > rc.max_final_cost) {  // PCR:561
-        for (int i = 0; i < 7; i++) st->pose_curr[i] = st->pose_last[i];
-        st->result = 0;
-        st->accepted = 0;
-    }
-}
-
-__global__ void cloud_transform_kernel(const float4 *in, float4 *out, int n, const double *pose)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double p[7];
-#pragma unroll
-    for (int k = 0; k < 7; k++) p[k] = pose[k];
-    const float4 v = in[i];
-    float o[3];
-    point_to_map(p, v.x, v.y, v.z, o);
-    out[i] = make_float4(o[0], o[1], o[2], v.w);  // intensity copied, PCR:659
-}
-
-// ---- launch wrappers -------------------------------------------------------------------------------------------
-void launch_reg_knn_build(const RegDev &rd, const RegConst &rc, const Grid &gc, const Grid &gs, int n_scans, int iter,
-                          int max_nc, int max_ns, hipStream_t s)
-{
-    if (iter >= rc.knn_reuse_from && rc.knn_reuse) {
-        if (max_nc + max_ns <= 0) return;
-        const int mx = max_nc > max_ns ? max_nc : max_ns;
-        dim3 cgrid((mx + RQ_PER * RQ_THREADS - 1) / (RQ_PER * RQ_THREADS), n_scans, 2);
-        (void)hipMemsetAsync(rd.work_cnt, 0, (size_t)n_scans * 4 * sizeof(int), s);
-        hipLaunchKernelGGL(reg_requery_kernel, cgrid, dim3(RQ_THREADS), 0, s, rd, rc, gc, gs, iter);
-        for (int seg0 = 0; seg0 < 2 * n_scans; seg0 += RL_MAX_SEG) {
-            const int n_seg = 2 * n_scans - seg0 < RL_MAX_SEG ? 2 * n_scans - seg0 : RL_MAX_SEG;
-            static const int local_seg = getenv("LL_LIST_NO_LOCAL_OFFSETS") ? 0 : RL_LOCAL_SEG;  // (A/B switch)
-            if (n_seg <= local_seg) {
-                hipLaunchKernelGGL(reg_list_kernel<true>, dim3(256), dim3(RL_THREADS), 0, s, rd, rc, gc, gs, iter, seg0, n_seg);
-            } else {
-                hipLaunchKernelGGL(reg_list_offsets_kernel, dim3(1), dim3(1024), 0, s, rd, seg0, n_seg);
-                hipLaunchKernelGGL(reg_list_kernel<false>, dim3(n_scans >= 64 ? RL_BLOCKS : 256), dim3(RL_THREADS), 0, s, rd, rc, gc, gs, iter, seg0, n_seg);
-            }
-        }
-        return;
-    }
-    // corner and surface queries share every launch (blockIdx.z = kind): the few hundred corner queries of a scan
-    // are latency-bound on their own and would otherwise serialise three more launches per iteration
-    const int mx = max_nc > max_ns ? max_nc : max_ns;
-    if (mx <= 0) return;
-    dim3 grid((mx + KB_THREADS - 1) / KB_THREADS, n_scans, 2);
-    // large scans: the surface queries go to the tile kernel (ll_knn_kernels.hip) in the order of the map cells they fall into (sorted at
-    // ICP iterations 0 and 1: the first pose update moves the queries by a good part of a cell, the later ones by centimetres); it also
-    // builds their blocks and, without motion deblur, transforms them itself
-    const bool tile = rc.knn_tile && max_ns >= LL_KNN_TILE_MIN_SURF && max_ns <= LL_KNN_TILE_MAX_SURF;
-    const bool fused = tile && !rc.if_motion_deblur;
-    // small batches: the corner queries one per wavefront, and the surface queries too when the scans are small
-    int coop_kinds = 0;
-    if (rc.knn_coop && n_scans <= LL_KNN_COOP_MAX_SCANS) {
-        if (max_nc > 0) coop_kinds |= 1;
-        if (max_ns > 0 && max_ns <= LL_KNN_COOP_MAX_SURF && !tile) coop_kinds |= 2;
-    }
-    const bool corner_in_tile = tile && max_nc > 0 && !(coop_kinds & 1);  // ... otherwise they ride in the tile launch
-    {
-        const int skip = fused ? (corner_in_tile ? 3 : 2) : 0;
-        if (skip != 3 && (skip == 0 || max_nc > 0)) {
-            const int mt = skip == 2 ? max_nc : mx;
-            hipLaunchKernelGGL(reg_transform_kernel, dim3((mt + KB_THREADS - 1) / KB_THREADS, n_scans, 2), dim3(KB_THREADS), 0, s, rd, rc, skip);
-        }
-    }
-    if (tile && iter <= rc.knn_tile_last_sort) launch_reg_qsort(rd, rc, gc, gs, n_scans, corner_in_tile ? max_nc : 0, max_ns, fused, s);
-    if (coop_kinds) {
-        const int mq = (coop_kinds & 2) ? mx : max_nc;
-        hipLaunchKernelGGL(reg_knn_coop_kernel, dim3((mq * 64 + KC_THREADS - 1) / KC_THREADS, n_scans, 2), dim3(KC_THREADS), 0, s, rd, rc, gc, gs, iter, coop_kinds);
-    }
-    const int done_kinds = coop_kinds | (tile ? 2 : 0) | (corner_in_tile ? 1 : 0);  // kinds that do not need the per-lane kernel
-    if ((max_nc > 0 && !(done_kinds & 1)) || (max_ns > 0 && !(done_kinds & 2))) {
-        const int mk = (done_kinds & 2) ? max_nc : ((done_kinds & 1) ? max_ns : mx);
-        hipLaunchKernelGGL(reg_knn_kernel, dim3((mk + KB_THREADS - 1) / KB_THREADS, n_scans, 2), dim3(KB_THREADS), 0, s, rd, rc, gc, gs, iter, done_kinds);
-    }
-    if (tile) {
-        launch_reg_knn_tile(rd, rc, gc, gs, n_scans, iter, corner_in_tile ? max_nc : 0, max_ns, fused, s);
-        if (max_nc > 0 && !corner_in_tile)
-            hipLaunchKernelGGL(reg_build_kernel, dim3((max_nc + KB_THREADS - 1) / KB_THREADS, n_scans, 2), dim3(KB_THREADS), 0, s, rd, rc, gc, gs, 2);
-    } else {
-        hipLaunchKernelGGL(reg_build_kernel, grid, dim3(KB_THREADS), 0, s, rd, rc, gc, gs, 0);
-    }
-}
-// batches reg_solve_kernel holds: no motion deblur, the largest scan within FAST_MAX_BLOCKS (planes padded to whole rounds + lines)
-bool reg_solve_fast_eligible(const RegConst &rc, int max_nc, int max_ns)
-{
-    return !rc.if_motion_deblur && !rc.force_general && (max_ns + RS_THREADS - 1) / RS_THREADS * RS_THREADS + max_nc <= FAST_MAX_BLOCKS;
-}
-void launch_reg_solve(const RegDev &rd, const RegConst &rc, const Grid &gs, int n_scans, int max_nc, int max_ns, int iter, hipStream_t s)
-{
-    if (reg_solve_small_eligible(rc, max_nc, max_ns))  // voxel-filtered scans: one or four wavefronts per scan (ll_reg_small_kernels.hip)
-        launch_reg_solve_small(rd, rc, gs, n_scans, max_nc, max_ns, iter, s);
-    else if (reg_solve_fast_eligible(rc, max_nc, max_ns))  // Mid-40 batches: solve_fast3 (one workgroup per scan, or a group of them for small batches)
-        hipLaunchKernelGGL(reg_solve_kernel, dim3(n_scans * (rc.solve_group > 1 ? rc.solve_group : 1)), dim3(RS_THREADS), 0, s, rd, rc, gs.pts);
-    else if (rc.if_motion_deblur)
-        hipLaunchKernelGGL(reg_solve_big_kernel<1>, dim3(n_scans), dim3(RS_THREADS), 0, s, rd, rc, gs.pts);
-    else
-        hipLaunchKernelGGL(reg_solve_big_kernel<0>, dim3(n_scans), dim3(RS_THREADS), 0, s, rd, rc, gs.pts);
-}
-// A map per slot: every query of every running scan is searched in every ICP iteration -- per lane (reg_knn_maps_kernel), or per
-// wavefront for the batches the single-map launcher serves that way -- and every block is rebuilt.  The tile search and the reuse
-// lists have no table form (their work items are not bound to one scan per workgroup); the caller clears rc.knn_tile and
-// rc.knn_reuse.  Every search form returns the same neighbour lists, so a slot gets the bits of its single-map registration.
-void launch_reg_knn_build_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, int iter, int max_nc, int max_ns, hipStream_t s)
-{
-    (void)iter;
-    const int mx = max_nc > max_ns ? max_nc : max_ns;
-    if (mx <= 0) return;
-    const dim3 grid((mx + KB_THREADS - 1) / KB_THREADS, n_scans, 2);
-    hipLaunchKernelGGL(reg_transform_kernel, grid, dim3(KB_THREADS), 0, s, rd, rc, 0);
-    int coop_kinds = 0;
-    if (rc.knn_coop && n_scans <= LL_KNN_COOP_MAX_SCANS) {
-        if (max_nc > 0) coop_kinds |= 1;
-        if (max_ns > 0 && max_ns <= LL_KNN_COOP_MAX_SURF) coop_kinds |= 2;
-    }
-    if (coop_kinds) {
-        const int mq = (coop_kinds & 2) ? mx : max_nc;
-        hipLaunchKernelGGL(reg_knn_coop_maps_kernel, dim3((mq * 64 + KC_THREADS - 1) / KC_THREADS, n_scans, 2), dim3(KC_THREADS), 0, s, rd, rc, map_tab, iter,
-                           coop_kinds);
-    }
-    if ((max_nc > 0 && !(coop_kinds & 1)) || (max_ns > 0 && !(coop_kinds & 2))) {
-        const int mk = (coop_kinds & 2) ? max_nc : ((coop_kinds & 1) ? max_ns : mx);
-        hipLaunchKernelGGL(reg_knn_maps_kernel, dim3((mk + KB_THREADS - 1) / KB_THREADS, n_scans, 2), dim3(KB_THREADS), 0, s, rd, rc, map_tab, iter,
-                           coop_kinds);
-    }
-    hipLaunchKernelGGL(reg_build_maps_kernel, grid, dim3(KB_THREADS), 0, s, rd, rc, map_tab);
-}
-void launch_reg_finalize(const RegDev &rd, const RegConst &rc, int n_scans, hipStream_t s)
-{
-    hipLaunchKernelGGL(reg_finalize_kernel, dim3((n_scans + 63) / 64), dim3(64), 0, s, rd, rc, n_scans);
-}
-// Mid-100: the selected features of `heads` consecutive extractor slots (the lidars of one sweep) become ONE registrar scan,
-// corner clouds and surface clouds each concatenated in head order (laser_feature_extractor.hpp:348-358), device to device.
-// grid (chunks of the extractor stride, n_scans * heads, 2 kinds).  Points beyond the registrar's capacity are not written;
-// the counts are, so the host sees the overflow.
-__global__ void reg_merge_heads_kernel(const float4 *fe_corner, const float4 *fe_surf, const int *fe_nc, const int *fe_ns, int fe_stride,
-                                       int heads, float4 *dst_corner, float4 *dst_surf, int *dst_nc, int *dst_ns, int dst_stride)
-{
-    const int slot = blockIdx.y, kind = blockIdx.z;
-    const int b = slot / heads, h = slot - b * heads;
-    const int *cnt = kind ? fe_ns : fe_nc;
-    int off = 0;
-    for (int k = 0; k < h; k++) off += cnt[b * heads + k];
-    const int n = cnt[slot];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && off + i < dst_stride) {
-        const float4 *src = (kind ? fe_surf : fe_corner) + (size_t)slot * fe_stride;
-        float4 *dst = (kind ? dst_surf : dst_corner) + (size_t)b * dst_stride;
-        dst[off + i] = src[i];
-    }
-    if (i == 0 && h == heads - 1) (kind ? dst_ns : dst_nc)[b] = off + n;
-}
-void launch_reg_merge_heads(const float4 *fe_corner, const float4 *fe_surf, const int *fe_nc, const int *fe_ns, int fe_stride, int heads,
-                            float4 *dst_corner, float4 *dst_surf, int *dst_nc, int *dst_ns, int dst_stride, int n_scans, hipStream_t s)
-{
-    hipLaunchKernelGGL(reg_merge_heads_kernel, dim3((fe_stride + 255) / 256, n_scans * heads, 2), dim3(256), 0, s, fe_corner, fe_surf, fe_nc,
-                       fe_ns, fe_stride, heads, dst_corner, dst_surf, dst_nc, dst_ns, dst_stride);
-}
-// The history's frames, oldest first, into one cloud (laser_mapping.hpp:519-530): segment g of the table is {first point of the frame in
-// `frames`, its first position in `out`}, the table ends with {-, total}.  One launch instead of one device-to-device copy per frame
-// (20 frames x 2 kinds per refresh of the match buffer: the copies' launch overhead was a third of the refresh).
-__global__ __launch_bounds__(256) void history_concat_kernel(const float4 *frames, const int2 *table, int n_seg, float4 *out)
-{
-    __shared__ int2 s_tab[LL_HIST_CONCAT_MAX + 1];
-    for (int e = threadIdx.x; e <= n_seg; e += 256) s_tab[e] = table[e];
-    __syncthreads();
-    const int total = s_tab[n_seg].y;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        int lo = 0, hi = n_seg - 1;  // the last segment whose first output position is <= i
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (s_tab[mid].y <= i)
-                lo = mid;
-            else
-                hi = mid - 1;
-        }
-        out[i] = frames[(size_t)s_tab[lo].x + (size_t)(i - s_tab[lo].y)];
-    }
-}
-void launch_history_concat(const float4 *frames, const int2 *d_table, int n_seg, int total, float4 *out, hipStream_t s)
-{
-    if (n_seg <= 0 || total <= 0) return;
-    const int blocks = (total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024;
-    hipLaunchKernelGGL(history_concat_kernel, dim3(blocks), dim3(256), 0, s, frames, d_table, n_seg, out);
-}
-
-void launch_cloud_transform(const float4 *in, float4 *out, int n, const double *d_pose, hipStream_t s)
-{
-    if (n <= 0) return;
-    hipLaunchKernelGGL(cloud_transform_kernel, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n, d_pose);
-}
-
-#else  // LL_REG_MAPS_TU
-// ---- the solver of a map per slot (ll_reg_enqueue_fe_maps), a translation unit of its own (ll_reg_maps_kernels.hip) ------------
-// A second kernel built on solve_fast3 in reg_solve_kernel's module changes how that kernel is compiled (two SGPR and two VGPR
-// spills moved when it was tried); compiled apart, reg_solve_kernel is the code it was.
-// reg_solve_kernel with the surface map of the scan the workgroup turns out to work on (the prologue is repeated rather than shared:
-// reg_solve_kernel keeps its code, registers and spills to the last one)
-__global__ __launch_bounds__(RS_THREADS) void reg_solve_maps_kernel(RegDev rd, RegConst rc, const Grid *map_tab, int grp_min)
-{
-    __shared__ SolveShared sh;
-    __shared__ uint4 s_raw[PT_LDS_BYTES / 16];
-    int b = blockIdx.x, g = 0, G = 1;
-    if (rc.solve_group > 1) {  // grouped launch (n_scans * G workgroups): scan and rank by ticket, see group_barrier
-        if (threadIdx.x == 0) sh.grp_seq = atomicAdd(rd.grp_ctl, 1);
-        __syncthreads();
-        G = rc.solve_group;
-        b = sh.grp_seq / G;
-        g = sh.grp_seq - b * G;
-        __syncthreads();
-    }
-    RegState *st = rd.state + b;
-    if (st->done) return;  // the same answer for every member: the epilogue that sets it runs behind the group's barriers
-    {
-        const int nS_ = rd.n_surf[b], nC_ = rd.n_corner[b];
-        if (reg_maps_class(rc, nC_, nS_, grp_min) != (G > 1 ? 3 : 2)) return;  // (the small solver's launches, or this kernel's other launch, have it)
-        if ((nS_ + RS_THREADS - 1) / RS_THREADS * RS_THREADS + nC_ > FAST_MAX_BLOCKS || !scan_is_compact(rd, rc, b)) {
-            // cannot happen (the host launches this kernel only for batches it holds): fail loudly -- rejected and reported -- instead of answering
-            if (g == 0 && threadIdx.x == 0) {
-                st->aborted = 1;
-                st->done = 1;
-                st->icp_iters += 1;
-            }
-            return;
-        }
-    }
-    if (threadIdx.x == 0) {
-        sh.grp_g = g;
-        sh.grp_G = G;
-        sh.grp_seq = 0;
-        sh.xch_seq = 0;
-        sh.xch_epoch = rc.xch_epoch;
-        sh.grp_abort = (rc.test_group_abort && G > 1) ? 1 : 0;  // test switch: behave as if the first barrier had timed out
-    }
-    __syncthreads();
-    const f4 *map_surf = map_tab[2 * b + 1].pts;
-    if (G > 1)
-        solve_fast3<true>(rd, rc, map_surf, b, st, sh, s_raw);
-    else
-        solve_fast3<false>(rd, rc, map_surf, b, st, sh, s_raw);
-}
-
-// (the caller has checked that one of the two table forms holds the batch: no motion deblur, nothing beyond reg_solve_kernel's size)
-void launch_reg_solve_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, const RegMapsClasses &cls, int iter, hipStream_t s)
-{
-    for (int c = 0; c < 2; c++)
-        if (cls.n[c] > 0) launch_reg_solve_small_maps(rd, rc, map_tab, n_scans, c, cls.max_nc[c], cls.max_ns[c], iter, s);
-    RegConst one = rc;  // (rc.solve_group is what the kernel reads: one workgroup per scan, or a group of LL_GRP)
-    one.solve_group = 1;
-    if (cls.n[2] > 0) hipLaunchKernelGGL(reg_solve_maps_kernel, dim3(n_scans), dim3(RS_THREADS), 0, s, rd, one, map_tab, cls.grp_min);
-    if (cls.n[3] > 0) {
-        one.solve_group = LL_GRP;
-        hipLaunchKernelGGL(reg_solve_maps_kernel, dim3(n_scans * LL_GRP), dim3(RS_THREADS), 0, s, rd, one, map_tab, cls.grp_min);
-    }
-}
-#endif  // LL_REG_MAPS_TU
 
 }  // namespace ll

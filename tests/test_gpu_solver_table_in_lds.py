@@ -1,4 +1,4 @@
-"""-m gpu: the Mid-40 solver's plane table, built straight into LDS (ll_reg_kernels.hip census_and_plane_table): the hash slots of
+"""-m gpu: the Mid-40 solver's plane table, built straight into LDS (ll_reg_solve_fast.h census_and_plane_table): the hash slots of
 a thread's blocks wait in registers between the two passes, the triples of its ids are pulled into registers before the planes
 overwrite the hash table.  Shapes at which that can go wrong -- block counts on either side of one round (512), one trip of eight
 rounds (4096) and one trip plus one block, a last trip of nothing but flag-cleared blocks, more distinct triples than the LDS part
@@ -20,7 +20,7 @@ ORACLE_TOL = 1e-7                       # "what we actually expect from identica
 GENERAL_TOL = 1e-12                     # plane table against per-block constants: the same numbers summed in another grouping
 ICP, CERES = 4, 20
 COUNTS = (1, 511, 512, 513, 4095, 4097)   # surface features: either side of one round, of one trip (8 rounds), one trip + one block (8 * 512 + 1)
-PT_TCAP = 4864                          # table entries the LDS part holds (ll_reg_kernels.hip)
+PT_TCAP = 4864                          # table entries the LDS part holds (ll_reg_solve_fast.h)
 
 
 def set_params(reg, icp=ICP):

@@ -3,7 +3,7 @@
 (-Rpass-analysis=kernel-resource-usage, gfx950, the library's flags), one markdown table row per kernel, sorted by name.
 Run it in two checkouts and diff the outputs to see whether a change moved a kernel it did not mean to touch:
 
-  python tools/kernel_resource_usage.py loam_livox_amd/csrc/ll_reg_kernels.hip loam_livox_amd/csrc/ll_reg_small_kernels.hip > after.md
+  python tools/kernel_resource_usage.py loam_livox_amd/csrc/ll_reg_*_kernels.hip > after.md
 """
 import os
 import re

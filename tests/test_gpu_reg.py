@@ -592,7 +592,11 @@ def test_pca_feature_checks_match_oracle(gpu_lib, small_world, scans, checks, ge
 def test_duplicate_residuals_follow_std_set_semantics(dev_map, small_world, scans, general):
     """compute_inlier_residual_threshold (PCR:155-160) ranks the DISTINCT loss-corrected residuals (it inserts them into a
     std::set).  Repeating features verbatim produces exact duplicates, which shift the rank of the 80 % threshold; the device
-    de-duplication (LDS hash table / HBM table) has to land on the same value as the oracle's set."""
+    de-duplication has to land on the same value as the oracle's set.  The repeats bring scan 0 to about 25.3 k surface features: padded to
+    whole rounds that exceeds FAST_MAX_BLOCKS (24 576), so general=False runs solve_big inside reg_solve_big_kernel<0> (its LDS bitmaps and,
+    with more than DD2_LIST twice-contested keys, its compare-and-swap table over every key in HBM), not reg_solve_kernel; general=True runs solve_general (hash partitions in HBM).
+    solve_fast3's fall-back for heavily duplicated input is held by test_heavy_duplicates_inside_the_fast_range
+    (tests/test_gpu_solver_size_classes.py) on the scan thinned to 12 000 surface features."""
     sc = scans[0]
     _, _, _, _, fc, fs = oracle_features(sc)
     rng = np.random.default_rng(3)

@@ -796,6 +796,31 @@ class Points_cloud_map {
         if (n_points) *n_points = n_pts;
         return n_found;
     }
+    // Maps_keyframe::extract_specify_points( Feature_type ) (:1263-1281) with the map standing for the key frame's cell set: the points
+    // of the line cells or of the plane cells, selected on the device (ll_cellmap_feature_clouds), cells in ascending cell order (the
+    // reference walks a std::set of cell pointers: address order), every cell's points in stored order, intensity 0.  The sphere
+    // cells are not selected by the scene alignment and have no device selection: asking for them throws.
+    template <class Cloud>
+    Cloud extract_specify_points(Feature_type select_type)
+    {
+        if (select_type != e_feature_line && select_type != e_feature_plane) check(-1, "extract_specify_points: only e_feature_line and e_feature_plane are selected on the device");
+        int64_t n_line = 0, n_plane = 0;
+        check(ll_cellmap_feature_clouds(h_, nullptr, 0, &n_line, nullptr, 0, &n_plane, nullptr), "ll_cellmap_feature_clouds");
+        const bool line = select_type == e_feature_line;
+        std::vector<float> v((size_t)(line ? n_line : n_plane) * 4);
+        float *buf = v.empty() ? nullptr : v.data();
+        check(ll_cellmap_feature_clouds(h_, line ? buf : nullptr, line ? (int64_t)(v.size() / 4) : 0, &n_line, line ? nullptr : buf,
+                                        line ? 0 : (int64_t)(v.size() / 4), &n_plane, nullptr), "ll_cellmap_feature_clouds");
+        Cloud out;
+        xyzi_to_cloud(v.data(), (int)(v.size() / 4), out);
+        return out;
+    }
+    // Maps_keyframe::get_center (:1291-1301): the float mean of the cell centres, cells in ascending cell order
+    void get_center(float centre[3])
+    {
+        int64_t n_line = 0, n_plane = 0;
+        check(ll_cellmap_feature_clouds(h_, nullptr, 0, &n_line, nullptr, 0, &n_plane, centre), "ll_cellmap_feature_clouds");
+    }
     // the stored points ({x, y, z, 0}, ordered by (cell, insertion)) and the 64-bit cell key of every point where they lie on the device;
     // valid until the next call that changes the map
     void device_view(const float **dev_xyz0, const uint64_t **dev_point_keys, int64_t *n_points, int64_t *n_cells = nullptr)
@@ -1285,6 +1310,101 @@ class Point_cloud_registration {
     }
     ll_reg *reg_ = nullptr;
     int reg_cap_ = 0;  // the feature capacity reg_ was acquired with
+};
+
+// ------------------------------------------------------------------------------------------------------------
+// Scene_alignment (scene_alignment.hpp:19-391): two key frames, each held as a Points_cloud_map, registered against each other coarse
+// to fine, on the device from the cell maps to the pose (ll_scene_align_run: no point of either key frame crosses to the host).
+// Member names and defaults are the reference's.  What differs, by design:
+//   - the key frames' cells come in ascending cell order, not in the order of their heap addresses;
+//   - every call starts from the identity and the centre offset: the previous pair's m_q_w_incre is not kept;
+//   - nothing is written to disk: if_save and mapping_save_path are accepted and ignored, init() takes no directory to create;
+//   - m_pc_reg is where the RESULT is read (m_q_w_curr, m_t_w_curr, m_inlier_threshold, summary); the registrar's settings are the
+//     class defaults, or those of init() once it has been called, and the fields of find_tranfrom_of_two_mappings (:296-303) on top.
+class Scene_alignment {
+   public:
+    float m_line_res = 0.4f;                                    // :27
+    float m_plane_res = 0.4f;                                   // :28
+    int pair_idx = 0;                                           // :31
+    Point_cloud_registration m_pc_reg;                          // :32
+    int m_para_scene_alignments_maximum_residual_block = 5000;  // :34
+    int m_maximum_icp_iteration = 10;                           // :35
+    float m_accepted_threshold = 0.2f;                          // :36
+    int m_if_verbose_screen_printf = 1;
+    int m_subsample_seed = 1;   // ll_reg_params.subsample_seed of the registrations
+    int device = 0;
+    int64_t initial_points = 1 << 16;  // what the handle starts with; it grows
+    std::vector<Point_cloud_registration::Opt_summary> reports;  // one per registration the last call ran (<= 3)
+
+    Scene_alignment() {}
+    explicit Scene_alignment(std::string path) { init(path); }
+    ~Scene_alignment()
+    {
+        if (h_) ll_scene_align_destroy(h_);
+    }
+    Scene_alignment(const Scene_alignment &) = delete;
+    Scene_alignment &operator=(const Scene_alignment &) = delete;
+
+    void set_downsample_resolution(const float &line_res, const float &plane_res)  // :55-62
+    {
+        m_line_res = line_res;
+        m_plane_res = plane_res;
+    }
+    // :222-245 without the log directory: the registrar settings the loop detector aligns with (laser_mapping.hpp:896)
+    void init(std::string path = std::string())
+    {
+        (void)path;
+        registrar_init_ = 1;
+        m_pc_reg.ICP_LINE = 0;
+        m_pc_reg.m_max_final_cost = 20000;
+        m_pc_reg.m_para_max_speed = 1000.0;
+        m_pc_reg.m_para_max_angular_rate = 360 * 57.3;
+        m_pc_reg.m_inliner_dis = 0.2;
+    }
+    // Registers key frame b (the scan) against key frame a (the map); returns m_pc_reg.m_inlier_threshold (:389)
+    double find_tranfrom_of_two_mappings(Points_cloud_map *keyframe_a, Points_cloud_map *keyframe_b, int if_save = 0,
+                                         std::string mapping_save_path = std::string(" "))
+    {
+        (void)if_save;
+        (void)mapping_save_path;
+        if (!keyframe_a || !keyframe_b) check(-1, "Scene_alignment::find_tranfrom_of_two_mappings: null key frame");
+        if (!h_) {
+            runtime_hints();
+            check(ll_scene_align_create(device, initial_points, &h_), "ll_scene_align_create");
+        }
+        ll_scene_align_params p;
+        ll_scene_align_default_params(&p);
+        p.line_res = m_line_res;
+        p.plane_res = m_plane_res;
+        p.maximum_icp_iteration = m_maximum_icp_iteration;
+        p.accepted_threshold = m_accepted_threshold;
+        p.maximum_residual_block = m_para_scene_alignments_maximum_residual_block;
+        p.registrar_init = registrar_init_;
+        p.subsample_seed = m_subsample_seed;
+        double pose[7], thr = 0.0;
+        ll_reg_report rep[3];
+        int32_t n_rep = 0;
+        check(ll_scene_align_run(h_, keyframe_a->handle(), keyframe_b->handle(), &p, pose, &thr, rep, &n_rep), "ll_scene_align_run");
+        m_pc_reg.m_q_w_curr.x() = pose[0], m_pc_reg.m_q_w_curr.y() = pose[1], m_pc_reg.m_q_w_curr.z() = pose[2], m_pc_reg.m_q_w_curr.w() = pose[3];
+        for (int i = 0; i < 3; i++) m_pc_reg.m_t_w_curr(i) = pose[4 + i];
+        m_pc_reg.m_inlier_threshold = thr;
+        reports.clear();
+        for (int i = 0; i < n_rep; i++) {
+            Point_cloud_registration::Opt_summary s;
+            static_cast<ll_reg_report &>(s) = rep[i];
+            s.num_residual_blocks = rep[i].n_blocks_last;
+            reports.push_back(s);
+        }
+        if (n_rep > 0) m_pc_reg.summary = m_pc_reg.m_final_opt_summary = reports.back();
+        pair_idx++;
+        return thr;
+    }
+    // test tap (ll_scene_align_work) on the last call
+    void work(int64_t out[4]) { check(ll_scene_align_work(h_, out), "ll_scene_align_work"); }
+
+   private:
+    ll_scene_align *h_ = nullptr;
+    int registrar_init_ = 0;
 };
 
 }  // namespace loam_livox_hip

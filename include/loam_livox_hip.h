@@ -646,6 +646,60 @@ int ll_cellmap_keyframe_images(ll_cellmap *c, float roi_ratio, float *images, fl
  * shifts of -30 .. +30 bins along both axes.  img_a, img_b: 60 x 60 host images. */
 int ll_keyframe_similarity(int32_t device, const float *img_a, const float *img_b, float *similarity);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Scene alignment of two key frames (the last link of service_loop_detection, laser_mapping.hpp:1034-1036).
+ * ll_cellmap_feature_clouds: extract_specify_points( e_feature_line ), ( e_feature_plane ) and get_center()
+ * (cell_map_keyframe.hpp:1263-1301) of a key frame held as a cell map: the points of the cells ll_cellmap_features labels 1 (line) and
+ * 2 (plane), cells in ascending cell order (the reference walks a std::set of cell pointers: address order), every cell's points in
+ * stored order, every point {x, y, z, 0}; centre = ll_cellmap_keyframe_images' centre (zeros for a map without cells).  The selection
+ * runs on the device (flag, one scan, one gather with a lane per stored point); this call is its host read-back.  Either buffer may be
+ * NULL with its capacity 0: only the count comes back.  A buffer that is too small is an error, and nothing is written; so is a NULL
+ * handle or count pointer.  centre may be NULL. */
+int ll_cellmap_feature_clouds(ll_cellmap *c, float *line_xyzi, int64_t capacity_line, int64_t *n_line, float *plane_xyzi, int64_t capacity_plane,
+                              int64_t *n_plane, float centre[3]);
+/* Scene_alignment (scene_alignment.hpp:18-41, 233-391) with the clouds staying on the device.  ll_scene_align_run is
+ * find_tranfrom_of_two_mappings( keyframe_a, keyframe_b ): key frame b (the scan) is registered against key frame a (the map), coarse to
+ * fine.
+ *   registrar   with registrar_init != 0 the settings of Scene_alignment::init (:233-243: ICP_LINE 0, m_max_final_cost 20000,
+ *               m_para_max_speed 1000, m_para_max_angular_rate 360 * 57.3, m_inliner_dis 0.2), otherwise the registrar's class defaults;
+ *               always current_frame_index 10000000, ceres_max_iterations 50, ceres_prerun_times 2 (:296-303);
+ *   start       identity rotation and centre_a - centre_b (float) as translation, in m_q/t_w_curr and in the increment, set on every
+ *               call: nothing of the previous pair is kept (the reference's object keeps m_q_w_incre);
+ *   scales      8, 4, 0 times line_res / plane_res, clamped from below to them; ICP iterations doubled at the finest (:313-327);
+ *   per scale   the four clouds through the VoxelGrid (an empty cloud is passed on empty); a's filtered line / plane clouds become the
+ *               map's corner / surface kind, b's the scan's corner / surface stack; the registration is skipped when either of a's is
+ *               empty (point_cloud_registration.hpp:595-602); stop when inlier_threshold > 2 * accepted_threshold (:350-351);
+ *   outputs     pose = m_q_w_curr, m_t_w_curr; *inlier_threshold (0.0 when nothing was registered); reports[0 .. *n_reports) of the
+ *               registrations run (<= 3).
+ * The results are those of the host route (ll_cellmap_dump + ll_cellmap_features, ll_voxel_filter, ll_map_upload, ll_reg_solve) bit for
+ * bit: the same kernels run on the same values in the same order.
+ * The handle owns one registrar, one map, one voxel filter, the four selected clouds and their filtered forms at the three scales;
+ * they start at initial_points, grow geometrically (every cloud of a run is bounded by its map's point count, known on the host) and
+ * are reused across calls.  No point of either key frame crosses to the host.  The three scales' filters do not depend on the
+ * registrations, so all twelve filtered clouds are enqueued behind the selection and the host waits ONCE for everything it has to
+ * know -- the filtered sizes, the two centres, the bounding boxes of the six clouds that become search grids -- and then once per
+ * registration, to collect it (the early stop needs that scale's report).
+ * Refused before anything is launched, every handle still usable: null arguments, a cell map on another device than the handle,
+ * keyframe_a == keyframe_b, non-positive resolutions or maximum_icp_iteration, a cell map of a history whose feeder has failed.
+ * ll_scene_align_work is a test tap on the last run: out[0] bytes of point data copied between host and device (0: there is no such
+ * copy), out[1] host waits (stream synchronisations, those inside the library calls included) = 1 + out[2], out[2] registrations run,
+ * out[3] kernel launches and library calls of the selection step (both key frames: cell labels, centre, flag, scan, gather each). */
+typedef struct ll_scene_align ll_scene_align;
+typedef struct {
+    float line_res, plane_res;      /* m_line_res, m_plane_res (scene_alignment.hpp:27-28) */
+    int32_t maximum_icp_iteration;  /* :35 */
+    float accepted_threshold;       /* :36 */
+    int32_t maximum_residual_block; /* m_para_scene_alignments_maximum_residual_block (:34) */
+    int32_t registrar_init;         /* Scene_alignment::init (:233-243) applied */
+    int32_t subsample_seed;         /* ll_reg_params.subsample_seed */
+} ll_scene_align_params;
+void ll_scene_align_default_params(ll_scene_align_params *p); /* 0.4, 0.4, 10, 0.2, 5000, 1, 1 */
+int ll_scene_align_create(int32_t device, int64_t initial_points, ll_scene_align **out);
+void ll_scene_align_destroy(ll_scene_align *h);
+int ll_scene_align_run(ll_scene_align *h, ll_cellmap *keyframe_a, ll_cellmap *keyframe_b, const ll_scene_align_params *p, double pose[7],
+                       double *inlier_threshold, ll_reg_report reports[3], int32_t *n_reports);
+int ll_scene_align_work(ll_scene_align *h, int64_t out[4]);
+
 /* The two cell maps of the mapping node, fed by every frame ll_history_add* receives (laser_mapping.hpp:1492-1493: the
  * voxel-filtered map-frame features, whether or not the frame enters the history), and the cell branch of
  * update_buff_for_matching: query + per-cell VoxelGrid (leaf line_res / plane_res) -> VoxelGrid of the concatenation ->

@@ -807,6 +807,17 @@ class Cell_map:
                                              ptr(out["eigen_val"]), nc), "ll_cellmap_features")
         return out
 
+    def feature_clouds(self):
+        """extract_specify_points( e_feature_line ), ( e_feature_plane ) and get_center() (cell_map_keyframe.hpp:1263-1301), selected on
+        the device (ll_cellmap_feature_clouds): (line xyzi [n, 4], plane xyzi [m, 4], centre float32[3]); cells in cell order, every
+        cell's points in stored order, intensity 0."""
+        line = np.zeros((max(1, self.stats()[1]), 4), np.float32)   # (either cloud holds at most the map's points)
+        plane = np.zeros_like(line)
+        nl, npl, centre = C.c_int64(0), C.c_int64(0), np.zeros(3, np.float32)
+        check(self.L.ll_cellmap_feature_clouds(self.h, ptr(line), line.shape[0], C.byref(nl), ptr(plane), plane.shape[0], C.byref(npl), ptr(centre)),
+              "ll_cellmap_feature_clouds")
+        return line[:nl.value].copy(), plane[:npl.value].copy(), centre
+
     def keyframe_images(self, roi_ratio: float = 0.9):
         """Maps_keyframe::analyze over the cells of this map (cell_map_keyframe.hpp:1385-1493): dict(images [4,60,60] =
         line, plane, line_roi, plane_roi; ratio_nonzero [4]; eigen_R [2,3,3]; n_vectors [4]; centre [3]; roi_range)."""
@@ -824,6 +835,49 @@ class Cell_map:
         last = np.zeros(max(nc, 1), np.int32)
         check(self.L.ll_cellmap_dump(self.h, ptr(xyzi), xyzi.shape[0], ptr(ijk), ptr(start), ptr(last), ijk.shape[0]), "ll_cellmap_dump")
         return xyzi[:npts, :3].copy(), ijk[:nc].copy(), start, last[:nc].copy()
+
+
+class Scene_aligner:
+    """The device route of Scene_alignment::find_tranfrom_of_two_mappings (scene_alignment.hpp:269-391; ll_scene_align_*): one registrar,
+    one map, one voxel filter, the selected clouds and their filtered forms, kept between calls and grown from initial_points.  No point of either key
+    frame crosses to the host."""
+
+    def __init__(self, initial_points: int = 1 << 16, device: int = 0):
+        self.L = capi.load()
+        self.h = C.c_void_p()
+        check(self.L.ll_scene_align_create(device, int(initial_points), C.byref(self.h)), "ll_scene_align_create")
+        self.params = capi.scene_align_default_params()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.ll_scene_align_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, keyframe_a: "Cell_map", keyframe_b: "Cell_map"):
+        """(pose float64[7] = m_q_w_curr, m_t_w_curr; m_inlier_threshold; the reports of the registrations run)"""
+        pose, thr, n = np.zeros(7, np.float64), C.c_double(0.0), C.c_int32(0)
+        reports = (RegReport * 3)()
+        check(self.L.ll_scene_align_run(self.h, keyframe_a.h, keyframe_b.h, C.byref(self.params), ptr(pose), C.byref(thr), reports, C.byref(n)),
+              "ll_scene_align_run")
+        out = []
+        for i in range(n.value):   # (copies: the array goes with this call)
+            r = RegReport()
+            C.memmove(C.byref(r), C.byref(reports[i]), C.sizeof(RegReport))
+            out.append(r)
+        return pose, float(thr.value), out
+
+    def work(self) -> np.ndarray:
+        """test tap (ll_scene_align_work) on the last run: bytes of point data copied between host and device, host waits,
+        registrations run, enqueues of the selection step"""
+        out = np.zeros(4, np.int64)
+        check(self.L.ll_scene_align_work(self.h, ptr(out)), "ll_scene_align_work")
+        return out
 
 
 def keyframe_similarity(img_a, img_b, device: int = 0) -> float:

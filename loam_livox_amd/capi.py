@@ -50,6 +50,11 @@ class RegReport(C.Structure):
                 ("lm_iterations_total", C.c_int32), ("accepted", C.c_int32), ("gated", C.c_int32), ("aborted", C.c_int32)]
 
 
+class SceneAlignParams(C.Structure):
+    _fields_ = [("line_res", C.c_float), ("plane_res", C.c_float), ("maximum_icp_iteration", C.c_int32), ("accepted_threshold", C.c_float),
+                ("maximum_residual_block", C.c_int32), ("registrar_init", C.c_int32), ("subsample_seed", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/loam_livox_hip.h declares
 _vp, _i32, _i64, _f, _d = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 SYMBOLS = {
@@ -153,6 +158,12 @@ SYMBOLS = {
     "ll_cellmap_features": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64]),
     "ll_cellmap_keyframe_images": (_i32, [_vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "ll_keyframe_similarity": (_i32, [_i32, _vp, _vp, _vp]),
+    "ll_cellmap_feature_clouds": (_i32, [_vp, _vp, _i64, C.POINTER(_i64), _vp, _i64, C.POINTER(_i64), _vp]),
+    "ll_scene_align_default_params": (None, [C.POINTER(SceneAlignParams)]),
+    "ll_scene_align_create": (_i32, [_i32, _i64, C.POINTER(_vp)]),
+    "ll_scene_align_destroy": (None, [_vp]),
+    "ll_scene_align_run": (_i32, [_vp, _vp, _vp, C.POINTER(SceneAlignParams), _vp, C.POINTER(_d), _vp, C.POINTER(_i32)]),
+    "ll_scene_align_work": (_i32, [_vp, _vp]),
     "ll_history_enable_cell_map": (_i32, [_vp, _i64, C.c_float, _i32]),
     "ll_history_set_cell_map_async": (_i32, [_vp, _i32]),
     "ll_history_sync_cell_maps": (_i32, [_vp]),
@@ -266,6 +277,12 @@ def spin_default_params() -> SpinParams:
 def reg_default_params() -> RegParams:
     p = RegParams()
     load().ll_reg_default_params(C.byref(p))
+    return p
+
+
+def scene_align_default_params() -> SceneAlignParams:
+    p = SceneAlignParams()
+    load().ll_scene_align_default_params(C.byref(p))
     return p
 
 

@@ -18,7 +18,7 @@ void ll::cellmap_release(ll_cellmap *c)
 // A cell map owned by a history may be fed on that history's service thread (ll_history_set_cell_map_async): every public entry point
 // that reads or changes a map first waits for the frames handed over so far (and reports the feeder's failure, if any), so a handle
 // borrowed from ll_history_cell_map never sees an append in flight or a map swapped by cellmap_grow under it.
-static int cellmap_settle(const ll_cellmap *c) { return (c && c->owner) ? history_cells_drain(c->owner) : 0; }
+int ll::cellmap_settle(const ll_cellmap *c) { return (c && c->owner) ? history_cells_drain(c->owner) : 0; }
 
 extern "C" int ll_cellmap_create(int32_t device, int64_t max_points, float resolution, int32_t minimum_revisit_threshold, ll_cellmap **out)
 {

@@ -164,6 +164,26 @@ struct ll_cellmap {
     int64_t list_cap = 0;
 };
 
+// ---------------------------------------------------------------------------------------------------- scene alignment
+// Scene_alignment (scene_alignment.hpp:18-41) with everything it runs on kept between calls: the registrar m_pc_reg, the map the
+// source key frame's filtered clouds are built into, one voxel filter, the four selected clouds and their filtered forms at the
+// three scales (ll_api_scene_align.hip).
+struct ll_scene_align {
+    int device = 0;
+    ll_reg *reg = nullptr;
+    int64_t reg_cap = 0;            // max_features_per_scan of reg
+    ll_map *map = nullptr;
+    ll_voxel *vox = nullptr;        // its scratch serves all twelve filter calls of a run, one after the other on one stream
+    int64_t vox_cap = 0;            // its max_points_per_cloud
+    float4 *sel[4] = {nullptr, nullptr, nullptr, nullptr};    // the selected clouds: a's line, a's plane, b's line, b's plane
+    float4 *filt[3][4] = {};        // the same four through the VoxelGrid at each of the three scales
+    int64_t sel_cap[2] = {0, 0};    // points each cloud of key frame a / b has room for, selected or filtered
+    int *d_ints = nullptr;          // [4] selected sizes, [12] filtered sizes (scale-major), [12] filter status
+    float *d_mm = nullptr;          // [3][2][6] bounding boxes of a's filtered clouds (the grids' geometry)
+    int64_t initial_points = 0;
+    int64_t work[4] = {0, 0, 0, 0}; // ll_scene_align_work
+};
+
 // ---------------------------------------------------------------------------------------------------- history
 struct ll_history {
     int device = 0;
@@ -243,9 +263,17 @@ std::shared_ptr<MapSnap> map_build_target(ll_map *m, int kind);
 int64_t map_publish(ll_map *m, int kind, const std::shared_ptr<MapSnap> &s);
 int map_rebuild(ll_map *m, int kind, const float *d_raw, int stride, int64_t n, float cell, hipStream_t s, const char **err,
                 int64_t *generation = nullptr);
+int map_rebuild_boxed(ll_map *m, int kind, const float *d_raw, int stride, int64_t n, float cell, const float mm[6], hipStream_t s, const char **err);
+// ll_api_reg.hip
+int reg_enqueue_device_clouds(const char *where, ll_reg *r, const ll_map *map, const float4 *d_corner, const int *d_n_corner, int n_corner,
+                              const float4 *d_surf, const int *d_n_surf, int n_surf, const ll_reg_params *prm, const double pose_last[7],
+                              const double pose_curr[7], const double pose_incre[7]);
 // ll_api_cellmap.hip
 void cellmap_release(ll_cellmap *c);
 int cellmap_make_room(ll_cellmap *c, int64_t max_points, const char *where);
+int cellmap_settle(const ll_cellmap *c);
+// ll_api_scene_align.hip
+int cellmap_feature_clouds_enqueue(ll_cellmap *c, float4 *d_line, float4 *d_plane, int *d_n_line, int *d_n_plane, hipStream_t s, const char *where);
 // ll_api_history.hip
 int history_cells_drain(ll_history *h);
 float match_cell_size(int kind, float leaf);

@@ -36,6 +36,15 @@ int ll::map_rebuild(ll_map *m, int kind, const float *d_raw, int stride, int64_t
     return 0;
 }
 
+// the same from a bounding box the caller has read back already (map_bbox_enqueue): only enqueues on s, no host wait
+int ll::map_rebuild_boxed(ll_map *m, int kind, const float *d_raw, int stride, int64_t n, float cell, const float mm[6], hipStream_t s, const char **err)
+{
+    std::shared_ptr<MapSnap> t = map_build_target(m, kind);
+    if (map_build_boxed(t->mk, d_raw, stride, n, cell, mm, false, s, err)) return -1;
+    map_publish(m, kind, t);
+    return 0;
+}
+
 extern "C" int ll_map_create(int32_t device, ll_map **out)
 {
     if (!out) return set_err("ll_map_create", "null argument");

@@ -309,8 +309,8 @@ static void reg_init_state(RegState &s, int b, const double *poses_last, const d
 }
 
 // States (and, for a map per slot, the grid table the driver filled) to the device, the feature counts to r->h_nc / r->h_ns;
-// returns with the stream drained
-static int reg_exchange_counts(ll_reg *r, int n_scans, bool map_tab)
+// returns with the stream drained -- or, for one scan whose counts the caller knows (`known`), without waiting at all
+static int reg_exchange_counts(ll_reg *r, int n_scans, bool map_tab, const int *known = nullptr)
 {
     for (hipEvent_t e : r->ev) (void)hipEventDestroy(e);
     r->ev.clear();
@@ -319,6 +319,11 @@ static int reg_exchange_counts(ll_reg *r, int n_scans, bool map_tab)
     if (map_tab) HC(hipMemcpyAsync(r->d_map_tab, r->h_map_tab.data(), (size_t)n_scans * 2 * sizeof(Grid), hipMemcpyHostToDevice, r->stream));
     // feature counts on the host: launch geometry, and the sub-sampling precondition (the reference's random
     // drop, PCR:232-238,339-345,438-458, is not reproduced)
+    if (known) {  // (one scan whose {corner, surface} counts the caller has on the host already: nothing to wait for)
+        r->h_nc[0] = known[0];
+        r->h_ns[0] = known[1];
+        return 0;
+    }
     HC(hipMemcpyAsync(r->h_nc.data(), r->dev.n_corner, (size_t)n_scans * sizeof(int), hipMemcpyDeviceToHost, r->stream));
     HC(hipMemcpyAsync(r->h_ns.data(), r->dev.n_surf, (size_t)n_scans * sizeof(int), hipMemcpyDeviceToHost, r->stream));
     HC(hipStreamSynchronize(r->stream));
@@ -348,7 +353,7 @@ static int reg_finish(ll_reg *r, int n_scans, PinGuard &pin_guard)
 // ---- one map for the batch -----------------------------------------------------------------------------------------------------------
 // common launch sequence; reg_bind has set the feature pointers in r->dev
 static int reg_enqueue(const char *where, ll_reg *r, const ll_map *map, int n_scans, const ll_reg_params *prm, const double *poses_last,
-                       const double *poses_curr, const double *poses_incre)
+                       const double *poses_curr, const double *poses_incre, const int *known_counts = nullptr)
 {
     if (!map) return set_err(where, "null argument");
     if (reg_params_check(where, r, n_scans, prm, poses_last, poses_curr)) return -1;
@@ -366,7 +371,7 @@ static int reg_enqueue(const char *where, ll_reg *r, const ll_map *map, int n_sc
     r->last_gated = run ? 0 : 1;
     r->last_n_scans = n_scans;
     for (int b = 0; b < n_scans; b++) reg_init_state(r->h_state[b], b, poses_last, poses_curr, poses_incre, run);
-    if (reg_exchange_counts(r, n_scans, false)) return -1;
+    if (reg_exchange_counts(r, n_scans, false, n_scans == 1 ? known_counts : nullptr)) return -1;
     int max_nc = 0, max_ns = 0;
     for (int b = 0; b < n_scans; b++) {
         max_nc = r->h_nc[b] > max_nc ? r->h_nc[b] : max_nc;
@@ -676,6 +681,20 @@ static int reg_downsample(const char *where, ll_reg *r, const FeatView &in, ll_v
     vc->last_stream = vs->last_stream = r->stream;
     *out = feat_view(vc, vs);
     return 0;
+}
+
+// One scan whose corner and surface cloud lie on the device, written on the registrar's own stream, with their sizes on the device
+// (where the kernels read them) AND on the host (n_corner, n_surf: the caller has read them back already), so the enqueue does not wait
+// for them (ll_api_scene_align.hip).  Collect with ll_reg_collect.
+int ll::reg_enqueue_device_clouds(const char *where, ll_reg *r, const ll_map *map, const float4 *d_corner, const int *d_n_corner, int n_corner,
+                                  const float4 *d_surf, const int *d_n_surf, int n_surf, const ll_reg_params *prm, const double pose_last[7],
+                                  const double pose_curr[7], const double pose_incre[7])
+{
+    HC(hipSetDevice(r->device));
+    const FeatView v{d_corner, d_surf, d_n_corner, d_n_surf, n_corner > 0 ? n_corner : 1, n_surf > 0 ? n_surf : 1, {nullptr, nullptr}};
+    if (reg_bind(r, v)) return -1;
+    const int known[2] = {n_corner, n_surf};
+    return reg_enqueue(where, r, map, 1, prm, pose_last, pose_curr, pose_incre, known);
 }
 
 extern "C" int ll_reg_enqueue_fe_downsampled(ll_reg *r, const ll_map *map, ll_fe *fe, ll_voxel *vc, ll_voxel *vs, float line_res,

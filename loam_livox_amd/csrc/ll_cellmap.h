@@ -70,5 +70,14 @@ int keyframe_similarity(const float *d_a, const float *d_b, float *d_result, hip
 
 // determine_feature (CMK:436-473) for every cell, in cell-table order; d_out: device array of n_cells entries
 int cellmap_stats(CellMapDev &m, CellStats *d_out, hipStream_t s, const char **err);
+// get_center (CMK:1291-1301) alone -> d_out->centre, the kernel cellmap_keyframe_images runs; zeros for a map without cells
+int cellmap_centre(CellMapDev &m, KfOut *d_out, hipStream_t s, const char **err);
+// extract_specify_points( e_feature_line ), ( e_feature_plane ) (CMK:1263-1281) with d_stats = cellmap_stats' result for the map as it
+// is (ll_cellmap_select_kernels.hip): the points of the line cells and of the plane cells, cells in key order, points in stored order,
+// {x, y, z, 0} each, into d_line / d_plane (room for m.n_pts points each) and the two counts into *d_n_line / *d_n_plane (device).
+// No host wait; uses m.skey, m.skey2 and m.tmp, which must hold cellmap_select_scratch( m ) bytes.
+size_t cellmap_select_scratch(const CellMapDev &m);
+int cellmap_select_features(CellMapDev &m, const CellStats *d_stats, float4 *d_line, float4 *d_plane, int *d_n_line, int *d_n_plane, hipStream_t s,
+                            const char **err);
 
 }  // namespace ll

@@ -513,6 +513,16 @@ int cellmap_keyframe_images(CellMapDev &m, CellStats *d_stats, float roi_ratio, 
     return 0;
 }
 
+int cellmap_centre(CellMapDev &m, KfOut *d_out, hipStream_t s, const char **err)
+{
+    if (m.n_cells == 0)
+        CMCHK(hipMemsetAsync(d_out->centre, 0, sizeof(d_out->centre), s));
+    else
+        hipLaunchKernelGGL(cm_kf_centre_kernel, dim3(1), dim3(64), 0, s, m.ckey, m.n_cells, m.geom, d_out);
+    CMCHK(hipGetLastError());
+    return 0;
+}
+
 int keyframe_similarity(const float *d_a, const float *d_b, float *d_result, hipStream_t s, const char **err)
 {
     hipLaunchKernelGGL(cm_kf_similarity_kernel, dim3(1), dim3(KF_THREADS), 0, s, d_a, d_b, d_result);

@@ -92,6 +92,10 @@ struct MapKind {
 
 // builds the grid for `n` device-resident raw points (stride floats apart); fills mk. Returns 0 or a HIP error.
 int map_build(MapKind &mk, const float *d_raw, int stride, int64_t n, float cell, hipStream_t s, const char **err);
+// map_build in two halves for a caller that reads the bounding box back in a wait of its own: the box of the first *d_n (<= n_max)
+// points into d_mm[6] (enqueued); then the grid from the box on -- wait = false only enqueues and leaves mk.n_valid 0
+int map_bbox_enqueue(const float *d_raw, int stride, const int *d_n, int64_t n_max, float *d_mm, hipStream_t s, const char **err);
+int map_build_boxed(MapKind &mk, const float *d_raw, int stride, int64_t n, float cell, const float mm[6], bool wait, hipStream_t s, const char **err);
 void map_free(MapKind &mk);
 // dimensions, origin, cell size and slack of the grid over a bounding box (host arithmetic; fills the geometry fields of g only)
 void map_grid_geometry(const float mm[6], float cell, Grid &g);

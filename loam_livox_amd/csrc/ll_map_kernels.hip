@@ -21,7 +21,7 @@ namespace ll {
         }                                          \
     } while (0)
 
-__global__ void aabb_kernel(const float *raw, int stride, int64_t n, float *mn, float *mx)
+__device__ __forceinline__ void aabb_body(const float *raw, int stride, int64_t n, float *mn, float *mx)
 {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -60,6 +60,14 @@ __global__ void aabb_kernel(const float *raw, int stride, int64_t n, float *mn, 
             }
         }
     }
+}
+
+__global__ void aabb_kernel(const float *raw, int stride, int64_t n, float *mn, float *mx) { aabb_body(raw, stride, n, mn, mx); }
+// the same with the point count where it lies on the device, and the box's start values written by a kernel (no host copy)
+__global__ void aabb_counted_kernel(const float *raw, int stride, const int *d_n, float *mn, float *mx) { aabb_body(raw, stride, (int64_t)*d_n, mn, mx); }
+__global__ void aabb_init_kernel(float *mm)
+{
+    if (threadIdx.x < 6) mm[threadIdx.x] = threadIdx.x < 3 ? INFINITY : -INFINITY;
 }
 
 __global__ void cellkey_kernel(const float *raw, int stride, int64_t n, Grid g, unsigned int ncell, unsigned int *keys,
@@ -144,14 +152,19 @@ void map_grid_geometry(const float mm_in[6], float cell, Grid &g)
     g.guard = 0.0f;
 }
 
+// {min x, y, z, max x, y, z} of the finite points among the first *d_n (<= n_max) of d_raw -> d_mm[6], enqueued: what map_build's first
+// half computes, for a caller that reads the box back with other results in a wait of its own and then calls map_build_boxed
+int map_bbox_enqueue(const float *d_raw, int stride, const int *d_n, int64_t n_max, float *d_mm, hipStream_t s, const char **err)
+{
+    hipLaunchKernelGGL(aabb_init_kernel, dim3(1), dim3(64), 0, s, d_mm);
+    if (n_max > 0)
+        hipLaunchKernelGGL(aabb_counted_kernel, dim3((unsigned)((n_max + 255) / 256 < 1024 ? (n_max + 255) / 256 : 1024)), dim3(256), 0, s, d_raw, stride, d_n, d_mm, d_mm + 3);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int map_build(MapKind &mk, const float *d_raw, int stride, int64_t n, float cell, hipStream_t s, const char **err)
 {
-    if (mk.pts16) (void)hipFree(mk.pts16);  // a previous fp16 conversion does not survive a rebuild
-    if (mk.perm) (void)hipFree(mk.perm);
-    mk.pts16 = nullptr;
-    mk.perm = nullptr;
-    mk.n = n;
-    mk.n_valid = 0;
     if (!mk.b_mm) HIPCHK(hipMalloc((void **)&mk.b_mm, 6 * sizeof(float)));
     float *d_mm = mk.b_mm;
     const float init[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
@@ -161,6 +174,20 @@ int map_build(MapKind &mk, const float *d_raw, int stride, int64_t n, float cell
     float mm[6];
     HIPCHK(hipMemcpyAsync(mm, d_mm, sizeof(mm), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return map_build_boxed(mk, d_raw, stride, n, cell, mm, true, s, err);
+}
+
+// map_build's second half, from the bounding box mm of the n points on.  wait: read the number of valid points and return with the
+// stream drained.  Without it the call only enqueues (the grid is complete for every reader ordered behind it on s) and mk.n_valid
+// stays 0: such a snapshot serves searches and registrations, not map_to_f16.
+int map_build_boxed(MapKind &mk, const float *d_raw, int stride, int64_t n, float cell, const float mm[6], bool wait, hipStream_t s, const char **err)
+{
+    if (mk.pts16) (void)hipFree(mk.pts16);  // a previous fp16 conversion does not survive a rebuild
+    if (mk.perm) (void)hipFree(mk.perm);
+    mk.pts16 = nullptr;
+    mk.perm = nullptr;
+    mk.n = n;
+    mk.n_valid = 0;
     Grid g{};
     map_grid_geometry(mm, cell, g);
     const size_t ncell = (size_t)g.nx * g.ny * g.nz;
@@ -208,11 +235,12 @@ int map_build(MapKind &mk, const float *d_raw, int stride, int64_t n, float cell
     // stable LSD radix sort: points of one cell stay in ascending original-index order
     if (n > 0) HIPCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_keys, d_keys2, d_vals, d_vals2, (int)n, 0, end_bit, s));
     int n_valid = 0;
-    HIPCHK(hipMemcpyAsync(&n_valid, mk.cell_start + ncell, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (wait) HIPCHK(hipMemcpyAsync(&n_valid, mk.cell_start + ncell, sizeof(int), hipMemcpyDeviceToHost, s));
     if (grow(&mk.pts, &mk.cap_pts, nn, err)) return -1;  // (room for every point given: n_valid <= n is known only after the drain below)
     if (n > 0)
         hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_raw, stride, mk.cell_start + ncell, d_vals2, mk.pts);
-    HIPCHK(hipStreamSynchronize(s));
+    if (wait) HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
     mk.n_valid = n_valid;
     g.pts = mk.pts;
     g.cell_start = mk.cell_start;

@@ -80,7 +80,8 @@ class Keyframe_assembly:
                  minimum_keyframe_differen: int = 200, minimum_similarity_linear: float = 0.65, minimum_similarity_planar: float = 0.95,
                  map_alignment_resolution: float = 0.2, map_alignment_inlier_threshold: float = 0.35,
                  map_alignment_maximum_icp_iteration: int = 2, scene_alignments_maximum_residual_block: int = 5000,
-                 keyframe_max_points: int = 1 << 20, full_cell_map=None, avail_ratio_plane: float = 0.05, avail_ratio_line: float = 0.03):
+                 keyframe_max_points: int = 1 << 20, full_cell_map=None, avail_ratio_plane: float = 0.05, avail_ratio_line: float = 0.03,
+                 device_alignment: bool = False):
         # parameter names and defaults: laser_mapping.hpp:698-710 (loop_closure/*), :686-687 (mapping/pt_cell_resolution, threshold_cell_revisit)
         self.device = device
         self.m_pt_cell_resolution = cell_resolution
@@ -111,6 +112,10 @@ class Keyframe_assembly:
         self.if_end = False
         self.log = []                   # one record per compared pair (what the node writes to loop_closure.log)
         self._prefetched = None         # (key frame, its cell map) handed over in advance (prefetch)
+        # device_alignment: candidate pairs are aligned without a host hop (Scene_alignment( on_device=True )) by ONE object, whose
+        # handle -- registrar, map, voxel filter -- serves every pair; off, every pair gets a Scene_alignment of its own, as before
+        self.device_alignment = device_alignment
+        self._scene_alignment = None
 
     def state(self) -> str:
         """the lists as tests/verbatim_build.py's harness prints them: open key frames frames:cells, waiting ones frames:cells:ending-index"""
@@ -122,6 +127,9 @@ class Keyframe_assembly:
         if self.m_pt_cell_map_full is not None:
             self.m_pt_cell_map_full.close()
             self.m_pt_cell_map_full = None
+        if self._scene_alignment is not None:
+            self._scene_alignment.close()
+            self._scene_alignment = None
 
     # ---- laser_mapping.hpp:1524-1562 ------------------------------------------------------------------------------------------------
     def add_scan(self, full_cloud_map_frame: np.ndarray, pose: np.ndarray, current_frame_index: int) -> np.ndarray:
@@ -248,9 +256,14 @@ class Keyframe_assembly:
                     if len(last.m_set_cell) < len(old.m_set_cell):
                         his += 1
                         continue
-                    sa = Scene_alignment(self.m_loop_closure_map_alignment_resolution, self.m_loop_closure_map_alignment_resolution,   # :1034
-                                         self.m_loop_closure_map_alignment_maximum_icp_iteration, self.m_loop_closure_map_alignment_inlier_threshold,
-                                         self.m_para_scene_alignments_maximum_residual_block, device=self.device)   # :897-898, 1035
+                    sa = self._scene_alignment
+                    if sa is None:
+                        sa = Scene_alignment(self.m_loop_closure_map_alignment_resolution, self.m_loop_closure_map_alignment_resolution,   # :1034
+                                             self.m_loop_closure_map_alignment_maximum_icp_iteration, self.m_loop_closure_map_alignment_inlier_threshold,
+                                             self.m_para_scene_alignments_maximum_residual_block, device=self.device,   # :897-898, 1035
+                                             on_device=self.device_alignment)
+                        if self.device_alignment:
+                            self._scene_alignment = sa
                     cm_last, cm_old = self.cell_map_of(last), self.cell_map_of(old)
                     thr = sa.find_tranfrom_of_two_mappings(cm_last, cm_old)   # :1036
                     _close(cm_last)

@@ -88,6 +88,7 @@ class Laser_mapping:
         self._host_vox = None
         # loop_closure/if_enable_loop_closure (laser_mapping.hpp:698; 0 in the shipped Mid-40 configs): the full-cloud cell map, the key frames
         # and the front half of loop detection (keyframes.py; laser_mapping.hpp:626, 1524-1562, 919-1060)
+        # (loop_closure: Keyframe_assembly's settings as they are, device_alignment=True -- candidate pairs aligned without a host hop -- among them)
         self.keyframes = None
         self.loops = []
         self.full_map_s = 0.0  # cumulative wall time of the full-map and key-frame part of the frames (part of stage_s[1])

@@ -6,12 +6,16 @@ other by the same registrar the mapping node uses, coarse to fine.  Loop-closure
 Differences from the reference, by design:
   * extract_specify_points walks a std::set of cell pointers (address order); cells come in cell-index order here;
   * the registrar object is created per call, so the previous pair's m_q_w_incre does not leak into the next one;
-  * nothing is written to disk (if_save)."""
+  * nothing is written to disk (if_save).
+
+Scene_alignment( on_device=True ) runs the same chain without a host hop (api.Scene_aligner, ll_scene_align_run): the clouds are selected
+from the cell maps on the device, filtered, built into the map and bound to the registrar where they lie; the handle lives as long as
+the object.  Same kernels on the same values in the same order: the two routes agree bit for bit.  The host route is the default."""
 from __future__ import annotations
 
 import numpy as np
 
-from .api import Cell_map, Map_buffer, Point_cloud_registration, VoxelGrid
+from .api import Cell_map, Map_buffer, Point_cloud_registration, Scene_aligner, VoxelGrid
 
 E_FEATURE_SPHERE, E_FEATURE_LINE, E_FEATURE_PLANE = 0, 1, 2   # Feature_type, cell_map_keyframe.hpp:46-51
 
@@ -33,7 +37,7 @@ def keyframe_clouds(km: Cell_map):
 class Scene_alignment:
     def __init__(self, line_res: float = 0.4, plane_res: float = 0.4, maximum_icp_iteration: int = 10, accepted_threshold: float = 0.2,
                  maximum_residual_block: int = 5000, max_points: int = 1 << 18, device: int = 0, subsample_seed: int = 1,
-                 registrar_init: bool = True):
+                 registrar_init: bool = True, on_device: bool = False):
         # registrar_init: apply the registrar settings of Scene_alignment::init (SA:233-243: ICP_LINE = 0, m_max_final_cost 20000,
         # m_para_max_speed 1000, m_para_max_angular_rate 360 * 57.3, m_inliner_dis 0.2) as the loop detector does before its first
         # alignment (laser_mapping.hpp:896); False = a default-constructed Scene_alignment (class defaults of the registrar)
@@ -44,9 +48,29 @@ class Scene_alignment:
         self.device, self.max_points, self.subsample_seed = device, max_points, subsample_seed
         self.pose = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)   # m_pc_reg.m_q_w_curr / m_t_w_curr after the call
         self.reports = []
+        self.on_device = on_device
+        self._aligner = None   # on_device: the handle, created by the first call and kept
+
+    def close(self):
+        if self._aligner is not None:
+            self._aligner.close()
+            self._aligner = None
+
+    def _find_on_device(self, keyframe_a: Cell_map, keyframe_b: Cell_map) -> float:
+        if self._aligner is None:
+            self._aligner = Scene_aligner(initial_points=self.max_points, device=self.device)
+        p = self._aligner.params
+        p.line_res, p.plane_res = float(self.m_line_res), float(self.m_plane_res)
+        p.maximum_icp_iteration, p.accepted_threshold = int(self.m_maximum_icp_iteration), float(self.m_accepted_threshold)
+        p.maximum_residual_block = int(self.m_para_scene_alignments_maximum_residual_block)
+        p.registrar_init, p.subsample_seed = int(bool(self.registrar_init)), int(self.subsample_seed)
+        self.pose, thr, self.reports = self._aligner.run(keyframe_a, keyframe_b)
+        return thr
 
     def find_tranfrom_of_two_mappings(self, keyframe_a: Cell_map, keyframe_b: Cell_map) -> float:
         """Registers key frame b (as the scan) against key frame a (as the map); returns m_inlier_threshold (SA:389)."""
+        if self.on_device:
+            return self._find_on_device(keyframe_a, keyframe_b)
         src_line, src_plane, centre_a = keyframe_clouds(keyframe_a)
         tgt_line, tgt_plane, centre_b = keyframe_clouds(keyframe_b)
         reg = Point_cloud_registration(max_scans=1, max_features=max(1, len(tgt_line), len(tgt_plane)), device=self.device)

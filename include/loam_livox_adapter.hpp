@@ -1407,4 +1407,56 @@ class Scene_alignment {
     int registrar_init_ = 0;
 };
 
+// ------------------------------------------------------------------------------------------------------------
+// Keyframe_bank: the line and plane image of every processed key frame kept on the device (ll_keyframe_bank_*), for the walk of
+// service_loop_detection over the earlier key frames (laser_mapping.hpp:988-1057): add a key frame when it is analysed, then ask for
+// max_similiarity_of_two_image of the new one against any number of earlier ones in ONE call.  The floats are those of
+// Points_cloud_map::max_similiarity_of_two_image, bit for bit.  Ids count from 0 in the order of the adds.
+class Keyframe_bank {
+   public:
+    explicit Keyframe_bank(int64_t initial_entries = 256, int device = 0)
+    {
+        runtime_hints();
+        check(ll_keyframe_bank_create(device, initial_entries, &h_), "ll_keyframe_bank_create");
+    }
+    ~Keyframe_bank()
+    {
+        if (h_) ll_keyframe_bank_destroy(h_);
+    }
+    Keyframe_bank(const Keyframe_bank &) = delete;
+    Keyframe_bank &operator=(const Keyframe_bank &) = delete;
+
+    // Points_cloud_map::analyze with the same outputs; the key frame's line and plane image also become a new entry, whose id is returned
+    int64_t add(Points_cloud_map &keyframe, std::vector<float> &images, float ratio_nonzero[4], float roi_ratio = 0.9f)
+    {
+        images.assign((size_t)4 * 60 * 60, 0.f);
+        int64_t id = -1;
+        check(ll_keyframe_bank_add_cellmap(h_, keyframe.handle(), roi_ratio, images.data(), ratio_nonzero, nullptr, nullptr, nullptr, &id),
+              "ll_keyframe_bank_add_cellmap");
+        return id;
+    }
+    // an entry from two 60 x 60 host images
+    int64_t add(const float *img_line, const float *img_plane)
+    {
+        int64_t id = -1;
+        check(ll_keyframe_bank_add_images(h_, img_line, img_plane, &id), "ll_keyframe_bank_add_images");
+        return id;
+    }
+    int64_t size() const { return ll_keyframe_bank_size(h_); }
+    // sim_line[p], sim_plane[p] of ( ids_a[p] = the new key frame, ids_b[p] = the old one )
+    void match(const std::vector<int64_t> &ids_a, const std::vector<int64_t> &ids_b, std::vector<float> &sim_line, std::vector<float> &sim_plane)
+    {
+        if (ids_a.size() != ids_b.size()) check(-1, "Keyframe_bank::match: ids_a and ids_b differ in length");
+        sim_line.assign(ids_a.size(), 0.f);
+        sim_plane.assign(ids_a.size(), 0.f);
+        check(ll_keyframe_bank_match(h_, (int64_t)ids_a.size(), ids_a.data(), ids_b.data(), sim_line.data(), sim_plane.data()), "ll_keyframe_bank_match");
+    }
+    // test tap (ll_keyframe_bank_work) on the last match
+    void work(int64_t out[4]) { check(ll_keyframe_bank_work(h_, out), "ll_keyframe_bank_work"); }
+    ll_keyframe_bank *handle() { return h_; }
+
+   private:
+    ll_keyframe_bank *h_ = nullptr;
+};
+
 }  // namespace loam_livox_hip

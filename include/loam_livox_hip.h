@@ -700,6 +700,41 @@ int ll_scene_align_run(ll_scene_align *h, ll_cellmap *keyframe_a, ll_cellmap *ke
                        double *inlier_threshold, ll_reg_report reports[3], int32_t *n_reports);
 int ll_scene_align_work(ll_scene_align *h, int64_t out[4]);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Key-frame descriptor bank: the line and the plane direction image of every processed key frame stay on the device, and "this key
+ * frame against these earlier ones" (service_loop_detection's walk, laser_mapping.hpp:988-1057, the two max_similiarity_of_two_image
+ * calls of :1009-1010) is ONE call for any number of pairs.  Every similarity is ll_keyframe_similarity( image of a, image of b ) bit
+ * for bit: the same sums in the same order (one accumulator per shift, rows outer, columns inner), the norms in that kernel's own
+ * summation order -- taken once, when an entry is added -- and its quotient.  A pair is ordered: a is the new key frame, b the old one.
+ *   layout      entry id: [2][60 * 60] floats, line image then plane image (28 800 bytes, a multiple of 16), and two doubles (the
+ *               norms).  ids count from 0 in the order of the adds and never change; the capacity doubles on demand.
+ *   add_cellmap ll_cellmap_keyframe_images with the same host outputs (any may be NULL); behind it, on the cell map's stream, images 0
+ *               and 1 are copied device to device into the new entry and their norms are taken: the descriptors are computed once.
+ *   add_images  the two images from the host (tests; callers that already hold descriptors).
+ *   images      an entry's two images back on the host.
+ *   match       sim_line[p], sim_plane[p] of ( ids_a[p], ids_b[p] ), p < n_pairs: the pairs are staged in one copy, then the
+ *               correlation launch (a workgroup per tile of 60 x 20 shifts, kind and pair), the finish launch and one copy back; ONE
+ *               host wait whatever n_pairs is; n_pairs == 0 returns at once.
+ *   debug_surface  test tap: all 3600 sums num( Y, X ), Y, X < 60 (shift index 60 repeats shift index 0), of one pair and kind (0 line,
+ *               1 plane) into out[Y * 60 + X].
+ *   work        test tap on the last match: out[0] enqueues (4), out[1] host waits (1), out[2] image bytes copied between host and
+ *               device (0: there is no such copy), out[3] pairs.
+ * Refused before anything is enqueued, the handle and its entries as they were: null arguments, ids out of range, negative counts (or
+ * more than 2^24 pairs), a cell map on another device than the bank, roi_ratio outside [0, 1], a cell map of a history whose feeder has
+ * failed, a bank that would pass 2^31 image floats (298 261 entries). */
+typedef struct ll_keyframe_bank ll_keyframe_bank;
+int ll_keyframe_bank_create(int32_t device, int64_t initial_entries, ll_keyframe_bank **out);
+void ll_keyframe_bank_destroy(ll_keyframe_bank *b);
+int ll_keyframe_bank_add_cellmap(ll_keyframe_bank *b, ll_cellmap *c, float roi_ratio, float *images, float *ratio_nonzero, float *eigen_R,
+                                 int32_t *n_vectors, float *centre_and_range, int64_t *id);
+int ll_keyframe_bank_add_images(ll_keyframe_bank *b, const float *img_line, const float *img_plane, int64_t *id);
+int ll_keyframe_bank_images(ll_keyframe_bank *b, int64_t id, float *img_line, float *img_plane);
+int64_t ll_keyframe_bank_size(const ll_keyframe_bank *b);
+int ll_keyframe_bank_match(ll_keyframe_bank *b, int64_t n_pairs, const int64_t *ids_a, const int64_t *ids_b, float *sim_line,
+                           float *sim_plane);
+int ll_keyframe_bank_debug_surface(ll_keyframe_bank *b, int64_t id_a, int64_t id_b, int32_t kind, double *out);
+int ll_keyframe_bank_work(ll_keyframe_bank *b, int64_t out[4]);
+
 /* The two cell maps of the mapping node, fed by every frame ll_history_add* receives (laser_mapping.hpp:1492-1493: the
  * voxel-filtered map-frame features, whether or not the frame enters the history), and the cell branch of
  * update_buff_for_matching: query + per-cell VoxelGrid (leaf line_res / plane_res) -> VoxelGrid of the concatenation ->

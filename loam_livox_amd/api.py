@@ -880,6 +880,76 @@ class Scene_aligner:
         return out
 
 
+class Keyframe_bank:
+    """The key-frame descriptor bank (ll_keyframe_bank_*): the line and plane direction image of every processed key frame stay on the
+    device with their norms; match answers "these (new, old) pairs" in one launch chain and one host wait, with keyframe_similarity's
+    floats bit for bit.  An entry's id is its position in the order of the adds; the capacity doubles on demand."""
+
+    def __init__(self, initial_entries: int = 256, device: int = 0):
+        self.L = capi.load()
+        self.h = C.c_void_p()
+        check(self.L.ll_keyframe_bank_create(device, int(initial_entries), C.byref(self.h)), "ll_keyframe_bank_create")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.ll_keyframe_bank_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return int(check(self.L.ll_keyframe_bank_size(self.h), "ll_keyframe_bank_size"))
+
+    def add_cell_map(self, cell_map: "Cell_map", roi_ratio: float = 0.9):
+        """(Cell_map.keyframe_images( roi_ratio ) of the map, the id of the new entry): images 0 and 1 go into the bank device to device"""
+        img = np.zeros((4, 60, 60), np.float32)
+        ratio, R, nv, cr = np.zeros(4, np.float32), np.zeros((2, 3, 3), np.float32), np.zeros(4, np.int32), np.zeros(4, np.float32)
+        eid = C.c_int64(-1)
+        check(self.L.ll_keyframe_bank_add_cellmap(self.h, cell_map.h, roi_ratio, ptr(img), ptr(ratio), ptr(R), ptr(nv), ptr(cr), C.byref(eid)),
+              "ll_keyframe_bank_add_cellmap")
+        return dict(images=img, ratio_nonzero=ratio, eigen_R=R, n_vectors=nv, centre=cr[:3].copy(), roi_range=float(cr[3])), int(eid.value)
+
+    def add_images(self, img_line, img_plane) -> int:
+        """an entry from two 60 x 60 host images; returns its id"""
+        a, b = np.ascontiguousarray(img_line, np.float32), np.ascontiguousarray(img_plane, np.float32)
+        if a.shape != (60, 60) or b.shape != (60, 60):
+            raise ValueError("direction images are 60 x 60")
+        eid = C.c_int64(-1)
+        check(self.L.ll_keyframe_bank_add_images(self.h, ptr(a), ptr(b), C.byref(eid)), "ll_keyframe_bank_add_images")
+        return int(eid.value)
+
+    def images(self, entry: int):
+        """(line image, plane image) of an entry, read back"""
+        a, b = np.zeros((60, 60), np.float32), np.zeros((60, 60), np.float32)
+        check(self.L.ll_keyframe_bank_images(self.h, int(entry), ptr(a), ptr(b)), "ll_keyframe_bank_images")
+        return a, b
+
+    def match(self, ids_a, ids_b):
+        """(sim_line float32[n], sim_plane float32[n]) of the ordered pairs ( ids_a[p], ids_b[p] ): a is the new key frame, b the old one"""
+        a, b = np.ascontiguousarray(ids_a, np.int64).reshape(-1), np.ascontiguousarray(ids_b, np.int64).reshape(-1)
+        if len(a) != len(b):
+            raise ValueError("ids_a and ids_b differ in length")
+        line, plane = np.zeros(len(a), np.float32), np.zeros(len(a), np.float32)
+        check(self.L.ll_keyframe_bank_match(self.h, len(a), ptr(a), ptr(b), ptr(line), ptr(plane)), "ll_keyframe_bank_match")
+        return line, plane
+
+    def surface(self, id_a: int, id_b: int, kind: int) -> np.ndarray:
+        """test tap (ll_keyframe_bank_debug_surface): the correlation sums of one pair and kind (0 line, 1 plane) over all 60 x 60 shifts"""
+        out = np.zeros((60, 60), np.float64)
+        check(self.L.ll_keyframe_bank_debug_surface(self.h, int(id_a), int(id_b), int(kind), ptr(out)), "ll_keyframe_bank_debug_surface")
+        return out
+
+    def work(self) -> np.ndarray:
+        """test tap (ll_keyframe_bank_work) on the last match: enqueues, host waits, image bytes copied between host and device, pairs"""
+        out = np.zeros(4, np.int64)
+        check(self.L.ll_keyframe_bank_work(self.h, ptr(out)), "ll_keyframe_bank_work")
+        return out
+
+
 def keyframe_similarity(img_a, img_b, device: int = 0) -> float:
     """Maps_keyframe::max_similiarity_of_two_image (cell_map_keyframe.hpp:1155-1224) of two 60 x 60 direction images."""
     a, b = np.ascontiguousarray(img_a, np.float32), np.ascontiguousarray(img_b, np.float32)

@@ -164,6 +164,15 @@ SYMBOLS = {
     "ll_scene_align_destroy": (None, [_vp]),
     "ll_scene_align_run": (_i32, [_vp, _vp, _vp, C.POINTER(SceneAlignParams), _vp, C.POINTER(_d), _vp, C.POINTER(_i32)]),
     "ll_scene_align_work": (_i32, [_vp, _vp]),
+    "ll_keyframe_bank_create": (_i32, [_i32, _i64, C.POINTER(_vp)]),
+    "ll_keyframe_bank_destroy": (None, [_vp]),
+    "ll_keyframe_bank_add_cellmap": (_i32, [_vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "ll_keyframe_bank_add_images": (_i32, [_vp, _vp, _vp, C.POINTER(_i64)]),
+    "ll_keyframe_bank_images": (_i32, [_vp, _i64, _vp, _vp]),
+    "ll_keyframe_bank_size": (_i64, [_vp]),
+    "ll_keyframe_bank_match": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "ll_keyframe_bank_debug_surface": (_i32, [_vp, _i64, _i64, _i32, _vp]),
+    "ll_keyframe_bank_work": (_i32, [_vp, _vp]),
     "ll_history_enable_cell_map": (_i32, [_vp, _i64, C.c_float, _i32]),
     "ll_history_set_cell_map_async": (_i32, [_vp, _i32]),
     "ll_history_sync_cell_maps": (_i32, [_vp]),

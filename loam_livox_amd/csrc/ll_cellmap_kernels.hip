@@ -20,6 +20,7 @@
 #include <utility>
 
 #include "ll_cellmap.h"
+#include "ll_keyframe_bank_core.h"
 
 namespace ll {
 
@@ -447,13 +448,12 @@ __global__ __launch_bounds__(KF_THREADS) void cm_kf_similarity_kernel(const floa
     __shared__ float s_a[KF_BINS], s_b[KF_BINS];
     __shared__ double s_w[KF_THREADS / 64][3];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double na = 0.0, nb = 0.0;
     for (int e = tid; e < KF_BINS; e += KF_THREADS) {
         s_a[e] = a[e];
         s_b[e] = b[e];
-        na += (double)a[e] * (double)a[e];
-        nb += (double)b[e] * (double)b[e];
     }
+    // the norms' summation order is shared with the key-frame bank, which takes them once per entry (ll_keyframe_bank_core.h)
+    double na = kf_block_norm_partial(a, tid), nb = kf_block_norm_partial(b, tid);
     __syncthreads();
     const int half = LL_KF_RES / 2, span = LL_KF_RES + 1;  // result is 61 x 61
     double best = -1.0e300;
@@ -466,9 +466,9 @@ __global__ __launch_bounds__(KF_THREADS) void cm_kf_similarity_kernel(const floa
         }
         best = num > best ? num : best;
     }
+    na = kf_wave_sum(na);
+    nb = kf_wave_sum(nb);
     for (int off = 32; off > 0; off >>= 1) {
-        na += __shfl_down(na, off);
-        nb += __shfl_down(nb, off);
         const double o = __shfl_down(best, off);
         best = o > best ? o : best;
     }
@@ -485,8 +485,7 @@ __global__ __launch_bounds__(KF_THREADS) void cm_kf_similarity_kernel(const floa
             B += s_w[w][1];
             M = s_w[w][2] > M ? s_w[w][2] : M;
         }
-        const double t = sqrt(A * B);
-        *result = t > 0.0 ? (float)(M / t) : 0.0f;
+        *result = kb_quotient(A, B, M);
     }
 }
 

@@ -25,7 +25,13 @@ cells, features and clouds) for the pairs that pass the similarity gates, and it
 max_points and doubles (ll_cellmap_reserve) when a scan would not fit, as the reference's heap-allocated cells grow.
 
 Differences from the node, by design: everything runs synchronously (the node's service thread polls every millisecond);
-m_accumulated_point_cloud (only consumed by the map refinement) is not kept."""
+m_accumulated_point_cloud (only consumed by the map refinement) is not kept.
+
+device_bank=True keeps the line and plane image of every processed key frame in a device-resident api.Keyframe_bank and asks for the
+similarities of a new key frame against ALL earlier key frames that pass the three scalar gates in one Keyframe_bank.match, instead of
+two keyframe_similarity calls per pair inside the walk; the floats are the same to the bit, and so are log, loops and if_end.
+process_waiting is the composition of analyse_front (materialise, analyse, gate), one match, and walk_front (the walk, reading the two
+arrays); an owner of many assemblies that share one bank runs the halves itself with one match for all of them."""
 from __future__ import annotations
 
 from collections import deque
@@ -81,7 +87,7 @@ class Keyframe_assembly:
                  map_alignment_resolution: float = 0.2, map_alignment_inlier_threshold: float = 0.35,
                  map_alignment_maximum_icp_iteration: int = 2, scene_alignments_maximum_residual_block: int = 5000,
                  keyframe_max_points: int = 1 << 20, full_cell_map=None, avail_ratio_plane: float = 0.05, avail_ratio_line: float = 0.03,
-                 device_alignment: bool = False):
+                 device_alignment: bool = False, device_bank: bool = False, bank=None):
         # parameter names and defaults: laser_mapping.hpp:698-710 (loop_closure/*), :686-687 (mapping/pt_cell_resolution, threshold_cell_revisit)
         self.device = device
         self.m_pt_cell_resolution = cell_resolution
@@ -116,6 +122,12 @@ class Keyframe_assembly:
         # handle -- registrar, map, voxel filter -- serves every pair; off, every pair gets a Scene_alignment of its own, as before
         self.device_alignment = device_alignment
         self._scene_alignment = None
+        # device_bank: the key frames' line and plane images stay on the device (api.Keyframe_bank) and a new key frame is compared
+        # against all gated earlier ones in one match.  bank: one to share (its owner closes it; anything with add_cell_map / match);
+        # without it the assembly creates its own with the first key frame it processes.
+        self.device_bank = bool(device_bank) or bank is not None
+        self._bank, self._owns_bank = bank, False
+        self._front = None              # (key frame, candidates) between analyse_front and walk_front
 
     def state(self) -> str:
         """the lists as tests/verbatim_build.py's harness prints them: open key frames frames:cells, waiting ones frames:cells:ending-index"""
@@ -130,6 +142,9 @@ class Keyframe_assembly:
         if self._scene_alignment is not None:
             self._scene_alignment.close()
             self._scene_alignment = None
+        if self._bank is not None and self._owns_bank:
+            self._bank.close()
+        self._bank = None
 
     # ---- laser_mapping.hpp:1524-1562 ------------------------------------------------------------------------------------------------
     def add_scan(self, full_cloud_map_frame: np.ndarray, pose: np.ndarray, current_frame_index: int) -> np.ndarray:
@@ -216,74 +231,120 @@ class Keyframe_assembly:
         return self._cell_map_from_points(kf.points) if kf.points is not None else self.materialize(kf)
 
     # ---- laser_mapping.hpp:919-1060 --------------------------------------------------------------------------------------------------
+    def bank(self):
+        """the key-frame bank of device_bank=True: the one handed in, else this assembly's own, created on first use"""
+        if self._bank is None:
+            from .api import Keyframe_bank
+            self._bank, self._owns_bank = Keyframe_bank(device=self.device), True
+        return self._bank
+
     def process_waiting(self, limit: int | None = None):
         """Every waiting key frame (the first `limit` of them, when given) through one pass of service_loop_detection's loop body.
         Returns the loops found in this call."""
         found = []
-        avail_ratio_plane, avail_ratio_line = self.avail_ratio_plane, self.avail_ratio_line   # :887-888
         while self.m_keyframe_need_precession_list and not self.if_end and (limit is None or limit > 0):
             limit = None if limit is None else limit - 1
-            last = self.m_keyframe_need_precession_list.popleft()
-            cm = self.materialize(last)                     # update_features_of_each_cells + analyze read the cells as they are now
+            candidates = self.analyse_front()
+            sims = self.bank().match(*self.front_pairs()) if self.device_bank and candidates else None
+            found += self.walk_front(sims)
+        return found
+
+    def analyse_front(self) -> list:
+        """The analysis half of one pass: the first waiting key frame leaves the list, is materialised and analysed (through the bank
+        with device_bank=True: the same dict, and its line and plane image stay on the device) and joins keyframe_vec.  Returns the
+        earlier key frames `his` that pass the gates of :994, :1001 and :1004 -- the only ones whose similarities the walk can ask for."""
+        last = self.m_keyframe_need_precession_list.popleft()
+        cm = self.materialize(last)                     # update_features_of_each_cells + analyze read the cells as they are now
+        if self.device_bank:
+            last.analysis, last.bank_id = self.bank().add_cell_map(cm)
+        else:
             last.analysis = cm.keyframe_images()
-            last.points = cm.dump()[0] if hasattr(cm, "dump") else None
-            _close(cm)
-            self.keyframe_vec.append(last)
-            self.pose3d_vec.append((last.m_pose_q.copy(), last.m_pose_t.copy()))
-            n_kf = len(self.keyframe_vec)
-            his = 0
-            while his < n_kf - 1:
-                if self.if_end:
-                    break
-                old = self.keyframe_vec[his]
-                rec = dict(last=n_kf - 1, his=his)
-                if n_kf - his < self.m_loop_closure_minimum_keyframe_differen:   # :994
-                    his += 1
-                    continue
-                if old.m_ratio_nonzero_plane < avail_ratio_plane and old.m_ratio_nonzero_line < avail_ratio_line:   # :1001
-                    his += 1
-                    continue
-                if abs(old.m_roi_range - last.m_roi_range) > 5.0:   # :1004
-                    his += 1
-                    continue
+        last.points = cm.dump()[0] if hasattr(cm, "dump") else None
+        _close(cm)
+        self.keyframe_vec.append(last)
+        self.pose3d_vec.append((last.m_pose_q.copy(), last.m_pose_t.copy()))
+        n_kf = len(self.keyframe_vec)
+        candidates = [his for his in range(n_kf - 1) if self._passes_gates(n_kf, his, last)]
+        self._front = (last, candidates)
+        return candidates
+
+    def front_pairs(self):
+        """(ids_a, ids_b) of the bank entries of analyse_front's candidates: a = the new key frame, b = the old one, as the detector
+        calls max_similiarity_of_two_image (:1009-1010)"""
+        last, candidates = self._front
+        return [last.bank_id] * len(candidates), [self.keyframe_vec[his].bank_id for his in candidates]
+
+    def _passes_gates(self, n_kf: int, his: int, last: Maps_keyframe) -> bool:
+        """the three scalar gates in front of the image comparison"""
+        old = self.keyframe_vec[his]
+        if n_kf - his < self.m_loop_closure_minimum_keyframe_differen:   # :994
+            return False
+        if old.m_ratio_nonzero_plane < self.avail_ratio_plane and old.m_ratio_nonzero_line < self.avail_ratio_line:   # :1001, :887-888
+            return False
+        if abs(old.m_roi_range - last.m_roi_range) > 5.0:   # :1004
+            return False
+        return True
+
+    def walk_front(self, sims=None):
+        """The walk half of one pass (laser_mapping.hpp:988-1057) for the key frame analyse_front added.  sims: (sim_line, sim_plane)
+        of analyse_front's candidates, in their order (one Keyframe_bank.match); None: every pair that reaches the comparison asks
+        keyframe_similarity itself.  A similarity of a candidate the walk skips (his += 11, += 6, the loop that ends the search) is
+        never read.  Returns the loops found."""
+        found = []
+        last, candidates = self._front
+        self._front = None
+        where = {his: k for k, his in enumerate(candidates)} if sims is not None else None
+        n_kf = len(self.keyframe_vec)
+        his = 0
+        while his < n_kf - 1:
+            if self.if_end:
+                break
+            old = self.keyframe_vec[his]
+            rec = dict(last=n_kf - 1, his=his)
+            if not self._passes_gates(n_kf, his, last):
+                his += 1
+                continue
+            if sims is not None:
+                sim_plane, sim_line = float(sims[1][where[his]]), float(sims[0][where[his]])
+            else:
                 sim_plane = keyframe_similarity(last.m_feature_img_plane, old.m_feature_img_plane, self.device)   # :1009-1010
                 sim_line = keyframe_similarity(last.m_feature_img_line, old.m_feature_img_line, self.device)
-                rec.update(sim_plane=sim_plane, sim_line=sim_line)
-                self.log.append(rec)
-                if (sim_line > self.m_loop_closure_minimum_similarity_linear and sim_plane > 0.92) or \
-                        sim_plane > self.m_loop_closure_minimum_similarity_planar:   # :1012-1013
-                    # :1030  ( a - b ) / ( a + b ) * 0.1 in size_t arithmetic: zero unless a < b, where a - b wraps around
-                    if len(last.m_set_cell) < len(old.m_set_cell):
-                        his += 1
-                        continue
-                    sa = self._scene_alignment
-                    if sa is None:
-                        sa = Scene_alignment(self.m_loop_closure_map_alignment_resolution, self.m_loop_closure_map_alignment_resolution,   # :1034
-                                             self.m_loop_closure_map_alignment_maximum_icp_iteration, self.m_loop_closure_map_alignment_inlier_threshold,
-                                             self.m_para_scene_alignments_maximum_residual_block, device=self.device,   # :897-898, 1035
-                                             on_device=self.device_alignment)
-                        if self.device_alignment:
-                            self._scene_alignment = sa
-                    cm_last, cm_old = self.cell_map_of(last), self.cell_map_of(old)
-                    thr = sa.find_tranfrom_of_two_mappings(cm_last, cm_old)   # :1036
-                    _close(cm_last)
-                    _close(cm_old)
-                    rec.update(inlier_threshold=thr, pose=sa.pose.copy())
-                    if thr > self.m_loop_closure_map_alignment_inlier_threshold * 2:   # :1048-1052
-                        his += 10 + 1
-                        continue
-                    if thr < self.m_loop_closure_map_alignment_inlier_threshold:   # :1054: "I believe this is true loop."
-                        q, t = sa.pose[:4], sa.pose[4:7]
-                        qi = np.array([-q[0], -q[1], -q[2], q[3]])                # :1064-1065  ICP_t = ICP_q^-1 * (-ICP_t); ICP_q = ICP_q^-1
-                        ti = _quat_rot(qi, -t)
-                        loop = dict(his=his, last=n_kf - 1, inlier_threshold=thr, icp_q=qi, icp_t=ti, sim_plane=sim_plane, sim_line=sim_line)
-                        self.loops.append(loop)
-                        found.append(loop)
-                        self.if_end = True   # :1108 (the pose graph optimisation and the map refinement in between are out of scope)
-                        break
-                    his += 5 + 1   # :1111-1114
+            rec.update(sim_plane=sim_plane, sim_line=sim_line)
+            self.log.append(rec)
+            if (sim_line > self.m_loop_closure_minimum_similarity_linear and sim_plane > 0.92) or \
+                    sim_plane > self.m_loop_closure_minimum_similarity_planar:   # :1012-1013
+                # :1030  ( a - b ) / ( a + b ) * 0.1 in size_t arithmetic: zero unless a < b, where a - b wraps around
+                if len(last.m_set_cell) < len(old.m_set_cell):
+                    his += 1
                     continue
-                his += 1
+                sa = self._scene_alignment
+                if sa is None:
+                    sa = Scene_alignment(self.m_loop_closure_map_alignment_resolution, self.m_loop_closure_map_alignment_resolution,   # :1034
+                                         self.m_loop_closure_map_alignment_maximum_icp_iteration, self.m_loop_closure_map_alignment_inlier_threshold,
+                                         self.m_para_scene_alignments_maximum_residual_block, device=self.device,   # :897-898, 1035
+                                         on_device=self.device_alignment)
+                    if self.device_alignment:
+                        self._scene_alignment = sa
+                cm_last, cm_old = self.cell_map_of(last), self.cell_map_of(old)
+                thr = sa.find_tranfrom_of_two_mappings(cm_last, cm_old)   # :1036
+                _close(cm_last)
+                _close(cm_old)
+                rec.update(inlier_threshold=thr, pose=sa.pose.copy())
+                if thr > self.m_loop_closure_map_alignment_inlier_threshold * 2:   # :1048-1052
+                    his += 10 + 1
+                    continue
+                if thr < self.m_loop_closure_map_alignment_inlier_threshold:   # :1054: "I believe this is true loop."
+                    q, t = sa.pose[:4], sa.pose[4:7]
+                    qi = np.array([-q[0], -q[1], -q[2], q[3]])                # :1064-1065  ICP_t = ICP_q^-1 * (-ICP_t); ICP_q = ICP_q^-1
+                    ti = _quat_rot(qi, -t)
+                    loop = dict(his=his, last=n_kf - 1, inlier_threshold=thr, icp_q=qi, icp_t=ti, sim_plane=sim_plane, sim_line=sim_line)
+                    self.loops.append(loop)
+                    found.append(loop)
+                    self.if_end = True   # :1108 (the pose graph optimisation and the map refinement in between are out of scope)
+                    break
+                his += 5 + 1   # :1111-1114
+                continue
+            his += 1
         return found
 
 

@@ -88,7 +88,8 @@ class Laser_mapping:
         self._host_vox = None
         # loop_closure/if_enable_loop_closure (laser_mapping.hpp:698; 0 in the shipped Mid-40 configs): the full-cloud cell map, the key frames
         # and the front half of loop detection (keyframes.py; laser_mapping.hpp:626, 1524-1562, 919-1060)
-        # (loop_closure: Keyframe_assembly's settings as they are, device_alignment=True -- candidate pairs aligned without a host hop -- among them)
+        # (loop_closure: Keyframe_assembly's settings as they are, device_alignment=True -- candidate pairs aligned without a host hop -- and
+        #  device_bank=True -- the key frames' images kept on the device, one similarity call per closed key frame -- among them)
         self.keyframes = None
         self.loops = []
         self.full_map_s = 0.0  # cumulative wall time of the full-map and key-frame part of the frames (part of stage_s[1])
@@ -318,7 +319,9 @@ class Laser_mapping_batch:
     closed leave the store in one History_buffer_batch.extract_cells and every slot runs its process_waiting on the map handed to it;
     keyframes[s] and loops[s] are those of Laser_mapping run alone on sequence s.  Nothing of the registration reads the full maps:
     poses and reports do not change by a bit.  loop_closure_if_enable itself stays refused: it names Laser_mapping's per-sequence
-    map."""
+    map.  loop_closure["device_bank"]=True (off by default): the loop owns ONE api.Keyframe_bank (keyframe_bank) for its S assemblies;
+    a round of key-frame processing is then the analysis half of every slot, one Keyframe_bank.match over all slots' pairs, and the
+    walk half of every slot -- the same logs and loops, float for float."""
 
     def __init__(self, n_sequences: int, refresh_threads: int | None = None, batched_history: bool = False, cell_maps: bool = False,
                  cell_matching: bool = False, full_maps: bool = False, key_frames: bool = False, **kw):
@@ -361,7 +364,7 @@ class Laser_mapping_batch:
         self.maps = [Map_buffer(device=device) for _ in range(S)]
         self.batched_history, self.cell_maps, self.cell_matching = bool(batched_history), bool(cell_maps), bool(cell_matching)
         self.full_maps, self.key_frames = bool(full_maps), bool(key_frames)
-        self.keyframes, self.loops = None, None
+        self.keyframes, self.loops, self.keyframe_bank = None, None, None
         self.full_map_s = 0.0  # cumulative wall time of the full-map phase (append_full, and the key-frame steps with key_frames)
         self.m_maximum_search_range = (a["maximum_search_range_corner"], a["maximum_search_range_surface"])
         self.m_maximum_in_fov_angle, self.m_down_sample_replace = a["maximum_in_fov_angle"], a["down_sample_replace"]
@@ -378,6 +381,10 @@ class Laser_mapping_batch:
                 self.history_batch.enable_full_maps(first, a["cell_resolution"], a["threshold_cell_revisit"])
                 if key_frames:
                     from .keyframes import Keyframe_assembly
+                    # loop_closure["device_bank"]: ONE key-frame bank for the S assemblies, and one match per round of _process_keyframes
+                    if lc.pop("device_bank", False):
+                        from .api import Keyframe_bank
+                        self.keyframe_bank = lc["bank"] = Keyframe_bank(device=device)
                     self.keyframes = [Keyframe_assembly(device=device, cell_resolution=a["cell_resolution"],
                                                         threshold_cell_revisit=a["threshold_cell_revisit"],
                                                         full_cell_map=self.history_batch.full_map(s), **lc) for s in range(S)]
@@ -414,6 +421,9 @@ class Laser_mapping_batch:
             self._pool = None
         for kf in self.keyframes or []:
             kf.close()
+        if self.keyframe_bank is not None:
+            self.keyframe_bank.close()
+            self.keyframe_bank = None
         for h in [self.fe, self.reg, self.vox[0], self.vox[1]] + self.maps + ([self.history_batch] if self.batched_history else self.histories):
             h.close()
 
@@ -449,7 +459,8 @@ class Laser_mapping_batch:
         """The waiting key frames of the step's slots, a round at a time: the first waiting key frame of every slot is extracted from
         the full-cloud store in ONE call, handed to its assembly, and processed.  No append happens between the extraction and the
         processing, so the cells are read as they are now (cell_map_keyframe.hpp:1243-1261), as by the assembly's own route.  A
-        slot with nothing waiting still gets its process_waiting, as before."""
+        slot with nothing waiting still gets its process_waiting, as before.  With a shared key-frame bank (loop_closure device_bank)
+        a round is the analysis half of every slot, ONE match over all slots' pairs, then the walk half of every slot."""
         def waiting(ka):
             todo = getattr(ka, "m_keyframe_need_precession_list", None)
             return len(todo) if todo and not ka.if_end else 0
@@ -470,10 +481,27 @@ class Laser_mapping_batch:
                     raise
                 for (_, ka), kf, km in zip(todo, fronts, dsts):
                     ka.prefetch(kf, km)
-            for s in (slots if first else [s for s, _ in todo]):
-                ka = self.keyframes[s]
-                self.loops[s] += ka.process_waiting(limit=1) if waiting(ka) > 1 else ka.process_waiting()
+            if getattr(self, "keyframe_bank", None) is not None:
+                self._bank_round([s for s, _ in todo])
+            else:
+                for s in (slots if first else [s for s, _ in todo]):
+                    ka = self.keyframes[s]
+                    self.loops[s] += ka.process_waiting(limit=1) if waiting(ka) > 1 else ka.process_waiting()
             first = False
+
+    def _bank_round(self, slots) -> None:
+        """one waiting key frame of every slot named (each has one): analysed and gated per slot, compared in one match, walked per slot"""
+        pairs = [(s, self.keyframes[s].analyse_front()) for s in slots]
+        ids_a, ids_b, cut = [], [], [0]
+        for s, candidates in pairs:
+            a, b = self.keyframes[s].front_pairs()
+            ids_a += a
+            ids_b += b
+            cut.append(len(ids_a))
+        line, plane = self.keyframe_bank.match(ids_a, ids_b) if ids_a else ((), ())
+        for k, (s, candidates) in enumerate(pairs):
+            sims = (line[cut[k]:cut[k + 1]], plane[cut[k]:cut[k + 1]]) if candidates else None
+            self.loops[s] += self.keyframes[s].walk_front(sims)
 
     def _upload(self, scans, stamps, active):
         S = self.n_sequences

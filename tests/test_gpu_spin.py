@@ -11,7 +11,7 @@ import pytest
 from loam_livox_amd import capi, synth
 from loam_livox_amd.api import Spinning_laser
 from loam_livox_amd.feature_node import Laser_feature
-from tests import spin_ref
+from tests import spin_inputs, spin_ref
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -116,6 +116,35 @@ def test_walk_reaching_the_ends_of_the_cloud(gpu_lib):
     x[9:380:9, 0] += 0.8  # spikes: walks break at them; the walks from the first and the last sharp points run to the cloud ends
     dev = Spinning_laser(scan_line=16)
     compare(dev.extract(x), spin_ref.extract(x, scan_line=16))
+    dev.close()
+
+
+@pytest.mark.parametrize("name", sorted(spin_inputs.FAMILIES))
+def test_family_matches_restatement(gpu_lib, name):
+    """the scans of tests/spin_inputs.py, which reach what tests/test_spin_host.py asserts of them: sub-regions on both sides of the
+    LDS / rank sort switch with runs of tied curvatures, the 20 / 200 pick bounds and the stop at the 201st pick, picks several
+    64-candidate chunks deep, walks of exactly 500 steps, cut at 499, to the ends of the cloud and across a line boundary, and lines
+    of more than 24 576 points (max_line_points >= the line: the per-line VoxelGrid takes the multi-kernel pipeline, status 0)"""
+    x, ref = spin_inputs.family(name)
+    dev = Spinning_laser(scan_line=16, max_points=len(x) + 1, max_line_points=max(8192, int(ref["line_n"].max())))
+    compare(dev.extract(x), ref)
+    counts, status = dev.counts(1)
+    assert status[0] == 0 and counts[0, 2] == len(ref["less_sharp"]) and counts[0, 4] == len(ref["less_flat"])
+    dev.close()
+
+
+def test_families_in_a_batch_next_to_a_world_scan(gpu_lib, world):
+    """the ladder and the spiked ring in slots other than 0, between ordinary scans: per-slot offsets of the sort and the selection"""
+    scans = [synth.make_spin_scan(world, 5, scan_line=16, n_azimuth=900).xyzi, spin_inputs.family("ladder")[0],
+             spin_inputs.family("ring")[0], synth.make_spin_scan(world, 6, scan_line=16, n_azimuth=1100, range_sigma=0.0).xyzi]
+    refs = [spin_ref.extract(scans[0], scan_line=16), spin_inputs.family("ladder")[1], spin_inputs.family("ring")[1],
+            spin_ref.extract(scans[3], scan_line=16)]
+    dev = Spinning_laser(scan_line=16, max_points=max(len(s) for s in scans), max_scans=4,
+                         max_line_points=int(max(r["line_n"].max() for r in refs)))
+    out = dev.extract_batch(scans)
+    assert np.all(dev.counts(4)[1] == 0)
+    for b in range(4):
+        compare(out[b], refs[b])
     dev.close()
 
 

@@ -18,7 +18,7 @@ import pytest
 from loam_livox_amd import capi, synth
 from loam_livox_amd.api import History_buffer, Livox_laser, Map_buffer, Point_cloud_registration, Spinning_laser, VoxelGrid
 from oracle import orc
-from tests import spin_ref
+from tests import spin_inputs, spin_ref
 from tests.test_spin_reg_host import MAP_ARGS, N_STATIC, make_sequence, run_oracle
 
 pytestmark = pytest.mark.gpu
@@ -271,6 +271,49 @@ def test_submap_device_spin_equals_cloud_transform(batches):
                                                   C.c_void_p(small.data_ptr()), int(small.shape[0]), C.byref(cnt))
         assert rc != 0 and cnt.value == lead and b"device buffer too small" in reg.L.ll_last_error()
     reg.close()
+
+
+@pytest.mark.parametrize("names,tight", [(("zigzag", "ring"), False), (("zigzag",), True), (("zigzag_jitter", "zigzag"), True)])
+def test_crowded_scans_are_handed_over_whole(gpu_lib, names, tight):
+    """scans with hundreds to thousands of less-sharp picks (tests/spin_inputs.py: sub-regions at the 200-pick bound; the scans above
+    have a few dozen): the packed corner stack, bounded by pack_stride = min(1200 * scan_line, max_points), holds every pick.  The
+    device sub-map append and the history add give the bits of the round trip through the downloaded clouds; `tight`: max_points
+    below 1200 * scan_line, so that max_points is the bound."""
+    import torch
+    scans = [spin_inputs.family(k)[0] for k in names]
+    refs = [spin_inputs.family(k)[1] for k in names]
+    B = len(scans)
+    max_points = max(len(x) for x in scans) + 1
+    assert (max_points < 1200 * 16) == tight and all(len(r["less_sharp"]) > 900 for r in refs)
+    sp = Spinning_laser(scan_line=16, max_points=max_points, max_scans=B, max_line_points=max_points)
+    clouds = sp.extract_batch(scans)
+    assert np.all(sp.counts(B)[1] == 0)
+    for c, r in zip(clouds, refs):
+        assert np.array_equal(c["less_sharp"], r["less_sharp"]) and np.array_equal(c[LS][:, :3], r["full"][r["less_sharp"], :3])
+    rng = np.random.default_rng(31)
+    poses = np.stack([np.r_[synth.quat_from_axis_angle(rng.normal(size=3), rng.uniform(0.1, 1.0)), rng.uniform(-5, 5, 3)] for _ in range(B)])
+    reg = Point_cloud_registration(max_scans=B, max_features=max_points)
+    accept = np.ones(B, np.int32)
+    for which in (Spinning_laser.LESS_SHARP, Spinning_laser.SHARP, Spinning_laser.LESS_FLAT, Spinning_laser.FULL):  # (no flat points here)
+        src = [clouds[b][spin_ref.TOPICS[which]] for b in range(B)]
+        expect = np.concatenate([reg.pointcloudAssociateToMap(src[b], poses[b]) for b in range(B)])
+        out = torch.full((3 + len(expect), 4), -1.0, dtype=torch.float32, device="cuda")
+        used = reg.append_to_submap_device_spin(sp, B, which, accept, poses, out, 3)
+        got = out.cpu().numpy()
+        assert used == 3 + len(expect) and np.all(got[:3] == -1.0) and np.array_equal(bits(got[3:]), bits(expect)), which
+    reg.close()
+    # the corner stack of the hand-off itself (spin_handoff: what ll_reg_enqueue_spin and ll_history_add_spin read)
+    cap = max(max(len(c[LS]) for c in clouds), max(len(c[LF]) for c in clouds))
+    dev, host = History_buffer(3, cap, 0.2, 0.5), History_buffer(3, cap, 0.2, 0.5)
+    md, mh = Map_buffer(), Map_buffer()
+    for b in range(B):
+        assert dev.add_spin(sp, b, poses[b], 0.0, 0.0) == host.add(clouds[b][LS], clouds[b][LF], poses[b], 0.0, 0.0)
+        assert dev.refresh(md) == host.refresh(mh)
+        for kind in (0, 1):
+            x, y = dev.map_cloud(kind), host.map_cloud(kind)
+            assert len(x) > 0 and np.array_equal(bits(x), bits(y)), (b, kind)
+    for h in (dev, host, md, mh, sp):
+        h.close()
 
 
 # ------------------------------------------------------------------------------------------------------ D

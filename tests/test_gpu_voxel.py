@@ -94,6 +94,16 @@ def test_one_workgroup_path_equals_the_kernel_pipeline(gpu_lib, monkeypatch):
         clouds = rng.uniform(-20, 20, (B, stride, 4)).astype(np.float32)
         clouds[rng.random((B, stride)) < 0.01, 1] = np.inf
         cases.append((stride, B, n, clouds))
+    # strides one past the 8-item and the 24-item instantiation (24 577: past the one-workgroup filter altogether), and one batch whose
+    # sizes sit on either side of the bounds between the instantiations
+    for stride, B, sizes in ((8193, 2, None), (24577, 1, None), (8193, 4, [4096, 4097, 8192, 8193])):
+        n = rng.integers(0, stride + 1, B).astype(np.int32)
+        n[0] = stride
+        if sizes is not None:
+            n = np.array(sizes, np.int32)
+        clouds = rng.uniform(-20, 20, (B, stride, 4)).astype(np.float32)
+        clouds[rng.random((B, stride)) < 0.01, 1] = np.inf
+        cases.append((stride, B, n, clouds))
     outs = []
     for general in (False, True):
         if general:
@@ -111,6 +121,47 @@ def test_one_workgroup_path_equals_the_kernel_pipeline(gpu_lib, monkeypatch):
         assert all(np.array_equal(x, y) for x, y in zip(a[2], b_[2]))
     s, ref = orc.voxel_grid(cases[4][3][0, :cases[4][2][0]], (0.35, 0.5, 0.35))
     assert np.array_equal(outs[0][4][2][0], bits(ref))
+    for k in (6, 7, 8):
+        stride, B, n, clouds = cases[k]
+        for b in range(B):
+            s, ref = orc.voxel_grid(clouds[b, :n[b]], (0.35, 0.5, 0.35))
+            for res in (outs[0][k], outs[1][k]):
+                assert res[1][b] == s and np.array_equal(res[2][b], bits(ref)), (k, b)
+
+
+def test_offsets_carry_past_256_clouds(gpu_lib, monkeypatch):
+    """vox_offsets_kernel scans the voxel counts 256 clouds a trip and carries the sum into the next: 600 ragged clouds of stride 64
+    through the multi-kernel pipeline (a spin batch with long lines gives it S x 16 or S x 51 clouds), with empty and all-NaN clouds
+    and one passed through, every cloud against the oracle; the one-workgroup path gives the same bits"""
+    rng = np.random.default_rng(17)
+    B, stride = 600, 64
+    n = rng.integers(1, stride + 1, B).astype(np.int32)
+    clouds = rng.uniform(-3, 3, (B, stride, 4)).astype(np.float32)
+    clouds[rng.random((B, stride)) < 0.02, 2] = np.nan
+    n[[3, 254, 258, 300, 510, 513]] = 0             # empty, next to the trip bounds too
+    clouds[[7, 253, 259, 400, 509, 514], :, 0] = np.nan   # no finite point
+    clouds[100] *= 1e6                              # more leaves than an int indexes: passed through
+    for b in (0, 255, 256, 257, 511, 512, 599):
+        n[b] = stride - (b % 3)
+        clouds[b] = rng.uniform(-3, 3, (stride, 4)).astype(np.float32)
+    refs = [orc.voxel_grid(clouds[b, :n[b]], 0.5) for b in range(B)]
+    assert {0, 1, 2} == {s for s, _ in refs} and all(refs[b][0] == 0 and len(refs[b][1]) > 8 for b in (255, 256, 257, 511, 512))
+    got = []
+    for general in (True, False):
+        if general:
+            monkeypatch.setenv("LL_VOXEL_GENERAL_PATH", "1")
+        else:
+            monkeypatch.delenv("LL_VOXEL_GENERAL_PATH")
+        vg = VoxelGrid(max_points=stride, max_clouds=B)
+        vg.setLeafSize(0.5, 0.5, 0.5)
+        out, n_out, st = vg.filter_batch(clouds, n)
+        vg.close()
+        for b in range(B):
+            s, ref = refs[b]
+            assert st[b] == s and n_out[b] == len(ref), (general, b)
+            assert np.array_equal(bits(out[b, :n_out[b]]), bits(ref)), (general, b)
+        got.append((n_out.copy(), [bits(out[b, :n_out[b]]).copy() for b in range(B)]))
+    assert np.array_equal(got[0][0], got[1][0]) and all(np.array_equal(x, y) for x, y in zip(got[0][1], got[1][1]))
 
 
 def test_properties_at_map_scale(gpu_lib):

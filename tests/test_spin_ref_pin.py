@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from loam_livox_amd import synth
-from tests import spin_ref, verbatim_build
+from tests import spin_inputs, spin_ref, verbatim_build
 
 REF = verbatim_build.REF
 ROOT = verbatim_build.ROOT
@@ -177,12 +177,16 @@ def run_pin(exe, tmp_path, clouds, scan_line, minimum_range=0.1, plane_resolutio
 def pin_scans(scan_line):
     """>= 8 in-domain scans (no NaN, nothing inside minimum_range): full revolutions (the halfPassed flip), noise-free ones (exact
     curvature ties), rooms with pillars (occlusions), coarse and fine azimuth steps (walks across sub-regions and lines), short and
-    empty lines (a scan of a few azimuths: lines of fewer than 12 points have empty sub-regions)"""
+    empty lines (a scan of a few azimuths: lines of fewer than 12 points have empty sub-regions); for 16 lines also the families of
+    tests/spin_inputs.py: crowded sub-regions (the 20 / 200 pick bounds, sub-regions of more than 4096 points, runs of tied curvatures),
+    walks of 500 steps, to the ends of the cloud and across a line boundary"""
     w = synth.make_world(4, 4)
     out = []
     for k, (n_az, sigma) in enumerate([(1800, 0.01), (1800, 0.0), (900, 0.02), (600, 0.0), (1200, 0.01), (300, 0.01), (8, 0.0), (20, 0.01)]):
         out.append(synth.make_spin_scan(w, 40 + k, scan_line=scan_line, n_azimuth=n_az if scan_line == 16 else n_az * 2 // 3,
                                         range_sigma=sigma).xyzi)
+    if scan_line == 16:
+        out += [spin_inputs.family(name)[0] for name in sorted(spin_inputs.FAMILIES)]
     return out
 
 
@@ -190,9 +194,10 @@ def pin_scans(scan_line):
 def test_restatement_is_the_reference(pin_exe, tmp_path, scan_line):
     clouds = pin_scans(scan_line)
     got = run_pin(pin_exe, tmp_path, clouds, scan_line)
-    n_flip = n_dropped = n_short = 0
+    n_flip = n_dropped = n_short = n_capped = 0
     for c, five in zip(clouds, got):
         r = spin_ref.extract(c, scan_line=scan_line)
+        n_capped += sum(w["less_sharp"] == 200 for w in spin_inputs.reach(r))
         assert len(r["full"]) + np.count_nonzero(~np.isin(np.arange(len(c)), r["full_src"])) == len(c)
         ref5 = spin_ref.clouds(r)
         for topic, mine in zip(spin_ref.TOPICS, five):
@@ -204,5 +209,6 @@ def test_restatement_is_the_reference(pin_exe, tmp_path, scan_line):
         n_flip += int(rel.max() > 0.05) if len(rel) else 0
     assert n_flip >= 4          # orientations past startOri + pi: the halfPassed branch ran
     assert n_short >= 1
+    assert n_capped >= (20 if scan_line == 16 else 0)  # sub-regions stopped at the 201st pick
     if scan_line == 64:
         assert n_dropped > 0    # beams outside the 0..50 scan-ID rule

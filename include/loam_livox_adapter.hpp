@@ -17,6 +17,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <set>
@@ -1313,6 +1314,133 @@ class Point_cloud_registration {
 };
 
 // ------------------------------------------------------------------------------------------------------------
+// ------------------------------------------------------------------------------------------------------------
+// Ceres_pose_graph_3d (ceres_pose_graph_3d.hpp:30-352): the types the loop detector fills and pose_graph_optimization, which runs on
+// the device (ll_pose_graph_solve: the same problem, the same trust-region sequence, pose poses.begin() held constant).  Pose ids are
+// the map's keys; the constraints name them.  Nothing is printed or written; the solver's summary is returned instead.
+namespace Ceres_pose_graph_3d {
+
+// the information matrix of a constraint, read and written as information( i, j ) like the reference's Eigen matrix
+struct Matrix6d {
+    double c[36];
+    double &operator()(int i, int j) { return c[i * 6 + j]; }
+    double operator()(int i, int j) const { return c[i * 6 + j]; }
+    void setIdentity()
+    {
+        for (int i = 0; i < 36; i++) c[i] = i % 7 == 0 ? 1.0 : 0.0;
+    }
+};
+
+struct Pose3d {
+    Vector3d p;
+    Quaterniond q;
+    Pose3d()
+    {
+        q.setIdentity();
+        p.setZero();
+    }
+    Pose3d(const Quaterniond &in_q, const Vector3d &in_t) : p(in_t), q(in_q) {}
+#if defined(LOAM_LIVOX_ADAPTER_EIGEN)
+    EIGEN_MAKE_ALIGNED_OPERATOR_NEW
+#endif
+};
+
+struct Constraint3d {
+    int id_begin = 0, id_end = 0;
+    Pose3d t_be;            // the measurement: the pose of id_end in the frame of id_begin
+    Matrix6d information;   // identity unless set
+    Constraint3d() { information.setIdentity(); }
+    Constraint3d(int id_a, int id_b, const Quaterniond &q_a2b, const Vector3d &t_a2b) : id_begin(id_a), id_end(id_b), t_be(q_a2b, t_a2b)
+    {
+        information.setIdentity();
+    }
+#if defined(LOAM_LIVOX_ADAPTER_EIGEN)
+    EIGEN_MAKE_ALIGNED_OPERATOR_NEW
+#endif
+};
+
+#if defined(LOAM_LIVOX_ADAPTER_EIGEN) && defined(EIGEN_WORLD_VERSION)
+typedef std::map<int, Pose3d, std::less<int>, Eigen::aligned_allocator<std::pair<const int, Pose3d>>> MapOfPoses;
+typedef std::vector<Constraint3d, Eigen::aligned_allocator<Constraint3d>> VectorOfConstraints;
+typedef std::vector<Pose3d, Eigen::aligned_allocator<Pose3d>> VectorOfPose;
+#else
+typedef std::map<int, Pose3d> MapOfPoses;
+typedef std::vector<Constraint3d> VectorOfConstraints;
+typedef std::vector<Pose3d> VectorOfPose;
+#endif
+
+// :336-352.  The poses are optimised in place.
+inline ll_pose_graph_summary pose_graph_optimization(MapOfPoses &poses, VectorOfConstraints &constraints, int device = 0)
+{
+    ll_pose_graph_summary summary = ll_pose_graph_summary();
+    summary.termination = LL_POSE_GRAPH_NOTHING_TO_OPTIMISE;
+    if (poses.empty()) return summary;
+    std::map<int, int> index;
+    std::vector<double> x;
+    for (MapOfPoses::const_iterator it = poses.begin(); it != poses.end(); ++it) {
+        index[it->first] = (int)index.size();
+        const double row[7] = {it->second.q.x(), it->second.q.y(), it->second.q.z(), it->second.q.w(), it->second.p(0), it->second.p(1), it->second.p(2)};
+        x.insert(x.end(), row, row + 7);
+    }
+    const int64_t n = (int64_t)poses.size(), e = (int64_t)constraints.size();
+    std::vector<int32_t> ab, first((size_t)n, 0);
+    std::vector<double> meas, info;
+    for (int64_t k = 1; k < n; k++) first[(size_t)k] = (int32_t)(k - 1);
+    for (size_t k = 0; k < constraints.size(); k++) {
+        const Constraint3d &c = constraints[k];
+        if (!index.count(c.id_begin) || !index.count(c.id_end)) check(-1, "pose_graph_optimization: a constraint names a pose that is not in the map");
+        const int a = index[c.id_begin], b = index[c.id_end];
+        ab.push_back(a), ab.push_back(b);
+        const double row[7] = {c.t_be.q.x(), c.t_be.q.y(), c.t_be.q.z(), c.t_be.q.w(), c.t_be.p(0), c.t_be.p(1), c.t_be.p(2)};
+        meas.insert(meas.end(), row, row + 7);
+        for (int i = 0; i < 6; i++)
+            for (int j = 0; j < 6; j++) info.push_back(c.information(i, j));
+        const int hi = a > b ? a : b, lo = a > b ? b : a;
+        if (lo >= 1 && first[(size_t)hi] > lo - 1) first[(size_t)hi] = lo - 1;
+    }
+    int64_t blocks = 1;
+    for (int64_t k = 1; k < n; k++) blocks += (k - 1) - first[(size_t)k] + 1;
+    runtime_hints();
+    ll_pose_graph *h = nullptr;
+    check(ll_pose_graph_create(device, 1, n, e > 0 ? e : 1, blocks, &h), "ll_pose_graph_create");
+    const int64_t pose_offsets[2] = {0, n}, edge_offsets[2] = {0, e};
+    const int rc = ll_pose_graph_solve(h, nullptr, 1, pose_offsets, x.data(), edge_offsets, ab.data(), meas.data(), info.data(), &summary);
+    const std::string why = rc < 0 ? ll_last_error() : "";
+    ll_pose_graph_destroy(h);
+    if (rc < 0) throw std::runtime_error("ll_pose_graph_solve: " + why);
+    size_t k = 0;
+    for (MapOfPoses::iterator it = poses.begin(); it != poses.end(); ++it, k++) {
+        it->second.q.x() = x[7 * k], it->second.q.y() = x[7 * k + 1], it->second.q.z() = x[7 * k + 2], it->second.q.w() = x[7 * k + 3];
+        for (int i = 0; i < 3; i++) it->second.p(i) = x[7 * k + 4 + i];
+    }
+    return summary;
+}
+
+// Eigen's quaternion arithmetic on {x, y, z, w}, for builds with and without Eigen
+namespace detail {
+inline void q_mul(const double a[4], const double b[4], double o[4])
+{
+    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+    o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+}
+inline void q_inverse(const double q[4], double o[4])
+{
+    const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+    o[0] = -q[0] / n2, o[1] = -q[1] / n2, o[2] = -q[2] / n2, o[3] = q[3] / n2;
+}
+inline void q_rotate(const double q[4], const double v[3], double o[3])
+{
+    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
+    for (int i = 0; i < 3; i++) uv[i] = uv[i] + uv[i];
+    const double uuv[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
+    for (int i = 0; i < 3; i++) o[i] = v[i] + q[3] * uv[i] + uuv[i];
+}
+}  // namespace detail
+
+}  // namespace Ceres_pose_graph_3d
+
 // Scene_alignment (scene_alignment.hpp:19-391): two key frames, each held as a Points_cloud_map, registered against each other coarse
 // to fine, on the device from the cell maps to the pose (ll_scene_align_run: no point of either key frame crosses to the host).
 // Member names and defaults are the reference's.  What differs, by design:
@@ -1401,6 +1529,31 @@ class Scene_alignment {
     }
     // test tap (ll_scene_align_work) on the last call
     void work(int64_t out[4]) { check(ll_scene_align_work(h_, out), "ll_scene_align_work"); }
+
+    // :97-129: the loop constraint s_idx -> t_idx from the poses of the two key frames and the alignment's inverted transform:
+    // q_res = q_b^-1 icp_q^-1 q_a, t_res = q_b^-1 ( icp_q^-1 ( t_a - icp_t ) - t_b ).  fp64 on the host, Eigen's operation order.
+    static Ceres_pose_graph_3d::Constraint3d add_constrain_of_loop(int s_idx, int t_idx, Quaterniond q_a, Vector3d t_a, Quaterniond q_b, Vector3d t_b,
+                                                                   Quaterniond icp_q, Vector3d icp_t, int if_verbose = 1)
+    {
+        (void)if_verbose;
+        namespace d = Ceres_pose_graph_3d::detail;
+        const double qa[4] = {q_a.x(), q_a.y(), q_a.z(), q_a.w()}, qb[4] = {q_b.x(), q_b.y(), q_b.z(), q_b.w()};
+        const double qi[4] = {icp_q.x(), icp_q.y(), icp_q.z(), icp_q.w()};
+        double qbi[4], qii[4], m[4], q_res[4], v[3], w[3], t_res[3];
+        d::q_inverse(qb, qbi);
+        d::q_inverse(qi, qii);
+        d::q_mul(qbi, qii, m);
+        d::q_mul(m, qa, q_res);
+        for (int i = 0; i < 3; i++) v[i] = t_a(i) - icp_t(i);
+        d::q_rotate(qii, v, w);
+        for (int i = 0; i < 3; i++) w[i] = w[i] - t_b(i);
+        d::q_rotate(qbi, w, t_res);
+        Ceres_pose_graph_3d::Constraint3d c;
+        c.id_begin = s_idx, c.id_end = t_idx;
+        c.t_be.q.x() = q_res[0], c.t_be.q.y() = q_res[1], c.t_be.q.z() = q_res[2], c.t_be.q.w() = q_res[3];
+        for (int i = 0; i < 3; i++) c.t_be.p(i) = t_res[i];
+        return c;
+    }
 
    private:
     ll_scene_align *h_ = nullptr;

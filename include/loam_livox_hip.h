@@ -735,6 +735,63 @@ int ll_keyframe_bank_match(ll_keyframe_bank *b, int64_t n_pairs, const int64_t *
 int ll_keyframe_bank_debug_surface(ll_keyframe_bank *b, int64_t id_a, int64_t id_b, int32_t kind, double *out);
 int ll_keyframe_bank_work(ll_keyframe_bank *b, int64_t out[4]);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Pose graph: what the detector does with an accepted loop (laser_mapping.hpp:948-960, 1058-1089; ceres_pose_graph_3d.hpp:198-352;
+ * scene_alignment.hpp:97-129).  G independent graphs are optimised by ONE launch (a workgroup per graph runs the whole
+ * Levenberg-Marquardt loop on the device) and ONE host wait.  The map refinement and the file dumps behind it are not here.
+ *   problem     a graph has N poses and E edges (a, b, measurement {q_m, p_m}, information 6 x 6); pose 0 is constant; any a != b.
+ *               error  e = [ conj(q_a) . (p_b - p_a) - p_m ; 2 vec( q_m (x) conj( conj(q_a) (x) q_b ) ) ],  residual L e with
+ *               information = L L' (factored on the host in fp64; an identity matrix skips the product).  Translation moves
+ *               additively, a quaternion by Plus(q, d) = ( sin|d| / |d| d, cos|d| ) (x) q without renormalisation; analytic Jacobian; fp64.
+ *   minimiser   Ceres' trust-region Levenberg-Marquardt with ll_pose_graph_params (no loss, no bounds): Jacobi scaling from the
+ *               first Jacobian, damping diag(J'J) clamped and divided by the radius, the normal equations solved exactly by a
+ *               Cholesky factorisation of their block envelope (poses in index order: a chain is block-tridiagonal, a loop edge
+ *               a -> b lengthens the row of max(a, b) back to min(a, b); about 2 N + sum |a - b| blocks of 6 x 6), the radius and
+ *               tolerance rules of Ceres 1.14's TrustRegionMinimizer.
+ *   determinism no atomics; every sum runs in an order fixed by the edge list; a graph's result does not depend on n_graphs, on its
+ *               place in the call, or on the run.
+ *   layout      poses7 [P][7] {qx, qy, qz, qw, tx, ty, tz} of all graphs one after the other, in and out; pose_offsets[G + 1] and
+ *               edge_offsets[G + 1] delimit the graphs; edge_ab[2 E] pose ids within the edge's graph; edge_meas7 [E][7] in the pose
+ *               layout; edge_information [E][36] row-major, or NULL for identities.  p may be NULL (the defaults).
+ *   summary     per graph.  A graph of one pose or without edges comes back unchanged with LL_POSE_GRAPH_NOTHING_TO_OPTIMISE.
+ *   work        test tap on the last solve: out[0] enqueues, out[1] host waits (1), out[2] envelope blocks, out[3] graphs.
+ * Refused before anything is enqueued, the poses untouched: null arguments, offsets that do not ascend from 0, ids out of range,
+ * a == b, a non-finite input, an information matrix that is not positive definite (its lower triangle is read, as Eigen's llt
+ * does), more graphs / poses / edges / envelope
+ * blocks than the handle was created for (the text names the size needed). */
+typedef struct ll_pose_graph ll_pose_graph;
+typedef struct {
+    int32_t max_num_iterations;                 /* 200 (ceres_pose_graph_3d.hpp:343) */
+    int32_t max_num_consecutive_invalid_steps;  /* 5 */
+    double initial_trust_region_radius;         /* 1e4 */
+    double max_trust_region_radius;             /* 1e16 */
+    double min_trust_region_radius;             /* 1e-32 */
+    double min_relative_decrease;               /* 1e-3 */
+    double min_lm_diagonal, max_lm_diagonal;    /* 1e-6, 1e32 */
+    double function_tolerance;                  /* 1e-6 */
+    double gradient_tolerance;                  /* 1e-10 */
+    double parameter_tolerance;                 /* 1e-8 */
+} ll_pose_graph_params;
+#define LL_POSE_GRAPH_MAX_ITERATIONS 0
+#define LL_POSE_GRAPH_GRADIENT 1
+#define LL_POSE_GRAPH_PARAMETER 2
+#define LL_POSE_GRAPH_FUNCTION 3
+#define LL_POSE_GRAPH_RADIUS 4
+#define LL_POSE_GRAPH_INVALID_STEPS 5
+#define LL_POSE_GRAPH_NOTHING_TO_OPTIMISE 6
+typedef struct {
+    int32_t iterations, successful_steps, unsuccessful_steps, termination;
+    double initial_cost, final_cost;
+} ll_pose_graph_summary;
+void ll_pose_graph_default_params(ll_pose_graph_params *p);
+int ll_pose_graph_create(int32_t device, int64_t max_graphs, int64_t max_poses_total, int64_t max_edges_total, int64_t max_envelope_blocks,
+                         ll_pose_graph **out);
+void ll_pose_graph_destroy(ll_pose_graph *h);
+int ll_pose_graph_solve(ll_pose_graph *h, const ll_pose_graph_params *p, int64_t n_graphs, const int64_t *pose_offsets, double *poses7,
+                        const int64_t *edge_offsets, const int32_t *edge_ab, const double *edge_meas7, const double *edge_information,
+                        ll_pose_graph_summary *summary);
+int ll_pose_graph_work(ll_pose_graph *h, int64_t out[4]);
+
 /* The two cell maps of the mapping node, fed by every frame ll_history_add* receives (laser_mapping.hpp:1492-1493: the
  * voxel-filtered map-frame features, whether or not the frame enters the history), and the cell branch of
  * update_buff_for_matching: query + per-cell VoxelGrid (leaf line_res / plane_res) -> VoxelGrid of the concatenation ->

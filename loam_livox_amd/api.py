@@ -950,6 +950,132 @@ class Keyframe_bank:
         return out
 
 
+class Pose_graph:
+    """The pose-graph optimiser (ll_pose_graph_*): Ceres_pose_graph_3d::pose_graph_optimization (ceres_pose_graph_3d.hpp:336-352) for
+    any number of independent graphs in one launch and one host wait.  A graph is a dict: poses [N, 7] {qx, qy, qz, qw, tx, ty, tz}
+    (pose 0 is held constant), ab [E, 2] pose ids of every edge, meas [E, 7] in the pose layout, and optionally information [E, 36].
+    The handle's capacities grow on demand (the handle is created again, larger: it keeps nothing between calls)."""
+
+    def __init__(self, max_graphs: int = 16, max_poses: int = 4096, max_edges: int = 8192, max_envelope_blocks: int = 1 << 16, device: int = 0,
+                 params=None):
+        self.L = capi.load()
+        self.device = device
+        self.params = params if params is not None else capi.pose_graph_default_params()
+        self.h = None
+        self._create([int(max_graphs), int(max_poses), int(max_edges), int(max_envelope_blocks)])
+
+    def _create(self, capacity):
+        self.close()
+        h = C.c_void_p()
+        check(self.L.ll_pose_graph_create(self.device, *capacity, C.byref(h)), "ll_pose_graph_create")
+        self.h, self.capacity = h, list(capacity)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.ll_pose_graph_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def envelope_blocks(n_poses: int, ab) -> int:
+        """6 x 6 blocks of the block envelope of a graph's normal matrix: row f (pose f + 1) reaches back to the lowest free pose an
+        edge joins it to"""
+        first = np.arange(max(n_poses - 1, 0), dtype=np.int64)
+        ab = np.asarray(ab, np.int64).reshape(-1, 2)
+        if len(ab) == 0 or len(first) == 0:
+            return len(first)
+        lo, hi = ab.min(axis=1) - 1, ab.max(axis=1) - 1
+        ok = (lo >= 0) & (hi < len(first))
+        np.minimum.at(first, hi[ok], lo[ok])
+        return int(np.sum(np.arange(len(first)) - first + 1))
+
+    def solve(self, graphs):
+        """-> (poses: one [N, 7] array per graph, summaries: one dict per graph with iterations, successful_steps, unsuccessful_steps,
+        initial_cost, final_cost, termination (a name of capi.POSE_GRAPH_TERMINATION)).  The inputs are not modified."""
+        graphs = list(graphs)
+        G = len(graphs)
+        poses = [np.array(g["poses"], np.float64).reshape(-1, 7) for g in graphs]
+        abs_ = [np.ascontiguousarray(g["ab"], np.int32).reshape(-1, 2) for g in graphs]
+        meas = [np.ascontiguousarray(g["meas"], np.float64).reshape(-1, 7) for g in graphs]
+        for p, a, m in zip(poses, abs_, meas):
+            if len(a) != len(m):
+                raise ValueError("a graph's ab and meas differ in length")
+        info = None
+        if any(g.get("information") is not None for g in graphs):
+            info = [np.asarray(g["information"], np.float64).reshape(-1, 36) if g.get("information") is not None
+                    else np.tile(np.eye(6).ravel(), (len(a), 1)) for g, a in zip(graphs, abs_)]
+            for i, a in zip(info, abs_):
+                if len(i) != len(a):
+                    raise ValueError("a graph's ab and information differ in length")
+            info = np.ascontiguousarray(np.concatenate(info)) if G else None
+        po = np.cumsum([0] + [len(p) for p in poses]).astype(np.int64)
+        eo = np.cumsum([0] + [len(a) for a in abs_]).astype(np.int64)
+        x = np.ascontiguousarray(np.concatenate(poses)) if G else np.zeros((0, 7))
+        ab = np.ascontiguousarray(np.concatenate(abs_)) if G else np.zeros((0, 2), np.int32)
+        ms = np.ascontiguousarray(np.concatenate(meas)) if G else np.zeros((0, 7))
+        need = [G, len(x), len(ab), sum(self.envelope_blocks(len(p), a) for p, a in zip(poses, abs_))]
+        if any(n > c for n, c in zip(need, self.capacity)):
+            self._create([max(c, 2 * n if n > c else 1) for n, c in zip(need, self.capacity)])
+        summary = (capi.PoseGraphSummary * max(G, 1))()
+        check(self.L.ll_pose_graph_solve(self.h, C.byref(self.params), G, ptr(po), ptr(x), ptr(eo), ptr(ab), ptr(ms), ptr(info), summary),
+              "ll_pose_graph_solve")
+        out = [dict(iterations=s.iterations, successful_steps=s.successful_steps, unsuccessful_steps=s.unsuccessful_steps,
+                    initial_cost=s.initial_cost, final_cost=s.final_cost, termination=capi.POSE_GRAPH_TERMINATION[s.termination])
+               for s in summary[:G]]
+        return [x[po[g]:po[g + 1]].copy() for g in range(G)], out
+
+    def work(self) -> np.ndarray:
+        """test tap (ll_pose_graph_work) on the last solve: enqueues, host waits, envelope blocks, graphs"""
+        out = np.zeros(4, np.int64)
+        check(self.L.ll_pose_graph_work(self.h, ptr(out)), "ll_pose_graph_work")
+        return out
+
+
+def _q_mul(a, b):
+    """Eigen's quaternion product on {x, y, z, w}, term for term"""
+    return np.array([a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1], a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2],
+                     a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0], a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2]], np.float64)
+
+
+def _q_inverse(q):
+    """Eigen's inverse(): the conjugate over the squared norm"""
+    n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]
+    return np.array([-q[0] / n2, -q[1] / n2, -q[2] / n2, q[3] / n2], np.float64)
+
+
+def _q_rotate(q, v):
+    """Eigen's quaternion * vector: uv = 2 (u x v); v + w uv + u x uv"""
+    u = q[:3]
+    uv = np.cross(u, v)
+    uv = uv + uv
+    return v + q[3] * uv + np.cross(u, uv)
+
+
+def relative_constraint(pose_prev, pose_curr) -> np.ndarray:
+    """The chain constraint of two consecutive key-frame poses (laser_mapping.hpp:954-958) as a measurement {q, t}:
+    relative_Q = q_prev^-1 q_curr, relative_T = q_prev^-1 ( t_curr - t_prev ).  fp64, on the host."""
+    a, b = np.asarray(pose_prev, np.float64).reshape(7), np.asarray(pose_curr, np.float64).reshape(7)
+    qi = _q_inverse(a[:4])
+    return np.concatenate([_q_mul(qi, b[:4]), _q_rotate(qi, b[4:7] - a[4:7])])
+
+
+def loop_constraint(s_idx: int, t_idx: int, pose_a, pose_b, icp_q, icp_t):
+    """Scene_alignment::add_constrain_of_loop (scene_alignment.hpp:97-129): (s_idx, t_idx, measurement {q, t}) with
+    q_res = q_b^-1 icp_q^-1 q_a and t_res = q_b^-1 ( icp_q^-1 ( t_a - icp_t ) - t_b ).  The detector calls it with s_idx the new key
+    frame, t_idx the old one, pose_a the OLD key frame's pose and pose_b the new one's (laser_mapping.hpp:1058-1078)."""
+    a, b = np.asarray(pose_a, np.float64).reshape(7), np.asarray(pose_b, np.float64).reshape(7)
+    iq, it = np.asarray(icp_q, np.float64).reshape(4), np.asarray(icp_t, np.float64).reshape(3)
+    qbi, qii = _q_inverse(b[:4]), _q_inverse(iq)
+    q_res = _q_mul(_q_mul(qbi, qii), a[:4])
+    t_res = _q_rotate(qbi, _q_rotate(qii, a[4:7] - it) - b[4:7])
+    return int(s_idx), int(t_idx), np.concatenate([q_res, t_res])
+
+
 def keyframe_similarity(img_a, img_b, device: int = 0) -> float:
     """Maps_keyframe::max_similiarity_of_two_image (cell_map_keyframe.hpp:1155-1224) of two 60 x 60 direction images."""
     a, b = np.ascontiguousarray(img_a, np.float32), np.ascontiguousarray(img_b, np.float32)

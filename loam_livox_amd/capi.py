@@ -55,6 +55,22 @@ class SceneAlignParams(C.Structure):
                 ("maximum_residual_block", C.c_int32), ("registrar_init", C.c_int32), ("subsample_seed", C.c_int32)]
 
 
+class PoseGraphParams(C.Structure):
+    _fields_ = [("max_num_iterations", C.c_int32), ("max_num_consecutive_invalid_steps", C.c_int32),
+                ("initial_trust_region_radius", C.c_double), ("max_trust_region_radius", C.c_double),
+                ("min_trust_region_radius", C.c_double), ("min_relative_decrease", C.c_double), ("min_lm_diagonal", C.c_double),
+                ("max_lm_diagonal", C.c_double), ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
+                ("parameter_tolerance", C.c_double)]
+
+
+class PoseGraphSummary(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("successful_steps", C.c_int32), ("unsuccessful_steps", C.c_int32), ("termination", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double)]
+
+
+POSE_GRAPH_TERMINATION = ("max_iterations", "gradient", "parameter", "function", "radius", "invalid_steps", "nothing")  # LL_POSE_GRAPH_*
+
+
 # name -> (restype, argtypes); every symbol include/loam_livox_hip.h declares
 _vp, _i32, _i64, _f, _d = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 SYMBOLS = {
@@ -173,6 +189,11 @@ SYMBOLS = {
     "ll_keyframe_bank_match": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "ll_keyframe_bank_debug_surface": (_i32, [_vp, _i64, _i64, _i32, _vp]),
     "ll_keyframe_bank_work": (_i32, [_vp, _vp]),
+    "ll_pose_graph_default_params": (None, [C.POINTER(PoseGraphParams)]),
+    "ll_pose_graph_create": (_i32, [_i32, _i64, _i64, _i64, _i64, C.POINTER(_vp)]),
+    "ll_pose_graph_destroy": (None, [_vp]),
+    "ll_pose_graph_solve": (_i32, [_vp, C.POINTER(PoseGraphParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ll_pose_graph_work": (_i32, [_vp, _vp]),
     "ll_history_enable_cell_map": (_i32, [_vp, _i64, C.c_float, _i32]),
     "ll_history_set_cell_map_async": (_i32, [_vp, _i32]),
     "ll_history_sync_cell_maps": (_i32, [_vp]),
@@ -292,6 +313,12 @@ def reg_default_params() -> RegParams:
 def scene_align_default_params() -> SceneAlignParams:
     p = SceneAlignParams()
     load().ll_scene_align_default_params(C.byref(p))
+    return p
+
+
+def pose_graph_default_params() -> PoseGraphParams:
+    p = PoseGraphParams()
+    load().ll_pose_graph_default_params(C.byref(p))
     return p
 
 

@@ -11,7 +11,9 @@ Mirrors hku-mars/loam_livox source/laser_mapping.hpp:
                 then against every earlier key frame: the distance-in-time gate, the non-zero ratio gate, the ROI range gate, the image
                 similarities, the cell-count gate, and Scene_alignment::find_tranfrom_of_two_mappings; a pair whose inlier threshold
                 ends below map_alignment_inlier_threshold is reported as a loop with the alignment's transform (:1054-1068).
-The pose graph, the map refinement and every file dump behind that point (:1069-1110; ceres_pose_graph_3d.hpp) are out of scope.
+pose_graph=True adds what the node does with an accepted loop (:948-960, 1058-1089): the chain constraints over pose3d_vec plus the one
+loop constraint, optimised on the device (api.Pose_graph); close_loop keeps poses_ori, poses_opm, constraints and pose_graph_summary.
+The map refinement and every file dump behind that point (:1069-1110) are out of scope.
 
 A key frame is a SET OF CELLS of the full cell map, not a copy: the reference's key frames hold shared pointers to the map's cells, so
 what a key frame is analysed with is whatever those cells contain when it is processed (earlier and later scans included).  Here a key
@@ -87,7 +89,7 @@ class Keyframe_assembly:
                  map_alignment_resolution: float = 0.2, map_alignment_inlier_threshold: float = 0.35,
                  map_alignment_maximum_icp_iteration: int = 2, scene_alignments_maximum_residual_block: int = 5000,
                  keyframe_max_points: int = 1 << 20, full_cell_map=None, avail_ratio_plane: float = 0.05, avail_ratio_line: float = 0.03,
-                 device_alignment: bool = False, device_bank: bool = False, bank=None):
+                 device_alignment: bool = False, device_bank: bool = False, bank=None, pose_graph=False):
         # parameter names and defaults: laser_mapping.hpp:698-710 (loop_closure/*), :686-687 (mapping/pt_cell_resolution, threshold_cell_revisit)
         self.device = device
         self.m_pt_cell_resolution = cell_resolution
@@ -128,6 +130,15 @@ class Keyframe_assembly:
         self.device_bank = bool(device_bank) or bank is not None
         self._bank, self._owns_bank = bank, False
         self._front = None              # (key frame, candidates) between analyse_front and walk_front
+        # pose_graph: False (off: nothing below is touched), True (an api.Pose_graph of this assembly's own, created when the first loop
+        # is accepted) or a handle to share (anything with solve( graphs ); its owner closes it).  An accepted loop is then closed:
+        # close_loop.  defer_pose_graph: an owner of many assemblies collects the accepted loops of a round and solves them in one call
+        # (loop_graph / take_solution).
+        self.pose_graph = bool(pose_graph)
+        self._pose_graph, self._owns_pose_graph = (None, False) if pose_graph is True or not pose_graph else (pose_graph, False)
+        self.defer_pose_graph = False
+        self.pending_loops = []         # accepted loops not yet closed (defer_pose_graph)
+        self.poses_ori, self.poses_opm, self.constraints, self.pose_graph_summary = None, None, None, None
 
     def state(self) -> str:
         """the lists as tests/verbatim_build.py's harness prints them: open key frames frames:cells, waiting ones frames:cells:ending-index"""
@@ -145,6 +156,9 @@ class Keyframe_assembly:
         if self._bank is not None and self._owns_bank:
             self._bank.close()
         self._bank = None
+        if self._pose_graph is not None and self._owns_pose_graph:
+            self._pose_graph.close()
+        self._pose_graph = None
 
     # ---- laser_mapping.hpp:1524-1562 ------------------------------------------------------------------------------------------------
     def add_scan(self, full_cloud_map_frame: np.ndarray, pose: np.ndarray, current_frame_index: int) -> np.ndarray:
@@ -285,6 +299,42 @@ class Keyframe_assembly:
             return False
         return True
 
+    # ---- laser_mapping.hpp:948-960, 1058-1089 -------------------------------------------------------------------------------------
+    def pose_graph_handle(self):
+        """the optimiser of pose_graph: the one handed in, else this assembly's own, created on first use"""
+        if self._pose_graph is None:
+            from .api import Pose_graph
+            self._pose_graph, self._owns_pose_graph = Pose_graph(device=self.device), True
+        return self._pose_graph
+
+    def loop_graph(self, loop) -> dict:
+        """The graph the node optimises when it accepts `loop` (a record of self.loops): pose3d_vec as the poses; constrain_vec -- the
+        chain constraint k -> k + 1 of every two consecutive key-frame poses, built from those poses (:951-960) -- and behind them the
+        loop constraint last -> his from the alignment's inverted transform (:1058-1078, add_constrain_of_loop)."""
+        from .api import loop_constraint, relative_constraint
+        poses = np.array([_pose7(q, t) for q, t in self.pose3d_vec], np.float64).reshape(-1, 7)
+        last, his = loop["last"], loop["his"]
+        ab = [(k, k + 1) for k in range(len(poses) - 1)]
+        meas = [relative_constraint(poses[k], poses[k + 1]) for k in range(len(poses) - 1)]
+        s_idx, t_idx, m = loop_constraint(last, his, poses[his], poses[last], loop["icp_q"], loop["icp_t"])
+        ab.append((s_idx, t_idx))
+        meas.append(m)
+        return dict(poses=poses, ab=np.array(ab, np.int32).reshape(-1, 2), meas=np.array(meas, np.float64).reshape(-1, 7))
+
+    def take_solution(self, graph: dict, poses_opm: np.ndarray, summary: dict) -> None:
+        """keeps what close_loop keeps, from a solve its caller made (one call for the loops of many assemblies)"""
+        self.poses_ori, self.poses_opm = graph["poses"].copy(), np.asarray(poses_opm, np.float64).reshape(-1, 7).copy()   # pose3d_map_ori, temp_pose_3d_map
+        self.constraints = dict(ab=graph["ab"].copy(), meas=graph["meas"].copy())                                           # constrain_vec_temp
+        self.pose_graph_summary = dict(summary)
+
+    def close_loop(self, loop) -> np.ndarray:
+        """Pose-graph optimisation of an accepted loop: builds loop_graph( loop ), solves it on the device and keeps poses_ori,
+        poses_opm, constraints and pose_graph_summary.  loops, log, if_end and state() are not touched.  Returns poses_opm."""
+        graph = self.loop_graph(loop)
+        poses, summaries = self.pose_graph_handle().solve([graph])
+        self.take_solution(graph, poses[0], summaries[0])
+        return self.poses_opm
+
     def walk_front(self, sims=None):
         """The walk half of one pass (laser_mapping.hpp:988-1057) for the key frame analyse_front added.  sims: (sim_line, sim_plane)
         of analyse_front's candidates, in their order (one Keyframe_bank.match); None: every pair that reaches the comparison asks
@@ -340,12 +390,22 @@ class Keyframe_assembly:
                     loop = dict(his=his, last=n_kf - 1, inlier_threshold=thr, icp_q=qi, icp_t=ti, sim_plane=sim_plane, sim_line=sim_line)
                     self.loops.append(loop)
                     found.append(loop)
-                    self.if_end = True   # :1108 (the pose graph optimisation and the map refinement in between are out of scope)
+                    if self.pose_graph:      # :1058-1089
+                        if self.defer_pose_graph:
+                            self.pending_loops.append(loop)
+                        else:
+                            self.close_loop(loop)
+                    self.if_end = True   # :1108 (the map refinement and the dumps in between are out of scope)
                     break
                 his += 5 + 1   # :1111-1114
                 continue
             his += 1
         return found
+
+
+
+def _pose7(q, t) -> np.ndarray:
+    return np.concatenate([np.asarray(q, np.float64).reshape(4), np.asarray(t, np.float64).reshape(3)])
 
 
 def _pack_cells(cell_ijk) -> np.ndarray:

@@ -7,7 +7,8 @@ This is the unit of BASELINE config C4 (one sequence per GPU, local map growth).
     and registers against whichever buffer is newest (laser_mapping.hpp:568-594, 1395-1403), which makes its output
     depend on thread timing;
   * no ROS or logging; the full-cloud cell map, the key frames and the front half of loop detection are optional
-    (loop_closure_if_enable, keyframes.py); the pose graph and the map refinement behind them are out of scope.
+    (loop_closure_if_enable, keyframes.py), with loop_closure["pose_graph"] the pose-graph optimisation of an accepted loop; the map
+    refinement and the file dumps behind it are out of scope.
 """
 from __future__ import annotations
 
@@ -321,7 +322,9 @@ class Laser_mapping_batch:
     poses and reports do not change by a bit.  loop_closure_if_enable itself stays refused: it names Laser_mapping's per-sequence
     map.  loop_closure["device_bank"]=True (off by default): the loop owns ONE api.Keyframe_bank (keyframe_bank) for its S assemblies;
     a round of key-frame processing is then the analysis half of every slot, one Keyframe_bank.match over all slots' pairs, and the
-    walk half of every slot -- the same logs and loops, float for float."""
+    walk half of every slot -- the same logs and loops, float for float.  loop_closure["pose_graph"]=True (off by default): the loop
+    owns ONE api.Pose_graph (pose_graph) for its S assemblies; the loops the slots accept in a round are closed -- their pose graphs
+    optimised -- in one Pose_graph.solve, and every assembly keeps its poses_ori, poses_opm, constraints and pose_graph_summary."""
 
     def __init__(self, n_sequences: int, refresh_threads: int | None = None, batched_history: bool = False, cell_maps: bool = False,
                  cell_matching: bool = False, full_maps: bool = False, key_frames: bool = False, **kw):
@@ -364,7 +367,7 @@ class Laser_mapping_batch:
         self.maps = [Map_buffer(device=device) for _ in range(S)]
         self.batched_history, self.cell_maps, self.cell_matching = bool(batched_history), bool(cell_maps), bool(cell_matching)
         self.full_maps, self.key_frames = bool(full_maps), bool(key_frames)
-        self.keyframes, self.loops, self.keyframe_bank = None, None, None
+        self.keyframes, self.loops, self.keyframe_bank, self.pose_graph = None, None, None, None
         self.full_map_s = 0.0  # cumulative wall time of the full-map phase (append_full, and the key-frame steps with key_frames)
         self.m_maximum_search_range = (a["maximum_search_range_corner"], a["maximum_search_range_surface"])
         self.m_maximum_in_fov_angle, self.m_down_sample_replace = a["maximum_in_fov_angle"], a["down_sample_replace"]
@@ -385,9 +388,16 @@ class Laser_mapping_batch:
                     if lc.pop("device_bank", False):
                         from .api import Keyframe_bank
                         self.keyframe_bank = lc["bank"] = Keyframe_bank(device=device)
+                    # loop_closure["pose_graph"]: ONE optimiser for the S assemblies; the loops accepted in a round of
+                    # _process_keyframes are closed in one solve
+                    if lc.pop("pose_graph", False):
+                        from .api import Pose_graph
+                        self.pose_graph = lc["pose_graph"] = Pose_graph(device=device)
                     self.keyframes = [Keyframe_assembly(device=device, cell_resolution=a["cell_resolution"],
                                                         threshold_cell_revisit=a["threshold_cell_revisit"],
                                                         full_cell_map=self.history_batch.full_map(s), **lc) for s in range(S)]
+                    for ka in self.keyframes:
+                        ka.defer_pose_graph = self.pose_graph is not None
                     self.loops = [[] for _ in range(S)]
         else:
             self.history_batch = None
@@ -424,6 +434,9 @@ class Laser_mapping_batch:
         if self.keyframe_bank is not None:
             self.keyframe_bank.close()
             self.keyframe_bank = None
+        if self.pose_graph is not None:
+            self.pose_graph.close()
+            self.pose_graph = None
         for h in [self.fe, self.reg, self.vox[0], self.vox[1]] + self.maps + ([self.history_batch] if self.batched_history else self.histories):
             h.close()
 
@@ -487,7 +500,20 @@ class Laser_mapping_batch:
                 for s in (slots if first else [s for s, _ in todo]):
                     ka = self.keyframes[s]
                     self.loops[s] += ka.process_waiting(limit=1) if waiting(ka) > 1 else ka.process_waiting()
+            if getattr(self, "pose_graph", None) is not None:
+                self._close_loops(slots)
             first = False
+
+    def _close_loops(self, slots) -> None:
+        """the loops the slots accepted in this round (loop_closure pose_graph): their graphs optimised in ONE solve"""
+        todo = [(self.keyframes[s], loop) for s in slots for loop in getattr(self.keyframes[s], "pending_loops", ())]
+        if not todo:
+            return
+        graphs = [ka.loop_graph(loop) for ka, loop in todo]
+        poses, summaries = self.pose_graph.solve(graphs)
+        for (ka, _), graph, x, summary in zip(todo, graphs, poses, summaries):
+            ka.take_solution(graph, x, summary)
+            ka.pending_loops.clear()
 
     def _bank_round(self, slots) -> None:
         """one waiting key frame of every slot named (each has one): analysed and gated per slot, compared in one match, walked per slot"""

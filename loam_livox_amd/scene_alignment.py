@@ -1,7 +1,8 @@
 """Host-side mirror of Scene_alignment::find_tranfrom_of_two_mappings (hku-mars/loam_livox source/scene_alignment.hpp:
 269-391) on top of the C ABI: the line / plane cells of two key frames (device cell maps) are registered against each
-other by the same registrar the mapping node uses, coarse to fine.  Loop-closure front half only: the pose graph
-(ceres_pose_graph_3d.hpp) and the map refinement that consume the result are out of scope.
+other by the same registrar the mapping node uses, coarse to fine.  The pose graph that consumes the result
+(ceres_pose_graph_3d.hpp) is api.Pose_graph, and add_constrain_of_loop (:97-129) is api.loop_constraint; only the map
+refinement and the file dumps are out of scope.
 
 Differences from the reference, by design:
   * extract_specify_points walks a std::set of cell pointers (address order); cells come in cell-index order here;

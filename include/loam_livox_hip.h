@@ -272,6 +272,15 @@ int ll_reg_collect(ll_reg *r, int32_t n_scans, double *poses_curr, double *poses
  * {f0, g0, x1, f1, g1, x2, f2, g2, lo, hi}: the two must agree to the bit. */
 int ll_debug_quintic(int32_t device, const double *args10, int32_t n, double *out_sequential, double *out_wavefront);
 
+/* Test tap: the Levenberg-Marquardt controller of the solver kernels on lane 0 (ll_reg_core.h lm_init / lm_update, the specification) and
+ * spread over its wavefront (ll_lm_wave.h, what the kernels run), on n scripted sequences of at most max_calls evaluations.  hdr12 holds
+ * per sequence {x0[7], bound, max_iter, n_active, calls, 0}, evals28 the 28 sums of evaluation k of sequence i at [(i * max_calls + k) * 28];
+ * call 0 is lm_init, the others lm_update, and a sequence ends with the first call that answers 0.  After call k the controller's state
+ * (*ctl_bytes bytes each) is written to out_*[(i * max_calls + k) * *ctl_bytes] and the answer to ret_*[i * max_calls + k] (-1: not
+ * called); the two forms must agree to the byte.  n = 0 returns *ctl_bytes alone. */
+int ll_debug_lm_sequence(int32_t device, const double *hdr12, const double *evals28, int32_t n, int32_t max_calls, void *out_lane0,
+                         void *out_wavefront, int32_t *ret_lane0, int32_t *ret_wavefront, int32_t *ctl_bytes);
+
 /* Debug/parity taps of the first ICP iteration of scan slot `scan` after a solve: 5-NN indices/sq-distances
  * per corner / surface query (row = query, -1/inf when not found within the match radius). NULL to skip. */
 int ll_reg_debug_knn(ll_reg *r, int32_t scan, int32_t *corner_idx5, float *corner_d25, int32_t *surf_idx5,

@@ -200,6 +200,7 @@ SYMBOLS = {
     "ll_history_cell_map": (_vp, [_vp, _i32]),
     "ll_history_refresh_cells": (_i32, [_vp, _vp, _vp, C.c_float, C.c_float, C.c_float, _i32, _vp, _vp]),
     "ll_debug_quintic": (_i32, [_i32, _vp, _i32, _vp, _vp]),
+    "ll_debug_lm_sequence": (_i32, [_i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ll_spin_default_params": (None, [C.POINTER(SpinParams)]),
     "ll_spin_create": (_i32, [C.POINTER(SpinParams), C.POINTER(_vp)]),
     "ll_spin_destroy": (None, [_vp]),

@@ -501,6 +501,47 @@ extern "C" int ll_debug_quintic(int32_t device, const double *args10, int32_t n,
     return rc ? set_err("ll_debug_quintic", "device error") : 0;
 }
 
+extern "C" int ll_debug_lm_sequence(int32_t device, const double *hdr12, const double *evals28, int32_t n, int32_t max_calls, void *out_lane0,
+                                    void *out_wavefront, int32_t *ret_lane0, int32_t *ret_wavefront, int32_t *ctl_bytes)
+{
+    if (!ctl_bytes || n < 0 || max_calls < 0) return set_err("ll_debug_lm_sequence", "bad argument");
+    *ctl_bytes = debug_lm_ctl_bytes();
+    if (n == 0 || max_calls == 0) return 0;  // (the size alone)
+    if (!hdr12 || !evals28 || !out_lane0 || !out_wavefront || !ret_lane0 || !ret_wavefront) return set_err("ll_debug_lm_sequence", "bad argument");
+    if (check_device(device)) return -1;
+    const size_t slots = (size_t)n * (size_t)max_calls, img = slots * (size_t)*ctl_bytes;
+    double *d_h = nullptr, *d_e = nullptr;
+    unsigned int *d_s = nullptr, *d_w = nullptr;
+    int *d_rs = nullptr, *d_rw = nullptr;
+    HC(hipMalloc((void **)&d_h, (size_t)n * 12 * sizeof(double)));
+    HC(hipMalloc((void **)&d_e, slots * 28 * sizeof(double)));
+    HC(hipMalloc((void **)&d_s, img));
+    HC(hipMalloc((void **)&d_w, img));
+    HC(hipMalloc((void **)&d_rs, slots * sizeof(int)));
+    HC(hipMalloc((void **)&d_rw, slots * sizeof(int)));
+    int rc = 0;
+    if (hipMemcpy(d_h, hdr12, (size_t)n * 12 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_e, evals28, slots * 28 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_s, 0, img) != hipSuccess ||
+        hipMemset(d_w, 0, img) != hipSuccess || hipMemset(d_rs, 0xff, slots * sizeof(int)) != hipSuccess ||
+        hipMemset(d_rw, 0xff, slots * sizeof(int)) != hipSuccess)
+        rc = -1;
+    if (!rc) {
+        launch_debug_lm_sequence(d_h, d_e, n, max_calls, d_s, d_w, d_rs, d_rw, nullptr);
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out_lane0, d_s, img, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out_wavefront, d_w, img, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(ret_lane0, d_rs, slots * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(ret_wavefront, d_rw, slots * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = -1;
+    }
+    (void)hipFree(d_h);
+    (void)hipFree(d_e);
+    (void)hipFree(d_s);
+    (void)hipFree(d_w);
+    (void)hipFree(d_rs);
+    (void)hipFree(d_rw);
+    return rc ? set_err("ll_debug_lm_sequence", "device error") : 0;
+}
+
 extern "C" int ll_reg_debug_cycles(ll_reg *r, int32_t scan, long long out[16])
 {
     if (!r || scan < 0 || scan >= r->max_scans) return set_err("ll_reg_debug_cycles", "bad argument");

@@ -203,6 +203,9 @@ void launch_reg_knn_build(const RegDev &rd, const RegConst &rc, const Grid &gc, 
 #define LL_QSORT_CORNER_MAX 2048
 void launch_reg_qsort(const RegDev &rd, const RegConst &rc, const Grid &gc, const Grid &gs, int n_scans, int max_nc, int max_ns, bool fused, hipStream_t s);
 void launch_debug_quintic(const double *args, int n, double *out_seq, double *out_wave, hipStream_t s);
+void launch_debug_lm_sequence(const double *hdr, const double *evals, int n, int max_calls, unsigned int *img_seq, unsigned int *img_wave, int *ret_seq,
+                              int *ret_wave, hipStream_t s);
+int debug_lm_ctl_bytes();  // sizeof(LmCtl)
 void launch_reg_knn_tile(const RegDev &rd, const RegConst &rc, const Grid &gc, const Grid &gs, int n_scans, int iter, int max_nc, int max_ns,
                          bool fused, hipStream_t s);
 void launch_reg_solve(const RegDev &rd, const RegConst &rc, const Grid &gs, int n_scans, int max_nc, int max_ns, int iter, hipStream_t s);

@@ -5,6 +5,7 @@
 //   reg_merge_heads_kernel : Mid-100, the feature clouds of a sweep's heads concatenated on the device
 //   history_concat_kernel  : the match buffer's frames into one cloud
 //   debug_quintic_kernel   : test tap of the line-search fit (ll_debug_quintic)
+//   debug_lm_sequence_kernel : test tap of the LM controller, lane-0 form against wavefront form (ll_debug_lm_sequence)
 // A translation unit of its own: nothing here shares device code with the query kernels or the solvers.
 #include <hip/hip_runtime.h>
 
@@ -126,5 +127,62 @@ void launch_debug_quintic(const double *args, int n, double *out_seq, double *ou
 {
     if (n > 0) hipLaunchKernelGGL(debug_quintic_kernel, dim3(n), dim3(64), 0, s, args, n, out_seq, out_wave);
 }
+
+// test tap (ll_debug_lm_sequence): the controller on lane 0 (lm_begin, lm_init, lm_update_lane0) and on the wavefront (ll_lm_wave.h) over
+// the same scripted evaluations, one wavefront per sequence.  hdr = {x0[7], bound, max_iter, n_active, calls, -} per sequence; after call k
+// the two LmCtl go to img_*[(i * max_calls + k) * sizeof(LmCtl)] and the return values to ret_*[i * max_calls + k].  A sequence ends
+// with the first call either form answers with 0.
+__global__ __launch_bounds__(64) void debug_lm_sequence_kernel(const double *hdr, const double *evals, int n, int max_calls, unsigned int *img_seq,
+                                                               unsigned int *img_wave, int *ret_seq, int *ret_wave)
+{
+    constexpr int WORDS = (int)(sizeof(LmCtl) / sizeof(unsigned int));
+    static_assert(sizeof(LmCtl) % sizeof(unsigned int) == 0, "LmCtl is copied in 32-bit words");
+    __shared__ LmCtl cs, cw;
+    __shared__ double sum[LL_NACC], fit_s[10], fit_w[10];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const double *h = hdr + 12 * (size_t)i;
+    for (int w = lane; w < WORDS; w += 64) ((unsigned int *)&cs)[w] = 0u, ((unsigned int *)&cw)[w] = 0u;
+    __syncthreads();
+    const int max_iter = (int)h[8], n_active = (int)h[9];
+    int calls = (int)h[10];
+    calls = calls < max_calls ? calls : max_calls;
+    if (lane == 0) {
+        double x0[7];
+        for (int k = 0; k < 7; k++) x0[k] = h[k];
+        lm_begin(cs, x0, max_iter, h[7]);
+        lm_begin(cw, x0, max_iter, h[7]);
+    }
+    for (int k = 0; k < calls; k++) {
+        const size_t slot = (size_t)i * max_calls + k;
+        __syncthreads();
+        if (lane < LL_NACC) sum[lane] = evals[slot * LL_NACC + lane];
+        __syncthreads();
+        int rs, rw;
+        if (k == 0) {
+            rs = lane == 0 ? lm_init(cs, sum, n_active) : 0;
+            rw = lmw_init(cw, sum, n_active, lane);
+        } else {
+            rs = lm_update_lane0(cs, sum, fit_s, lane);
+            rw = lmw_update(cw, sum, fit_w, lane);
+        }
+        rs = __shfl(rs, 0);
+        rw = __shfl(rw, 0);
+        __syncthreads();
+        for (int w = lane; w < WORDS; w += 64) {
+            img_seq[slot * WORDS + w] = ((const unsigned int *)&cs)[w];
+            img_wave[slot * WORDS + w] = ((const unsigned int *)&cw)[w];
+        }
+        if (lane == 0) ret_seq[slot] = rs, ret_wave[slot] = rw;
+        if (!rs || !rw) break;
+    }
+}
+void launch_debug_lm_sequence(const double *hdr, const double *evals, int n, int max_calls, unsigned int *img_seq, unsigned int *img_wave, int *ret_seq,
+                              int *ret_wave, hipStream_t s)
+{
+    if (n > 0 && max_calls > 0)
+        hipLaunchKernelGGL(debug_lm_sequence_kernel, dim3(n), dim3(64), 0, s, hdr, evals, n, max_calls, img_seq, img_wave, ret_seq, ret_wave);
+}
+int debug_lm_ctl_bytes() { return (int)sizeof(LmCtl); }
 
 }  // namespace ll

@@ -514,7 +514,10 @@ __device__ __forceinline__ void big_lm(const RegDev &rd, const RegConst &rc, int
     }
     {
         LL_T0(t1);
-        if (tid == 0) sh.need = lm_init(sh.ctl, sh.sum, n_active);
+        if (tid < 64) {  // the controller's wavefront
+            const int need = lm_init_wave(sh.ctl, sh.sum, n_active, tid);
+            if (tid == 0) sh.need = need;
+        }
         __syncthreads();
         LL_TACC(1, t1);
     }
@@ -527,8 +530,8 @@ __device__ __forceinline__ void big_lm(const RegDev &rd, const RegConst &rc, int
             big_eval<false, DEBLUR>(rd, rc, b, nC, nS, sh.ctl.cand, act, s_raw, q_last, sh);
         LL_TACC(0, t0);
         LL_T0(t1);
-        if (tid < 64) {  // the controller's wavefront: lane 0 steps the controller, all of it fits a line search's interpolant
-            const int need = lm_update_wave(sh.ctl, sh.sum, sh.fit, tid);
+        if (tid < 64) {  // the controller's wavefront steps the controller (ll_lm_wave.h); lane 0 has the answer
+            const int need = lm_update_wave(sh.ctl, sh.sum, sh.fit, tid, sh.tcyc + 14);
             if (tid == 0) {
                 sh.need = need;
                 sh.l1_valid = (spec && !need && sh.ctl.last_accept == 1) ? 1 : 0;
@@ -966,7 +969,7 @@ __device__ void solve_big(const RegDev &rd, const RegConst &rc, const f4 *map_pt
     }
     lm_iters += sh.ctl.iteration;
     solve_epilogue(rc, st, sh, lm_iters);
-#ifdef LL_SOLVE_TIMING
+#if defined(LL_SOLVE_TIMING) || defined(LL_LM_COUNTS)
     LL_TACC(5, t_total);
     if (tid == 0)
         for (int i = 0; i < 16; i++) st->dbg_cycles[i] += sh.tcyc[i];

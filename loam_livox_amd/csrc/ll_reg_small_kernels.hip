@@ -226,7 +226,10 @@ __device__ __forceinline__ void small_lm(const SmallBlocks &B, const RegConst &r
     }
     {
         SM_T0(t1);
-        if (tid == 0) sh.need = lm_init(sh.ctl, sh.sum, sh.n_active);
+        if (tid < 64) {  // the controller's wavefront
+            const int need = lm_init_wave(sh.ctl, sh.sum, sh.n_active, tid);
+            if (tid == 0) sh.need = need;
+        }
         __syncthreads();
         SM_TACC(1, t1);
     }
@@ -235,8 +238,8 @@ __device__ __forceinline__ void small_lm(const SmallBlocks &B, const RegConst &r
         small_eval<W>(B, sh.ctl.cand, rc.huber_a, act, sh.nL, sh.nA, sh);
         SM_TACC(0, t0);
         SM_T0(t1);
-        if (tid < 64) {  // the controller's wavefront: lane 0 steps the controller, all of it fits a line search's interpolant
-            const int need = lm_update_wave(sh.ctl, sh.sum, sh.fit, tid);
+        if (tid < 64) {  // the controller's wavefront steps the controller (ll_lm_wave.h); lane 0 has the answer
+            const int need = lm_update_wave(sh.ctl, sh.sum, sh.fit, tid, sh.tcyc + 14);
             if (tid == 0) {
                 sh.need = need;
                 sh.n_eval++;

@@ -42,7 +42,7 @@ void LL_SMALL_KERNEL(SmallArgs rd, RegConst rc LL_SMALL_MORE_ARGS)
     }
     const size_t sb = (size_t)b * rd.cap_all;
     const unsigned char *flag0 = rd.blk_flag0 + sb;
-#ifdef LL_SOLVE_TIMING
+#if defined(LL_SOLVE_TIMING) || defined(LL_LM_COUNTS)
     if (tid < 16) sh.tcyc[tid] = 0;
     __syncthreads();
 #endif
@@ -372,7 +372,7 @@ void LL_SMALL_KERNEL(SmallArgs rd, RegConst rc LL_SMALL_MORE_ARGS)
     lm_iters += sh.ctl.iteration;
     solve_epilogue(rc, st, sh, lm_iters);
     if (tid == 0) st->last_work = sh.n_eval;  // next launch: the scans that worked longest start first
-#ifdef LL_SOLVE_TIMING
+#if defined(LL_SOLVE_TIMING) || defined(LL_LM_COUNTS)
     SM_TACC(5, t_total);
     if (tid == 0)
         for (int i = 0; i < 16; i++) st->dbg_cycles[i] += sh.tcyc[i];

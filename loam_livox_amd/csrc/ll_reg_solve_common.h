@@ -1,6 +1,6 @@
 // ll_reg_solve_common.h -- device helpers shared by the solver kernels (ll_reg_solve_kernels.hip and ll_reg_maps_kernels.hip: one 512-thread workgroup per scan, and
 // ll_reg_small_kernels.hip: one wavefront / four wavefronts per small scan): the wavefront reduction of the 28 accumulators of a cost
-// evaluation, the Levenberg-Marquardt controller step with the line-search fit on the controller's whole wavefront, and the epilogue of
+// evaluation, the Levenberg-Marquardt controller step on the controller's whole wavefront (ll_lm_wave.h), and the epilogue of
 // one ICP iteration (pose composition, convergence test: point_cloud_registration.hpp:509-531).  Device only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -196,8 +196,9 @@ __device__ __forceinline__ double lm_quintic_min_step_wave_call(const double *a,
     return lm_quintic_min_step_wave(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], lane);
 }
 
-// lm_update with the three-sample fit on the wavefront: called by every lane of the controller's wavefront (lane 0 holds the controller)
-__device__ __forceinline__ int lm_update_wave(LmCtl &c, const double *sum, double *fit, int lane)
+// lm_update with the three-sample fit on the wavefront and everything else on lane 0: the controller as it ran before ll_lm_wave.h, kept
+// for the A/B build (-DLL_LM_LANE0) and the test tap.  Called by every lane of the controller's wavefront.
+__device__ __forceinline__ int lm_update_lane0(LmCtl &c, const double *sum, double *fit, int lane, int *fits = nullptr)
 {
     int code = 0;
     double e[LL_NACC];  // lane 0's register copy of the evaluation
@@ -217,10 +218,54 @@ __device__ __forceinline__ int lm_update_wave(LmCtl &c, const double *sum, doubl
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const double step = lm_quintic_min_step_wave_call(fit, lane);
         if (lane == 0) code = lm_update_post(c, fit[3], fit[4], step);
+        if (fits) *fits += 1;
     }
     int r = 0;
     if (lane == 0) r = lm_update_close(c, e, code);
     return r;  // (lane 0's is the answer)
+}
+
+}  // namespace ll
+
+#include "ll_lm_wave.h"
+
+namespace ll {
+
+// The controller step of the solver kernels, called by every lane of the controller's wavefront; lane 0's return value is the answer.
+// The rows of the 6 x 6 system, the copies of the evaluation and the two state_plus of an accepted step are spread over the lanes
+// (ll_lm_wave.h); -DLL_LM_LANE0 builds the kernels with the controller on lane 0 instead (same LmCtl after every call, byte for byte).
+__device__ __forceinline__ int lm_init_wave(LmCtl &c, const double *sum, int n_active, int lane)
+{
+#if defined(LL_LM_LANE0)
+    return lane == 0 ? lm_init(c, sum, n_active) : 0;
+#else
+    return lmw_init(c, sum, n_active, lane);
+#endif
+}
+// -DLL_LM_COUNTS (with -DLL_LM_LANE0: the test build of tests/test_gpu_lm_wave.py) counts on lane 0, in counts[0] the three-sample fits and
+// in counts[1] the solves that end on a rejected step (the kernels hand in two unused slots of their cycle counters, which such a build
+// adds to RegState::dbg_cycles[14] and [15]: ll_reg_debug_cycles).  No other build touches counts.
+__device__ __forceinline__ int lm_update_wave(LmCtl &c, const double *sum, double *fit, int lane, long long *counts)
+{
+#if defined(LL_LM_COUNTS)
+#if !defined(LL_LM_LANE0) || defined(LL_SOLVE_TIMING)
+#error "LL_LM_COUNTS goes with LL_LM_LANE0 and without LL_SOLVE_TIMING"
+#endif
+    int fits = 0;
+    const double radius = c.radius;
+    const int need = lm_update_lane0(c, sum, fit, lane, &fits);
+    if (lane == 0) {
+        counts[0] += fits;
+        if (!need && c.last_accept == 0 && c.radius != radius) counts[1] += 1;  // (a rejected step changes the radius, a tolerance that ends the solve does not)
+    }
+    return need;
+#elif defined(LL_LM_LANE0)
+    (void)counts;
+    return lm_update_lane0(c, sum, fit, lane);
+#else
+    (void)counts;
+    return lmw_update(c, sum, fit, lane);
+#endif
 }
 
 }  // namespace ll

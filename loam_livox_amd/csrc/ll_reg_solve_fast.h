@@ -6,7 +6,7 @@
 // runs what the reference does between point_cloud_registration.hpp:460 and :531: the 2-iteration prerun solve, the loss-corrected
 // L1 evaluation, the std::set-deduplicated 80-th percentile inlier threshold (:153-161), the prune, the final solve and the pose
 // composition -- replacing ceres::Solve / Problem::Evaluate by a 28-value (21 H + 6 g + 1 cost) workgroup reduction and a
-// Levenberg-Marquardt controller on lane 0.  No host round trip per iteration.  solve_fast3 holds every scan within
+// Levenberg-Marquardt controller on the first wavefront.  No host round trip per iteration.  solve_fast3 holds every scan within
 // FAST_MAX_BLOCKS without motion deblur: plane table in LDS, 18 B streamed per plane block, 64-bit activity masks and register
 // tiles.  In order: evaluation-context and timing macros, SolveShared, the group barrier and reduction, block sums, capacities,
 // inlier_threshold_regs, BlkRegs / load_blk, census_and_plane_table, plane_table_reload, solver_eval3, solver_lm3, inlier_phase3,
@@ -1233,7 +1233,10 @@ __device__ __forceinline__ void solver_lm3(const RegDev &rd, const RegConst &rc,
     }
     {
         LL_T0(t1);
-        if (tid == 0) sh.need = lm_init(sh.ctl, sh.sum, n_active);
+        if (tid < 64) {  // the controller's wavefront
+            const int need = lm_init_wave(sh.ctl, sh.sum, n_active, tid);
+            if (tid == 0) sh.need = need;
+        }
         __syncthreads();
         LL_TACC(1, t1);
     }
@@ -1246,8 +1249,8 @@ __device__ __forceinline__ void solver_lm3(const RegDev &rd, const RegConst &rc,
             solver_eval3<false, false, GROUPED>(rd, b, nC, nS, sh.ctl.cand, rc.huber_a, act, s_raw, q_last, sh);
         LL_TACC(0, t0);
         LL_T0(t1);
-        if (tid < 64) {  // the controller's wavefront: lane 0 steps the controller, all of it fits a line search's interpolant
-            const int need = lm_update_wave(sh.ctl, sh.sum, sh.fit, tid);
+        if (tid < 64) {  // the controller's wavefront steps the controller (ll_lm_wave.h); lane 0 has the answer
+            const int need = lm_update_wave(sh.ctl, sh.sum, sh.fit, tid, sh.tcyc + 14);
             if (tid == 0) {
                 sh.need = need;
                 sh.l1_valid = (spec && !need && sh.ctl.last_accept == 1) ? 1 : 0;
@@ -1354,8 +1357,9 @@ __device__ __noinline__ unsigned long long inlier_phase3(const RegDev &rd, const
     return act;
 }
 
+// (inlined into its kernel by force: left to the inliner's size estimate, the one-workgroup form became a call when the controller grew)
 template <bool GROUPED>
-__device__ void solve_fast3(const RegDev &rd, const RegConst &rc, const f4 *map_pts, int b, RegState *st, SolveShared &sh, uint4 *s_raw)
+__device__ __forceinline__ void solve_fast3(const RegDev &rd, const RegConst &rc, const f4 *map_pts, int b, RegState *st, SolveShared &sh, uint4 *s_raw)
 {
     constexpr int DEBLUR = 0;
     const int tid = threadIdx.x;
@@ -1401,7 +1405,7 @@ __device__ void solve_fast3(const RegDev &rd, const RegConst &rc, const f4 *map_
         }
     }
     solve_epilogue(rc, st, sh, lm_iters);
-#ifdef LL_SOLVE_TIMING
+#if defined(LL_SOLVE_TIMING) || defined(LL_LM_COUNTS)
     LL_TACC(5, t_total);
     if (tid == 0)
         for (int i = 0; i < 16; i++) st->dbg_cycles[i] += sh.tcyc[i];

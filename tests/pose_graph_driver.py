@@ -4,6 +4,8 @@ import subprocess
 
 import numpy as np
 
+from tests import pose_graph_ref as ref
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -27,11 +29,46 @@ def pack(graphs):
     return po, np.ascontiguousarray(poses), eo, np.ascontiguousarray(ab), np.ascontiguousarray(meas), info
 
 
-def run_driver(exe, tmp, graphs, mode=0, expect_refusal=False):
+PARAM_INTS = ("max_num_iterations", "max_num_consecutive_invalid_steps")
+PARAM_DOUBLES = ("initial_trust_region_radius", "max_trust_region_radius", "min_trust_region_radius", "min_relative_decrease", "min_lm_diagonal",
+                 "max_lm_diagonal", "function_tolerance", "gradient_tolerance", "parameter_tolerance")
+
+
+def all_options(options):
+    """pose_graph_ref.OPTIONS with `options` over them: the numbers the reference, the driver and the device are all given"""
+    unknown = set(options or {}) - set(ref.OPTIONS)
+    assert not unknown, unknown
+    return dict(ref.OPTIONS, **(options or {}))
+
+
+def params_block(options):
+    """the driver's params block: the two ints as int64, the nine doubles, in ll_pose_graph_params' order"""
+    o = all_options(options)
+    return np.array([o[k] for k in PARAM_INTS], np.int64).tobytes() + np.array([o[k] for k in PARAM_DOUBLES], np.float64).tobytes()
+
+
+def params_struct(options):
+    """the same dict as a capi.PoseGraphParams (what api.Pose_graph( params=... ) takes)"""
+    from loam_livox_amd import capi
+    o = all_options(options)
+    assert [k for k, _ in capi.PoseGraphParams._fields_] == list(PARAM_INTS + PARAM_DOUBLES)
+    p = capi.PoseGraphParams()
+    for k in PARAM_INTS:
+        setattr(p, k, int(o[k]))
+    for k in PARAM_DOUBLES:
+        setattr(p, k, float(o[k]))
+    return p
+
+
+def run_driver(exe, tmp, graphs, mode=0, expect_refusal=False, options=None):
+    """mode 0: (poses per graph, summaries); mode 1: the first linearisation of one graph; mode 2: envelope blocks per graph and of
+    the call, as the plan counts them.  options: a dict keyed like pose_graph_ref.OPTIONS, or None for the driver's defaults."""
     po, poses, eo, ab, meas, info = pack(graphs)
     pin, pout = os.path.join(tmp, "pg_in.bin"), os.path.join(tmp, "pg_out.bin")
     with open(pin, "wb") as f:
-        f.write(np.array([mode, len(graphs), len(poses), len(ab), 0 if info is None else 1], np.int64).tobytes())
+        f.write(np.array([mode, len(graphs), len(poses), len(ab), 0 if info is None else 1, 0 if options is None else 1], np.int64).tobytes())
+        if options is not None:
+            f.write(params_block(options))
         f.write(po.tobytes() + eo.tobytes() + poses.tobytes() + ab.tobytes() + meas.tobytes())
         if info is not None:
             f.write(np.ascontiguousarray(info).tobytes())
@@ -48,6 +85,8 @@ def run_driver(exe, tmp, graphs, mode=0, expect_refusal=False):
         summaries = [dict(iterations=int(r[0]), successful_steps=int(r[1]), unsuccessful_steps=int(r[2]), termination=int(r[3]),
                           initial_cost=r[4], final_cost=r[5]) for r in rec]
         return [out[po[g]:po[g + 1]] for g in range(G)], summaries
+    if mode == 2:
+        return [int(b) for b in raw[:len(graphs)]], int(raw[len(graphs)])
     E = len(ab)
     J = raw[:72 * E].reshape(E, 2, 6, 6)
     n = int(raw[72 * E])

@@ -2,11 +2,15 @@
 // ll_pose_graph.h with a host compiler, one work item per graph (tests/test_pose_graph_host.py).
 //
 //   pose_graph_host <in> <out>
-// in:  int64 {mode, G, P, E, has_information}, int64 pose_offsets[G + 1], int64 edge_offsets[G + 1], double poses[7 P],
-//      int32 edge_ab[2 E], double meas[7 E], double information[36 E] when has_information.
+// in:  int64 {mode, G, P, E, has_information, has_params}; when has_params int64 {max_num_iterations,
+//      max_num_consecutive_invalid_steps} and double {initial, max, min trust-region radius, min_relative_decrease, min, max
+//      lm_diagonal, function, gradient, parameter tolerance} -- ll_pose_graph_params in its order, the defaults otherwise;
+//      int64 pose_offsets[G + 1], int64 edge_offsets[G + 1], double poses[7 P], int32 edge_ab[2 E], double meas[7 E],
+//      double information[36 E] when has_information.
 // out, mode 0 (solve): double poses[7 P], then per graph double {iterations, successful, unsuccessful, termination, initial cost, final cost}.
 // out, mode 1 (one graph, the first linearisation): double J[72 E] unscaled, double n, A[n n] damped normal matrix expanded from its
 //      envelope, rhs[n], y[n] of the envelope solve, double ok.
+// out, mode 2 (the plan alone): per graph double envelope blocks, then double envelope blocks of the call.
 // A call the plan refuses: its text on stdout, exit status 3.
 #include <stdio.h>
 #include <stdlib.h>
@@ -33,8 +37,11 @@ int main(int argc, char **argv)
     std::vector<int64_t> head, pose_off, edge_off;
     std::vector<double> poses, meas, info;
     std::vector<int32_t> ab;
-    if (!read_n(f, head, 5)) return 2;
+    if (!read_n(f, head, 6)) return 2;
     const int64_t mode = head[0], G = head[1], P = head[2], E = head[3];
+    std::vector<int64_t> prm_i;
+    std::vector<double> prm_d;
+    if (head[5] && (!read_n(f, prm_i, 2) || !read_n(f, prm_d, 9))) return 2;
     if (!read_n(f, pose_off, G + 1) || !read_n(f, edge_off, G + 1) || !read_n(f, poses, 7 * P) || !read_n(f, ab, 2 * E) || !read_n(f, meas, 7 * E)) return 2;
     if (head[4] && !read_n(f, info, 36 * E)) return 2;
     fclose(f);
@@ -59,6 +66,12 @@ int main(int argc, char **argv)
     v.prm.initial_trust_region_radius = 1e4, v.prm.max_trust_region_radius = 1e16, v.prm.min_trust_region_radius = 1e-32;
     v.prm.min_relative_decrease = 1e-3, v.prm.min_lm_diagonal = 1e-6, v.prm.max_lm_diagonal = 1e32;
     v.prm.function_tolerance = 1e-6, v.prm.gradient_tolerance = 1e-10, v.prm.parameter_tolerance = 1e-8;
+    if (head[5]) {
+        v.prm.max_num_iterations = (int32_t)prm_i[0], v.prm.max_num_consecutive_invalid_steps = (int32_t)prm_i[1];
+        v.prm.initial_trust_region_radius = prm_d[0], v.prm.max_trust_region_radius = prm_d[1], v.prm.min_trust_region_radius = prm_d[2];
+        v.prm.min_relative_decrease = prm_d[3], v.prm.min_lm_diagonal = prm_d[4], v.prm.max_lm_diagonal = prm_d[5];
+        v.prm.function_tolerance = prm_d[6], v.prm.gradient_tolerance = prm_d[7], v.prm.parameter_tolerance = prm_d[8];
+    }
     std::unique_ptr<PgShared> sh(new PgShared());
 
     FILE *o = fopen(argv[2], "wb");
@@ -70,6 +83,14 @@ int main(int argc, char **argv)
             const double rec[6] = {(double)s.iterations, (double)s.successful_steps, (double)s.unsuccessful_steps, (double)s.termination, s.initial_cost, s.final_cost};
             fwrite(rec, sizeof(double), 6, o);
         }
+    } else if (mode == 2) {
+        for (int64_t gi = 0; gi < G; gi++) {
+            double blocks = 0.0;
+            for (int64_t k = 1; k < plan.graphs[gi].n_poses; k++) blocks += (double)(k - plan.first[pose_off[gi] + k]);
+            fwrite(&blocks, sizeof(double), 1, o);
+        }
+        const double all = (double)plan.envelope_blocks;
+        fwrite(&all, sizeof(double), 1, o);
     } else {
         if (G != 1 || P < 2 || E < 1) return 2;
         const PgGraph gr = plan.graphs[0];

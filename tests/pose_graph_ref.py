@@ -259,11 +259,11 @@ def pose_distance(a, b):
     return dt, dr
 
 
-def sensitivity(poses7, edge_ab, edge_meas7, information=None, trials=8, seed=0, base=None):
+def sensitivity(poses7, edge_ab, edge_meas7, information=None, trials=8, seed=0, base=None, options=None, rows=None):
     """the largest pose change (m, rad) of solve()'s result when every input moves by one unit in the last place, up or down at
-    random, over `trials` draws"""
+    random, over `trials` draws; rows: the poses the change is measured on (all of them when None)"""
     rng = np.random.default_rng(seed)
-    base = solve(poses7, edge_ab, edge_meas7, information)[0] if base is None else base
+    base = solve(poses7, edge_ab, edge_meas7, information, options)[0] if base is None else base
     worst = (0.0, 0.0)
 
     def nudge(a):
@@ -272,8 +272,8 @@ def sensitivity(poses7, edge_ab, edge_meas7, information=None, trials=8, seed=0,
 
     draws = [(nudge(poses7), nudge(edge_meas7), None if information is None else nudge(information)) for _ in range(trials)]
     with ThreadPoolExecutor(max_workers=trials) as pool:       # (the draws are made above, in sequence: the result does not depend on the threads)
-        results = list(pool.map(lambda d: solve(d[0], edge_ab, d[1], d[2])[0], draws))
+        results = list(pool.map(lambda d: solve(d[0], edge_ab, d[1], d[2], options)[0], draws))
     for got in results:
-        d = pose_distance(base, got)
+        d = pose_distance(base, got) if rows is None else pose_distance(base[rows], got[rows])
         worst = (max(worst[0], d[0]), max(worst[1], d[1]))
     return worst

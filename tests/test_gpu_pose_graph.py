@@ -10,7 +10,15 @@ is asserted.
 The shapes are the smallest at which the kernel can go wrong: one pose, no edges, two poses, an envelope row reaching the constant
 pose, nested and overlapping envelopes, more than 64 and more than 256 edges (the work items of a workgroup), rejected steps,
 information matrices on a third of the edges, edges of both directions, a graph 50 km from the origin, 1 / 5 / 70 graphs of mixed sizes in
-one call."""
+one call.
+
+And where the kernel's text changes form: N = 342 and N = 343 (the vector of the triangular solves in LDS, and past LL_PG_LDS_VEC in
+the workspace, where two graphs of one call must not share it), poses without edges, a component that never touches pose 0, repeated
+and reversed edges, information of a wide spectrum on every edge, quaternions far from unit norm, a normal matrix and a cost that
+overflow, the exits on the iteration cap, the radius floor and a run of invalid steps, parameters other than the defaults, handles of
+exactly the size a call needs and one short of it, and api.Pose_graph growing."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -20,7 +28,8 @@ from tests import pose_graph_ref as ref
 pytestmark = pytest.mark.gpu
 
 SINGLE = ["n2", "n3_loop_to_fixed", "n17_three_loops", "n17_far", "n33_detector", "n66", "n300_six_loops", "n40_hard", "n66_hard_rejected_steps",
-          "n24_information", "n20_both_directions", "n17_consistent", "n30_consistent"]
+          "n24_information", "n20_both_directions", "n17_consistent", "n30_consistent"] + [n for n in pgi.NEW_CASES if n not in pgi.UNCHANGED]
+HBM_BATCH = ["n17_three_loops", "n343_hbm_first", "n343_hbm_other", "n17_three_loops", "n342_lds_top", "n343_hbm_first"]
 ABSOLUTE_BAR = 1e-7
 
 
@@ -37,7 +46,23 @@ def graph_of(name):
     return dict(poses=g["poses"], ab=g["ab"], meas=g["meas"], information=g["information"])
 
 
+def check_unchanged(name, poses, summary):
+    """a run that takes no step: the poses of the input in their bytes, the reference's counts and exit, its cost to 1e-12"""
+    want, ws = pgi.reference(name)
+    print(f"{name}: {summary}; reference cost {ws['initial_cost']!r}")
+    assert poses.tobytes() == np.ascontiguousarray(pgi.case(name)["poses"]).tobytes() == want.tobytes(), name
+    assert (summary["iterations"], summary["successful_steps"], summary["unsuccessful_steps"], summary["termination"]) == \
+        (ws["iterations"], ws["successful_steps"], ws["unsuccessful_steps"], ws["termination"]), (name, summary)
+    assert summary["initial_cost"] == summary["final_cost"], (name, summary)
+    if np.isinf(ws["initial_cost"]):
+        assert summary["initial_cost"] == ws["initial_cost"], (name, summary)
+    else:
+        assert abs(summary["initial_cost"] - ws["initial_cost"]) <= 1e-12 * ws["initial_cost"], (name, summary, ws["initial_cost"])
+
+
 def check_against_reference(name, poses, summary):
+    if name in pgi.UNCHANGED:
+        return check_unchanged(name, poses, summary)
     want, ws = pgi.reference(name)
     tol_m, tol_rad = pgi.tolerance(name)
     d_m, d_rad = ref.pose_distance(want, poses)
@@ -55,6 +80,155 @@ def test_one_graph_equals_the_reference(handle, name):
     poses, summaries = handle.solve([graph_of(name)])
     check_against_reference(name, poses[0], summaries[0])
     assert np.array_equal(poses[0][0], pgi.case(name)["poses"][0])             # the constant pose, to the bit
+
+
+@pytest.fixture(scope="module")
+def alone(handle):
+    """name -> (poses, summary) of the graph solved alone on the shared handle, once"""
+    class Alone(dict):
+        def __missing__(self, name):
+            poses, summaries = handle.solve([graph_of(name)])
+            self[name] = (poses[0], summaries[0])
+            return self[name]
+    return Alone()
+
+
+@pytest.mark.parametrize("name", ["b24_overflow", "b24_cost_overflow"])
+def test_an_overflowing_graph_comes_back_as_it_went_in(handle, name):
+    """b24_overflow: no step can be solved, the radius is halved four times and the fifth invalid step ends the solve;
+    b24_cost_overflow: the step is valid, the cost of the candidate is not finite and is taken as the largest double"""
+    poses, summaries = handle.solve([graph_of(name)])
+    check_unchanged(name, poses[0], summaries[0])
+    assert summaries[0]["termination"] == {"b24_overflow": "invalid_steps", "b24_cost_overflow": "function"}[name]
+    poses, summaries = handle.solve([graph_of("n17_three_loops")])                 # and the handle still works
+    check_against_reference("n17_three_loops", poses[0], summaries[0])
+
+
+def test_the_solve_vector_outside_lds_in_a_batch(handle, alone):
+    """the N = 343 graphs keep the vector of the triangular solves in the workspace, at their own poses' offset: two of them beside
+    each other, a third later in the call, graphs with the vector in LDS between them.  Were two workgroups' vectors to overlap, a
+    graph would not come out as it does alone."""
+    poses, summaries = handle.solve([graph_of(n) for n in HBM_BATCH])
+    work = handle.work()
+    assert work[1] == 1 and work[3] == len(HBM_BATCH), work
+    for k, n in enumerate(HBM_BATCH):
+        assert poses[k].tobytes() == alone[n][0].tobytes() and summaries[k] == alone[n][1], (k, n)
+    for n in sorted(set(HBM_BATCH)):
+        check_against_reference(n, *alone[n])
+
+
+def test_the_solve_vector_outside_lds_of_graphs_that_share_an_l2(handle, alone):
+    """The batch above alone does not see two workgroups sharing that vector: with `gr.pose0` taken out of its offset the batch
+    still passed on an MI355X.  The workgroups of a launch are dealt to the eight XCDs in turn, each XCD has its own L2, and one
+    L2's lines are not refreshed by another's stores within a launch, so three graphs in slots 1, 2 and 5 each saw their own copy.
+    Here the N = 343 graphs stand eight slots apart -- 0 and 8, 1 and 9, each pair of two different graphs -- so that, dealt in
+    turn, a pair shares an L2 and every store of one is what the other loads."""
+    names = ["n343_hbm_first", "n343_hbm_other"] + ["n17_three_loops"] * 6 + ["n343_hbm_other", "n343_hbm_first"]
+    poses, summaries = handle.solve([graph_of(n) for n in names])
+    assert handle.work()[1] == 1
+    for k, n in enumerate(names):
+        assert poses[k].tobytes() == alone[n][0].tobytes() and summaries[k] == alone[n][1], (k, n)
+
+
+@pytest.mark.parametrize("name", list(pgi.OPTION_CASES))
+def test_parameters_other_than_the_defaults(gpu_lib, name):
+    from loam_livox_amd.api import Pose_graph
+    from tests.pose_graph_driver import params_struct
+    options = pgi.OPTION_CASES[name][1]
+    h = Pose_graph(max_graphs=1, max_poses=80, max_edges=80, max_envelope_blocks=512, params=params_struct(options))
+    try:
+        poses, summaries = h.solve([graph_of(name)])
+        assert h.capacity == [1, 80, 80, 512]
+    finally:
+        h.close()
+    check_against_reference(name, poses[0], summaries[0])
+    assert summaries[0]["termination"] == pgi.reference(name)[1]["termination"]
+
+
+def needs(names):
+    from loam_livox_amd.api import Pose_graph
+    graphs = [pgi.case(n) for n in names]
+    return [len(graphs), sum(len(g["poses"]) for g in graphs), sum(len(g["ab"]) for g in graphs),
+            sum(Pose_graph.envelope_blocks(len(g["poses"]), g["ab"]) for g in graphs)]
+
+
+@pytest.mark.parametrize("names", [["n17_three_loops"], HBM_BATCH], ids=["n17", "hbm_batch"])
+def test_a_handle_of_exactly_the_size_and_one_short(gpu_lib, handle, names):
+    from loam_livox_amd import capi
+    from loam_livox_amd.api import Pose_graph
+    from tests.pose_graph_driver import pack
+    need = needs(names)
+    want_poses, want_summaries = handle.solve([graph_of(n) for n in names])
+    assert list(handle.work()[2:4]) == [need[3], need[0]]
+    exact = Pose_graph(*need)
+    try:
+        h0 = exact.h.value
+        poses, summaries = exact.solve([graph_of(n) for n in names])
+        assert exact.capacity == need and exact.h.value == h0                     # (it did not grow)
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(poses, want_poses)) and summaries == want_summaries
+    finally:
+        exact.close()
+    po, x, eo, ab, meas, _ = pack([graph_of(n) for n in names])
+    text = ("capacity exceeded: the call needs %d graphs, %d poses, %d edges and %d envelope blocks" % tuple(need)).encode()
+    L = gpu_lib
+    for k in range(4):
+        short = list(need)
+        short[k] -= 1
+        h = C.c_void_p()
+        if short[k] < 1:                                                         # (a handle for no graph at all cannot be created)
+            assert L.ll_pose_graph_create(0, *short, C.byref(h)) < 0 and b"out of range" in L.ll_last_error() and not h.value
+            continue
+        assert L.ll_pose_graph_create(0, *short, C.byref(h)) == 0, L.ll_last_error()
+        try:
+            xs = x.copy()
+            summary = (capi.PoseGraphSummary * len(names))()
+            rc = L.ll_pose_graph_solve(h, None, len(names), capi.ptr(po), capi.ptr(xs), capi.ptr(eo), capi.ptr(ab), capi.ptr(meas), None, summary)
+            assert rc < 0 and text in L.ll_last_error(), (k, L.ll_last_error())
+            assert ("(the handle has %d, %d, %d, %d)" % tuple(short)).encode() in L.ll_last_error()
+            assert xs.tobytes() == x.tobytes()
+        finally:
+            L.ll_pose_graph_destroy(h)
+
+
+def test_the_python_handle_grows(gpu_lib, handle):
+    from loam_livox_amd.api import Pose_graph
+    small = Pose_graph(max_graphs=1, max_poses=8, max_edges=8, max_envelope_blocks=8)
+    try:
+        for names in (["n33_detector"], HBM_BATCH):
+            before, h_before = list(small.capacity), small.h.value
+            want_poses, want_summaries = handle.solve([graph_of(n) for n in names])
+            poses, summaries = small.solve([graph_of(n) for n in names])
+            assert all(a.tobytes() == b.tobytes() for a, b in zip(poses, want_poses)) and summaries == want_summaries, names
+            need = needs(names)
+            assert all(c >= n and c >= b for c, n, b in zip(small.capacity, need, before)) and small.capacity != before
+            assert small.h.value and small.h is not None and list(small.work()[2:4]) == [need[3], need[0]]
+            print(f"{names[0]} ...: capacity {before} -> {small.capacity}, handle {h_before:#x} -> {small.h.value:#x}")
+        again = small.solve([graph_of("n33_detector")])                            # large enough now: the handle stays
+        h_now = small.h.value
+        assert small.solve([graph_of("n33_detector")])[0][0].tobytes() == again[0][0].tobytes() and small.h.value == h_now
+    finally:
+        small.close()
+    assert small.h is None
+    small.close()                                                                # closing twice is harmless
+
+
+def test_poses_without_edges_and_a_component_apart(handle, alone):
+    for name, at in (("b24_edgeless_last", 24), ("b24_edgeless_middle", 10)):
+        poses, summary = alone[name]
+        assert poses[at].tobytes() == pgi.FAR_POSE.tobytes(), name
+        check_against_reference(name, poses, summary)
+    # the pose in the middle changes no other pose's arithmetic: the two graphs differ by where it stands alone
+    assert np.delete(alone["b24_edgeless_middle"][0], 10, axis=0).tobytes() == alone["b24_edgeless_last"][0][:24].tobytes()
+    for name in ("b24_floating_component", "b24_floating_component_loops"):
+        poses, summary = alone[name]
+        check_against_reference(name, poses, summary)
+        want = pgi.reference(name)[0]
+        tol_m, tol_rad = pgi.tolerance(name)
+        for part in (slice(0, 12), slice(12, 24)):
+            d_m, d_rad = ref.pose_distance(want[part], poses[part])
+            print(f"{name}: poses {part.start} .. {part.stop - 1}: device - reference {d_m:.3e} m {d_rad:.3e} rad")
+            assert d_m <= tol_m and d_rad <= tol_rad
+    assert alone["b24_floating_component_loops"][1]["successful_steps"] > 1
 
 
 def test_rejected_steps_and_all_three_terminations_occur(handle):

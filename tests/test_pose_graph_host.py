@@ -6,7 +6,11 @@ with the tolerance of the GPU tier: device - reference <= max( 1000 s, 1e-11 ), 
 < 1e-7 in every case; equal iteration and step counts and termination.  The analytic Jacobian against the complex step; the envelope
 factorisation against the dense solution; the driver once more under the address and undefined-behaviour sanitizers.
 Cases: every accept ratio and tolerance test of the reference's run stays 1e-6 (relative) from its threshold; the set holds rejected
-steps and each of the three tolerance terminations; the consistent graphs recover the truth.
+steps, each of the three tolerance terminations and the exits on the iteration cap, the radius floor and a run of invalid steps; the
+consistent graphs recover the truth.  The new cases stand where the kernel's text changes form: 6 (N - 1) on either side of
+LL_PG_LDS_VEC (read from the header here), poses without edges, a component that never touches pose 0, repeated and reversed edges,
+information of a wide spectrum on every edge, quaternions far from unit norm, a graph whose normal matrix overflows, and parameters
+other than the defaults (tests/pose_graph_inputs.OPTION_CASES), which the driver takes in a block of its input.
 Symbols: declared, exported, bound; bad arguments are refused without a device.
 Bookkeeping: Keyframe_assembly( pose_graph=stub ) on the scripted walks of tests/test_keyframes.py leaves loops, log, if_end and
 state() as pose_graph=False has them, and hands the stub the constraints of the numpy formulas bit for bit; Laser_mapping_batch's
@@ -24,9 +28,21 @@ from tests import pose_graph_ref as ref
 from tests.pose_graph_driver import build_driver, run_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def header_constant(name):
+    text = open(os.path.join(ROOT, "loam_livox_amd", "csrc", "ll_pose_graph_core.h")).read()
+    found = re.findall(r"^#define\s+" + name + r"\s+(\d+)\b", text, flags=re.M)
+    assert len(found) == 1, (name, found)
+    return int(found[0])
+
+
+LDS_VEC, THREADS = header_constant("LL_PG_LDS_VEC"), header_constant("LL_PG_THREADS")
 # (the N = 300 case is run by the GPU tier; here its plan and one linearisation are checked, not its eight-fold sensitivity)
 SOLVED = ["n2", "n3_loop_to_fixed", "n17_three_loops", "n17_far", "n33_detector", "n66", "n40_hard", "n66_hard_rejected_steps", "n24_information",
           "n20_both_directions", "n17_consistent", "n30_consistent"]
+NEW_CASES = list(pgi.NEW_CASES)
+OPTION_CASES = list(pgi.OPTION_CASES)
 
 
 def graph_of(name):
@@ -42,30 +58,83 @@ def driver(tmp_path_factory):
 @pytest.fixture(scope="module")
 def solved(driver, tmp_path_factory):
     """the driver's result of every case, all in ONE call (a batch), computed once and shared"""
-    poses, summaries = run_driver(driver, str(tmp_path_factory.mktemp("pose_graph_run")), [graph_of(n) for n in SOLVED])
-    return dict(zip(SOLVED, zip(poses, summaries)))
+    tmp = str(tmp_path_factory.mktemp("pose_graph_run"))
+    poses, summaries = run_driver(driver, tmp, [graph_of(n) for n in SOLVED + NEW_CASES])
+    out = dict(zip(SOLVED + NEW_CASES, zip(poses, summaries)))
+    for name, (_, options) in pgi.OPTION_CASES.items():             # one call per row of parameters
+        (x,), (s,) = run_driver(driver, tmp, [graph_of(name)], options=options)
+        out[name] = (x, s)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ the cases
-@pytest.mark.parametrize("name", SOLVED + ["n300_six_loops"])
+@pytest.mark.parametrize("name", SOLVED + ["n300_six_loops"] + NEW_CASES + OPTION_CASES)
 def test_no_decision_of_the_reference_run_is_near_its_threshold(name):
     _, s = pgi.reference(name)
     worst = {}
     for test, margin in s["margins"]:
         worst[test] = min(worst.get(test, np.inf), margin)
-    print(name, s["iterations"], s["termination"], {k: f"{v:.2e}" for k, v in worst.items()})
-    assert min(worst.values()) >= 1e-6, (name, worst)
+    print(name, s["iterations"], s["successful_steps"], s["unsuccessful_steps"], s["termination"], {k: f"{v:.2e}" for k, v in worst.items()})
+    assert min(worst.values(), default=np.inf) >= 1e-6, (name, worst)      # (no iteration: no decision was made)
 
 
 def test_the_set_holds_rejected_steps_and_the_three_terminations():
-    runs = {n: pgi.reference(n)[1] for n in SOLVED}
+    runs = {n: pgi.reference(n)[1] for n in SOLVED + NEW_CASES + OPTION_CASES}
     assert runs["n66_hard_rejected_steps"]["unsuccessful_steps"] > 0
-    assert {"function", "gradient", "parameter"} <= {s["termination"] for s in runs.values()}
+    assert {"function", "gradient", "parameter"} <= {runs[n]["termination"] for n in SOLVED}
+    assert {"max_iterations", "radius", "invalid_steps"} <= {s["termination"] for s in runs.values()}
+    over = runs["b24_overflow"]
+    assert over["termination"] == "invalid_steps" and over["successful_steps"] == 0
+    assert (over["iterations"], over["unsuccessful_steps"]) == (5, 4)       # four halvings, the fifth invalid step ends the solve
+    two = runs["b24_overflow_two_invalid"]                           # one halving, then the run of two ends the solve
+    assert (two["iterations"], two["successful_steps"], two["unsuccessful_steps"], two["termination"]) == (2, 0, 1, "invalid_steps")
+    for name, want in (("n66_hard_max_iterations_0", (0, 0, 0, "max_iterations")), ("n66_hard_max_iterations_1", (1, 0, 1, "max_iterations")),
+                       ("n66_hard_max_iterations_3", (3, 1, 2, "max_iterations")), ("n66_hard_min_radius_1e4", (0, 0, 0, "radius")),
+                       ("n66_hard_min_radius_6e3", (1, 0, 1, "radius")), ("n66_hard_min_radius_3e3", (2, 0, 2, "radius"))):
+        r = runs[name]
+        assert (r["iterations"], r["successful_steps"], r["unsuccessful_steps"], r["termination"]) == want, name
+    # the cap on the radius, the small first radius and the raised acceptance bar each change the run they are given to
+    base = runs["n66_hard_rejected_steps"]
+    for name in ("n66_hard_max_radius_1e4", "n66_hard_first_radius_1e-3", "n66_hard_min_decrease_0.9"):
+        assert runs[name]["termination"] == "function" and runs[name]["iterations"] != base["iterations"], name
+    assert runs["n66_hard_min_decrease_0.9"]["unsuccessful_steps"] > base["unsuccessful_steps"]
+    for name in pgi.UNCHANGED:
+        assert pgi.reference(name)[0].tobytes() == np.ascontiguousarray(pgi.case(name)["poses"]).tobytes(), name
+    # what the new graphs are there for
+    assert 6 * (len(pgi.case("n342_lds_top")["poses"]) - 1) <= LDS_VEC < 6 * (len(pgi.case("n343_hbm_first")["poses"]) - 1)
+    assert len(pgi.case("n343_hbm_other")["poses"]) == 343 and not np.array_equal(pgi.case("n343_hbm_other")["ab"], pgi.case("n343_hbm_first")["ab"])
+    for name, at in (("b24_edgeless_last", 24), ("b24_edgeless_middle", 10)):
+        g = pgi.case(name)
+        assert len(g["poses"]) == 25 and not (g["ab"] == at).any() and np.array_equal(g["poses"][at], pgi.FAR_POSE)
+        assert pgi.reference(name)[0][at].tobytes() == pgi.FAR_POSE.tobytes()
+        assert runs[name]["termination"] == "function" and runs[name]["iterations"] == runs["b24_edgeless_last"]["iterations"] > 1
+    for name in ("b24_floating_component", "b24_floating_component_loops"):
+        ab = pgi.case(name)["ab"]
+        assert not ((ab.min(axis=1) <= 11) & (ab.max(axis=1) >= 12)).any() and (ab.min(axis=1) >= 12).any(), name
+    assert runs["b24_floating_component_loops"]["successful_steps"] > 1
+    g = pgi.case("b24_repeated_edges")
+    pairs = [tuple(e) for e in g["ab"]]
+    assert pairs.count((5, 6)) == 3 and pairs.count((23, 1)) == 2 and pairs.count((7, 8)) == 1 and pairs.count((8, 7)) == 1
+    assert np.abs(ref.residuals(g["poses"], g["ab"].astype(np.int64)[-1:], g["meas"][-1:], None)).max() < 1e-9     # the inverse measurement
+    info = pgi.case("b24_information_all")["information"].reshape(-1, 6, 6)
+    eig = np.linalg.eigvalsh(info)
+    assert (eig > 0).all() and (eig[:, -1] / eig[:, 0]).min() > 10.0 and eig.max() / eig.min() > 1e5
+    assert not any(np.array_equal(m, np.eye(6)) for m in info)
+    g = pgi.case("b24_non_unit")
+    for q in (g["poses"][:, :4], g["meas"][:, :4]):
+        n = np.linalg.norm(q, axis=1)
+        assert n.min() < 0.7 and n.max() > 1.5 and 0.5 <= n.min() and n.max() <= 2.0
+    assert np.isfinite(pgi.case("b24_overflow")["poses"]).all()
+    over = runs["b24_cost_overflow"]                                 # a valid step whose candidate's cost is not finite
+    assert (over["iterations"], over["successful_steps"], over["unsuccessful_steps"], over["termination"]) == (1, 0, 0, "function")
+    assert np.isinf(over["initial_cost"]) and any(t == "model" for t, _ in over["margins"])
+    g = pgi.case("b24_cost_overflow")
+    assert np.isfinite(g["meas"]).all() and np.isfinite(g["information"]).all()
     assert {runs[n]["termination"] for n in ("n17_consistent", "n30_consistent", "n2")} >= {"gradient", "parameter"}
     assert len(pgi.case("n66")["ab"]) > 64 and len(pgi.case("n300_six_loops")["ab"]) > 256
     ab = pgi.case("n20_both_directions")["ab"]
     assert (ab[:, 0] > ab[:, 1]).any() and (ab[:, 0] < ab[:, 1]).any()
-    for name in SOLVED:                                              # chain edges from the estimates: satisfied at the start
+    for name in SOLVED + NEW_CASES[:3]:                              # chain edges from the estimates: satisfied at the start
         g = pgi.case(name)
         if not pgi.CASES[name].get("consistent") and not pgi.CASES[name].get("hard"):
             chain = np.arange(len(g["poses"]) - 1)
@@ -74,17 +143,46 @@ def test_the_set_holds_rejected_steps_and_the_three_terminations():
 
 
 # ------------------------------------------------------------------------------------------------ the kernel's text under g++
-@pytest.mark.parametrize("name", SOLVED)
+def test_the_header_puts_the_new_graphs_on_either_side_of_the_lds_vector():
+    """6 (N - 1) doubles: N = 342 is the last graph whose vector fits, N = 343 the first that does not"""
+    assert 6 * 341 <= LDS_VEC < 6 * 342
+    assert THREADS == 256                                            # more than 64 and more than 256 edges are what the old cases were sized for
+    assert len(pgi.case("n66")["ab"]) > 64 and len(pgi.case("n300_six_loops")["ab"]) > THREADS
+
+
+@pytest.mark.parametrize("name", SOLVED + NEW_CASES + OPTION_CASES)
 def test_driver_equals_the_reference(solved, name):
     want, ws = pgi.reference(name)
     got, s = solved[name]
+    assert (s["iterations"], s["successful_steps"], s["unsuccessful_steps"], ref.TERMINATION[s["termination"]]) == \
+        (ws["iterations"], ws["successful_steps"], ws["unsuccessful_steps"], ws["termination"])
+    if name in pgi.UNCHANGED:                                        # no step is taken: nothing to be sensitive about, the bytes of the input
+        start = np.ascontiguousarray(pgi.case(name)["poses"])
+        print(f"{name}: {s}; reference cost {ws['initial_cost']!r} -> {ws['final_cost']!r}")
+        assert got.tobytes() == start.tobytes() == want.tobytes()
+        for k in ("initial_cost", "final_cost"):
+            assert s[k] == ws[k] if np.isinf(ws[k]) else abs(s[k] - ws[k]) <= 1e-12 * ws[k], (name, k, s[k], ws[k])
+        assert s["initial_cost"] == s["final_cost"]
+        return
     tol_m, tol_rad = pgi.tolerance(name)
     d_m, d_rad = ref.pose_distance(want, got)
     print(f"{name}: driver - reference {d_m:.3e} m {d_rad:.3e} rad (allowed {tol_m:.3e} m {tol_rad:.3e} rad); {s}")
     assert d_m <= tol_m and d_rad <= tol_rad and d_m < 1e-7 and d_rad < 1e-7
-    assert (s["iterations"], s["successful_steps"], s["unsuccessful_steps"], ref.TERMINATION[s["termination"]]) == \
-        (ws["iterations"], ws["successful_steps"], ws["unsuccessful_steps"], ws["termination"])
     assert np.array_equal(got[0], pgi.case(name)["poses"][0])
+    for at in {"b24_edgeless_last": [24], "b24_edgeless_middle": [10]}.get(name, []):
+        assert got[at].tobytes() == pgi.FAR_POSE.tobytes()          # a pose without edges comes back as it went in
+
+
+def test_envelope_blocks_of_the_python_side_are_the_plans(driver, tmp_path):
+    """api.Pose_graph sizes its handle by Pose_graph.envelope_blocks; ll_pose_graph_solve refuses by pg_plan's count"""
+    from loam_livox_amd.api import Pose_graph
+    names = list(pgi.CASES)
+    per_graph, total = run_driver(driver, str(tmp_path), [graph_of(n) for n in names], mode=2)
+    want = [Pose_graph.envelope_blocks(len(pgi.case(n)["poses"]), pgi.case(n)["ab"]) for n in names]
+    print(dict(zip(names, per_graph)))
+    assert per_graph == want and total == sum(want)
+    assert Pose_graph.envelope_blocks(1, np.zeros((0, 2))) == 0 and Pose_graph.envelope_blocks(5, np.zeros((0, 2))) == 4
+    assert run_driver(driver, str(tmp_path), [dict(poses=pgi.case("n2")["poses"][:1], ab=np.zeros((0, 2), np.int32), meas=np.zeros((0, 7)))], mode=2) == ([0], 0)
 
 
 @pytest.mark.parametrize("name", ["n17_consistent", "n30_consistent"])
@@ -137,7 +235,7 @@ def test_analytic_jacobian_and_envelope_solve(driver, tmp_path, name):
 
 def test_driver_runs_clean_under_the_sanitizers(tmp_path, solved):
     exe = build_driver(str(tmp_path / "pose_graph_host_san"), ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"])
-    names = ["n17_three_loops", "n24_information", "n66_hard_rejected_steps", "n2"]
+    names = ["n17_three_loops", "n24_information", "n66_hard_rejected_steps", "n2"] + NEW_CASES      # (the N = 343 graphs after others: pose0 != 0)
     empty = dict(poses=pgi.case("n2")["poses"], ab=np.zeros((0, 2), np.int32), meas=np.zeros((0, 7)))
     poses, summaries = run_driver(exe, str(tmp_path), [graph_of(n) for n in names] + [empty])     # (asserts exit status 0 and an empty stderr)
     for n, x, s in zip(names, poses, summaries):

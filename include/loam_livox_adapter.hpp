@@ -17,6 +17,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <iterator>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1610,6 +1611,159 @@ class Keyframe_bank {
 
    private:
     ll_keyframe_bank *h_ = nullptr;
+};
+
+// ------------------------------------------------------------------------------------------------------------
+// Mapping_refine (ceres_pose_graph_3d.hpp:368-538): the corrected key-frame clouds behind a closed loop, on the device
+// (ll_map_refine_*).  Templated on the cloud type like VoxelGrid above (the reference's is on the point type:
+// Mapping_refine< pcl::PointCloud< PointType > > here).  The clouds of map_idx_pc are uploaded as they are the first time a call meets
+// them (ll_map_refine_add_stored; a key whose cloud has changed in size is uploaded again) and stay on the device for the later
+// calls of the node's loop at laser_mapping.hpp:1091-1100.  if_save must be 0: the JSON dumps are out of scope.
+//   refine_pointcloud   VoxelGrid at m_down_sample_res, then the centroids moved with R_opm R_ori^T (:476-485): ll_map_refine_run, mode 0
+//   refine_mapping      every cloud moved, then VoxelGrid (:511-533), ONE run for all clouds (mode 1); fills m_pts_aft_refind
+//   refine_pts          the affine and the move of :437-452 on the host; it takes the two poses, not their rotation matrices --
+//                       toRotationMatrix is part of the arithmetic (ll_map_refine_affine)
+// Output intensity is 0, as eigen_to_pcl_pt leaves it.
+template <class Cloud>
+class Mapping_refine {
+   public:
+    Ceres_pose_graph_3d::MapOfPoses pose3d_map_oir, pose3d_map_opm;
+    Cloud m_pts_aft_refind;
+    float m_down_sample_res = 0.2f;
+    int m_step_skip = 2;
+
+    explicit Mapping_refine(int64_t initial_points = 1 << 20, int device = 0) : initial_points_(initial_points), device_(device) {}
+    ~Mapping_refine()
+    {
+        if (h_) ll_map_refine_destroy(h_);
+    }
+    Mapping_refine(const Mapping_refine &) = delete;
+    Mapping_refine &operator=(const Mapping_refine &) = delete;
+
+    void set_down_sample_resolution(float res) { m_down_sample_res = res; }
+    // ( laser_mapping.hpp:902 ) kept, not used: nothing is written
+    void set_save_dir(const std::string &path_name) { m_save_path = path_name; }
+    std::string m_save_path;
+
+#if defined(__clang__)
+#define LOAM_LIVOX_NO_CONTRACT
+#elif defined(__GNUC__)
+#define LOAM_LIVOX_NO_CONTRACT __attribute__((optimize("fp-contract=off")))
+#else
+#define LOAM_LIVOX_NO_CONTRACT
+#endif
+    // V: a 3-vector of float read and written as v( i ) (Eigen::Matrix< float, 3, 1 >)
+    template <class V>
+    LOAM_LIVOX_NO_CONTRACT static std::vector<V> refine_pts(const std::vector<V> &raw_pt_vec, const Quaterniond &q_ori, const Vector3d &t_ori,
+                                                             const Quaterniond &q_opm, const Vector3d &t_opm)
+    {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+        float R[9], T[3];
+        const double ori[7] = {q_ori.x(), q_ori.y(), q_ori.z(), q_ori.w(), t_ori(0), t_ori(1), t_ori(2)};
+        const double opm[7] = {q_opm.x(), q_opm.y(), q_opm.z(), q_opm.w(), t_opm(0), t_opm(1), t_opm(2)};
+        check(ll_map_refine_affine(ori, opm, R, T), "ll_map_refine_affine");
+        std::vector<V> out(raw_pt_vec.size());
+        for (size_t k = 0; k < raw_pt_vec.size(); k++) {
+            const float x = raw_pt_vec[k](0), y = raw_pt_vec[k](1), z = raw_pt_vec[k](2);
+            for (int i = 0; i < 3; i++) {
+                const float e0 = R[3 * i] * x, e1 = R[3 * i + 1] * y, e2 = R[3 * i + 2] * z;
+                out[k](i) = (e0 + (e1 + e2)) + T[i];
+            }
+        }
+        return out;
+    }
+
+    Cloud refine_pointcloud(const std::map<int, Cloud> &map_idx_pc, const Ceres_pose_graph_3d::MapOfPoses &poses_ori,
+                            const Ceres_pose_graph_3d::MapOfPoses &poses_opm, int idx = 0, int if_save = 0)
+    {
+        if (if_save != 0) check_arg("Mapping_refine::refine_pointcloud: if_save must be 0 (the JSON dumps are out of scope)");
+        Cloud out;
+        if (idx < 0 || (size_t)idx >= map_idx_pc.size()) return out;  // ( it == map_idx_pc.end(), :465-468 )
+        typename std::map<int, Cloud>::const_iterator it = map_idx_pc.begin();
+        std::advance(it, idx);
+        std::vector<int> keys(1, it->first);
+        std::vector<Cloud> got = run(0, map_idx_pc, poses_ori, poses_opm, keys);
+        return got[0];
+    }
+
+    void refine_mapping(const std::map<int, Cloud> &map_idx_pc, const Ceres_pose_graph_3d::MapOfPoses &poses_ori,
+                        const Ceres_pose_graph_3d::MapOfPoses &poses_opm, int if_save = 0)
+    {
+        if (if_save != 0) check_arg("Mapping_refine::refine_mapping: if_save must be 0 (the JSON dumps are out of scope)");
+        std::vector<int> keys;
+        for (Ceres_pose_graph_3d::MapOfPoses::const_iterator it = poses_ori.begin(); it != poses_ori.end(); ++it) keys.push_back(it->first);  // :512
+        std::vector<Cloud> got = run(1, map_idx_pc, poses_ori, poses_opm, keys);
+        for (size_t k = 0; k < got.size(); k++) m_pts_aft_refind.points.insert(m_pts_aft_refind.points.end(), got[k].points.begin(), got[k].points.end());  // :533
+    }
+
+    // :577-578 over the last refine_mapping / refine_pointcloud outputs still on the device: VoxelGrid of them as one cloud
+    Cloud merge_last()
+    {
+        Cloud out;
+        if (!h_) return out;
+        int64_t n = 0;
+        check(ll_map_refine_merge(h_, m_down_sample_res, &n, nullptr), "ll_map_refine_merge");
+        std::vector<float> v((size_t)(n > 0 ? n : 1) * 4);
+        check(ll_map_refine_fetch_merged(h_, v.data(), n), "ll_map_refine_fetch_merged");
+        xyzi_to_cloud(v.data(), (int)n, out);
+        return out;
+    }
+    // test tap (ll_map_refine_work) on the last run and its fetch
+    void work(int64_t out[4]) { check(ll_map_refine_work(h_, out), "ll_map_refine_work"); }
+    ll_map_refine *handle() { return h_; }
+
+   private:
+    static void check_arg(const char *what) { throw std::runtime_error(what); }
+
+    int64_t stored_id(int key, const Cloud &c)
+    {
+        std::map<int, std::pair<int64_t, size_t> >::const_iterator it = ids_.find(key);
+        if (it != ids_.end() && it->second.second == c.points.size()) return it->second.first;
+        const std::vector<float> v = cloud_to_xyzi(c);
+        int64_t id = -1;
+        check(ll_map_refine_add_stored(h_, v.empty() ? nullptr : v.data(), (int64_t)c.points.size(), &id), "ll_map_refine_add_stored");
+        ids_[key] = std::make_pair(id, c.points.size());
+        return id;
+    }
+
+    std::vector<Cloud> run(int mode, const std::map<int, Cloud> &map_idx_pc, const Ceres_pose_graph_3d::MapOfPoses &poses_ori,
+                           const Ceres_pose_graph_3d::MapOfPoses &poses_opm, const std::vector<int> &keys)
+    {
+        if (map_idx_pc.size() != poses_ori.size() || map_idx_pc.size() != poses_opm.size())   // ( the asserts of :461-462, :508-509 )
+            check_arg("Mapping_refine: map_idx_pc, poses_ori and poses_opm differ in size");
+        if (!h_) {
+            runtime_hints();
+            check(ll_map_refine_create(device_, initial_points_, &h_), "ll_map_refine_create");
+        }
+        std::vector<int64_t> ids;
+        std::vector<double> ori, opm;
+        for (size_t k = 0; k < keys.size(); k++) {
+            typename std::map<int, Cloud>::const_iterator pc = map_idx_pc.find(keys[k]);
+            Ceres_pose_graph_3d::MapOfPoses::const_iterator a = poses_ori.find(keys[k]), b = poses_opm.find(keys[k]);
+            if (pc == map_idx_pc.end() || a == poses_ori.end() || b == poses_opm.end()) check_arg("Mapping_refine: an id is missing from a map");
+            ids.push_back(stored_id(keys[k], pc->second));
+            const double ra[7] = {a->second.q.x(), a->second.q.y(), a->second.q.z(), a->second.q.w(), a->second.p(0), a->second.p(1), a->second.p(2)};
+            const double rb[7] = {b->second.q.x(), b->second.q.y(), b->second.q.z(), b->second.q.w(), b->second.p(0), b->second.p(1), b->second.p(2)};
+            ori.insert(ori.end(), ra, ra + 7);
+            opm.insert(opm.end(), rb, rb + 7);
+        }
+        std::vector<int64_t> offsets(keys.size() + 1, 0);
+        std::vector<int32_t> status(keys.size() + 1, 0);
+        check(ll_map_refine_run(h_, mode, (int64_t)keys.size(), ids.data(), ori.data(), opm.data(), m_down_sample_res, offsets.data(), status.data()),
+              "ll_map_refine_run");
+        std::vector<float> v((size_t)(offsets.back() > 0 ? offsets.back() : 1) * 4);
+        check(ll_map_refine_fetch(h_, v.data(), offsets.back()), "ll_map_refine_fetch");
+        std::vector<Cloud> out(keys.size());
+        for (size_t k = 0; k < keys.size(); k++) xyzi_to_cloud(v.data() + 4 * offsets[k], (int)(offsets[k + 1] - offsets[k]), out[k]);
+        return out;
+    }
+
+    int64_t initial_points_;
+    int device_;
+    ll_map_refine *h_ = nullptr;
+    std::map<int, std::pair<int64_t, size_t> > ids_;  // key of map_idx_pc -> (id in the store, points it had when uploaded)
 };
 
 }  // namespace loam_livox_hip

@@ -747,7 +747,7 @@ int ll_keyframe_bank_work(ll_keyframe_bank *b, int64_t out[4]);
 /* ------------------------------------------------------------------------------------------------------------
  * Pose graph: what the detector does with an accepted loop (laser_mapping.hpp:948-960, 1058-1089; ceres_pose_graph_3d.hpp:198-352;
  * scene_alignment.hpp:97-129).  G independent graphs are optimised by ONE launch (a workgroup per graph runs the whole
- * Levenberg-Marquardt loop on the device) and ONE host wait.  The map refinement and the file dumps behind it are not here.
+ * Levenberg-Marquardt loop on the device) and ONE host wait.  The map refinement behind it is ll_map_refine_*; the file dumps are not here.
  *   problem     a graph has N poses and E edges (a, b, measurement {q_m, p_m}, information 6 x 6); pose 0 is constant; any a != b.
  *               error  e = [ conj(q_a) . (p_b - p_a) - p_m ; 2 vec( q_m (x) conj( conj(q_a) (x) q_b ) ) ],  residual L e with
  *               information = L L' (factored on the host in fp64; an identity matrix skips the product).  Translation moves
@@ -800,6 +800,56 @@ int ll_pose_graph_solve(ll_pose_graph *h, const ll_pose_graph_params *p, int64_t
                         const int64_t *edge_offsets, const int32_t *edge_ab, const double *edge_meas7, const double *edge_information,
                         ll_pose_graph_summary *summary);
 int ll_pose_graph_work(ll_pose_graph *h, int64_t out[4]);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Map refinement: the corrected clouds behind a closed loop (Mapping_refine, ceres_pose_graph_3d.hpp:368-538; the node's call
+ * site, laser_mapping.hpp:943-946 and 1091-1100).  The key frames' accumulated clouds stay on the device in one ragged store;
+ * n_sel of them are filtered and moved into their corrected frames by ONE launch chain over the SUM of their points and ONE
+ * host wait, whatever n_sel is (a fixed number of enqueue calls: see work).
+ *   store       one float4 {x, y, z, intensity} array and host-known offsets; a cloud's id is its position in the order of the
+ *               adds (map_id_pc.size(), :944) and never changes; the capacity doubles by a device-to-device copy.
+ *   add_cloud   one upload, pcl::VoxelGrid with leaf `leaf` (surround_pointcloud_resolution, :943-946) -- ll_voxel_filter's
+ *               arithmetic bit for bit, intensity averaged -- appended to the store; one host wait, for the count.
+ *   affine      refine_pts' R_aff and T_aff (:444-445) from two poses {qx, qy, qz, qw, tx, ty, tz}, on the host in fp64:
+ *               toRotationMatrix as Eigen writes it (no renormalisation), R_aff = float( R_opm R_ori^T ) with every double
+ *               product reduced ( e0 + e1 ) + e2, T_aff = float( double( R_aff ) ( -t_ori ) + t_opm ).  Row-major R9.
+ *   move        out_i = ( R_i0 x + ( R_i1 y + R_i2 z ) ) + T_i in float, not contracted (:449: Eigen's lazy product for float);
+ *               the output intensity is 0 (eigen_to_pcl_pt leaves PointXYZI's default).
+ *   run         selection s is cloud ids[s] (any order, duplicates and empty clouds allowed) with poses_ori7[s], poses_opm7[s].
+ *               mode 0 = refine_pointcloud( ..., if_save = 0 ) (:476-485): VoxelGrid with `leaf`, then the centroids are moved
+ *               (what the node runs).  mode 1 = refine_mapping's in-memory overload (:511-533): every point is moved, then
+ *               VoxelGrid.  The outputs are packed in selection order and stay on the device: selection s is points
+ *               offsets_out[s] .. offsets_out[s + 1] of what ll_map_refine_fetch copies out (one more copy, one more wait).
+ *   status      ll_voxel_filter's: 0 filtered; 1 leaf too small for the (mode 1: moved) cloud's extent, the output is the input,
+ *               moved (a non-finite point is carried along, its image whatever the float operations give); 2 no finite point.
+ *   merge       VoxelGrid with `leaf` over the last run's outputs taken as one cloud (:577-578): the single corrected map.
+ *   determinism no float atomics; a voxel's sums run in input order; a selection's result does not depend on n_sel, on its
+ *               slot or on the run.
+ *   work        test tap on the last add / run / merge and the fetches behind it: out[0] enqueue calls of the host (copies, kernel
+ *               launches, the sort and the scan counted as one call each: 14 per chain whatever n_sel is -- the number of kernels
+ *               inside the sort grows with the key bits in use, 32 + ceil( log2( n_sel + 1 ) )), out[1] host waits, out[2] bytes
+ *               copied between host and device, out[3] points of the chain.
+ * Limits: n_sel <= 2^20; fewer than 2^31 points per run and in the store.  Refused before anything is enqueued, with the
+ * store and the last outputs untouched: null arguments, a mode other than 0 / 1, ids out of range, negative counts, a leaf that
+ * is not positive and finite, non-finite poses, a run or a store beyond its limit, a capacity below what is to be copied out. */
+typedef struct ll_map_refine ll_map_refine;
+int ll_map_refine_create(int32_t device, int64_t initial_points, ll_map_refine **out);
+void ll_map_refine_destroy(ll_map_refine *h);
+int ll_map_refine_add_cloud(ll_map_refine *h, const float *xyzi, int64_t n, float leaf, int64_t *id, int64_t *n_kept, int32_t *status);
+/* a cloud that is filtered already (a host-side map_id_pc entry, the adapter's Mapping_refine): stored as it is, one upload, one wait */
+int ll_map_refine_add_stored(ll_map_refine *h, const float *xyzi, int64_t n, int64_t *id);
+/* clouds held (the next id) */
+int64_t ll_map_refine_size(const ll_map_refine *h);
+/* a stored cloud back; xyzi_out NULL: its size alone */
+int ll_map_refine_cloud(ll_map_refine *h, int64_t id, float *xyzi_out, int64_t capacity_points, int64_t *n);
+/* host only: no device is touched */
+int ll_map_refine_affine(const double *ori7, const double *opm7, float *R9_out, float *T3_out);
+int ll_map_refine_run(ll_map_refine *h, int32_t mode, int64_t n_sel, const int64_t *ids, const double *poses_ori7, const double *poses_opm7,
+                      float leaf, int64_t *offsets_out, int32_t *status_out);
+int ll_map_refine_fetch(ll_map_refine *h, float *xyzi_out, int64_t capacity_points);
+int ll_map_refine_merge(ll_map_refine *h, float leaf, int64_t *n_out, int32_t *status);
+int ll_map_refine_fetch_merged(ll_map_refine *h, float *xyzi_out, int64_t capacity_points);
+int ll_map_refine_work(ll_map_refine *h, int64_t out[4]);
 
 /* The two cell maps of the mapping node, fed by every frame ll_history_add* receives (laser_mapping.hpp:1492-1493: the
  * voxel-filtered map-frame features, whether or not the frame enters the history), and the cell branch of

@@ -950,6 +950,98 @@ class Keyframe_bank:
         return out
 
 
+def map_refine_affine(pose_ori, pose_opm):
+    """(R_aff float32[3, 3], T_aff float32[3]) of refine_pts (ceres_pose_graph_3d.hpp:444-445) from two poses {qx, qy, qz, qw, tx, ty, tz};
+    host arithmetic only (ll_map_refine_affine)"""
+    a, b = np.ascontiguousarray(pose_ori, np.float64).reshape(7), np.ascontiguousarray(pose_opm, np.float64).reshape(7)
+    R, T = np.zeros((3, 3), np.float32), np.zeros(3, np.float32)
+    check(capi.load().ll_map_refine_affine(ptr(a), ptr(b), ptr(R), ptr(T)), "ll_map_refine_affine")
+    return R, T
+
+
+class Map_refine:
+    """The key-frame map refinement (ll_map_refine_*): Mapping_refine of ceres_pose_graph_3d.hpp:368-538 over key-frame clouds that stay
+    on the device.  add_cloud filters an accumulated cloud into the store and returns its id (its position in the order of the adds);
+    refine moves and filters any selection of them in one launch chain and one host wait; merge filters the last outputs as one cloud."""
+
+    def __init__(self, initial_points: int = 1 << 20, device: int = 0):
+        self.L = capi.load()
+        self.h = C.c_void_p()
+        check(self.L.ll_map_refine_create(device, int(initial_points), C.byref(self.h)), "ll_map_refine_create")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.ll_map_refine_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return int(check(self.L.ll_map_refine_size(self.h), "ll_map_refine_size"))
+
+    def add_cloud(self, cloud, leaf: float = 0.5):
+        """(id, points kept, status) of a cloud [n, 4] filtered with `leaf` (surround_pointcloud_resolution, laser_mapping.hpp:943-946)"""
+        c = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4)
+        cid, kept, st = C.c_int64(-1), C.c_int64(0), C.c_int32(0)
+        check(self.L.ll_map_refine_add_cloud(self.h, ptr(c), len(c), leaf, C.byref(cid), C.byref(kept), C.byref(st)), "ll_map_refine_add_cloud")
+        return int(cid.value), int(kept.value), int(st.value)
+
+    def add_stored(self, cloud) -> int:
+        """the id of a cloud [n, 4] stored as it is: one that is filtered already (a map_id_pc entry kept on the host)"""
+        c = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4)
+        cid = C.c_int64(-1)
+        check(self.L.ll_map_refine_add_stored(self.h, ptr(c), len(c), C.byref(cid)), "ll_map_refine_add_stored")
+        return int(cid.value)
+
+    def cloud(self, cloud_id: int) -> np.ndarray:
+        """a stored cloud [n, 4], read back"""
+        n = C.c_int64(0)
+        check(self.L.ll_map_refine_cloud(self.h, int(cloud_id), None, 0, C.byref(n)), "ll_map_refine_cloud")
+        out = np.zeros((int(n.value), 4), np.float32)
+        check(self.L.ll_map_refine_cloud(self.h, int(cloud_id), ptr(out), len(out), C.byref(n)), "ll_map_refine_cloud")
+        return out
+
+    def run(self, ids, poses_ori, poses_opm, leaf: float = 0.2, transform_first: bool = False):
+        """(offsets int64[n_sel + 1], status int32[n_sel]) of a run whose outputs stay on the device"""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        a, b = np.ascontiguousarray(poses_ori, np.float64).reshape(-1, 7), np.ascontiguousarray(poses_opm, np.float64).reshape(-1, 7)
+        if len(a) != len(ids) or len(b) != len(ids):
+            raise ValueError("a pose pair per selected id")
+        offsets, status = np.zeros(len(ids) + 1, np.int64), np.zeros(len(ids), np.int32)
+        check(self.L.ll_map_refine_run(self.h, 1 if transform_first else 0, len(ids), ptr(ids), ptr(a), ptr(b), leaf, ptr(offsets), ptr(status)),
+              "ll_map_refine_run")
+        self.status = status
+        return offsets, status
+
+    def refine(self, ids, poses_ori, poses_opm, leaf: float = 0.2, transform_first: bool = False) -> list:
+        """the corrected clouds [n, 4] (intensity 0) of the selected ids, in selection order: refine_pointcloud( ..., if_save = 0 ) per id,
+        or with transform_first refine_mapping's move-then-filter.  The status values of the run are left in self.status."""
+        offsets, _ = self.run(ids, poses_ori, poses_opm, leaf, transform_first)
+        flat = np.zeros((int(offsets[-1]), 4), np.float32)
+        check(self.L.ll_map_refine_fetch(self.h, ptr(flat), len(flat)), "ll_map_refine_fetch")
+        return [flat[offsets[s]:offsets[s + 1]].copy() for s in range(len(offsets) - 1)]
+
+    def merge(self, leaf: float = 0.2) -> np.ndarray:
+        """VoxelGrid over the last run's concatenated outputs (ceres_pose_graph_3d.hpp:577-578): the single corrected map [n, 4]"""
+        n, st = C.c_int64(0), C.c_int32(0)
+        check(self.L.ll_map_refine_merge(self.h, leaf, C.byref(n), C.byref(st)), "ll_map_refine_merge")
+        out = np.zeros((int(n.value), 4), np.float32)
+        check(self.L.ll_map_refine_fetch_merged(self.h, ptr(out), len(out)), "ll_map_refine_fetch_merged")
+        self.merge_status = int(st.value)
+        return out
+
+    def work(self) -> np.ndarray:
+        """test tap (ll_map_refine_work) on the last add / run / merge and its fetch: the host's enqueue calls (the sort and the scan one
+        each), host waits, bytes between host and device, points of the chain"""
+        out = np.zeros(4, np.int64)
+        check(self.L.ll_map_refine_work(self.h, ptr(out)), "ll_map_refine_work")
+        return out
+
+
 class Pose_graph:
     """The pose-graph optimiser (ll_pose_graph_*): Ceres_pose_graph_3d::pose_graph_optimization (ceres_pose_graph_3d.hpp:336-352) for
     any number of independent graphs in one launch and one host wait.  A graph is a dict: poses [N, 7] {qx, qy, qz, qw, tx, ty, tz}

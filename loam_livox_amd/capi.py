@@ -194,6 +194,18 @@ SYMBOLS = {
     "ll_pose_graph_destroy": (None, [_vp]),
     "ll_pose_graph_solve": (_i32, [_vp, C.POINTER(PoseGraphParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ll_pose_graph_work": (_i32, [_vp, _vp]),
+    "ll_map_refine_create": (_i32, [_i32, _i64, C.POINTER(_vp)]),
+    "ll_map_refine_destroy": (None, [_vp]),
+    "ll_map_refine_add_cloud": (_i32, [_vp, _vp, _i64, C.c_float, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32)]),
+    "ll_map_refine_add_stored": (_i32, [_vp, _vp, _i64, C.POINTER(_i64)]),
+    "ll_map_refine_size": (_i64, [_vp]),
+    "ll_map_refine_cloud": (_i32, [_vp, _i64, _vp, _i64, C.POINTER(_i64)]),
+    "ll_map_refine_affine": (_i32, [_vp, _vp, _vp, _vp]),
+    "ll_map_refine_run": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, C.c_float, _vp, _vp]),
+    "ll_map_refine_fetch": (_i32, [_vp, _vp, _i64]),
+    "ll_map_refine_merge": (_i32, [_vp, C.c_float, C.POINTER(_i64), C.POINTER(_i32)]),
+    "ll_map_refine_fetch_merged": (_i32, [_vp, _vp, _i64]),
+    "ll_map_refine_work": (_i32, [_vp, _vp]),
     "ll_history_enable_cell_map": (_i32, [_vp, _i64, C.c_float, _i32]),
     "ll_history_set_cell_map_async": (_i32, [_vp, _i32]),
     "ll_history_sync_cell_maps": (_i32, [_vp]),

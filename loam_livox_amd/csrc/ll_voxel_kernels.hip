@@ -16,21 +16,11 @@
 #include <hipcub/hipcub.hpp>
 
 #include "ll_voxel.h"
+#include "ll_ordered_float.h"  // f2ord, ord2f
 
 namespace ll {
 
 #define VOX_SENTINEL 0xffffffffffffffffull
-
-__device__ __forceinline__ unsigned int f2ord(float f)
-{
-    const unsigned int b = (unsigned int)__float_as_int(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned int o)
-{
-    const unsigned int b = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    return __int_as_float((int)b);
-}
 
 // mm[b][0..2] = min (ordered encoding), [3..5] = max, [6] = finite count
 __global__ __launch_bounds__(256) void vox_minmax_kernel(const float4 *in, const int *n, int stride, unsigned int *mm)

@@ -13,7 +13,12 @@ Mirrors hku-mars/loam_livox source/laser_mapping.hpp:
                 ends below map_alignment_inlier_threshold is reported as a loop with the alignment's transform (:1054-1068).
 pose_graph=True adds what the node does with an accepted loop (:948-960, 1058-1089): the chain constraints over pose3d_vec plus the one
 loop constraint, optimised on the device (api.Pose_graph); close_loop keeps poses_ori, poses_opm, constraints and pose_graph_summary.
-The map refinement and every file dump behind that point (:1069-1110) are out of scope.
+map_refinement=True (it needs pose_graph) adds the corrected map behind that (:943-946, 1091-1100): every key frame's accumulated cloud
+goes through api.Map_refine.add_cloud when the key frame is processed (VoxelGrid at surround_pointcloud_resolution; the host copy is
+dropped, the key frame keeps the id -- its index in keyframe_vec, as map_id_pc.size() is, when the store is the assembly's own; a
+shared handle gives whatever id comes next, and refine_map goes through the key frames' ids), and refine_map() re-projects every
+second one, newest first, with R_opm R_ori^T after a VoxelGrid at map_refinement_resolution: self.refined holds the
+/pc_aft_loop_closure messages.  The file dumps behind the pose graph (:1069-1110) are out of scope.
 
 A key frame is a SET OF CELLS of the full cell map, not a copy: the reference's key frames hold shared pointers to the map's cells, so
 what a key frame is analysed with is whatever those cells contain when it is processed (earlier and later scans included).  Here a key
@@ -27,7 +32,9 @@ cells, features and clouds) for the pairs that pass the similarity gates, and it
 max_points and doubles (ll_cellmap_reserve) when a scan would not fit, as the reference's heap-allocated cells grow.
 
 Differences from the node, by design: everything runs synchronously (the node's service thread polls every millisecond);
-m_accumulated_point_cloud (only consumed by the map refinement) is not kept.
+m_accumulated_point_cloud (only consumed by the map refinement) is kept with map_refinement=True alone: the full clouds of the scans the
+history's add rule let in wait in a host FIFO (m_laser_cloud_full_history, :1456, trimmed to maximum_history_size, :1480-1486), and the
+whole FIFO is appended to the BACK key frame at the moment the next one is opened, then cleared (:1545-1558).
 
 device_bank=True keeps the line and plane image of every processed key frame in a device-resident api.Keyframe_bank and asks for the
 similarities of a new key frame against ALL earlier key frames that pass the three scalar gates in one Keyframe_bank.match, instead of
@@ -53,6 +60,8 @@ class Maps_keyframe:
         self.m_ending_frame_idx = 0
         self.m_pose_q = np.array([0, 0, 0, 1], np.float64)
         self.m_pose_t = np.zeros(3, np.float64)
+        self.m_accumulated_point_cloud = []   # full clouds [n, 4] appended at :1552 (map_refinement); emptied once the cloud is on the device
+        self.cloud_id = None             # its id in the api.Map_refine store, once processed
         self.points = None               # xyz of its cells as they were when it was processed, in the full map's (cell, insertion) order
         self.analysis = None             # Cell_map.keyframe_images() of those cells
 
@@ -89,7 +98,9 @@ class Keyframe_assembly:
                  map_alignment_resolution: float = 0.2, map_alignment_inlier_threshold: float = 0.35,
                  map_alignment_maximum_icp_iteration: int = 2, scene_alignments_maximum_residual_block: int = 5000,
                  keyframe_max_points: int = 1 << 20, full_cell_map=None, avail_ratio_plane: float = 0.05, avail_ratio_line: float = 0.03,
-                 device_alignment: bool = False, device_bank: bool = False, bank=None, pose_graph=False):
+                 device_alignment: bool = False, device_bank: bool = False, bank=None, pose_graph=False,
+                 map_refinement=False, surround_pointcloud_resolution: float = 0.5, map_refinement_resolution: float = 0.2,
+                 maximum_history_size: int = 100):
         # parameter names and defaults: laser_mapping.hpp:698-710 (loop_closure/*), :686-687 (mapping/pt_cell_resolution, threshold_cell_revisit)
         self.device = device
         self.m_pt_cell_resolution = cell_resolution
@@ -139,6 +150,17 @@ class Keyframe_assembly:
         self.defer_pose_graph = False
         self.pending_loops = []         # accepted loops not yet closed (defer_pose_graph)
         self.poses_ori, self.poses_opm, self.constraints, self.pose_graph_summary = None, None, None, None
+        # map_refinement: False (off: nothing below is touched), True (an api.Map_refine of this assembly's own, created with the first
+        # key frame it processes) or a handle to share (anything with add_cloud / refine / merge; its owner closes it).
+        # surround_pointcloud_resolution: :696, the leaf of the add; map_refinement_resolution: :903, Mapping_refine's leaf.
+        if map_refinement and not pose_graph:
+            raise ValueError("map_refinement needs pose_graph: the corrected map is made from the optimised poses")
+        self.map_refinement = bool(map_refinement)
+        self._map_refine, self._owns_map_refine = (None, False) if map_refinement is True or not map_refinement else (map_refinement, False)
+        self.surround_pointcloud_resolution, self.map_refinement_resolution = surround_pointcloud_resolution, map_refinement_resolution
+        self.m_maximum_history_size = maximum_history_size
+        self.m_laser_cloud_full_history = deque()   # :1456
+        self.refined = None             # [(pc_idx, cloud [n, 4])] of the last refine_map: the /pc_aft_loop_closure messages, in their order
 
     def state(self) -> str:
         """the lists as tests/verbatim_build.py's harness prints them: open key frames frames:cells, waiting ones frames:cells:ending-index"""
@@ -159,11 +181,20 @@ class Keyframe_assembly:
         if self._pose_graph is not None and self._owns_pose_graph:
             self._pose_graph.close()
         self._pose_graph = None
+        if self._map_refine is not None and self._owns_map_refine:
+            self._map_refine.close()
+        self._map_refine = None
 
     # ---- laser_mapping.hpp:1524-1562 ------------------------------------------------------------------------------------------------
-    def add_scan(self, full_cloud_map_frame: np.ndarray, pose: np.ndarray, current_frame_index: int) -> np.ndarray:
+    def add_scan(self, full_cloud_map_frame: np.ndarray, pose: np.ndarray, current_frame_index: int, history_added: bool = True) -> np.ndarray:
         """One accepted scan.  full_cloud_map_frame: current_laser_cloud_full after pointcloudAssociateToMap; pose: m_q_w_curr /
-        m_t_w_curr as {qx, qy, qz, qw, tx, ty, tz}.  Returns the touched cells (cell_vec)."""
+        m_t_w_curr as {qx, qy, qz, qw, tx, ty, tz}; history_added: whether the history's add rule let the scan in (:1446-1448), which is
+        what puts its full cloud into m_laser_cloud_full_history (read with map_refinement alone).  Returns the touched cells (cell_vec)."""
+        if self.map_refinement:   # :1456, :1480-1486 -- before the key-frame step of the same scan
+            if history_added:
+                self.m_laser_cloud_full_history.append(np.array(full_cloud_map_frame, np.float32).reshape(-1, 4))
+            if len(self.m_laser_cloud_full_history) > self.m_maximum_history_size:
+                self.m_laser_cloud_full_history.popleft()
         full = self.m_pt_cell_map_full
         if hasattr(full, "reserve"):  # the reference's map grows on the heap: double the device map's capacity when this scan would not fit
             need = full.stats()[1] + len(full_cloud_map_frame)
@@ -184,6 +215,9 @@ class Keyframe_assembly:
         if not self.m_keyframe_of_updating_list:
             self.m_keyframe_of_updating_list.append(Maps_keyframe())
         elif self.m_keyframe_of_updating_list[-1].m_accumulate_frames >= self.m_para_scans_between_two_keyframe:
+            if self.map_refinement:   # :1550-1553, 1558: the whole FIFO to the back key frame, then cleared
+                self.m_keyframe_of_updating_list[-1].m_accumulated_point_cloud.extend(self.m_laser_cloud_full_history)
+                self.m_laser_cloud_full_history.clear()
             if len(self.m_keyframe_need_precession_list) > self.m_loop_closure_maximum_keyframe_in_wating_list:
                 self.m_keyframe_need_precession_list.popleft()
             self.m_keyframe_of_updating_list.append(Maps_keyframe())
@@ -275,6 +309,10 @@ class Keyframe_assembly:
             last.analysis = cm.keyframe_images()
         last.points = cm.dump()[0] if hasattr(cm, "dump") else None
         _close(cm)
+        if self.map_refinement:   # :943-946: down_sample_filter over the accumulated cloud; map_id_pc's key is its size
+            acc = np.concatenate(last.m_accumulated_point_cloud) if last.m_accumulated_point_cloud else np.zeros((0, 4), np.float32)
+            last.cloud_id = self.map_refine_handle().add_cloud(acc, self.surround_pointcloud_resolution)[0]
+            last.m_accumulated_point_cloud = []
         self.keyframe_vec.append(last)
         self.pose3d_vec.append((last.m_pose_q.copy(), last.m_pose_t.copy()))
         n_kf = len(self.keyframe_vec)
@@ -326,6 +364,37 @@ class Keyframe_assembly:
         self.poses_ori, self.poses_opm = graph["poses"].copy(), np.asarray(poses_opm, np.float64).reshape(-1, 7).copy()   # pose3d_map_ori, temp_pose_3d_map
         self.constraints = dict(ab=graph["ab"].copy(), meas=graph["meas"].copy())                                           # constrain_vec_temp
         self.pose_graph_summary = dict(summary)
+        if self.map_refinement:
+            self.refine_map()
+
+    # ---- laser_mapping.hpp:1091-1100; ceres_pose_graph_3d.hpp:368-538 -------------------------------------------------------------------
+    def map_refine_handle(self):
+        """the store of map_refinement: the one handed in, else this assembly's own, created on first use"""
+        if self._map_refine is None:
+            from .api import Map_refine
+            self._map_refine, self._owns_map_refine = Map_refine(device=self.device), True
+        return self._map_refine
+
+    def refine_map(self) -> list:
+        """The node's loop at :1091-1100: refine_pointcloud( map_id_pc, pose3d_map_ori, temp_pose_3d_map, pc_idx, 0 ) for pc_idx = K - 1,
+        K - 3, ... >= 0 -- one run on the device for all of them.  Keeps and returns self.refined = [(pc_idx, cloud)]."""
+        if not self.map_refinement or self.poses_opm is None:
+            raise ValueError("refine_map needs map_refinement=True and a closed loop (close_loop / take_solution)")
+        ids = list(range(len(self.poses_ori) - 1, -1, -2))
+        clouds = self.map_refine_handle().refine([self.keyframe_vec[k].cloud_id for k in ids], self.poses_ori[ids], self.poses_opm[ids],
+                                                 self.map_refinement_resolution, False)
+        self.refined = list(zip(ids, clouds))
+        return self.refined
+
+    def refined_mapping(self) -> np.ndarray:
+        """Mapping_refine::refine_mapping's in-memory overload over ALL key frames of the closed loop (move, then VoxelGrid,
+        ceres_pose_graph_3d.hpp:511-533), concatenated and filtered once more (:577-578): the single corrected map [n, 4]"""
+        if not self.map_refinement or self.poses_opm is None:
+            raise ValueError("refined_mapping needs map_refinement=True and a closed loop (close_loop / take_solution)")
+        ids = list(range(len(self.poses_ori)))
+        h = self.map_refine_handle()
+        h.refine([self.keyframe_vec[k].cloud_id for k in ids], self.poses_ori, self.poses_opm, self.map_refinement_resolution, True)
+        return h.merge(self.map_refinement_resolution)
 
     def close_loop(self, loop) -> np.ndarray:
         """Pose-graph optimisation of an accepted loop: builds loop_graph( loop ), solves it on the device and keeps poses_ori,
@@ -395,7 +464,7 @@ class Keyframe_assembly:
                             self.pending_loops.append(loop)
                         else:
                             self.close_loop(loop)
-                    self.if_end = True   # :1108 (the map refinement and the dumps in between are out of scope)
+                    self.if_end = True   # :1108 (the dumps in between are out of scope)
                     break
                 his += 5 + 1   # :1111-1114
                 continue

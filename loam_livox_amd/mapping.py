@@ -7,8 +7,8 @@ This is the unit of BASELINE config C4 (one sequence per GPU, local map growth).
     and registers against whichever buffer is newest (laser_mapping.hpp:568-594, 1395-1403), which makes its output
     depend on thread timing;
   * no ROS or logging; the full-cloud cell map, the key frames and the front half of loop detection are optional
-    (loop_closure_if_enable, keyframes.py), with loop_closure["pose_graph"] the pose-graph optimisation of an accepted loop; the map
-    refinement and the file dumps behind it are out of scope.
+    (loop_closure_if_enable, keyframes.py), with loop_closure["pose_graph"] the pose-graph optimisation of an accepted loop and
+    loop_closure["map_refinement"] the corrected key-frame clouds behind it (keyframes.refined); the file dumps are out of scope.
 """
 from __future__ import annotations
 
@@ -97,7 +97,7 @@ class Laser_mapping:
         if loop_closure_if_enable:
             from .keyframes import Keyframe_assembly
             self.keyframes = Keyframe_assembly(device=device, cell_resolution=cell_resolution, threshold_cell_revisit=threshold_cell_revisit,
-                                               **(loop_closure or {}))
+                                               **{"maximum_history_size": maximum_history_size, **(loop_closure or {})})
 
     def close(self):
         for h in tuple(f for f in self._fe_pair if f is not None) + (self.reg, self.map, self.vox[0], self.vox[1], self.history):
@@ -105,13 +105,14 @@ class Laser_mapping:
         if self.keyframes is not None:
             self.keyframes.close()
 
-    def _keyframe_step(self, full_xyzi: np.ndarray) -> None:
+    def _keyframe_step(self, full_xyzi: np.ndarray, history_added: bool = True) -> None:
         """laser_mapping.hpp:1442 + 1524-1562 (+ the detector's loop body for whatever key frame that closed): the scan's full cloud,
-        moved into the map frame with the accepted pose, goes into the full cell map and the open key frames"""
+        moved into the map frame with the accepted pose, goes into the full cell map and the open key frames.  history_added: what the
+        history's add answered for this scan (:1446-1448) -- the scan's full cloud joins m_laser_cloud_full_history with it (:1456)"""
         full = np.ascontiguousarray(full_xyzi, np.float32)
         full = full[np.isfinite(full[:, :3]).all(axis=1)]
         cloud = self.reg.pointcloudAssociateToMap(full, self.pose) if len(full) else full
-        self.keyframes.add_scan(cloud, self.pose, self.m_current_frame_index)
+        self.keyframes.add_scan(cloud, self.pose, self.m_current_frame_index, history_added=history_added)
         self.loops += self.keyframes.process_waiting()
 
     def sync(self) -> None:
@@ -205,15 +206,15 @@ class Laser_mapping:
             return 0
         self.history.set_gate_pose(self.pose)  # m_q_w_curr is still the pre-registration pose at LM:1439-1451
         if self.m_if_input_downsample_mode:
-            self.history.add_voxel(self.vox[0], self.vox[1], 0, pc[0], self.history_add_t_step, self.history_add_angle_step)
+            added = self.history.add_voxel(self.vox[0], self.vox[1], 0, pc[0], self.history_add_t_step, self.history_add_angle_step)
         elif self._spin:
-            self.history.add_spin(fe, 0, pc[0], self.history_add_t_step, self.history_add_angle_step)
+            added = self.history.add_spin(fe, 0, pc[0], self.history_add_t_step, self.history_add_angle_step)
         else:
-            self.history.add_fe(fe, 0, pc[0], self.history_add_t_step, self.history_add_angle_step)
+            added = self.history.add_fe(fe, 0, pc[0], self.history_add_t_step, self.history_add_angle_step)
         self.pose = pc[0].copy()  # :1496-1500
         if self.keyframes is not None:
             tk = time.perf_counter()
-            self._keyframe_step(np.asarray(xyzi, np.float32)[fe.get_features(0.0, 1.0)["full_idx"]])  # /pc2_full of this scan
+            self._keyframe_step(np.asarray(xyzi, np.float32)[fe.get_features(0.0, 1.0)["full_idx"]], bool(added))  # /pc2_full of this scan
             self.full_map_s += time.perf_counter() - tk
         t2 = time.perf_counter()
         if self.m_matching_mode:  # update_buff_for_matching (service thread in the node), synchronous here
@@ -261,9 +262,9 @@ class Laser_mapping:
             return 0
         self.history.set_gate_pose(self.pose)  # m_q_w_curr is still the pre-registration pose at LM:1439-1451
         self.pose = np.array(reg.m_pose_w_curr, np.float64)
-        self.history.add(corner_stack, surf_stack, self.pose, self.history_add_t_step, self.history_add_angle_step)
+        added = self.history.add(corner_stack, surf_stack, self.pose, self.history_add_t_step, self.history_add_angle_step)
         if self.keyframes is not None:
-            self._keyframe_step(full)
+            self._keyframe_step(full, bool(added))
         self.map_sizes = self.history.refresh(self.map)
         return 1
 
@@ -324,7 +325,9 @@ class Laser_mapping_batch:
     a round of key-frame processing is then the analysis half of every slot, one Keyframe_bank.match over all slots' pairs, and the
     walk half of every slot -- the same logs and loops, float for float.  loop_closure["pose_graph"]=True (off by default): the loop
     owns ONE api.Pose_graph (pose_graph) for its S assemblies; the loops the slots accept in a round are closed -- their pose graphs
-    optimised -- in one Pose_graph.solve, and every assembly keeps its poses_ori, poses_opm, constraints and pose_graph_summary."""
+    optimised -- in one Pose_graph.solve, and every assembly keeps its poses_ori, poses_opm, constraints and pose_graph_summary.
+    loop_closure["map_refinement"] is refused with ValueError: the refinement needs every accepted scan's full cloud in a FIFO
+    (laser_mapping.hpp:1456), and this loop's full clouds never reach the host; a device FIFO for them is left to a later change."""
 
     def __init__(self, n_sequences: int, refresh_threads: int | None = None, batched_history: bool = False, cell_maps: bool = False,
                  cell_matching: bool = False, full_maps: bool = False, key_frames: bool = False, **kw):
@@ -344,6 +347,8 @@ class Laser_mapping_batch:
                              "maps on the batched history)")
         if a["loop_closure_if_enable"]:
             raise ValueError("loop_closure_if_enable must be 0 in the batched loop")
+        if (a["loop_closure"] or {}).get("map_refinement"):
+            raise ValueError("map_refinement is not available in the batched loop: its full clouds never reach the host")
         if a["keep_cell_maps"]:
             raise ValueError("keep_cell_maps is not offered by the batched loop (cell_maps=True keeps them on the batched history)")
         if cell_maps and not batched_history:

@@ -724,6 +724,34 @@ class History_batch {
         if (n_points) *n_points = n_pts;
         return n_found;
     }
+    // The scan log: m_laser_cloud_full_history of every slot on the device (laser_mapping.hpp:1456, 1480-1486, 1545-1558).  It needs
+    // the full maps (ll_history_batch_enable_full_maps); log_full follows the ll_history_batch_append_full_fe of the same step with
+    // that call's extractor.  Thin wrappers of the C ABI, which documents them.
+    void enable_scan_log(int maximum_history_size, int64_t initial_scans)
+    {
+        check(ll_history_batch_enable_scan_log(h_, maximum_history_size, initial_scans), "ll_history_batch_enable_scan_log");
+    }
+    void log_full(ll_fe *fe, const int32_t *active = nullptr) { check(ll_history_batch_log_full_fe(h_, fe, active), "ll_history_batch_log_full_fe"); }
+    int64_t hand_over(int sequence)
+    {
+        int64_t id = 0;
+        check(ll_history_batch_scan_log_hand_over(h_, sequence, &id), "ll_history_batch_scan_log_hand_over");
+        return id;
+    }
+    void drop_groups(const std::vector<int64_t> &group_ids)
+    {
+        check(ll_history_batch_scan_log_drop(h_, (int64_t)group_ids.size(), group_ids.empty() ? nullptr : group_ids.data()), "ll_history_batch_scan_log_drop");
+    }
+    // the group's points {x, y, z, intensity}, scan after scan
+    std::vector<float> read_group(int64_t group_id)
+    {
+        int64_t n = 0;
+        check(ll_history_batch_scan_log_read(h_, group_id, nullptr, 0, &n), "ll_history_batch_scan_log_read");
+        std::vector<float> v((size_t)n * 4);
+        if (n > 0) check(ll_history_batch_scan_log_read(h_, group_id, v.data(), n, &n), "ll_history_batch_scan_log_read");
+        return v;
+    }
+    void scan_log_work(int64_t out[4]) { check(ll_history_batch_scan_log_work(h_, out), "ll_history_batch_scan_log_work"); }
 
    private:
     ll_history_batch *h_ = nullptr;
@@ -1709,6 +1737,31 @@ class Mapping_refine {
         check(ll_map_refine_fetch_merged(h_, v.data(), n), "ll_map_refine_fetch_merged");
         xyzi_to_cloud(v.data(), (int)n, out);
         return out;
+    }
+    // ll_map_refine_add_logged: request r is the concatenation of the logged scans of groups_per_request[r] (ids of
+    // History_batch::hand_over), filtered at `leaf` into the store, device to device; the groups are consumed.  Returns the store's ids
+    // (for ll_map_refine_run on handle()); n_kept and status when given.
+    std::vector<int64_t> add_logged(History_batch &batch, const std::vector<std::vector<int64_t> > &groups_per_request, float leaf,
+                                    std::vector<int64_t> *n_kept = nullptr, std::vector<int32_t> *status = nullptr)
+    {
+        if (!h_) {
+            runtime_hints();
+            check(ll_map_refine_create(device_, initial_points_, &h_), "ll_map_refine_create");
+        }
+        const size_t R = groups_per_request.size();
+        std::vector<int64_t> off(R + 1, 0), gids, ids(R > 0 ? R : 1, -1), kept(R > 0 ? R : 1, 0);
+        std::vector<int32_t> st(R > 0 ? R : 1, 0);
+        for (size_t r = 0; r < R; r++) {
+            gids.insert(gids.end(), groups_per_request[r].begin(), groups_per_request[r].end());
+            off[r + 1] = (int64_t)gids.size();
+        }
+        check(ll_map_refine_add_logged(h_, batch.handle(), (int64_t)R, off.data(), gids.empty() ? nullptr : gids.data(), leaf, ids.data(), kept.data(),
+                                       st.data()),
+              "ll_map_refine_add_logged");
+        ids.resize(R), kept.resize(R), st.resize(R);
+        if (n_kept) *n_kept = kept;
+        if (status) *status = st;
+        return ids;
     }
     // test tap (ll_map_refine_work) on the last run and its fetch
     void work(int64_t out[4]) { check(ll_map_refine_work(h_, out), "ll_map_refine_work"); }

@@ -516,6 +516,36 @@ int ll_history_batch_append_full_fe(ll_history_batch *h, ll_fe *fe, const int32_
                                     int64_t *n_touched);
 int ll_history_batch_full_touched(ll_history_batch *h, int32_t sequence, int32_t *cell_ijk, int64_t capacity_cells, int64_t *n);
 int ll_history_batch_full_map_work(ll_history_batch *h, int64_t out[4]);
+/* The scan log: m_laser_cloud_full_history of every slot kept on the device (laser_mapping.hpp:1456, 1480-1486, 1545-1558) -- the full
+ * cloud, in the map frame, of every scan the history's add rule let in, which the key frames accumulate and the map refinement
+ * filters (ll_map_refine_add_logged).  It needs the full maps.
+ *   storage     a pool of blocks, one scan per block (max_points_per_frame float4, 384 KB at 24 000 points), allocated in chunks of
+ *               initial_scans blocks that never move: the pool grows by another chunk and nothing is copied.  The free list, the
+ *               slots' FIFOs and the groups are host bookkeeping.
+ *   log_full_fe follows the append_full_fe of the same step, whose slots and selection sizes the handle remembers: every slot that
+ *               is named (active NULL: all) and was active in that append gets a block; ONE launch for all slots copies x, y, z
+ *               from the gathered clouds -- the very floats the full map received -- and the intensity from the scan through the
+ *               extractor's full selection, which is what pointcloudAssociateToMap leaves in column 3; the block joins the slot's
+ *               FIFO (:1456); then the FIFO of every slot of the append, named or not, is trimmed to maximum_history_size
+ *               (:1480-1486).  No host wait; four enqueue calls whatever n_sequences is (none when every selection is empty); the
+ *               extractor's stream is made to wait for the launch, so the next upload cannot replace a scan being read.
+ *               The marker the append's gather writes for a refused point (non-finite coordinates, intensity 0) stays in the block:
+ *               the VoxelGrid of ll_map_refine_add_logged drops it, so a filtered cloud is that of the host route, which removes
+ *               such points first -- except for a pass-through selection (status 1), whose output is its input, markers included.
+ *   hand_over   the slot's whole FIFO becomes a group -- an ordered list of scans under a 64-bit id that is never reused -- and the
+ *               FIFO is empty afterwards (:1550-1553, 1558).  Host work only; an empty FIFO gives an empty group.
+ *   drop        the groups' blocks go back to the free list (a key frame pushed out of the waiting list; close).
+ *   read        test tap and debug read: the group's points in order; xyzi NULL: their number alone.
+ *   work        out[0] enqueue calls and out[1] host waits of the last log call, out[2] blocks in use, out[3] blocks allocated.
+ * Refused with the log untouched: null arguments, a call before the enable, a second enable, the enable before the full maps, a log
+ * without an append or a second log for one append, another extractor than the append's, a sequence out of range, an unknown,
+ * dropped or consumed group, a group named twice in one drop, a capacity below the group's size. */
+int ll_history_batch_enable_scan_log(ll_history_batch *h, int32_t maximum_history_size, int64_t initial_scans);
+int ll_history_batch_log_full_fe(ll_history_batch *h, ll_fe *fe, const int32_t *active);
+int ll_history_batch_scan_log_hand_over(ll_history_batch *h, int32_t sequence, int64_t *group_id);
+int ll_history_batch_scan_log_drop(ll_history_batch *h, int64_t n, const int64_t *group_ids);
+int ll_history_batch_scan_log_read(ll_history_batch *h, int64_t group_id, float *xyzi, int64_t capacity_points, int64_t *n);
+int ll_history_batch_scan_log_work(ll_history_batch *h, int64_t out[4]);
 /* Host arithmetic only (no device needed): the geometry ll_map_upload and both refreshes give the search grid over the bounding
  * box {min x, y, z, max x, y, z} of a cloud's finite points (min > max: no finite point) with cells of cell_size metres.  The
  * cell grows by 1.5 x until the dense table has at most 2^27 cells. */
@@ -836,6 +866,16 @@ typedef struct ll_map_refine ll_map_refine;
 int ll_map_refine_create(int32_t device, int64_t initial_points, ll_map_refine **out);
 void ll_map_refine_destroy(ll_map_refine *h);
 int ll_map_refine_add_cloud(ll_map_refine *h, const float *xyzi, int64_t n, float leaf, int64_t *id, int64_t *n_kept, int32_t *status);
+/* add_cloud for several key frames at once, device to device, out of the scan log of a batched match buffer
+ * (ll_history_batch_enable_scan_log): request r is the concatenation, in order, of the scans of the groups
+ * group_ids[group_off[r] .. group_off[r + 1]] (m_accumulated_point_cloud, laser_mapping.hpp:943-946).  One gather launch puts all
+ * requests into the staging array, one filter chain over n_req selections puts them into the store under consecutive ids; ONE host
+ * wait and a number of enqueue calls that does not depend on n_req; the two handles' streams are ordered with an event.  ids, n_kept,
+ * status and the stored clouds are bit for bit what add_cloud gives for the same points.  The groups are consumed: their blocks are
+ * free afterwards.  Refused before anything is enqueued, store and log untouched: null arguments, a scan log that is not enabled or
+ * lives on another device, an unknown or consumed group, a group named twice, and add_cloud's limits. */
+int ll_map_refine_add_logged(ll_map_refine *h, ll_history_batch *hb, int64_t n_req, const int64_t *group_off, const int64_t *group_ids,
+                             float leaf, int64_t *ids, int64_t *n_kept, int32_t *status);
 /* a cloud that is filtered already (a host-side map_id_pc entry, the adapter's Mapping_refine): stored as it is, one upload, one wait */
 int ll_map_refine_add_stored(ll_map_refine *h, const float *xyzi, int64_t n, int64_t *id);
 /* clouds held (the next id) */

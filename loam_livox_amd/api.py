@@ -612,6 +612,63 @@ class History_buffer_batch:
         check(self.L.ll_history_batch_full_map_work(self.h, ptr(out)), "ll_history_batch_full_map_work")
         return out
 
+    def enable_scan_log(self, maximum_history_size: int = 100, initial_scans: int | None = None) -> None:
+        """the scan log of every slot (m_laser_cloud_full_history, laser_mapping.hpp:1456, kept on the device): fed by log_full behind
+        every append_full, trimmed to maximum_history_size scans per slot; it needs enable_full_maps.  The pool of one-scan blocks
+        starts with initial_scans of them (n_sequences unless given) and grows by as many"""
+        first = self.n_sequences if initial_scans is None else int(initial_scans)
+        check(self.L.ll_history_batch_enable_scan_log(self.h, int(maximum_history_size), first), "ll_history_batch_enable_scan_log")
+
+    def log_full(self, fe: "Livox_laser", active=None) -> None:
+        """behind the append_full of the same step: the full cloud of every slot named in `active` (all, when None) that the append took
+        joins the slot's FIFO, and every FIFO of the append's slots is trimmed (:1456, 1480-1486).  One launch, no host wait."""
+        S = self.n_sequences
+        act = None if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.int32).reshape(S)
+        check(self.L.ll_history_batch_log_full_fe(self.h, fe.h, ptr(act)), "ll_history_batch_log_full_fe")
+
+    def hand_over(self, sequence: int) -> int:
+        """the slot's whole FIFO as a group (its id); the FIFO is empty afterwards (:1550-1553, 1558).  Host work only."""
+        gid = C.c_int64(0)
+        check(self.L.ll_history_batch_scan_log_hand_over(self.h, int(sequence), C.byref(gid)), "ll_history_batch_scan_log_hand_over")
+        return int(gid.value)
+
+    def drop_groups(self, group_ids) -> None:
+        """the groups' blocks back to the free list"""
+        ids = np.ascontiguousarray(group_ids, np.int64).reshape(-1)
+        check(self.L.ll_history_batch_scan_log_drop(self.h, len(ids), ptr(ids) if len(ids) else None), "ll_history_batch_scan_log_drop")
+
+    def read_group(self, group_id: int) -> np.ndarray:
+        """test tap and debug read: the group's points [n, 4], scan after scan"""
+        n = C.c_int64(0)
+        check(self.L.ll_history_batch_scan_log_read(self.h, int(group_id), None, 0, C.byref(n)), "ll_history_batch_scan_log_read")
+        out = np.zeros((int(n.value), 4), np.float32)
+        check(self.L.ll_history_batch_scan_log_read(self.h, int(group_id), ptr(out), len(out), C.byref(n)), "ll_history_batch_scan_log_read")
+        return out
+
+    def scan_log_work(self) -> np.ndarray:
+        """test tap (ll_history_batch_scan_log_work): enqueue calls and host waits of the last log_full, blocks in use, blocks allocated"""
+        out = np.zeros(4, np.int64)
+        check(self.L.ll_history_batch_scan_log_work(self.h, ptr(out)), "ll_history_batch_scan_log_work")
+        return out
+
+    def scan_log(self, sequence: int) -> "Scan_log_slot":
+        return Scan_log_slot(self, int(sequence))
+
+
+class Scan_log_slot:
+    """Slot s of a History_buffer_batch's scan log, as a Keyframe_assembly sees it (scan_log=): the FIFO lives in the log and the
+    owner of the batch makes the push for all slots, so the view only hands the FIFO over and drops the groups nobody will read."""
+
+    def __init__(self, batch: "History_buffer_batch", sequence: int):
+        self.batch, self.sequence = batch, sequence
+
+    def hand_over(self) -> int:
+        return self.batch.hand_over(self.sequence)
+
+    def drop(self, group_ids) -> None:
+        if len(group_ids):
+            self.batch.drop_groups(group_ids)
+
 
 class Cell_map_slot:
     """One cell map of one slot of a History_buffer_batch, read the way a Cell_map is: stats(), dump() and device_view(device) have
@@ -989,6 +1046,21 @@ class Map_refine:
         cid, kept, st = C.c_int64(-1), C.c_int64(0), C.c_int32(0)
         check(self.L.ll_map_refine_add_cloud(self.h, ptr(c), len(c), leaf, C.byref(cid), C.byref(kept), C.byref(st)), "ll_map_refine_add_cloud")
         return int(cid.value), int(kept.value), int(st.value)
+
+    def add_logged(self, batch: "History_buffer_batch", groups_per_request, leaf: float = 0.5):
+        """add_cloud for several key frames at once, device to device: request r is the concatenation of the logged scans of the groups
+        groups_per_request[r] (ids of batch.hand_over) -- one gather, one filter chain, one host wait for all of them.  The groups are
+        consumed.  Returns (ids [R], points kept [R], status [R]); bit for bit what add_cloud gives for the same points."""
+        if not isinstance(batch, History_buffer_batch):
+            raise TypeError("add_logged reads the scan log of a History_buffer_batch")
+        lists = [np.ascontiguousarray(g, np.int64).reshape(-1) for g in groups_per_request]
+        R = len(lists)
+        off = np.zeros(R + 1, np.int64)
+        off[1:] = np.cumsum([len(g) for g in lists])
+        gids = np.ascontiguousarray(np.concatenate(lists)) if R and off[-1] else None
+        ids, kept, st = np.zeros(max(R, 1), np.int64), np.zeros(max(R, 1), np.int64), np.zeros(max(R, 1), np.int32)
+        check(self.L.ll_map_refine_add_logged(self.h, batch.h, R, ptr(off), ptr(gids), leaf, ptr(ids), ptr(kept), ptr(st)), "ll_map_refine_add_logged")
+        return ids[:R], kept[:R], st[:R]
 
     def add_stored(self, cloud) -> int:
         """the id of a cloud [n, 4] stored as it is: one that is filtered already (a map_id_pc entry kept on the host)"""

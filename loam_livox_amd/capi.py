@@ -157,6 +157,12 @@ SYMBOLS = {
     "ll_history_batch_append_full_fe": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
     "ll_history_batch_full_touched": (_i32, [_vp, _i32, _vp, _i64, _vp]),
     "ll_history_batch_full_map_work": (_i32, [_vp, _vp]),
+    "ll_history_batch_enable_scan_log": (_i32, [_vp, _i32, _i64]),
+    "ll_history_batch_log_full_fe": (_i32, [_vp, _vp, _vp]),
+    "ll_history_batch_scan_log_hand_over": (_i32, [_vp, _i32, C.POINTER(_i64)]),
+    "ll_history_batch_scan_log_drop": (_i32, [_vp, _i64, _vp]),
+    "ll_history_batch_scan_log_read": (_i32, [_vp, _i64, _vp, _i64, C.POINTER(_i64)]),
+    "ll_history_batch_scan_log_work": (_i32, [_vp, _vp]),
     "ll_history_batch_extract_cells": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ll_history_batch_extract_work": (_i32, [_vp, _vp]),
     "ll_map_grid_geometry": (_i32, [_vp, _f, _vp, _vp, _vp]),
@@ -197,6 +203,7 @@ SYMBOLS = {
     "ll_map_refine_create": (_i32, [_i32, _i64, C.POINTER(_vp)]),
     "ll_map_refine_destroy": (None, [_vp]),
     "ll_map_refine_add_cloud": (_i32, [_vp, _vp, _i64, C.c_float, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32)]),
+    "ll_map_refine_add_logged": (_i32, [_vp, _vp, _i64, _vp, _vp, C.c_float, _vp, _vp, _vp]),
     "ll_map_refine_add_stored": (_i32, [_vp, _vp, _i64, C.POINTER(_i64)]),
     "ll_map_refine_size": (_i64, [_vp]),
     "ll_map_refine_cloud": (_i32, [_vp, _i64, _vp, _i64, C.POINTER(_i64)]),

@@ -78,6 +78,7 @@ extern "C" void ll_history_batch_destroy(ll_history_batch *h)
         if (p) (void)hipFree(p);
     for (int k = 0; k < 2; k++) hb_store_free(h->st[k]);
     hb_full_free(h);
+    hb_scan_log_free(h);
     for (const CmbDev &q : h->cq) {
         void *ptrs[] = {q.csel, q.cflag, q.crank, q.ccell, q.key, q.key2, q.val, q.val2, q.hflag, q.hrank, q.head, q.leaf, q.leaf_cell, q.out, q.tmp};
         for (void *p : ptrs)

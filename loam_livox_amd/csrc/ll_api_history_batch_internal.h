@@ -5,6 +5,7 @@
 #include "ll_cellmap_batch_extract_core.h"
 #include "ll_cellmatch_batch.h"
 #include "ll_fullmap_batch.h"
+#include "ll_scan_log.h"
 
 struct HbArena {
     int device = 0;
@@ -31,6 +32,20 @@ struct __attribute__((visibility("hidden"))) HbStore {
     int *hp_n = nullptr;           // [S] points per slot of the call (filtered counts / full-selection sizes)
     int *hp_coff = nullptr, *hp_poff = nullptr;  // [S + 1] each
     int *hp_counts = nullptr;      // [4]
+};
+
+// The scan log (ll_history_batch_enable_scan_log, ll_api_history_batch_scanlog.hip): the book of ll_scan_log.h, the chunks its blocks
+// lie in, and what the last append_full_fe left for the log call behind it.
+struct __attribute__((visibility("hidden"))) HbScanLog {
+    bool on = false;
+    SlBook book;
+    std::vector<float4 *> chunks;      // chunk c holds blocks c * chunk_blocks ..; never moved, freed with the handle
+    SlSlot *hp_tab = nullptr, *d_tab = nullptr;  // [S] the table of a log call, pinned / device
+    hipEvent_t ev = nullptr;           // behind the last log kernel: the extractor's stream waits for it before a scan is replaced
+    bool pending = false;              // an append_full_fe came and no log call yet
+    const ll_fe *fe = nullptr;         // that append's extractor
+    std::vector<int> n;                // [S] that append's selection sizes, -1 for a slot it left out
+    int64_t work[2] = {0, 0};          // enqueue calls and host waits of the last log call
 };
 
 struct ll_history_batch {
@@ -86,6 +101,7 @@ struct ll_history_batch {
     int *hp_cx_out = nullptr, *d_cx_out = nullptr;      // [4 S + 2]
     CxbDst *hp_cx_dst = nullptr, *d_cx_dst = nullptr;   // [S]
     int64_t cx_work[4] = {0, 0, 0, 0};       // ll_history_batch_extract_work
+    HbScanLog sl;
 };
 
 #pragma GCC visibility push(hidden)  // what follows is shared by the units and no part of the library's surface
@@ -140,5 +156,13 @@ int hb_check_maps(const char *where, const ll_history_batch *h, ll_map *const *m
 void hb_sizes_out(const ll_history_batch *h, int64_t *n_map_corner, int64_t *n_map_surf);
 int hb_refresh_second_half(const char *where, ll_history_batch *h, ll_map *const *maps, const int max_cat[2], const int cat_stride[2],
                            int64_t *n_map_corner, int64_t *n_map_surf);
+// ---- defined in the scan-log unit
+void hb_scan_log_free(ll_history_batch *h);
+// where a block of the scan log lies
+inline float4 *hb_scan_log_block(const ll_history_batch *h, int block)
+{
+    const int per = h->sl.book.chunk_blocks;
+    return h->sl.chunks[(size_t)(block / per)] + (size_t)(block % per) * (size_t)h->max_pts;
+}
 
 #pragma GCC visibility pop

@@ -437,6 +437,11 @@ extern "C" int ll_history_batch_append_full_fe(ll_history_batch *h, ll_fe *fe, c
         n_touched[s] = (int64_t)(list.size() / 3);
     }
     if (n_new > 0) h->fm_dirty = true;
+    if (h->sl.on) {  // what ll_history_batch_log_full_fe logs: this call's slots and sizes, out of t.xf as it stands now
+        for (int s = 0; s < S; s++) h->sl.n[(size_t)s] = !on(s) ? -1 : (in_n[s] > 0 ? in_n[s] : 0);
+        h->sl.fe = fe;
+        h->sl.pending = true;
+    }
     h->fm_work[0] = enq;
     h->fm_work[1] = waits;
     return 0;

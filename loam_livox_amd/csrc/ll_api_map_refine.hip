@@ -1,7 +1,8 @@
 // ll_api_map_refine.hip -- the key-frame map refinement of the C ABI (ll_map_refine_*): the key frames' accumulated clouds stay on
 // the device in one ragged store, and "these key frames into their corrected frames, filtered" is one launch chain and one host wait
 // for any number of them (ll_map_refine_kernels.hip).  Mapping_refine of the reference, ceres_pose_graph_3d.hpp:368-538.
-#include "ll_api_internal.h"
+// ll_map_refine_add_logged takes the clouds of several key frames out of the scan log of a batched match buffer, device to device.
+#include "ll_api_history_batch_internal.h"
 #include "ll_map_refine.h"
 
 struct ll_map_refine {
@@ -21,6 +22,10 @@ struct ll_map_refine {
     char *hp = nullptr;                 // page-locked staging: selections and work list in, offsets and status out
     size_t hp_bytes = 0;
     int64_t work[4] = {0, 0, 0, 0};
+    // ll_map_refine_add_logged: the gather's work list (page-locked / device) and the event that orders this stream behind the log's
+    SlCopy *hp_gwork = nullptr, *d_gwork = nullptr;
+    int64_t gwork_cap = 0;
+    hipEvent_t ev_log = nullptr;
 };
 
 static const int64_t kMrMaxPoints = 0x7ffffffeLL;  // the store, like a run, stays below 2^31 points
@@ -35,6 +40,9 @@ extern "C" void ll_map_refine_destroy(ll_map_refine *h)
     for (void *p : dev)
         if (p) (void)hipFree(p);
     if (h->hp) (void)hipHostFree(h->hp);
+    if (h->d_gwork) (void)hipFree(h->d_gwork);
+    if (h->hp_gwork) (void)hipHostFree(h->hp_gwork);
+    if (h->ev_log) (void)hipEventDestroy(h->ev_log);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -168,6 +176,94 @@ extern "C" int ll_map_refine_add_cloud(ll_map_refine *h, const float *xyzi, int6
     *id = (int64_t)h->off.size() - 2;
     if (n_kept) *n_kept = offsets[1];
     if (status) *status = st;
+    return 0;
+}
+
+// room for the work list of a gather of n_work items (the stream is idle)
+static int mr_gather_room(ll_map_refine *h, int64_t n_work, const char *where)
+{
+    if (!h->ev_log && hipEventCreateWithFlags(&h->ev_log, hipEventDisableTiming) != hipSuccess) return set_err(where, "allocation failed");
+    if (n_work <= h->gwork_cap) return 0;
+    const int64_t cap = std::max<int64_t>(2 * h->gwork_cap, n_work);
+    if (h->d_gwork) (void)hipFree(h->d_gwork);
+    if (h->hp_gwork) (void)hipHostFree(h->hp_gwork);
+    h->d_gwork = nullptr, h->hp_gwork = nullptr, h->gwork_cap = 0;
+    if (hipMalloc((void **)&h->d_gwork, (size_t)cap * sizeof(SlCopy)) != hipSuccess ||
+        hipHostMalloc((void **)&h->hp_gwork, (size_t)cap * sizeof(SlCopy), hipHostMallocDefault) != hipSuccess)
+        return set_err(where, "allocation failed");
+    h->gwork_cap = cap;
+    return 0;
+}
+
+// ll_map_refine_add_cloud for the key frames of a round, device to device: request r is the concatenation of the logged scans of its
+// groups (the scan log of a batched match buffer, ll_api_history_batch_scanlog.hip).  One gather launch puts all requests into the
+// staging array, one MR_FILTER_ONLY chain over n_req selections filters them into the store, the host waits once.
+extern "C" int ll_map_refine_add_logged(ll_map_refine *h, ll_history_batch *hb, int64_t n_req, const int64_t *group_off, const int64_t *group_ids,
+                                        float leaf, int64_t *ids, int64_t *n_kept, int32_t *status)
+{
+    const char *fn = "ll_map_refine_add_logged";
+    if (!h || !hb || !group_off || (n_req > 0 && !ids)) return set_err(fn, "null argument");
+    if (n_req < 0) return set_err(fn, "negative count");
+    if (n_req > MR_MAX_SEL) return set_err(fn, "a run holds at most 2^20 selections");
+    if (!(leaf > 0.f) || !std::isfinite(leaf)) return set_err(fn, "the leaf must be positive and finite");
+    if (!hb->sl.on) return set_err(fn, "the scan log is not enabled (ll_history_batch_enable_scan_log)");
+    if (hb->device != h->device) return set_err(fn, "the scan log lives on another device");
+    if (group_off[0] != 0) return set_err(fn, "group offsets must start at 0");
+    for (int64_t r = 0; r < n_req; r++)
+        if (group_off[r + 1] < group_off[r]) return set_err(fn, "group offsets must ascend");
+    const int64_t n_groups = group_off[n_req];
+    if (n_groups > 0 && !group_ids) return set_err(fn, "null argument");
+    SlBook &book = hb->sl.book;
+    std::string why = sl_check_groups(book, n_groups, group_ids);
+    if (!why.empty()) return set_err(fn, why.c_str());
+    const int64_t used = h->off.back();
+    int64_t total = 0;
+    for (int64_t g = 0; g < n_groups; g++)
+        for (const SlScan &e : *sl_group(book, group_ids[g])) {
+            total += e.n;
+            if (total > kMrMaxPoints - used) return set_err(fn, "the store would pass 2^31 points");
+        }
+    SlPlan gather;
+    sl_gather_plan(book, n_req, group_off, group_ids, &gather);
+    std::vector<int64_t> req_ids((size_t)n_req);
+    for (int64_t r = 0; r < n_req; r++) req_ids[(size_t)r] = r;
+    MrPlan plan;
+    why = mr_plan(MR_FILTER_ONLY, n_req, req_ids.data(), nullptr, nullptr, leaf, gather.req_off, &plan);
+    if (!why.empty()) return set_err(fn, why.c_str());
+    HC(hipSetDevice(h->device));
+    const int64_t n_work = (int64_t)gather.items.size();
+    if (mr_store_room(h, used + total, fn) || mr_scratch_room(&h->d_stage, &h->stage_cap, total, fn) || mr_gather_room(h, n_work, fn)) return -1;
+    h->work[0] = h->work[1] = h->work[2] = 0;
+    h->work[3] = total;
+    if (n_work > 0) {
+        for (int64_t w = 0; w < n_work; w++) {
+            const SlItem &it = gather.items[(size_t)w];
+            h->hp_gwork[w] = SlCopy{hb_scan_log_block(hb, it.block) + it.first, it.dst, it.n, it.req};
+        }
+        // this stream behind the log kernels that filled the blocks; then the work list up and the one gather.  A failure leaves the
+        // stream idle, as mr_run_plan does.
+        const char *err = nullptr;
+        hipError_t e = hipEventRecord(h->ev_log, hb->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_log, 0);
+        if (e == hipSuccess) e = hipMemcpyAsync(h->d_gwork, h->hp_gwork, (size_t)n_work * sizeof(SlCopy), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess && sl_gather(h->d_gwork, (int)n_work, h->d_stage, h->stream, &err)) e = hipErrorUnknown;
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h->stream);
+            return set_err(fn, err ? err : hipGetErrorString(e));
+        }
+        h->work[0] += 4;
+        h->work[2] += n_work * (int64_t)sizeof(SlCopy);
+    }
+    std::vector<int64_t> offsets((size_t)n_req + 1, 0);
+    std::vector<int32_t> st((size_t)n_req, 0);
+    if (mr_run_plan(h, plan, h->d_stage, MR_FILTER_ONLY, leaf, h->d_store + used, offsets.data(), st.data(), fn)) return -1;
+    for (int64_t r = 0; r < n_req; r++) {  // consecutive ids, as n_req add_cloud calls would give
+        h->off.push_back(used + offsets[(size_t)r + 1]);
+        ids[r] = (int64_t)h->off.size() - 2;
+        if (n_kept) n_kept[r] = offsets[(size_t)r + 1] - offsets[(size_t)r];
+        if (status) status[r] = st[(size_t)r];
+    }
+    for (int64_t g = 0; g < n_groups; g++) sl_drop(book, group_ids[g]);  // consumed: the host has waited for the chain that read them
     return 0;
 }
 

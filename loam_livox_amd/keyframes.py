@@ -34,7 +34,10 @@ max_points and doubles (ll_cellmap_reserve) when a scan would not fit, as the re
 Differences from the node, by design: everything runs synchronously (the node's service thread polls every millisecond);
 m_accumulated_point_cloud (only consumed by the map refinement) is kept with map_refinement=True alone: the full clouds of the scans the
 history's add rule let in wait in a host FIFO (m_laser_cloud_full_history, :1456, trimmed to maximum_history_size, :1480-1486), and the
-whole FIFO is appended to the BACK key frame at the moment the next one is opened, then cleared (:1545-1558).
+whole FIFO is appended to the BACK key frame at the moment the next one is opened, then cleared (:1545-1558).  With scan_log= (slot s
+of a History_buffer_batch's scan log, handed in by the lock-step loop) that FIFO lives on the device: the owner of the batch pushes
+for all slots (log_full), the flush is a hand_over whose group id the back key frame keeps, a key frame's stored cloud comes from
+Map_refine.add_logged, and the groups of a key frame nobody will process are dropped.
 
 device_bank=True keeps the line and plane image of every processed key frame in a device-resident api.Keyframe_bank and asks for the
 similarities of a new key frame against ALL earlier key frames that pass the three scalar gates in one Keyframe_bank.match, instead of
@@ -100,7 +103,7 @@ class Keyframe_assembly:
                  keyframe_max_points: int = 1 << 20, full_cell_map=None, avail_ratio_plane: float = 0.05, avail_ratio_line: float = 0.03,
                  device_alignment: bool = False, device_bank: bool = False, bank=None, pose_graph=False,
                  map_refinement=False, surround_pointcloud_resolution: float = 0.5, map_refinement_resolution: float = 0.2,
-                 maximum_history_size: int = 100):
+                 maximum_history_size: int = 100, scan_log=None):
         # parameter names and defaults: laser_mapping.hpp:698-710 (loop_closure/*), :686-687 (mapping/pt_cell_resolution, threshold_cell_revisit)
         self.device = device
         self.m_pt_cell_resolution = cell_resolution
@@ -153,14 +156,27 @@ class Keyframe_assembly:
         # map_refinement: False (off: nothing below is touched), True (an api.Map_refine of this assembly's own, created with the first
         # key frame it processes) or a handle to share (anything with add_cloud / refine / merge; its owner closes it).
         # surround_pointcloud_resolution: :696, the leaf of the add; map_refinement_resolution: :903, Mapping_refine's leaf.
-        if map_refinement and not pose_graph:
+        # (a handle is "on" whatever its truth value: an empty api.Map_refine has length 0)
+        shared_refine = None if map_refinement is None or isinstance(map_refinement, (bool, int)) else map_refinement
+        self.map_refinement = shared_refine is not None or bool(map_refinement)
+        if self.map_refinement and not pose_graph:
             raise ValueError("map_refinement needs pose_graph: the corrected map is made from the optimised poses")
-        self.map_refinement = bool(map_refinement)
-        self._map_refine, self._owns_map_refine = (None, False) if map_refinement is True or not map_refinement else (map_refinement, False)
+        self._map_refine, self._owns_map_refine = shared_refine, False
         self.surround_pointcloud_resolution, self.map_refinement_resolution = surround_pointcloud_resolution, map_refinement_resolution
         self.m_maximum_history_size = maximum_history_size
         self.m_laser_cloud_full_history = deque()   # :1456
         self.refined = None             # [(pc_idx, cloud [n, 4])] of the last refine_map: the /pc_aft_loop_closure messages, in their order
+        # scan_log: slot s of a batched match buffer's scan log (api.Scan_log_slot; anything with hand_over() / drop( ids ) and, for the
+        # assembly's own add, a .batch), in the manner of full_cell_map=.  With it m_laser_cloud_full_history lives on the device and the
+        # owner of the batch makes the push for all slots (History_buffer_batch.log_full): add_scan keeps no host arrays, the flush is a
+        # hand_over, and a key frame's m_accumulated_point_cloud holds group ids, which Map_refine.add_logged turns into its stored cloud.
+        # defer_cloud_add: analyse_front leaves the key frame's groups for the owner, who adds the key frames of a round in one call and
+        # completes each with take_cloud_id.  defer_refine: take_solution does not call refine_map; the owner refines the loops of a
+        # round in one run and hands `refined` in.
+        self.scan_log = scan_log
+        self.defer_cloud_add = False
+        self.defer_refine = False
+        self.pending_clouds = []        # key frames analysed and not yet added (defer_cloud_add)
 
     def state(self) -> str:
         """the lists as tests/verbatim_build.py's harness prints them: open key frames frames:cells, waiting ones frames:cells:ending-index"""
@@ -169,6 +185,14 @@ class Keyframe_assembly:
         return ("U " + u).rstrip() + " W" + (" " + w if w else "")
 
     def close(self):
+        if self.scan_log is not None:   # the groups nobody will read any more
+            orphans = [g for kf in list(self.m_keyframe_of_updating_list) + list(self.m_keyframe_need_precession_list) + self.pending_clouds
+                       for g in kf.m_accumulated_point_cloud]
+            for kf in list(self.m_keyframe_of_updating_list) + list(self.m_keyframe_need_precession_list) + self.pending_clouds:
+                kf.m_accumulated_point_cloud = []
+            self.pending_clouds = []
+            self.scan_log.drop(orphans)
+            self.scan_log = None
         if self.m_pt_cell_map_full is not None:
             self.m_pt_cell_map_full.close()
             self.m_pt_cell_map_full = None
@@ -190,7 +214,7 @@ class Keyframe_assembly:
         """One accepted scan.  full_cloud_map_frame: current_laser_cloud_full after pointcloudAssociateToMap; pose: m_q_w_curr /
         m_t_w_curr as {qx, qy, qz, qw, tx, ty, tz}; history_added: whether the history's add rule let the scan in (:1446-1448), which is
         what puts its full cloud into m_laser_cloud_full_history (read with map_refinement alone).  Returns the touched cells (cell_vec)."""
-        if self.map_refinement:   # :1456, :1480-1486 -- before the key-frame step of the same scan
+        if self.map_refinement and self.scan_log is None:   # :1456, :1480-1486 -- before the key-frame step of the same scan
             if history_added:
                 self.m_laser_cloud_full_history.append(np.array(full_cloud_map_frame, np.float32).reshape(-1, 4))
             if len(self.m_laser_cloud_full_history) > self.m_maximum_history_size:
@@ -215,11 +239,16 @@ class Keyframe_assembly:
         if not self.m_keyframe_of_updating_list:
             self.m_keyframe_of_updating_list.append(Maps_keyframe())
         elif self.m_keyframe_of_updating_list[-1].m_accumulate_frames >= self.m_para_scans_between_two_keyframe:
-            if self.map_refinement:   # :1550-1553, 1558: the whole FIFO to the back key frame, then cleared
+            if self.map_refinement and self.scan_log is not None:   # the same on the device: the slot's FIFO becomes a group
+                self.m_keyframe_of_updating_list[-1].m_accumulated_point_cloud.append(self.scan_log.hand_over())
+            elif self.map_refinement:   # :1550-1553, 1558: the whole FIFO to the back key frame, then cleared
                 self.m_keyframe_of_updating_list[-1].m_accumulated_point_cloud.extend(self.m_laser_cloud_full_history)
                 self.m_laser_cloud_full_history.clear()
             if len(self.m_keyframe_need_precession_list) > self.m_loop_closure_maximum_keyframe_in_wating_list:
-                self.m_keyframe_need_precession_list.popleft()
+                out = self.m_keyframe_need_precession_list.popleft()
+                if self.scan_log is not None:   # its groups are orphans
+                    self.scan_log.drop(out.m_accumulated_point_cloud)
+                    out.m_accumulated_point_cloud = []
             self.m_keyframe_of_updating_list.append(Maps_keyframe())
         return cell_vec
 
@@ -309,7 +338,13 @@ class Keyframe_assembly:
             last.analysis = cm.keyframe_images()
         last.points = cm.dump()[0] if hasattr(cm, "dump") else None
         _close(cm)
-        if self.map_refinement:   # :943-946: down_sample_filter over the accumulated cloud; map_id_pc's key is its size
+        if self.map_refinement and self.scan_log is not None:   # the same out of the scan log, device to device
+            if self.defer_cloud_add:
+                self.pending_clouds.append(last)
+            else:
+                ids, _, _ = self.map_refine_handle().add_logged(self.scan_log.batch, [last.m_accumulated_point_cloud], self.surround_pointcloud_resolution)
+                self.take_cloud_id(last, int(ids[0]))
+        elif self.map_refinement:   # :943-946: down_sample_filter over the accumulated cloud; map_id_pc's key is its size
             acc = np.concatenate(last.m_accumulated_point_cloud) if last.m_accumulated_point_cloud else np.zeros((0, 4), np.float32)
             last.cloud_id = self.map_refine_handle().add_cloud(acc, self.surround_pointcloud_resolution)[0]
             last.m_accumulated_point_cloud = []
@@ -319,6 +354,13 @@ class Keyframe_assembly:
         candidates = [his for his in range(n_kf - 1) if self._passes_gates(n_kf, his, last)]
         self._front = (last, candidates)
         return candidates
+
+    def take_cloud_id(self, kf: Maps_keyframe, cloud_id: int) -> None:
+        """completes a key frame analyse_front left for the owner (defer_cloud_add): its groups have become stored cloud `cloud_id`"""
+        kf.cloud_id = int(cloud_id)
+        kf.m_accumulated_point_cloud = []
+        if kf in self.pending_clouds:
+            self.pending_clouds.remove(kf)
 
     def front_pairs(self):
         """(ids_a, ids_b) of the bank entries of analyse_front's candidates: a = the new key frame, b = the old one, as the detector
@@ -364,7 +406,7 @@ class Keyframe_assembly:
         self.poses_ori, self.poses_opm = graph["poses"].copy(), np.asarray(poses_opm, np.float64).reshape(-1, 7).copy()   # pose3d_map_ori, temp_pose_3d_map
         self.constraints = dict(ab=graph["ab"].copy(), meas=graph["meas"].copy())                                           # constrain_vec_temp
         self.pose_graph_summary = dict(summary)
-        if self.map_refinement:
+        if self.map_refinement and not self.defer_refine:
             self.refine_map()
 
     # ---- laser_mapping.hpp:1091-1100; ceres_pose_graph_3d.hpp:368-538 -------------------------------------------------------------------
@@ -380,11 +422,16 @@ class Keyframe_assembly:
         K - 3, ... >= 0 -- one run on the device for all of them.  Keeps and returns self.refined = [(pc_idx, cloud)]."""
         if not self.map_refinement or self.poses_opm is None:
             raise ValueError("refine_map needs map_refinement=True and a closed loop (close_loop / take_solution)")
-        ids = list(range(len(self.poses_ori) - 1, -1, -2))
-        clouds = self.map_refine_handle().refine([self.keyframe_vec[k].cloud_id for k in ids], self.poses_ori[ids], self.poses_opm[ids],
-                                                 self.map_refinement_resolution, False)
+        ids, cloud_ids, ori, opm = self.refine_request()
+        clouds = self.map_refine_handle().refine(cloud_ids, ori, opm, self.map_refinement_resolution, False)
         self.refined = list(zip(ids, clouds))
         return self.refined
+
+    def refine_request(self):
+        """what refine_map asks of the store: (pc_idx list, their cloud ids, poses_ori, poses_opm) for pc_idx = K - 1, K - 3, ... >= 0;
+        an owner with defer_refine puts the requests of a round into one run and sets self.refined = list( zip( pc_idx, clouds ) )"""
+        ids = list(range(len(self.poses_ori) - 1, -1, -2))
+        return ids, [self.keyframe_vec[k].cloud_id for k in ids], self.poses_ori[ids], self.poses_opm[ids]
 
     def refined_mapping(self) -> np.ndarray:
         """Mapping_refine::refine_mapping's in-memory overload over ALL key frames of the closed loop (move, then VoxelGrid,

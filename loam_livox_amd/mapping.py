@@ -326,8 +326,15 @@ class Laser_mapping_batch:
     walk half of every slot -- the same logs and loops, float for float.  loop_closure["pose_graph"]=True (off by default): the loop
     owns ONE api.Pose_graph (pose_graph) for its S assemblies; the loops the slots accept in a round are closed -- their pose graphs
     optimised -- in one Pose_graph.solve, and every assembly keeps its poses_ori, poses_opm, constraints and pose_graph_summary.
-    loop_closure["map_refinement"] is refused with ValueError: the refinement needs every accepted scan's full cloud in a FIFO
-    (laser_mapping.hpp:1456), and this loop's full clouds never reach the host; a device FIFO for them is left to a later change."""
+    loop_closure["map_refinement"]=True (off by default; with batched_history, full_maps, key_frames and loop_closure["pose_graph"]
+    only -- every other configuration raises ValueError): the corrected map behind a closed loop, without a full cloud ever reaching
+    the host.  The History_buffer_batch keeps a scan log (enable_scan_log: m_laser_cloud_full_history of every slot, laser_mapping.hpp:
+    1456, in device blocks) and the loop owns ONE api.Map_refine (map_refine) for its S assemblies.  A step is then append_full,
+    ONE log_full for the accepted slots whose history add let the scan in (:1456 before :1524), the slots' add_scan -- whose flush is
+    a hand-over of the slot's FIFO -- and the key-frame rounds; in a round the key frames analysed get their stored clouds from ONE
+    Map_refine.add_logged at surround_pointcloud_resolution, and the loops closed are refined in ONE Map_refine.refine over all
+    their selections (every second key frame, newest first), split back into each assembly's `refined`.  Stored clouds and `refined`
+    are those of Laser_mapping run alone on the sequence, bit for bit; poses and reports do not change."""
 
     def __init__(self, n_sequences: int, refresh_threads: int | None = None, batched_history: bool = False, cell_maps: bool = False,
                  cell_matching: bool = False, full_maps: bool = False, key_frames: bool = False, **kw):
@@ -347,8 +354,10 @@ class Laser_mapping_batch:
                              "maps on the batched history)")
         if a["loop_closure_if_enable"]:
             raise ValueError("loop_closure_if_enable must be 0 in the batched loop")
-        if (a["loop_closure"] or {}).get("map_refinement"):
-            raise ValueError("map_refinement is not available in the batched loop: its full clouds never reach the host")
+        if (a["loop_closure"] or {}).get("map_refinement") and not (batched_history and full_maps and key_frames and a["loop_closure"].get("pose_graph")):
+            raise ValueError("map_refinement is not available in the batched loop without batched_history=True, full_maps=True, "
+                             "key_frames=True and loop_closure pose_graph: its full clouds never reach the host, they wait in the "
+                             "scan log of the History_buffer_batch")
         if a["keep_cell_maps"]:
             raise ValueError("keep_cell_maps is not offered by the batched loop (cell_maps=True keeps them on the batched history)")
         if cell_maps and not batched_history:
@@ -372,7 +381,7 @@ class Laser_mapping_batch:
         self.maps = [Map_buffer(device=device) for _ in range(S)]
         self.batched_history, self.cell_maps, self.cell_matching = bool(batched_history), bool(cell_maps), bool(cell_matching)
         self.full_maps, self.key_frames = bool(full_maps), bool(key_frames)
-        self.keyframes, self.loops, self.keyframe_bank, self.pose_graph = None, None, None, None
+        self.keyframes, self.loops, self.keyframe_bank, self.pose_graph, self.map_refine = None, None, None, None, None
         self.full_map_s = 0.0  # cumulative wall time of the full-map phase (append_full, and the key-frame steps with key_frames)
         self.m_maximum_search_range = (a["maximum_search_range_corner"], a["maximum_search_range_surface"])
         self.m_maximum_in_fov_angle, self.m_down_sample_replace = a["maximum_in_fov_angle"], a["down_sample_replace"]
@@ -398,11 +407,22 @@ class Laser_mapping_batch:
                     if lc.pop("pose_graph", False):
                         from .api import Pose_graph
                         self.pose_graph = lc["pose_graph"] = Pose_graph(device=device)
+                    # loop_closure["map_refinement"]: the scan log on the batch, ONE store for the S assemblies; the key frames of
+                    # a round are added in one add_logged and the loops of a round refined in one run
+                    logs = [None] * S
+                    if lc.pop("map_refinement", False):
+                        from .api import Map_refine
+                        lc.setdefault("maximum_history_size", a["maximum_history_size"])  # (as Laser_mapping hands it on)
+                        self.history_batch.enable_scan_log(lc["maximum_history_size"])
+                        self.map_refine = lc["map_refinement"] = Map_refine(device=device)
+                        logs = [dict(scan_log=self.history_batch.scan_log(s)) for s in range(S)]
                     self.keyframes = [Keyframe_assembly(device=device, cell_resolution=a["cell_resolution"],
                                                         threshold_cell_revisit=a["threshold_cell_revisit"],
-                                                        full_cell_map=self.history_batch.full_map(s), **lc) for s in range(S)]
+                                                        full_cell_map=self.history_batch.full_map(s), **lc, **(logs[s] or {})) for s in range(S)]
                     for ka in self.keyframes:
                         ka.defer_pose_graph = self.pose_graph is not None
+                        if self.map_refine is not None:
+                            ka.defer_cloud_add = ka.defer_refine = True
                     self.loops = [[] for _ in range(S)]
         else:
             self.history_batch = None
@@ -442,6 +462,9 @@ class Laser_mapping_batch:
         if self.pose_graph is not None:
             self.pose_graph.close()
             self.pose_graph = None
+        if self.map_refine is not None:
+            self.map_refine.close()
+            self.map_refine = None
         for h in [self.fe, self.reg, self.vox[0], self.vox[1]] + self.maps + ([self.history_batch] if self.batched_history else self.histories):
             h.close()
 
@@ -460,16 +483,23 @@ class Laser_mapping_batch:
             raise ValueError("no full maps: create the loop with batched_history=True, full_maps=True")
         return self.history_batch.full_map(sequence)
 
-    def _full_step(self, jobs, on, new) -> None:
+    def _full_step(self, jobs, on, new, added=None) -> None:
         """laser_mapping.hpp:1442 + 1524-1562 for the accepted slots: their scans' full clouds into the full-cloud maps in one append,
-        then per slot the key-frame bookkeeping on the cells that scan touched"""
+        then per slot the key-frame bookkeeping on the cells that scan touched.  With loop_closure map_refinement the scans the
+        history's add let in (`added`) join the scan log in between, in one call (:1456 comes before :1524)."""
         import time
         t0 = time.perf_counter()
         self.history_batch.append_full(self.fe, new, on, 3, lists=False)  # (a key frame reads its slot's list through its view)
+        logging = getattr(self, "map_refine", None) is not None
+        if logging:
+            self.history_batch.log_full(self.fe, np.asarray(on, bool) & np.asarray(added, bool))
         if self.key_frames:
             none = np.zeros((0, 4), np.float32)  # (the slot view answers with the append's list; the cloud itself stays on the device)
             for s, _, pose_new in jobs:
-                self.keyframes[s].add_scan(none, pose_new, int(self.frame_index[s]))
+                if logging:
+                    self.keyframes[s].add_scan(none, pose_new, int(self.frame_index[s]), history_added=bool(added[s]))
+                else:
+                    self.keyframes[s].add_scan(none, pose_new, int(self.frame_index[s]))
             self._process_keyframes([s for s, _, _ in jobs])
         self.full_map_s += time.perf_counter() - t0
 
@@ -505,9 +535,22 @@ class Laser_mapping_batch:
                 for s in (slots if first else [s for s, _ in todo]):
                     ka = self.keyframes[s]
                     self.loops[s] += ka.process_waiting(limit=1) if waiting(ka) > 1 else ka.process_waiting()
+            if getattr(self, "map_refine", None) is not None:
+                self._add_clouds(slots)
             if getattr(self, "pose_graph", None) is not None:
                 self._close_loops(slots)
             first = False
+
+    def _add_clouds(self, slots) -> None:
+        """the key frames the slots analysed in this round (loop_closure map_refinement): their accumulated clouds out of the scan log
+        into the store in ONE add_logged (laser_mapping.hpp:943-946 for each)"""
+        todo = [(self.keyframes[s], kf) for s in slots for kf in list(getattr(self.keyframes[s], "pending_clouds", ()))]
+        if not todo:
+            return
+        leaf = todo[0][0].surround_pointcloud_resolution
+        ids, _, _ = self.map_refine.add_logged(self.history_batch, [kf.m_accumulated_point_cloud for _, kf in todo], leaf)
+        for (ka, kf), cid in zip(todo, ids):
+            ka.take_cloud_id(kf, int(cid))
 
     def _close_loops(self, slots) -> None:
         """the loops the slots accepted in this round (loop_closure pose_graph): their graphs optimised in ONE solve"""
@@ -519,6 +562,14 @@ class Laser_mapping_batch:
         for (ka, _), graph, x, summary in zip(todo, graphs, poses, summaries):
             ka.take_solution(graph, x, summary)
             ka.pending_loops.clear()
+        if getattr(self, "map_refine", None) is not None:  # :1091-1100 for every loop of the round, in ONE run
+            reqs = [ka.refine_request() for ka, _ in todo]
+            clouds = self.map_refine.refine([c for r in reqs for c in r[1]], np.concatenate([r[2] for r in reqs]),
+                                            np.concatenate([r[3] for r in reqs]), todo[0][0].map_refinement_resolution, False)
+            at = 0
+            for (ka, _), r in zip(todo, reqs):
+                ka.refined = list(zip(r[0], clouds[at:at + len(r[0])]))
+                at += len(r[0])
 
     def _bank_round(self, slots) -> None:
         """one waiting key frame of every slot named (each has one): analysed and gated per slot, compared in one match, walked per slot"""
@@ -576,13 +627,13 @@ class Laser_mapping_batch:
             gate[s], new[s] = pose_before, pose_new  # m_q_w_curr is still the pre-registration pose at LM:1439-1451
         hb = self.history_batch
         if self.m_if_input_downsample_mode:
-            hb.add_voxel(self.vox[0], self.vox[1], new, gate, on, self.history_add_t_step, self.history_add_angle_step)
+            added = hb.add_voxel(self.vox[0], self.vox[1], new, gate, on, self.history_add_t_step, self.history_add_angle_step)
         else:
-            hb.add_fe(self.fe, new, gate, on, self.history_add_t_step, self.history_add_angle_step)
+            added = hb.add_fe(self.fe, new, gate, on, self.history_add_t_step, self.history_add_angle_step)
         t1 = time.perf_counter()
         t_full = self.full_map_s
         if self.full_maps:
-            self._full_step(jobs, on, new)
+            self._full_step(jobs, on, new, added)
         t_full = self.full_map_s - t_full  # (its own figure: neither the add's nor the refresh's)
         maps = [self.maps[s] if on[s] else None for s in range(S)]
         if self.cell_matching:  # update_buff_for_matching with m_matching_mode == 1, at the poses the step just accepted

@@ -42,14 +42,17 @@ Map_refine.add_logged, and the groups of a key frame nobody will process are dro
 device_bank=True keeps the line and plane image of every processed key frame in a device-resident api.Keyframe_bank and asks for the
 similarities of a new key frame against ALL earlier key frames that pass the three scalar gates in one Keyframe_bank.match, instead of
 two keyframe_similarity calls per pair inside the walk; the floats are the same to the bit, and so are log, loops and if_end.
-process_waiting is the composition of analyse_front (materialise, analyse, gate), one match, and walk_front (the walk, reading the two
-arrays); an owner of many assemblies that share one bank runs the halves itself with one match for all of them."""
+
+One pass over a waiting key frame -- analyse_front (materialise, analyse, gate, store its cloud), one match, walk_front, close and refine
+an accepted loop -- is written once, in Keyframe_rounds, for any number of assemblies that share the services: process_waiting is that
+driver over the assembly alone, and the lock-step loop runs it over all its slots."""
 from __future__ import annotations
 
 from collections import deque
 
 import numpy as np
 
+from . import api
 from .api import Cell_map, keyframe_similarity
 from .scene_alignment import Scene_alignment
 
@@ -138,30 +141,23 @@ class Keyframe_assembly:
         # handle -- registrar, map, voxel filter -- serves every pair; off, every pair gets a Scene_alignment of its own, as before
         self.device_alignment = device_alignment
         self._scene_alignment = None
-        # device_bank: the key frames' line and plane images stay on the device (api.Keyframe_bank) and a new key frame is compared
-        # against all gated earlier ones in one match.  bank: one to share (its owner closes it; anything with add_cell_map / match);
-        # without it the assembly creates its own with the first key frame it processes.
-        self.device_bank = bool(device_bank) or bank is not None
-        self._bank, self._owns_bank = bank, False
         self._front = None              # (key frame, candidates) between analyse_front and walk_front
-        # pose_graph: False (off: nothing below is touched), True (an api.Pose_graph of this assembly's own, created when the first loop
-        # is accepted) or a handle to share (anything with solve( graphs ); its owner closes it).  An accepted loop is then closed:
-        # close_loop.  defer_pose_graph: an owner of many assemblies collects the accepted loops of a round and solves them in one call
-        # (loop_graph / take_solution).
-        self.pose_graph = bool(pose_graph)
-        self._pose_graph, self._owns_pose_graph = (None, False) if pose_graph is True or not pose_graph else (pose_graph, False)
-        self.defer_pose_graph = False
-        self.pending_loops = []         # accepted loops not yet closed (defer_pose_graph)
-        self.poses_ori, self.poses_opm, self.constraints, self.pose_graph_summary = None, None, None, None
-        # map_refinement: False (off: nothing below is touched), True (an api.Map_refine of this assembly's own, created with the first
-        # key frame it processes) or a handle to share (anything with add_cloud / refine / merge; its owner closes it).
-        # surround_pointcloud_resolution: :696, the leaf of the add; map_refinement_resolution: :903, Mapping_refine's leaf.
-        # (a handle is "on" whatever its truth value: an empty api.Map_refine has length 0)
-        shared_refine = None if map_refinement is None or isinstance(map_refinement, (bool, int)) else map_refinement
-        self.map_refinement = shared_refine is not None or bool(map_refinement)
-        if self.map_refinement and not pose_graph:
+        # The three services of the detector's back end, each off, this assembly's own (created on first use) or a handle to share, whose
+        # owner closes it (Keyframe_rounds has the rule):
+        #   device_bank=True / bank=: the key frames' line and plane images stay on the device (api.Keyframe_bank; anything with
+        #     add_cell_map / match) and a new key frame is compared against all gated earlier ones in one match;
+        #   pose_graph=True or a handle (api.Pose_graph; anything with solve( graphs )): an accepted loop is closed, close_loop;
+        #   map_refinement=True or a handle (api.Map_refine; anything with add_cloud / refine / merge -- "on" whatever its truth value: an
+        #     empty api.Map_refine has length 0).  surround_pointcloud_resolution: :696, the leaf of the add; map_refinement_resolution:
+        #     :903, Mapping_refine's leaf.
+        # self.rounds is the driver that serves this assembly: its own over [self], until an owner of many assemblies builds one over them.
+        self.rounds = self._own_rounds = Keyframe_rounds([self], bank=bank if bank is not None else bool(device_bank), pose_graph=pose_graph,
+                                                         map_refinement=map_refinement)
+        self.device_bank, self.pose_graph, self.map_refinement = self.rounds.bank.on, self.rounds.pose_graph.on, self.rounds.map_refine.on
+        if self.map_refinement and not self.pose_graph:
             raise ValueError("map_refinement needs pose_graph: the corrected map is made from the optimised poses")
-        self._map_refine, self._owns_map_refine = shared_refine, False
+        self.pending_loops = []         # accepted loops not yet closed: the round's one solve takes them; a solve that raised leaves them
+        self.poses_ori, self.poses_opm, self.constraints, self.pose_graph_summary = None, None, None, None
         self.surround_pointcloud_resolution, self.map_refinement_resolution = surround_pointcloud_resolution, map_refinement_resolution
         self.m_maximum_history_size = maximum_history_size
         self.m_laser_cloud_full_history = deque()   # :1456
@@ -170,13 +166,7 @@ class Keyframe_assembly:
         # assembly's own add, a .batch), in the manner of full_cell_map=.  With it m_laser_cloud_full_history lives on the device and the
         # owner of the batch makes the push for all slots (History_buffer_batch.log_full): add_scan keeps no host arrays, the flush is a
         # hand_over, and a key frame's m_accumulated_point_cloud holds group ids, which Map_refine.add_logged turns into its stored cloud.
-        # defer_cloud_add: analyse_front leaves the key frame's groups for the owner, who adds the key frames of a round in one call and
-        # completes each with take_cloud_id.  defer_refine: take_solution does not call refine_map; the owner refines the loops of a
-        # round in one run and hands `refined` in.
         self.scan_log = scan_log
-        self.defer_cloud_add = False
-        self.defer_refine = False
-        self.pending_clouds = []        # key frames analysed and not yet added (defer_cloud_add)
 
     def state(self) -> str:
         """the lists as tests/verbatim_build.py's harness prints them: open key frames frames:cells, waiting ones frames:cells:ending-index"""
@@ -185,12 +175,11 @@ class Keyframe_assembly:
         return ("U " + u).rstrip() + " W" + (" " + w if w else "")
 
     def close(self):
-        if self.scan_log is not None:   # the groups nobody will read any more
-            orphans = [g for kf in list(self.m_keyframe_of_updating_list) + list(self.m_keyframe_need_precession_list) + self.pending_clouds
-                       for g in kf.m_accumulated_point_cloud]
-            for kf in list(self.m_keyframe_of_updating_list) + list(self.m_keyframe_need_precession_list) + self.pending_clouds:
+        if self.scan_log is not None:   # the groups nobody will read any more: open and waiting key frames, and one analysed but not yet stored
+            orphans = []
+            for kf in list(self.m_keyframe_of_updating_list) + list(self.m_keyframe_need_precession_list) + self.keyframe_vec[-1:]:
+                orphans += kf.m_accumulated_point_cloud
                 kf.m_accumulated_point_cloud = []
-            self.pending_clouds = []
             self.scan_log.drop(orphans)
             self.scan_log = None
         if self.m_pt_cell_map_full is not None:
@@ -199,15 +188,7 @@ class Keyframe_assembly:
         if self._scene_alignment is not None:
             self._scene_alignment.close()
             self._scene_alignment = None
-        if self._bank is not None and self._owns_bank:
-            self._bank.close()
-        self._bank = None
-        if self._pose_graph is not None and self._owns_pose_graph:
-            self._pose_graph.close()
-        self._pose_graph = None
-        if self._map_refine is not None and self._owns_map_refine:
-            self._map_refine.close()
-        self._map_refine = None
+        self._own_rounds.close()
 
     # ---- laser_mapping.hpp:1524-1562 ------------------------------------------------------------------------------------------------
     def add_scan(self, full_cloud_map_frame: np.ndarray, pose: np.ndarray, current_frame_index: int, history_added: bool = True) -> np.ndarray:
@@ -308,45 +289,31 @@ class Keyframe_assembly:
         return self._cell_map_from_points(kf.points) if kf.points is not None else self.materialize(kf)
 
     # ---- laser_mapping.hpp:919-1060 --------------------------------------------------------------------------------------------------
-    def bank(self):
-        """the key-frame bank of device_bank=True: the one handed in, else this assembly's own, created on first use"""
-        if self._bank is None:
-            from .api import Keyframe_bank
-            self._bank, self._owns_bank = Keyframe_bank(device=self.device), True
-        return self._bank
-
     def process_waiting(self, limit: int | None = None):
-        """Every waiting key frame (the first `limit` of them, when given) through one pass of service_loop_detection's loop body.
-        Returns the loops found in this call."""
-        found = []
-        while self.m_keyframe_need_precession_list and not self.if_end and (limit is None or limit > 0):
-            limit = None if limit is None else limit - 1
-            candidates = self.analyse_front()
-            sims = self.bank().match(*self.front_pairs()) if self.device_bank and candidates else None
-            found += self.walk_front(sims)
-        return found
+        """Every waiting key frame (the first `limit` of them, when given) through one pass of service_loop_detection's loop body: the
+        rounds of Keyframe_rounds.run over this assembly alone.  Returns the loops found in this call."""
+        return self.rounds.run([self.rounds.assemblies.index(self)], limit)[0]
 
     def analyse_front(self) -> list:
         """The analysis half of one pass: the first waiting key frame leaves the list, is materialised and analysed (through the bank
-        with device_bank=True: the same dict, and its line and plane image stay on the device) and joins keyframe_vec.  Returns the
-        earlier key frames `his` that pass the gates of :994, :1001 and :1004 -- the only ones whose similarities the walk can ask for."""
+        with device_bank=True: the same dict, and its line and plane image stay on the device), its accumulated cloud goes into the
+        map-refinement store, and it joins keyframe_vec.  Returns the earlier key frames `his` that pass the gates of :994, :1001 and
+        :1004 -- the only ones whose similarities the walk can ask for."""
+        return self.rounds.analyse([self])[0]
+
+    def _analyse(self) -> list:
+        """analyse_front without the stored cloud of the scan-log route, which the driver adds for all key frames of a round at once"""
         last = self.m_keyframe_need_precession_list.popleft()
         cm = self.materialize(last)                     # update_features_of_each_cells + analyze read the cells as they are now
-        if self.device_bank:
-            last.analysis, last.bank_id = self.bank().add_cell_map(cm)
+        if self.rounds.bank.on:
+            last.analysis, last.bank_id = self.rounds.bank().add_cell_map(cm)
         else:
             last.analysis = cm.keyframe_images()
         last.points = cm.dump()[0] if hasattr(cm, "dump") else None
         _close(cm)
-        if self.map_refinement and self.scan_log is not None:   # the same out of the scan log, device to device
-            if self.defer_cloud_add:
-                self.pending_clouds.append(last)
-            else:
-                ids, _, _ = self.map_refine_handle().add_logged(self.scan_log.batch, [last.m_accumulated_point_cloud], self.surround_pointcloud_resolution)
-                self.take_cloud_id(last, int(ids[0]))
-        elif self.map_refinement:   # :943-946: down_sample_filter over the accumulated cloud; map_id_pc's key is its size
+        if self.map_refinement and self.scan_log is None:   # :943-946: down_sample_filter over the accumulated cloud; map_id_pc's key is its size
             acc = np.concatenate(last.m_accumulated_point_cloud) if last.m_accumulated_point_cloud else np.zeros((0, 4), np.float32)
-            last.cloud_id = self.map_refine_handle().add_cloud(acc, self.surround_pointcloud_resolution)[0]
+            last.cloud_id = self.rounds.map_refine().add_cloud(acc, self.surround_pointcloud_resolution)[0]
             last.m_accumulated_point_cloud = []
         self.keyframe_vec.append(last)
         self.pose3d_vec.append((last.m_pose_q.copy(), last.m_pose_t.copy()))
@@ -354,13 +321,6 @@ class Keyframe_assembly:
         candidates = [his for his in range(n_kf - 1) if self._passes_gates(n_kf, his, last)]
         self._front = (last, candidates)
         return candidates
-
-    def take_cloud_id(self, kf: Maps_keyframe, cloud_id: int) -> None:
-        """completes a key frame analyse_front left for the owner (defer_cloud_add): its groups have become stored cloud `cloud_id`"""
-        kf.cloud_id = int(cloud_id)
-        kf.m_accumulated_point_cloud = []
-        if kf in self.pending_clouds:
-            self.pending_clouds.remove(kf)
 
     def front_pairs(self):
         """(ids_a, ids_b) of the bank entries of analyse_front's candidates: a = the new key frame, b = the old one, as the detector
@@ -380,13 +340,6 @@ class Keyframe_assembly:
         return True
 
     # ---- laser_mapping.hpp:948-960, 1058-1089 -------------------------------------------------------------------------------------
-    def pose_graph_handle(self):
-        """the optimiser of pose_graph: the one handed in, else this assembly's own, created on first use"""
-        if self._pose_graph is None:
-            from .api import Pose_graph
-            self._pose_graph, self._owns_pose_graph = Pose_graph(device=self.device), True
-        return self._pose_graph
-
     def loop_graph(self, loop) -> dict:
         """The graph the node optimises when it accepts `loop` (a record of self.loops): pose3d_vec as the poses; constrain_vec -- the
         chain constraint k -> k + 1 of every two consecutive key-frame poses, built from those poses (:951-960) -- and behind them the
@@ -402,36 +355,24 @@ class Keyframe_assembly:
         return dict(poses=poses, ab=np.array(ab, np.int32).reshape(-1, 2), meas=np.array(meas, np.float64).reshape(-1, 7))
 
     def take_solution(self, graph: dict, poses_opm: np.ndarray, summary: dict) -> None:
-        """keeps what close_loop keeps, from a solve its caller made (one call for the loops of many assemblies)"""
+        """keeps what close_loop keeps, from a solve its caller made, and refines the map behind it with map_refinement"""
+        self._keep_solution(graph, poses_opm, summary)
+        if self.map_refinement:
+            self.refine_map()
+
+    def _keep_solution(self, graph: dict, poses_opm: np.ndarray, summary: dict) -> None:
         self.poses_ori, self.poses_opm = graph["poses"].copy(), np.asarray(poses_opm, np.float64).reshape(-1, 7).copy()   # pose3d_map_ori, temp_pose_3d_map
         self.constraints = dict(ab=graph["ab"].copy(), meas=graph["meas"].copy())                                           # constrain_vec_temp
         self.pose_graph_summary = dict(summary)
-        if self.map_refinement and not self.defer_refine:
-            self.refine_map()
 
     # ---- laser_mapping.hpp:1091-1100; ceres_pose_graph_3d.hpp:368-538 -------------------------------------------------------------------
-    def map_refine_handle(self):
-        """the store of map_refinement: the one handed in, else this assembly's own, created on first use"""
-        if self._map_refine is None:
-            from .api import Map_refine
-            self._map_refine, self._owns_map_refine = Map_refine(device=self.device), True
-        return self._map_refine
-
     def refine_map(self) -> list:
         """The node's loop at :1091-1100: refine_pointcloud( map_id_pc, pose3d_map_ori, temp_pose_3d_map, pc_idx, 0 ) for pc_idx = K - 1,
         K - 3, ... >= 0 -- one run on the device for all of them.  Keeps and returns self.refined = [(pc_idx, cloud)]."""
         if not self.map_refinement or self.poses_opm is None:
             raise ValueError("refine_map needs map_refinement=True and a closed loop (close_loop / take_solution)")
-        ids, cloud_ids, ori, opm = self.refine_request()
-        clouds = self.map_refine_handle().refine(cloud_ids, ori, opm, self.map_refinement_resolution, False)
-        self.refined = list(zip(ids, clouds))
+        self.rounds.refine([self])
         return self.refined
-
-    def refine_request(self):
-        """what refine_map asks of the store: (pc_idx list, their cloud ids, poses_ori, poses_opm) for pc_idx = K - 1, K - 3, ... >= 0;
-        an owner with defer_refine puts the requests of a round into one run and sets self.refined = list( zip( pc_idx, clouds ) )"""
-        ids = list(range(len(self.poses_ori) - 1, -1, -2))
-        return ids, [self.keyframe_vec[k].cloud_id for k in ids], self.poses_ori[ids], self.poses_opm[ids]
 
     def refined_mapping(self) -> np.ndarray:
         """Mapping_refine::refine_mapping's in-memory overload over ALL key frames of the closed loop (move, then VoxelGrid,
@@ -439,16 +380,15 @@ class Keyframe_assembly:
         if not self.map_refinement or self.poses_opm is None:
             raise ValueError("refined_mapping needs map_refinement=True and a closed loop (close_loop / take_solution)")
         ids = list(range(len(self.poses_ori)))
-        h = self.map_refine_handle()
+        h = self.rounds.map_refine()
         h.refine([self.keyframe_vec[k].cloud_id for k in ids], self.poses_ori, self.poses_opm, self.map_refinement_resolution, True)
         return h.merge(self.map_refinement_resolution)
 
     def close_loop(self, loop) -> np.ndarray:
         """Pose-graph optimisation of an accepted loop: builds loop_graph( loop ), solves it on the device and keeps poses_ori,
-        poses_opm, constraints and pose_graph_summary.  loops, log, if_end and state() are not touched.  Returns poses_opm."""
-        graph = self.loop_graph(loop)
-        poses, summaries = self.pose_graph_handle().solve([graph])
-        self.take_solution(graph, poses[0], summaries[0])
+        poses_opm, constraints and pose_graph_summary; with map_refinement, refine_map behind it.  loops, log, if_end and state() are
+        not touched.  Returns poses_opm."""
+        self.rounds.close_loops([(self, loop)])
         return self.poses_opm
 
     def walk_front(self, sims=None):
@@ -506,11 +446,8 @@ class Keyframe_assembly:
                     loop = dict(his=his, last=n_kf - 1, inlier_threshold=thr, icp_q=qi, icp_t=ti, sim_plane=sim_plane, sim_line=sim_line)
                     self.loops.append(loop)
                     found.append(loop)
-                    if self.pose_graph:      # :1058-1089
-                        if self.defer_pose_graph:
-                            self.pending_loops.append(loop)
-                        else:
-                            self.close_loop(loop)
+                    if self.pose_graph:      # :1058-1089, in the round's one solve (Keyframe_rounds.close_loops)
+                        self.pending_loops.append(loop)
                     self.if_end = True   # :1108 (the dumps in between are out of scope)
                     break
                 his += 5 + 1   # :1111-1114
@@ -518,6 +455,141 @@ class Keyframe_assembly:
             his += 1
         return found
 
+
+class _Service:
+    """One shared device handle of a Keyframe_rounds: off, handed in (its owner closes it), or created on first use and closed here.
+    how: None / False / 0 (off), True (an api.<kind> of the driver's own) or the handle to share."""
+
+    def __init__(self, kind: str, how, device: int):
+        own = how is None or isinstance(how, (bool, int))
+        self.kind, self.device, self.on, self.handle, self.own = kind, device, bool(how) or not own, None if own else how, False
+
+    def __call__(self):
+        if self.handle is None:
+            self.handle, self.own = getattr(api, self.kind)(device=self.device), True
+        return self.handle
+
+    def close(self):
+        if self.own and self.handle is not None:
+            self.handle.close()
+        self.handle = None
+
+
+class Keyframe_rounds:
+    """The detector's loop body for many assemblies at once: Keyframe_assembly.process_waiting is this over [itself], and the lock-step
+    loop (mapping.Laser_mapping_batch) runs it once per step over the slots that accepted a scan.  Slot s gives, bit for bit, what
+    assembly s gives run alone -- log, loops, poses_opm, stored clouds and `refined` -- because alone is the same text with one slot.
+
+    It owns the assemblies' shared services (bank, pose_graph, map_refine: _Service each; an assembly reaches them through its
+    `rounds`) and, optionally, the batched full-cloud store the key frames' cells are read from (store: anything with
+    extract_cells( kind, sequences, cell_lists, dsts ), slot s of this driver being its sequence s).
+
+    One round takes the first waiting key frame of every named slot that has one and has not ended:
+      1. extraction: with a store, ONE extract_cells into maps handed to the assemblies in advance (prefetch); no append happens
+         between that and the analysis, so the cells are read as they are now (cell_map_keyframe.hpp:1243-1261).  Without a store
+         every assembly reads its own full map (materialize);
+      2. the analysis half of every slot (through the bank when there is one), and with a scan log ONE Map_refine.add_logged for the
+         key frames just analysed, at surround_pointcloud_resolution: stored ids are consecutive in slot order (on the host-FIFO
+         route the analysis itself makes an add_cloud per key frame);
+      3. with a bank, ONE Keyframe_bank.match over all slots' gated pairs;
+      4. the walk half of every slot;
+      5. ONE Pose_graph.solve over the loops the round accepted, then ONE Map_refine.refine over all their selections (every second
+         key frame, newest first, at map_refinement_resolution), split back into each assembly's `refined`.
+    A solve that raises leaves its loops in the assemblies' pending_loops; the next run solves them first."""
+
+    def __init__(self, assemblies, bank=False, pose_graph=False, map_refinement=False, store=None):
+        self.assemblies, self.store = list(assemblies), store
+        device = self.assemblies[0].device
+        self.bank, self.pose_graph = _Service("Keyframe_bank", bank, device), _Service("Pose_graph", pose_graph, device)
+        self.map_refine = _Service("Map_refine", map_refinement, device)
+        for ka in self.assemblies:
+            ka.rounds = self
+
+    def close(self):
+        for service in (self.bank, self.pose_graph, self.map_refine):
+            service.close()
+
+    def run(self, slots, limit: int | None = None) -> list:
+        """rounds while a named slot has a key frame waiting and has not ended (at most `limit` of them, when given).  Returns the
+        loops found, a list per named slot."""
+        found = [[] for _ in slots]
+        while True:
+            todo = [k for k, s in enumerate(slots) if self.assemblies[s].m_keyframe_need_precession_list and not self.assemblies[s].if_end
+                    and (limit is None or limit > 0)]
+            kas = [self.assemblies[slots[k]] for k in todo]
+            if kas and self.store is not None:
+                self.extract([slots[k] for k in todo])
+            self.analyse(kas)
+            for k, ka, sims in zip(todo, kas, self.match(kas)):
+                found[k] += ka.walk_front(sims)
+            pending = [(self.assemblies[s], loop) for s in slots for loop in self.assemblies[s].pending_loops]
+            self.close_loops(pending)
+            for ka, _ in pending:
+                ka.pending_loops.clear()
+            if not todo:
+                return found
+            limit = None if limit is None else limit - 1
+
+    def extract(self, slots) -> None:
+        """the first waiting key frame of every slot out of the store in one call, each handed to its assembly for its next materialize"""
+        kas = [self.assemblies[s] for s in slots]
+        fronts = [ka.m_keyframe_need_precession_list[0] for ka in kas]
+        wants = [ka.wanted_cells(kf) for ka, kf in zip(kas, fronts)]
+        dsts = [ka.new_keyframe_map(len(w)) for ka, w in zip(kas, wants)]
+        try:
+            self.store.extract_cells(2, list(slots), wants, dsts)
+        except Exception:
+            for km in dsts:
+                km.close()
+            raise
+        for ka, kf, km in zip(kas, fronts, dsts):
+            ka.prefetch(kf, km)
+
+    def analyse(self, kas) -> list:
+        """the analysis half for every assembly named, and their key frames' accumulated clouds out of the scan log into the store in one
+        add_logged (laser_mapping.hpp:943-946 for each).  Returns every assembly's candidates."""
+        candidates = [ka._analyse() for ka in kas]
+        logged = [ka for ka in kas if ka.map_refinement and ka.scan_log is not None]
+        if logged:
+            fronts = [ka._front[0] for ka in logged]
+            ids, _, _ = self.map_refine().add_logged(logged[0].scan_log.batch, [kf.m_accumulated_point_cloud for kf in fronts],
+                                                     logged[0].surround_pointcloud_resolution)
+            for kf, cloud_id in zip(fronts, ids):
+                kf.cloud_id, kf.m_accumulated_point_cloud = int(cloud_id), []
+        return candidates
+
+    def match(self, kas) -> list:
+        """(sim_line, sim_plane) of every assembly's candidates out of one Keyframe_bank.match; None for an assembly without candidates,
+        and for all without a bank (the walk then asks keyframe_similarity per pair)"""
+        if not self.bank.on:
+            return [None] * len(kas)
+        pairs = [ka.front_pairs() for ka in kas]
+        cut = np.cumsum([0] + [len(a) for a, _ in pairs])
+        line, plane = self.bank().match([i for a, _ in pairs for i in a], [i for _, b in pairs for i in b]) if cut[-1] else ((), ())
+        return [(line[cut[k]:cut[k + 1]], plane[cut[k]:cut[k + 1]]) if pairs[k][0] else None for k in range(len(kas))]
+
+    def close_loops(self, todo) -> None:
+        """todo: [(assembly, accepted loop)].  Their pose graphs optimised in one solve (:1058-1089), every assembly keeping its
+        solution, and with map_refinement the maps behind them refined in one run (:1091-1100)."""
+        if not todo:
+            return
+        graphs = [ka.loop_graph(loop) for ka, loop in todo]
+        poses, summaries = self.pose_graph().solve(graphs)
+        for (ka, _), graph, x, summary in zip(todo, graphs, poses, summaries):
+            ka._keep_solution(graph, x, summary)
+        self.refine([ka for ka, _ in todo if ka.map_refinement])
+
+    def refine(self, kas) -> None:
+        """Keyframe_assembly.refine_map for every assembly named, in one Map_refine.refine: key frames K - 1, K - 3, ... >= 0 of each"""
+        if not kas:
+            return
+        ids = [list(range(len(ka.poses_ori) - 1, -1, -2)) for ka in kas]
+        clouds = self.map_refine().refine([ka.keyframe_vec[k].cloud_id for ka, sel in zip(kas, ids) for k in sel],
+                                          np.concatenate([ka.poses_ori[sel] for ka, sel in zip(kas, ids)]),
+                                          np.concatenate([ka.poses_opm[sel] for ka, sel in zip(kas, ids)]), kas[0].map_refinement_resolution, False)
+        cut = np.cumsum([0] + [len(sel) for sel in ids])
+        for k, (ka, sel) in enumerate(zip(kas, ids)):
+            ka.refined = list(zip(sel, clouds[cut[k]:cut[k + 1]]))
 
 
 def _pose7(q, t) -> np.ndarray:

@@ -317,24 +317,18 @@ class Laser_mapping_batch:
     add.  The store starts at loop_closure["max_points"] points per map (2^18 unless given; it grows) under cell_resolution and
     threshold_cell_revisit; full_map(s) reads slot s (stats(), dump()).  key_frames=True (with full_maps=True only) also owns one
     keyframes.Keyframe_assembly per sequence, built with the rest of loop_closure, on top of its slot: per accepted slot add_scan with
-    the new pose and the slot's frame index after the increment, as Laser_mapping._keyframe_step does; then the key frames the slots
-    closed leave the store in one History_buffer_batch.extract_cells and every slot runs its process_waiting on the map handed to it;
-    keyframes[s] and loops[s] are those of Laser_mapping run alone on sequence s.  Nothing of the registration reads the full maps:
-    poses and reports do not change by a bit.  loop_closure_if_enable itself stays refused: it names Laser_mapping's per-sequence
-    map.  loop_closure["device_bank"]=True (off by default): the loop owns ONE api.Keyframe_bank (keyframe_bank) for its S assemblies;
-    a round of key-frame processing is then the analysis half of every slot, one Keyframe_bank.match over all slots' pairs, and the
-    walk half of every slot -- the same logs and loops, float for float.  loop_closure["pose_graph"]=True (off by default): the loop
-    owns ONE api.Pose_graph (pose_graph) for its S assemblies; the loops the slots accept in a round are closed -- their pose graphs
-    optimised -- in one Pose_graph.solve, and every assembly keeps its poses_ori, poses_opm, constraints and pose_graph_summary.
-    loop_closure["map_refinement"]=True (off by default; with batched_history, full_maps, key_frames and loop_closure["pose_graph"]
-    only -- every other configuration raises ValueError): the corrected map behind a closed loop, without a full cloud ever reaching
-    the host.  The History_buffer_batch keeps a scan log (enable_scan_log: m_laser_cloud_full_history of every slot, laser_mapping.hpp:
-    1456, in device blocks) and the loop owns ONE api.Map_refine (map_refine) for its S assemblies.  A step is then append_full,
-    ONE log_full for the accepted slots whose history add let the scan in (:1456 before :1524), the slots' add_scan -- whose flush is
-    a hand-over of the slot's FIFO -- and the key-frame rounds; in a round the key frames analysed get their stored clouds from ONE
-    Map_refine.add_logged at surround_pointcloud_resolution, and the loops closed are refined in ONE Map_refine.refine over all
-    their selections (every second key frame, newest first), split back into each assembly's `refined`.  Stored clouds and `refined`
-    are those of Laser_mapping run alone on the sequence, bit for bit; poses and reports do not change."""
+    the new pose and the slot's frame index after the increment, as Laser_mapping._keyframe_step does; then ONE keyframes.Keyframe_rounds
+    (rounds) over the S assemblies processes the key frames the slots closed, a round at a time, out of the batched store; keyframes[s]
+    and loops[s] are those of Laser_mapping run alone on sequence s.  Nothing of the registration reads the full maps: poses and reports
+    do not change by a bit.  loop_closure_if_enable itself stays refused: it names Laser_mapping's per-sequence map.  The options of
+    loop_closure below are off by default, and what each does in a round is told in Keyframe_rounds:
+    loop_closure["device_bank"]=True: ONE api.Keyframe_bank (keyframe_bank) for the S assemblies, one match per round.
+    loop_closure["pose_graph"]=True: ONE api.Pose_graph (pose_graph) for the S assemblies, one solve per round.
+    loop_closure["map_refinement"]=True (with batched_history, full_maps, key_frames and loop_closure["pose_graph"] only -- every other
+    configuration raises ValueError): ONE api.Map_refine (map_refine) for the S assemblies and a scan log on the History_buffer_batch
+    (enable_scan_log: m_laser_cloud_full_history of every slot, laser_mapping.hpp:1456, in device blocks), so that no full cloud reaches
+    the host.  A step is then append_full, ONE log_full for the accepted slots whose history add let the scan in (:1456 before :1524),
+    the slots' add_scan -- whose flush is a hand-over of the slot's FIFO -- and the rounds: one add_logged and one refine each."""
 
     def __init__(self, n_sequences: int, refresh_threads: int | None = None, batched_history: bool = False, cell_maps: bool = False,
                  cell_matching: bool = False, full_maps: bool = False, key_frames: bool = False, **kw):
@@ -381,7 +375,7 @@ class Laser_mapping_batch:
         self.maps = [Map_buffer(device=device) for _ in range(S)]
         self.batched_history, self.cell_maps, self.cell_matching = bool(batched_history), bool(cell_maps), bool(cell_matching)
         self.full_maps, self.key_frames = bool(full_maps), bool(key_frames)
-        self.keyframes, self.loops, self.keyframe_bank, self.pose_graph, self.map_refine = None, None, None, None, None
+        self.keyframes, self.loops, self.rounds, self.keyframe_bank, self.pose_graph, self.map_refine = None, None, None, None, None, None
         self.full_map_s = 0.0  # cumulative wall time of the full-map phase (append_full, and the key-frame steps with key_frames)
         self.m_maximum_search_range = (a["maximum_search_range_corner"], a["maximum_search_range_surface"])
         self.m_maximum_in_fov_angle, self.m_down_sample_replace = a["maximum_in_fov_angle"], a["down_sample_replace"]
@@ -397,32 +391,23 @@ class Laser_mapping_batch:
                 first = max(int(lc.pop("max_points", 1 << 18)), int(scan_points))
                 self.history_batch.enable_full_maps(first, a["cell_resolution"], a["threshold_cell_revisit"])
                 if key_frames:
-                    from .keyframes import Keyframe_assembly
-                    # loop_closure["device_bank"]: ONE key-frame bank for the S assemblies, and one match per round of _process_keyframes
-                    if lc.pop("device_bank", False):
-                        from .api import Keyframe_bank
-                        self.keyframe_bank = lc["bank"] = Keyframe_bank(device=device)
-                    # loop_closure["pose_graph"]: ONE optimiser for the S assemblies; the loops accepted in a round of
-                    # _process_keyframes are closed in one solve
-                    if lc.pop("pose_graph", False):
-                        from .api import Pose_graph
-                        self.pose_graph = lc["pose_graph"] = Pose_graph(device=device)
-                    # loop_closure["map_refinement"]: the scan log on the batch, ONE store for the S assemblies; the key frames of
-                    # a round are added in one add_logged and the loops of a round refined in one run
-                    logs = [None] * S
-                    if lc.pop("map_refinement", False):
-                        from .api import Map_refine
+                    from .keyframes import Keyframe_assembly, Keyframe_rounds
+                    # the services named in loop_closure are the driver's, ONE of each for the S assemblies, closed with it
+                    on = {k: bool(lc.get(k)) for k in ("device_bank", "pose_graph", "map_refinement")}
+                    lc.update({k: True for k in on if on[k]})
+                    logs = [{}] * S
+                    if on["map_refinement"]:  # the full clouds wait in the scan log on the batch
                         lc.setdefault("maximum_history_size", a["maximum_history_size"])  # (as Laser_mapping hands it on)
                         self.history_batch.enable_scan_log(lc["maximum_history_size"])
-                        self.map_refine = lc["map_refinement"] = Map_refine(device=device)
                         logs = [dict(scan_log=self.history_batch.scan_log(s)) for s in range(S)]
                     self.keyframes = [Keyframe_assembly(device=device, cell_resolution=a["cell_resolution"],
                                                         threshold_cell_revisit=a["threshold_cell_revisit"],
-                                                        full_cell_map=self.history_batch.full_map(s), **lc, **(logs[s] or {})) for s in range(S)]
-                    for ka in self.keyframes:
-                        ka.defer_pose_graph = self.pose_graph is not None
-                        if self.map_refine is not None:
-                            ka.defer_cloud_add = ka.defer_refine = True
+                                                        full_cell_map=self.history_batch.full_map(s), **lc, **logs[s]) for s in range(S)]
+                    self.rounds = Keyframe_rounds(self.keyframes, store=self.history_batch, bank=on["device_bank"],
+                                                  pose_graph=on["pose_graph"], map_refinement=on["map_refinement"])
+                    self.keyframe_bank = self.rounds.bank() if on["device_bank"] else None
+                    self.pose_graph = self.rounds.pose_graph() if on["pose_graph"] else None
+                    self.map_refine = self.rounds.map_refine() if on["map_refinement"] else None
                     self.loops = [[] for _ in range(S)]
         else:
             self.history_batch = None
@@ -456,15 +441,8 @@ class Laser_mapping_batch:
             self._pool = None
         for kf in self.keyframes or []:
             kf.close()
-        if self.keyframe_bank is not None:
-            self.keyframe_bank.close()
-            self.keyframe_bank = None
-        if self.pose_graph is not None:
-            self.pose_graph.close()
-            self.pose_graph = None
-        if self.map_refine is not None:
-            self.map_refine.close()
-            self.map_refine = None
+        if self.rounds is not None:
+            self.rounds.close()
         for h in [self.fe, self.reg, self.vox[0], self.vox[1]] + self.maps + ([self.history_batch] if self.batched_history else self.histories):
             h.close()
 
@@ -490,7 +468,7 @@ class Laser_mapping_batch:
         import time
         t0 = time.perf_counter()
         self.history_batch.append_full(self.fe, new, on, 3, lists=False)  # (a key frame reads its slot's list through its view)
-        logging = getattr(self, "map_refine", None) is not None
+        logging = self.map_refine is not None
         if logging:
             self.history_batch.log_full(self.fe, np.asarray(on, bool) & np.asarray(added, bool))
         if self.key_frames:
@@ -500,90 +478,10 @@ class Laser_mapping_batch:
                     self.keyframes[s].add_scan(none, pose_new, int(self.frame_index[s]), history_added=bool(added[s]))
                 else:
                     self.keyframes[s].add_scan(none, pose_new, int(self.frame_index[s]))
-            self._process_keyframes([s for s, _, _ in jobs])
+            slots = [s for s, _, _ in jobs]
+            for s, found in zip(slots, self.rounds.run(slots)):
+                self.loops[s] += found
         self.full_map_s += time.perf_counter() - t0
-
-    def _process_keyframes(self, slots) -> None:
-        """The waiting key frames of the step's slots, a round at a time: the first waiting key frame of every slot is extracted from
-        the full-cloud store in ONE call, handed to its assembly, and processed.  No append happens between the extraction and the
-        processing, so the cells are read as they are now (cell_map_keyframe.hpp:1243-1261), as by the assembly's own route.  A
-        slot with nothing waiting still gets its process_waiting, as before.  With a shared key-frame bank (loop_closure device_bank)
-        a round is the analysis half of every slot, ONE match over all slots' pairs, then the walk half of every slot."""
-        def waiting(ka):
-            todo = getattr(ka, "m_keyframe_need_precession_list", None)
-            return len(todo) if todo and not ka.if_end else 0
-        first = True
-        while True:
-            todo = [(s, self.keyframes[s]) for s in slots if waiting(self.keyframes[s])]
-            if not todo and not first:
-                return
-            if todo:
-                fronts = [ka.m_keyframe_need_precession_list[0] for _, ka in todo]
-                wants = [ka.wanted_cells(kf) for (_, ka), kf in zip(todo, fronts)]
-                dsts = [ka.new_keyframe_map(len(w)) for (_, ka), w in zip(todo, wants)]
-                try:
-                    self.history_batch.extract_cells(2, [s for s, _ in todo], wants, dsts)
-                except Exception:
-                    for km in dsts:
-                        km.close()
-                    raise
-                for (_, ka), kf, km in zip(todo, fronts, dsts):
-                    ka.prefetch(kf, km)
-            if getattr(self, "keyframe_bank", None) is not None:
-                self._bank_round([s for s, _ in todo])
-            else:
-                for s in (slots if first else [s for s, _ in todo]):
-                    ka = self.keyframes[s]
-                    self.loops[s] += ka.process_waiting(limit=1) if waiting(ka) > 1 else ka.process_waiting()
-            if getattr(self, "map_refine", None) is not None:
-                self._add_clouds(slots)
-            if getattr(self, "pose_graph", None) is not None:
-                self._close_loops(slots)
-            first = False
-
-    def _add_clouds(self, slots) -> None:
-        """the key frames the slots analysed in this round (loop_closure map_refinement): their accumulated clouds out of the scan log
-        into the store in ONE add_logged (laser_mapping.hpp:943-946 for each)"""
-        todo = [(self.keyframes[s], kf) for s in slots for kf in list(getattr(self.keyframes[s], "pending_clouds", ()))]
-        if not todo:
-            return
-        leaf = todo[0][0].surround_pointcloud_resolution
-        ids, _, _ = self.map_refine.add_logged(self.history_batch, [kf.m_accumulated_point_cloud for _, kf in todo], leaf)
-        for (ka, kf), cid in zip(todo, ids):
-            ka.take_cloud_id(kf, int(cid))
-
-    def _close_loops(self, slots) -> None:
-        """the loops the slots accepted in this round (loop_closure pose_graph): their graphs optimised in ONE solve"""
-        todo = [(self.keyframes[s], loop) for s in slots for loop in getattr(self.keyframes[s], "pending_loops", ())]
-        if not todo:
-            return
-        graphs = [ka.loop_graph(loop) for ka, loop in todo]
-        poses, summaries = self.pose_graph.solve(graphs)
-        for (ka, _), graph, x, summary in zip(todo, graphs, poses, summaries):
-            ka.take_solution(graph, x, summary)
-            ka.pending_loops.clear()
-        if getattr(self, "map_refine", None) is not None:  # :1091-1100 for every loop of the round, in ONE run
-            reqs = [ka.refine_request() for ka, _ in todo]
-            clouds = self.map_refine.refine([c for r in reqs for c in r[1]], np.concatenate([r[2] for r in reqs]),
-                                            np.concatenate([r[3] for r in reqs]), todo[0][0].map_refinement_resolution, False)
-            at = 0
-            for (ka, _), r in zip(todo, reqs):
-                ka.refined = list(zip(r[0], clouds[at:at + len(r[0])]))
-                at += len(r[0])
-
-    def _bank_round(self, slots) -> None:
-        """one waiting key frame of every slot named (each has one): analysed and gated per slot, compared in one match, walked per slot"""
-        pairs = [(s, self.keyframes[s].analyse_front()) for s in slots]
-        ids_a, ids_b, cut = [], [], [0]
-        for s, candidates in pairs:
-            a, b = self.keyframes[s].front_pairs()
-            ids_a += a
-            ids_b += b
-            cut.append(len(ids_a))
-        line, plane = self.keyframe_bank.match(ids_a, ids_b) if ids_a else ((), ())
-        for k, (s, candidates) in enumerate(pairs):
-            sims = (line[cut[k]:cut[k + 1]], plane[cut[k]:cut[k + 1]]) if candidates else None
-            self.loops[s] += self.keyframes[s].walk_front(sims)
 
     def _upload(self, scans, stamps, active):
         S = self.n_sequences

@@ -410,12 +410,13 @@ def test_full_step_extracts_once_per_round_between_the_adds_and_the_processing(m
     lm.history_batch, lm.key_frames, lm.full_maps, lm.full_map_s, lm.fe = batch, True, True, 0.0, None
     lm.keyframes = [keyframes.Keyframe_assembly(full_cell_map=Full_map_slot(batch, s), scans_of_each_keyframe=2, scans_between_two_keyframe=1)
                     for s in range(4)]
-    lm.loops = [[] for _ in range(4)]
+    lm.loops, lm.map_refine = [[] for _ in range(4)], None
+    lm.rounds = keyframes.Keyframe_rounds(lm.keyframes, store=batch)
     lm.frame_index = np.zeros(4, np.int32)
-    for s in range(4):
-        real_add, real_proc = lm.keyframes[s].add_scan, lm.keyframes[s].process_waiting
+    for s in range(4):      # ("process": the slot's key frame goes through its pass, walk_front being the half the driver calls by name)
+        real_add, real_proc = lm.keyframes[s].add_scan, lm.keyframes[s].walk_front
         lm.keyframes[s].add_scan = lambda *a, _f=real_add, _s=s: (events.append(("add_scan", _s)), _f(*a))[1]
-        lm.keyframes[s].process_waiting = lambda *a, _f=real_proc, _s=s, **k: (events.append(("process", _s)), _f(*a, **k))[1]
+        lm.keyframes[s].walk_front = lambda *a, _f=real_proc, _s=s, **k: (events.append(("process", _s)), _f(*a, **k))[1]
     pose = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)
     jobs = [(s, pose, pose) for s in (0, 2, 3)]
     on = np.array([True, False, True, True])

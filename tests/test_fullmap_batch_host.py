@@ -255,12 +255,21 @@ def stubbed(monkeypatch):
         def add_scan(self, cloud, pose, frame_index):
             outer.log.append(("add_scan", self.slot, len(cloud), np.array(pose, np.float64).copy(), frame_index))
 
-        def process_waiting(self):
-            outer.log.append(("process_waiting", self.slot))
-            return [("loop", self.slot)] if self.slot == 0 else []
-
         def close(self):
             outer.log.append(("assembly_close", self.slot))
+
+    class Rounds:
+        """stands in for keyframes.Keyframe_rounds: the key-frame rounds of a step, asked for once, for the slots named"""
+
+        def __init__(self, assemblies, store=None, **services):
+            assert not any(services.values())
+
+        def run(self, slots):
+            outer.log.append(("process_waiting", list(slots)))
+            return [[("loop", s)] if s == 0 else [] for s in slots]
+
+        def close(self):
+            pass
 
     def no_single_handles(*a, **kw):
         raise AssertionError("the batched mode must not create per-sequence History_buffer handles")
@@ -269,6 +278,7 @@ def stubbed(monkeypatch):
     for k, v in classes.items():
         monkeypatch.setattr(mapping, k, v)
     monkeypatch.setattr(keyframes, "Keyframe_assembly", Assembly)
+    monkeypatch.setattr(keyframes, "Keyframe_rounds", Rounds)
     return st
 
 
@@ -301,7 +311,7 @@ def test_loop_appends_once_per_step_for_the_accepted_slots_and_feeds_their_key_f
         assert [e[1] for e in scans] == [s for s in range(3) if accepted[s]]  # rejected and idle slots get none
         for e in scans:
             assert e[2] == 0 and np.array_equal(e[3], lb.poses[e[1]]) and e[4] == int(lb.frame_index[e[1]])  # its own frame index, after the increment
-        assert [e[1] for e in st.log if e[0] == "process_waiting"] == [e[1] for e in scans]
+        assert [e[1] for e in st.log if e[0] == "process_waiting"] == [[e[1] for e in scans]]
         n_loops += accepted[0]
     assert out.tolist() == [1, 0, 1]  # (sequence 1 started a step late: this is its frame 4)
     assert lb.frame_index.tolist() == [6, 5, 6]

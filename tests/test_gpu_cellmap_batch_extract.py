@@ -341,7 +341,7 @@ def test_loop_on_the_batched_route_equals_the_host_route_and_the_sequences_alone
     batched, host = Laser_mapping_batch(S, **kw), Laser_mapping_batch(S, **kw)
     for ka in host.keyframes:       # materialize forced to the route through the host, and nothing extracted in advance
         ka.materialize = ka._materialize_host
-    host._process_keyframes = lambda slots: [host.loops[s].extend(host.keyframes[s].process_waiting()) for s in slots]
+    host.rounds.store = None
     alone = [Laser_mapping(scan_points=N_PTS, loop_closure_if_enable=1, loop_closure=LOOP_CLOSURE, **FULL_KW, **MAP_ARGS) for _ in range(S)]
     real_dump, real_step = Full_map_slot.dump, Laser_mapping_batch._full_step
     in_full_step = []

@@ -214,7 +214,7 @@ def test_keyframe_assembly_with_the_bank_gives_the_same_log_and_loops(gpu_lib):
     assert same_records(on.log, off.log) and same_records(on.loops, off.loops) and same_records(found[1], found[0])
     for g, w in zip(on.keyframe_vec, off.keyframe_vec):
         assert sorted(g.analysis) == sorted(w.analysis) and all(same_value(g.analysis[k], w.analysis[k]) for k in g.analysis)
-    assert any("sim_plane" in r for r in on.log) and len(on.bank()) == len(on.keyframe_vec) == 3 and on._owns_bank and off._bank is None
+    assert any("sim_plane" in r for r in on.log) and len(on.rounds.bank()) == len(on.keyframe_vec) == 3 and on.rounds.bank.own and off.rounds.bank.handle is None
     off.close(); on.close()
 
 
@@ -228,7 +228,7 @@ def test_batched_loop_with_one_bank_equals_the_loop_without_and_the_sequences_al
     on = Laser_mapping_batch(S, loop_closure=dict(LOOP_CLOSURE, device_bank=True), **kw)
     off = Laser_mapping_batch(S, loop_closure=LOOP_CLOSURE, **kw)
     alone = [Laser_mapping(scan_points=N_PTS, loop_closure_if_enable=1, loop_closure=LOOP_CLOSURE, **FULL_KW, **MAP_ARGS) for _ in range(S)]
-    assert on.keyframe_bank is not None and off.keyframe_bank is None and all(ka._bank is on.keyframe_bank for ka in on.keyframes)
+    assert on.keyframe_bank is not None and off.keyframe_bank is None and all(ka.rounds.bank() is on.keyframe_bank for ka in on.keyframes)
     matches = 0
     for step in range(n_frames + 2):
         frame = [step - s % 3 for s in range(S)]  # ragged, as tests/test_gpu_fullmap_batch.py runs them

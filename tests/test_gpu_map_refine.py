@@ -278,7 +278,7 @@ def test_mapping_loop_refines_the_map_when_its_detector_accepts_a_loop(gpu_lib):
                     acc.append(np.concatenate(fifo) if fifo else np.zeros((0, 4), np.float32))
                     fifo = []
             K = len(ka.keyframe_vec)
-            store = ka.map_refine_handle()
+            store = ka.rounds.map_refine()
             stored = [mi.filtered(acc[j], 0.5)[1] for j in range(K)]
             for j, kf in enumerate(ka.keyframe_vec):
                 assert kf.cloud_id == j and same(store.cloud(j), stored[j]), j

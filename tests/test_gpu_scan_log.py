@@ -324,7 +324,7 @@ def test_loop_with_map_refinement_equals_the_sequences_run_alone(gpu_lib):
         assert np.array_equal(out, out_off), step
         assert lb.poses.tobytes() == off.poses.tobytes(), (step, "poses")
         assert [None if r is None else report_tuple(r) for r in lb.last_reports] == [None if r is None else report_tuple(r) for r in off.last_reports], step
-    store = solo.map_refine_handle()
+    store = solo.rounds.map_refine()
     for s in range(S):
         ka = lb.keyframes[s]
         assert_same_keyframes(ka, solo, s)

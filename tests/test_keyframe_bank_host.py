@@ -7,7 +7,7 @@ reference's own max_similiarity_of_two_image; the driver runs clean under the ad
 Symbols: the new entry points are declared, exported and bound and refuse null handles and bad arguments without a device.
 Bookkeeping: Keyframe_assembly( device_bank=True ) over a stub bank, on the scripted walks of tests/test_keyframes.py, gives the
 state, log, loops and if_end of device_bank=False, asks for exactly the pairs that pass the three gates, once per processed key frame;
-Laser_mapping_batch's round over stub handles makes one match for all its slots."""
+a Keyframe_rounds over stub assemblies and handles makes one match per round for all its slots."""
 import ctypes as C
 import os
 import re
@@ -315,14 +315,13 @@ def test_device_bank_over_a_stub_gives_the_walk_of_the_pairwise_route(monkeypatc
     assert off.similarity.calls == 2 * len([r for r in off.log if "sim_plane" in r])
     if seed % 2 == 1:
         assert sum(len(a) for a, _ in bank.calls) > len(on.log)        # similarities of candidates the walk skipped were computed, and never seen
-    assert not on._owns_bank
+    assert on.rounds.bank.handle is bank and not on.rounds.bank.own
     on.close()
     assert bank.entries                                                # a bank handed in is not closed by the assembly
 
 
 def test_batched_loop_makes_one_match_per_round_over_all_slots(monkeypatch):
     from loam_livox_amd import keyframes as kfm
-    from loam_livox_amd.mapping import Laser_mapping_batch
     S, min_diff = 3, 2
     scripts = [script(seed) for seed in (2, 3, 6)]
     alone = [stub_assembly(monkeypatch, sc, min_diff, []) for sc in scripts]
@@ -336,8 +335,7 @@ def test_batched_loop_makes_one_match_per_round_over_all_slots(monkeypatch):
             Store.calls += 1
             assert kind == 2 and len(sequences) == len(cell_lists) == len(dsts)
 
-    lm = object.__new__(Laser_mapping_batch)      # the loop's key-frame rounds alone: no device handle is created
-    lm.keyframes, lm.loops, lm.history_batch, lm.keyframe_bank = slots, [[] for _ in range(S)], Store(), bank
+    rounds_of_the_loop, loops = kfm.Keyframe_rounds(slots, store=Store(), bank=bank), [[] for _ in range(S)]
     rounds = 0
     for k in range(K):
         busy = [s for s in range(S) if not alone[s].if_end]
@@ -352,7 +350,8 @@ def test_batched_loop_makes_one_match_per_round_over_all_slots(monkeypatch):
         for s in range(S):
             monkeypatch.setattr(kfm, "keyframe_similarity", alone[s].similarity)
             alone[s].process_waiting()
-        lm._process_keyframes(list(range(S)))
+        for s, found in enumerate(rounds_of_the_loop.run(list(range(S)))):
+            loops[s] += found
         step_rounds = Store.calls - stores                                        # one extraction per round
         assert len(bank.calls) - before <= step_rounds
         if k == 7 and 1 in busy:
@@ -360,7 +359,7 @@ def test_batched_loop_makes_one_match_per_round_over_all_slots(monkeypatch):
         rounds += step_rounds
     for s in range(S):
         assert outcome(slots[s]) == outcome(alone[s]), s
-        assert [dict(r, icp_q=None, icp_t=None) for r in lm.loops[s]] == [dict(r, icp_q=None, icp_t=None) for r in alone[s].loops], s
+        assert [dict(r, icp_q=None, icp_t=None) for r in loops[s]] == [dict(r, icp_q=None, icp_t=None) for r in alone[s].loops], s
     assert any(a.if_end for a in alone) and not all(a.if_end for a in alone)
     # a round's match carries the pairs of all its slots: some call holds entries of more than one sequence, and there are far fewer
     # matches than processed key frames with candidates

@@ -392,7 +392,6 @@ def test_close_loop_over_a_stub_leaves_the_walk_as_it_was(monkeypatch, seed, min
 
 def test_batched_loop_makes_one_solve_per_round_over_all_slots_that_looped(monkeypatch):
     from loam_livox_amd import keyframes as kfm
-    from loam_livox_amd.mapping import Laser_mapping_batch
     from tests import test_keyframe_bank_host as kb
     S, min_diff = 3, 2
     scripts = [kb.script(seed) for seed in (2, 3, 2)]                 # slots 0 and 2 walk the same script: they loop in the same round
@@ -400,15 +399,12 @@ def test_batched_loop_makes_one_solve_per_round_over_all_slots_that_looped(monke
     alone = [kb.stub_assembly(monkeypatch, sc, min_diff, []) for sc in scripts]
     bank, stub = kb.StubBank(), StubPoseGraph()
     slots = [kb.stub_assembly(monkeypatch, sc, min_diff, [], device_bank=True, bank=bank, pose_graph=stub) for sc in scripts]
-    for ka in slots:
-        ka.defer_pose_graph = True                                     # (what Laser_mapping_batch sets on the assemblies it builds)
 
     class Store:
         def extract_cells(self, kind, sequences, cell_lists, dsts):
             pass
 
-    lm = object.__new__(Laser_mapping_batch)      # the loop's key-frame rounds alone: no device handle is created
-    lm.keyframes, lm.loops, lm.history_batch, lm.keyframe_bank, lm.pose_graph = slots, [[] for _ in range(S)], Store(), bank, stub
+    rounds = kfm.Keyframe_rounds(slots, store=Store(), bank=bank, pose_graph=stub)
     solves_per_step = []
     for k in range(kb.K):
         for s in range(S):
@@ -420,7 +416,7 @@ def test_batched_loop_makes_one_solve_per_round_over_all_slots_that_looped(monke
             monkeypatch.setattr(kfm, "keyframe_similarity", alone[s].similarity)
             alone[s].process_waiting()
         before = len(stub.calls)
-        lm._process_keyframes(list(range(S)))
+        rounds.run(list(range(S)))
         solves_per_step.append(len(stub.calls) - before)
     for s in range(S):
         assert kb.outcome(slots[s]) == kb.outcome(alone[s]), s

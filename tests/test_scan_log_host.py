@@ -365,7 +365,7 @@ def test_loop_logs_hands_over_adds_and_refines_once_per_step_and_round(stubbed):
     lb = mapping.Laser_mapping_batch(3, batched_history=True, full_maps=True, key_frames=True, scan_points=100, init_accumulate_frames=2,
                                      maximum_history_size=4, loop_closure=lc)
     assert [e for e in st.log if e[0] == "enable_scan_log"] == [("enable_scan_log", 4)]
-    assert isinstance(lb.map_refine, StubRefine) and all(ka._map_refine is lb.map_refine and ka.defer_cloud_add and ka.defer_refine for ka in lb.keyframes)
+    assert isinstance(lb.map_refine, StubRefine) and lb.rounds.assemblies == lb.keyframes and all(ka.rounds is lb.rounds for ka in lb.keyframes) and lb.rounds.map_refine.handle is lb.map_refine
     assert lc["map_refinement"] is True                                        # the caller's dictionary is left alone
     scan = np.zeros((100, 4), np.float32)
     hand_overs, rounds_with_loops, refines, n_steps = {0: [], 1: [], 2: []}, 0, 0, 16

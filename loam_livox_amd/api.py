@@ -22,12 +22,89 @@ from . import capi
 from .capi import FeParams, RegParams, RegReport, check, ptr
 
 
-class Livox_laser:
+class _Handle:
+    """A class that owns one device handle: L is the library, h the handle (a c_void_p, None once closed), _destroy the name of the
+    entry point that frees it.  close() may be called any number of times and destroys the handle once; an object whose constructor
+    raised before or inside its ll_*_create holds no handle (no h at all, or a null one) and never destroys; __del__ closes and swallows
+    whatever that raises."""
+
+    _destroy = None
+
+    def __init__(self):
+        self.L = capi.load()
+        self.h = C.c_void_p()
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.L, self._destroy)(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _call(self, name: str, *args) -> int:
+        """check( ll_<name>( h, args... ) ), for the bodies that several entry points share"""
+        return check(getattr(self.L, name)(self.h, *args), name)
+
+    def _tap(self, name: str, *lead, n: int = 4) -> np.ndarray:
+        """a test tap: the entry point fills int64[n] behind its leading arguments"""
+        out = np.zeros(n, np.int64)
+        self._call(name, *lead, ptr(out))
+        return out
+
+    def _read_cloud(self, name: str, key: int) -> np.ndarray:
+        """size, then fill, with the count through the last argument: the points [n, 4] an entry point keeps under `key`"""
+        n = C.c_int64(0)
+        self._call(name, int(key), None, 0, C.byref(n))
+        out = np.zeros((int(n.value), 4), np.float32)
+        self._call(name, int(key), ptr(out), len(out), C.byref(n))
+        return out
+
+    def _read_counted_cloud(self, name: str, *lead) -> np.ndarray:
+        """size, then fill, with the count returned (negative: the library's error): the match cloud [n, 4] of a history"""
+        n = self._call(name, *lead, None, 0)
+        out = np.zeros((n, 4), np.float32)
+        if n > 0:
+            check(min(0, getattr(self.L, name)(self.h, *lead, ptr(out), n)), name)
+        return out
+
+
+def _active_mask(active, S: int):
+    """the slots a batched call serves as int32[S], None for all of them"""
+    return None if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.int32).reshape(S)
+
+
+def _handle_table(objs):
+    """the handles of a list of objects as a C array of pointers; None stays a null entry (an idle slot)"""
+    return (C.c_void_p * max(len(objs), 1))(*[None if o is None else o.h for o in objs])
+
+
+def _poses(x, n: int) -> np.ndarray:
+    """n poses as a contiguous float64[n, 7] block (n = -1: as many as x holds)"""
+    return np.ascontiguousarray(x, np.float64).reshape(n, 7)
+
+
+def _keyframe_outputs():
+    """the five output arrays of Maps_keyframe::analyze: images [4, 60, 60], ratio_nonzero [4], eigen_R [2, 3, 3], n_vectors [4],
+    (centre, roi_range) [4]"""
+    return np.zeros((4, 60, 60), np.float32), np.zeros(4, np.float32), np.zeros((2, 3, 3), np.float32), np.zeros(4, np.int32), np.zeros(4, np.float32)
+
+
+def _keyframe_result(img, ratio, R, nv, cr) -> dict:
+    return dict(images=img, ratio_nonzero=ratio, eigen_R=R, n_vectors=nv, centre=cr[:3].copy(), roi_range=float(cr[3]))
+
+
+class Livox_laser(_Handle):
     """Device-backed Livox_laser.  Tunables are the public fields of the reference class
     (livox_feature_extractor.hpp:143-167); they are fixed at construction."""
 
+    _destroy = "ll_fe_destroy"
+
     def __init__(self, max_points: int = 24000, max_scans: int = 1, device: int = 0, piecewise_number: int = 3, **tunables):
-        self.L = capi.load()
+        super().__init__()
         p = capi.fe_default_params()
         p.max_points, p.max_scans, p.device, p.piecewise_number = max_points, max_scans, device, piecewise_number
         for k, v in tunables.items():
@@ -35,21 +112,9 @@ class Livox_laser:
                 raise AttributeError(k)
             setattr(p, k, v)
         self.params = p
-        self.h = C.c_void_p()
         check(self.L.ll_fe_create(C.byref(p), C.byref(self.h)), "ll_fe_create")
         self.m_input_points_size = 0
         self._n = [0] * max_scans
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ll_fe_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # -- per-message path (laser_feature_extractor.hpp:285) ---------------------------------------------------
     def extract_laser_features(self, xyzi: np.ndarray, time_stamp: float) -> int:
@@ -136,35 +201,25 @@ class Livox_laser:
         check(self.L.ll_fe_sync(self.h), "ll_fe_sync")
 
 
-class Spinning_laser:
+class Spinning_laser(_Handle):
     """The spinning-lidar branch of Laser_feature::laserCloudHandler (lidar_type != "livox",
     source/laser_feature_extractor.hpp:393-787) on the device: one message in, the five published clouds out
     (include/loam_livox_hip.h, ll_spin_*).  `extract` is the one-message call, `extract_batch` the batched one."""
+
+    _destroy = "ll_spin_destroy"
 
     TOPICS = ("/laser_points_2", "/laser_cloud_sharp", "/laser_cloud_less_sharp", "/laser_cloud_flat", "/laser_cloud_less_flat")
     FULL, SHARP, LESS_SHARP, FLAT, LESS_FLAT, LESS_FLAT_PRE = range(6)
 
     def __init__(self, scan_line: int = 16, minimum_range: float = 0.1, plane_resolution: float = 0.8, max_points: int = 32768,
                  max_scans: int = 1, max_line_points: int = 8192, device: int = 0):
-        self.L = capi.load()
+        super().__init__()
         p = capi.spin_default_params()
         p.scan_line, p.minimum_range, p.plane_resolution = scan_line, minimum_range, plane_resolution
         p.max_points, p.max_scans, p.max_line_points, p.device = max_points, max_scans, max_line_points, device
         self.params = p
-        self.h = C.c_void_p()
         check(self.L.ll_spin_create(C.byref(p), C.byref(self.h)), "ll_spin_create")
         self.n_ambiguous = 0
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ll_spin_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def upload(self, scans, first_scan: int = 0):
         """scans: a list of (n_b, 4) clouds"""
@@ -254,30 +309,20 @@ class Spinning_laser:
         return ms
 
 
-class VoxelGrid:
+class VoxelGrid(_Handle):
     """pcl::VoxelGrid<pcl::PointXYZI> as the reference uses it (setLeafSize / setInputCloud / filter:
     laser_feature_extractor.hpp:192-193,372-381; laser_mapping.hpp:742-743,1367-1373,1434-1437,533-537),
     PCL 1.9 semantics with a deterministic in-leaf order (include/loam_livox_hip.h)."""
 
+    _destroy = "ll_voxel_destroy"
+
     def __init__(self, max_points: int = 100000, max_clouds: int = 1, device: int = 0):
-        self.L = capi.load()
-        self.h = C.c_void_p()
+        super().__init__()
         self.max_points, self.max_clouds = max_points, max_clouds
         check(self.L.ll_voxel_create(device, max_clouds, max_points, C.byref(self.h)), "ll_voxel_create")
         self.leaf = np.array([0.4, 0.4, 0.4], np.float32)
         self._cloud = None
         self.status = 0
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ll_voxel_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def setLeafSize(self, lx: float, ly: float, lz: float):
         self.leaf = np.array([lx, ly, lz], np.float32)
@@ -311,62 +356,43 @@ class VoxelGrid:
         return n_out, st
 
 
-class History_buffer:
+class History_buffer(_Handle):
     """m_laser_cloud_{corner,surface}_history + update_buff_for_matching (history mode), laser_mapping.hpp:1417-1478,
     517-546, resident on the device (include/loam_livox_hip.h, ll_history_*)."""
 
+    _destroy = "ll_history_destroy"
+
     def __init__(self, maximum_history_size: int = 100, max_points_per_frame: int = 24000, line_res: float = 0.1,
                  plane_res: float = 0.4, device: int = 0):
-        self.L = capi.load()
-        self.h = C.c_void_p()
+        super().__init__()
         self.device = device
         check(self.L.ll_history_create(device, maximum_history_size, max_points_per_frame, line_res, plane_res, C.byref(self.h)),
               "ll_history_create")
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ll_history_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def __len__(self):
         return int(self.L.ll_history_size(self.h))
 
-    def add(self, corner, surf, pose, history_add_t_step: float = 0.0, history_add_angle_step: float = 0.0) -> bool:
-        corner, surf = capi.as_f32(corner, 4), capi.as_f32(surf, 4)
+    def _add(self, name: str, source, pose, t_step: float, angle_step: float) -> bool:
+        """the four adds: the entry point's own arguments (`source`), then the pose, the two steps of the add rule and the added flag"""
         pose = np.ascontiguousarray(pose, np.float64)
         added = C.c_int32(0)
-        check(self.L.ll_history_add(self.h, ptr(corner), corner.shape[0], ptr(surf), surf.shape[0], ptr(pose), history_add_t_step,
-                                    history_add_angle_step, C.byref(added)), "ll_history_add")
+        self._call(name, *source, ptr(pose), t_step, angle_step, C.byref(added))
         return bool(added.value)
 
+    def add(self, corner, surf, pose, history_add_t_step: float = 0.0, history_add_angle_step: float = 0.0) -> bool:
+        corner, surf = capi.as_f32(corner, 4), capi.as_f32(surf, 4)
+        return self._add("ll_history_add", (ptr(corner), corner.shape[0], ptr(surf), surf.shape[0]), pose, history_add_t_step, history_add_angle_step)
+
     def add_fe(self, fe: "Livox_laser", scan: int, pose, history_add_t_step: float = 0.0, history_add_angle_step: float = 0.0) -> bool:
-        pose = np.ascontiguousarray(pose, np.float64)
-        added = C.c_int32(0)
-        check(self.L.ll_history_add_fe(self.h, fe.h, scan, ptr(pose), history_add_t_step, history_add_angle_step, C.byref(added)),
-              "ll_history_add_fe")
-        return bool(added.value)
+        return self._add("ll_history_add_fe", (fe.h, scan), pose, history_add_t_step, history_add_angle_step)
 
     def add_spin(self, spin: "Spinning_laser", scan: int, pose, history_add_t_step: float = 0.0, history_add_angle_step: float = 0.0) -> bool:
         """add_fe for a spinning-lidar handle: the less-sharp and the less-flat cloud of slot `scan`, device to device"""
-        pose = np.ascontiguousarray(pose, np.float64)
-        added = C.c_int32(0)
-        check(self.L.ll_history_add_spin(self.h, spin.h, scan, ptr(pose), history_add_t_step, history_add_angle_step, C.byref(added)),
-              "ll_history_add_spin")
-        return bool(added.value)
+        return self._add("ll_history_add_spin", (spin.h, scan), pose, history_add_t_step, history_add_angle_step)
 
     def add_voxel(self, vox_corner: "VoxelGrid", vox_surf: "VoxelGrid", cloud: int, pose, history_add_t_step: float = 0.0,
                   history_add_angle_step: float = 0.0) -> bool:
-        pose = np.ascontiguousarray(pose, np.float64)
-        added = C.c_int32(0)
-        check(self.L.ll_history_add_voxel(self.h, vox_corner.h, vox_surf.h, cloud, ptr(pose), history_add_t_step,
-                                          history_add_angle_step, C.byref(added)), "ll_history_add_voxel")
-        return bool(added.value)
+        return self._add("ll_history_add_voxel", (vox_corner.h, vox_surf.h, cloud), pose, history_add_t_step, history_add_angle_step)
 
     def refresh(self, map_buffer: "Map_buffer"):
         nc, ns = C.c_int64(0), C.c_int64(0)
@@ -408,12 +434,7 @@ class History_buffer:
         check(self.L.ll_history_set_gate_pose(self.h, ptr(p)), "ll_history_set_gate_pose")
 
     def map_cloud(self, kind: int) -> np.ndarray:
-        n = self.L.ll_history_map_cloud(self.h, kind, None, 0)
-        out = np.zeros((max(n, 0), 4), np.float32)
-        if n > 0:
-            check(min(0, self.L.ll_history_map_cloud(self.h, kind, ptr(out), n)), "ll_history_map_cloud")
-        return out
-
+        return self._read_counted_cloud("ll_history_map_cloud", kind)
 
     def map_cloud_device(self, kind: int):
         """The same cloud as a torch tensor (n, 4) float32 ON THE DEVICE, copied device-to-device out of the handle's
@@ -426,36 +447,31 @@ class History_buffer:
         return torch.as_tensor(_DeviceView(p.value, n.value), device=f"cuda:{self.device}").clone()
 
 
-class History_buffer_batch:
+class History_buffer_batch(_Handle):
     """The match buffers of n_sequences sequences in one handle (include/loam_livox_hip.h, ll_history_batch_*): slot s is a
     History_buffer in every result -- add rule with the gate pose, FIFO, concatenation, VoxelGrid, the snapshots published into
     maps[s] -- while one add_voxel / add_fe and one refresh serve all slots with a fixed number of launches and host waits."""
 
+    _destroy = "ll_history_batch_destroy"
+
     def __init__(self, n_sequences: int, maximum_history_size: int = 100, max_points_per_frame: int = 24000, line_res: float = 0.1,
                  plane_res: float = 0.4, device: int = 0):
-        self.L = capi.load()
-        self.h = C.c_void_p()
+        super().__init__()
         self.device, self.n_sequences = device, int(n_sequences)
         check(self.L.ll_history_batch_create(device, n_sequences, maximum_history_size, max_points_per_frame, line_res, plane_res,
                                              C.byref(self.h)), "ll_history_batch_create")
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ll_history_batch_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _slots(self, active, poses, gate_poses):
         S = self.n_sequences
-        act = None if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.int32).reshape(S)
-        poses = np.ascontiguousarray(poses, np.float64).reshape(S, 7)
-        gate = None if gate_poses is None else np.ascontiguousarray(gate_poses, np.float64).reshape(S, 7)
-        return act, poses, gate, np.zeros(S, np.int32)
+        act = _active_mask(active, S)
+        return act, _poses(poses, S), None if gate_poses is None else _poses(gate_poses, S), np.zeros(S, np.int32)
+
+    def _maps(self, maps, active):
+        """(handle table of maps, active mask, two int64[S] for the sizes) of a refresh: a map per slot, None for an inactive one"""
+        S = self.n_sequences
+        if len(maps) != S:
+            raise ValueError(f"{len(maps)} maps for {S} sequences")
+        return _handle_table(maps), _active_mask(active, S), np.zeros(S, np.int64), np.zeros(S, np.int64)
 
     def add_voxel(self, vox_corner: "VoxelGrid", vox_surf: "VoxelGrid", poses, gate_poses=None, active=None, history_add_t_step: float = 0.0,
                   history_add_angle_step: float = 0.0) -> np.ndarray:
@@ -475,12 +491,7 @@ class History_buffer_batch:
 
     def refresh(self, maps, active=None):
         """maps: n_sequences Map_buffer (None allowed for an inactive slot).  Returns (n_corner [S], n_surf [S]) of the match buffers."""
-        S = self.n_sequences
-        if len(maps) != S:
-            raise ValueError(f"{len(maps)} maps for {S} sequences")
-        act = None if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.int32).reshape(S)
-        arr = (C.c_void_p * S)(*[None if m is None else m.h for m in maps])
-        nc, ns = np.zeros(S, np.int64), np.zeros(S, np.int64)
+        arr, act, nc, ns = self._maps(maps, active)
         check(self.L.ll_history_batch_refresh(self.h, arr, ptr(act), ptr(nc), ptr(ns)), "ll_history_batch_refresh")
         return nc, ns
 
@@ -489,13 +500,8 @@ class History_buffer_batch:
         """update_buff_for_matching in the cell mode (m_matching_mode == 1) for every active slot, at poses [S][7]: the cells in range
         and in the field of view, each through the VoxelGrid (and replaced by its leaves with down_sample_replace), concatenated,
         filtered, published into maps[s].  Needs enable_cell_maps.  Returns (n_corner [S], n_surf [S])."""
-        S = self.n_sequences
-        if len(maps) != S:
-            raise ValueError(f"{len(maps)} maps for {S} sequences")
-        act = None if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.int32).reshape(S)
-        poses = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(S, 7)
-        arr = (C.c_void_p * S)(*[None if m is None else m.h for m in maps])
-        nc, ns = np.zeros(S, np.int64), np.zeros(S, np.int64)
+        arr, act, nc, ns = self._maps(maps, active)
+        poses = None if poses is None else _poses(poses, self.n_sequences)
         check(self.L.ll_history_batch_refresh_cells(self.h, arr, ptr(act), ptr(poses), maximum_search_range_corner, maximum_search_range_surface,
                                                     maximum_in_fov_angle, int(down_sample_replace), ptr(nc), ptr(ns)), "ll_history_batch_refresh_cells")
         return nc, ns
@@ -503,22 +509,13 @@ class History_buffer_batch:
     def cell_match_work(self) -> np.ndarray:
         """test tap (ll_history_batch_cell_match_work): enqueues and host waits of the last refresh_cells, compactions so far, log and live
         entries of the corner and of the surface stores, candidates of the last refresh"""
-        out = np.zeros(8, np.int64)
-        check(self.L.ll_history_batch_cell_match_work(self.h, ptr(out)), "ll_history_batch_cell_match_work")
-        return out
+        return self._tap("ll_history_batch_cell_match_work", n=8)
 
     def size(self, sequence: int) -> int:
         return int(self.L.ll_history_batch_size(self.h, sequence))
 
     def map_cloud(self, sequence: int, kind: int) -> np.ndarray:
-        n = self.L.ll_history_batch_map_cloud(self.h, sequence, kind, None, 0)
-        if n < 0:
-            check(-1, "ll_history_batch_map_cloud")
-        out = np.zeros((n, 4), np.float32)
-        if n > 0:
-            check(min(0, self.L.ll_history_batch_map_cloud(self.h, sequence, kind, ptr(out), n)), "ll_history_batch_map_cloud")
-        return out
-
+        return self._read_counted_cloud("ll_history_batch_map_cloud", sequence, kind)
 
     def enable_cell_maps(self, initial_points_per_map: int = 1 << 20, cell_resolution: float = 1.0, threshold_cell_revisit: int = 5000) -> None:
         """the two cell maps of every slot (laser_mapping.hpp:274-275, 617-624): fed by every active slot of add_voxel / add_fe, put in
@@ -537,9 +534,7 @@ class History_buffer_batch:
     def cell_map_work(self) -> np.ndarray:
         """test tap (ll_history_batch_cell_map_work): points appended, points sorted or gathered inside adds, materialisations, launches of
         the cell-map part of the last add"""
-        out = np.zeros(4, np.int64)
-        check(self.L.ll_history_batch_cell_map_work(self.h, ptr(out)), "ll_history_batch_cell_map_work")
-        return out
+        return self._tap("ll_history_batch_cell_map_work")
 
     def enable_full_maps(self, initial_points_per_map: int = 1 << 20, cell_resolution: float = 1.0, threshold_cell_revisit: int = 5000) -> None:
         """the full-cloud map of every slot (m_pt_cell_map_full, laser_mapping.hpp:1442, 1527), independent of enable_cell_maps: fed by
@@ -554,8 +549,8 @@ class History_buffer_batch:
         per slot the cells [n, 3] its last appended scan touched (Cell_map.append_cloud_touched's list; an inactive slot keeps its own),
         with lists=False only their numbers [S] (full_touched(s) reads a list later)"""
         S = self.n_sequences
-        act = None if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.int32).reshape(S)
-        poses = np.ascontiguousarray(poses, np.float64).reshape(S, 7)
+        act = _active_mask(active, S)
+        poses = _poses(poses, S)
         n = np.zeros(S, np.int64)
         check(self.L.ll_history_batch_append_full_fe(self.h, fe.h, ptr(act), ptr(poses), int(min_points), ptr(n)), "ll_history_batch_append_full_fe")
         self._full_min_points = int(min_points)
@@ -590,7 +585,7 @@ class History_buffer_batch:
         off = np.zeros(R + 1, np.int64)
         off[1:] = np.cumsum([len(c) for c in lists])
         ijk = np.ascontiguousarray(np.concatenate(lists)) if R and off[-1] else None
-        arr = (C.c_void_p * max(R, 1))(*[d.h for d in dsts])
+        arr = _handle_table(dsts)
         nc, npts = np.zeros(max(R, 1), np.int64), np.zeros(max(R, 1), np.int64)
         check(self.L.ll_history_batch_extract_cells(self.h, int(kind), R, ptr(seq), ptr(off), ptr(ijk), arr, ptr(nc), ptr(npts)),
               "ll_history_batch_extract_cells")
@@ -601,16 +596,12 @@ class History_buffer_batch:
     def extract_work(self) -> np.ndarray:
         """test tap (ll_history_batch_extract_work): enqueues and host waits of the last extract_cells, stored points sorted or moved
         by extractions (stays 0), materialisations extractions caused"""
-        out = np.zeros(4, np.int64)
-        check(self.L.ll_history_batch_extract_work(self.h, ptr(out)), "ll_history_batch_extract_work")
-        return out
+        return self._tap("ll_history_batch_extract_work")
 
     def full_map_work(self) -> np.ndarray:
         """test tap (ll_history_batch_full_map_work): enqueues and host waits of the last append_full, stored points sorted or gathered
         inside append_full calls, materialisations of the full store"""
-        out = np.zeros(4, np.int64)
-        check(self.L.ll_history_batch_full_map_work(self.h, ptr(out)), "ll_history_batch_full_map_work")
-        return out
+        return self._tap("ll_history_batch_full_map_work")
 
     def enable_scan_log(self, maximum_history_size: int = 100, initial_scans: int | None = None) -> None:
         """the scan log of every slot (m_laser_cloud_full_history, laser_mapping.hpp:1456, kept on the device): fed by log_full behind
@@ -623,7 +614,7 @@ class History_buffer_batch:
         """behind the append_full of the same step: the full cloud of every slot named in `active` (all, when None) that the append took
         joins the slot's FIFO, and every FIFO of the append's slots is trimmed (:1456, 1480-1486).  One launch, no host wait."""
         S = self.n_sequences
-        act = None if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.int32).reshape(S)
+        act = _active_mask(active, S)
         check(self.L.ll_history_batch_log_full_fe(self.h, fe.h, ptr(act)), "ll_history_batch_log_full_fe")
 
     def hand_over(self, sequence: int) -> int:
@@ -639,17 +630,11 @@ class History_buffer_batch:
 
     def read_group(self, group_id: int) -> np.ndarray:
         """test tap and debug read: the group's points [n, 4], scan after scan"""
-        n = C.c_int64(0)
-        check(self.L.ll_history_batch_scan_log_read(self.h, int(group_id), None, 0, C.byref(n)), "ll_history_batch_scan_log_read")
-        out = np.zeros((int(n.value), 4), np.float32)
-        check(self.L.ll_history_batch_scan_log_read(self.h, int(group_id), ptr(out), len(out), C.byref(n)), "ll_history_batch_scan_log_read")
-        return out
+        return self._read_cloud("ll_history_batch_scan_log_read", group_id)
 
     def scan_log_work(self) -> np.ndarray:
         """test tap (ll_history_batch_scan_log_work): enqueue calls and host waits of the last log_full, blocks in use, blocks allocated"""
-        out = np.zeros(4, np.int64)
-        check(self.L.ll_history_batch_scan_log_work(self.h, ptr(out)), "ll_history_batch_scan_log_work")
-        return out
+        return self._tap("ll_history_batch_scan_log_work")
 
     def scan_log(self, sequence: int) -> "Scan_log_slot":
         return Scan_log_slot(self, int(sequence))
@@ -670,7 +655,45 @@ class Scan_log_slot:
             self.batch.drop_groups(group_ids)
 
 
-class Cell_map_slot:
+class _Cell_map_readers:
+    """stats(), dump() and device_view() of a cell map, for Cell_map (ll_cellmap_*) and for the view of a History_buffer_batch's slot
+    (ll_history_batch_cell_map_*): the two families take the same arguments behind what names the map.  A class says in _map() where
+    its map is: (library, prefix of the entry points, leading arguments)."""
+
+    def stats(self):
+        """(cells, points, m_current_frame_idx)"""
+        L, prefix, lead = self._map()
+        nc, npts, fr = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        check(getattr(L, prefix + "stats")(*lead, C.byref(nc), C.byref(npts), C.byref(fr)), prefix + "stats")
+        return nc.value, npts.value, fr.value
+
+    def dump(self):
+        """(xyz [n,3] in (cell, insertion) order, cell indices [c,3], first point of each cell [c+1], last-update frame [c])"""
+        L, prefix, lead = self._map()
+        nc, npts, _ = self.stats()
+        xyzi = np.zeros((max(npts, 1), 4), np.float32)
+        ijk = np.zeros((max(nc, 1), 3), np.int32)
+        start = np.zeros(nc + 1, np.int32)
+        last = np.zeros(max(nc, 1), np.int32)
+        check(getattr(L, prefix + "dump")(*lead, ptr(xyzi), xyzi.shape[0], ptr(ijk), ptr(start), ptr(last), ijk.shape[0]), prefix + "dump")
+        return xyzi[:npts, :3].copy(), ijk[:nc].copy(), start, last[:nc].copy()
+
+    def device_view(self, device: int = 0):
+        """(points (n, 4) float32, cell keys (n,) int64) as torch DEVICE tensors, copied device-to-device out of the handle's arrays
+        (which the next append rewrites; a batch's store, which the next add writes behind and may move): the input of
+        multigpu.gather_cell_maps, no host hop"""
+        import torch
+        L, prefix, lead = self._map()
+        p, k, n, nc = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(0)
+        check(getattr(L, prefix + "device_view")(*lead, C.byref(p), C.byref(k), C.byref(n), C.byref(nc)), prefix + "device_view")
+        if n.value == 0:
+            return torch.zeros((0, 4), dtype=torch.float32, device=f"cuda:{device}"), torch.zeros(0, dtype=torch.int64, device=f"cuda:{device}")
+        pts = torch.as_tensor(_DeviceView(p.value, n.value), device=f"cuda:{device}").clone()
+        keys = torch.as_tensor(_DeviceView64(k.value, n.value), device=f"cuda:{device}").clone()
+        return pts, keys
+
+
+class Cell_map_slot(_Cell_map_readers):
     """One cell map of one slot of a History_buffer_batch, read the way a Cell_map is: stats(), dump() and device_view(device) have
     Cell_map's return shapes, so what gathers a Cell_map (multigpu.gather_cell_maps) takes a slot's view unchanged."""
 
@@ -678,39 +701,8 @@ class Cell_map_slot:
         self.batch, self.sequence, self.kind = batch, sequence, kind
         self.resolution = getattr(batch, "_full_resolution" if kind == 2 else "_cell_resolution", None)
 
-    def stats(self):
-        """(cells, points, m_current_frame_idx)"""
-        b = self.batch
-        nc, npts, fr = C.c_int64(0), C.c_int64(0), C.c_int32(0)
-        check(b.L.ll_history_batch_cell_map_stats(b.h, self.sequence, self.kind, C.byref(nc), C.byref(npts), C.byref(fr)),
-              "ll_history_batch_cell_map_stats")
-        return nc.value, npts.value, fr.value
-
-    def dump(self):
-        """(xyz [n,3] in (cell, insertion) order, cell indices [c,3], first point of each cell [c+1], last-update frame [c])"""
-        b = self.batch
-        nc, npts, _ = self.stats()
-        xyzi = np.zeros((max(npts, 1), 4), np.float32)
-        ijk = np.zeros((max(nc, 1), 3), np.int32)
-        start = np.zeros(nc + 1, np.int32)
-        last = np.zeros(max(nc, 1), np.int32)
-        check(b.L.ll_history_batch_cell_map_dump(b.h, self.sequence, self.kind, ptr(xyzi), xyzi.shape[0], ptr(ijk), ptr(start), ptr(last),
-                                                 ijk.shape[0]), "ll_history_batch_cell_map_dump")
-        return xyzi[:npts, :3].copy(), ijk[:nc].copy(), start, last[:nc].copy()
-
-    def device_view(self, device: int = 0):
-        """(points (n, 4) float32, cell keys (n,) int64) as torch DEVICE tensors, copied device-to-device out of the handle's store
-        (which the next add writes behind and may move)"""
-        import torch
-        b = self.batch
-        p, k, n, nc = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(0)
-        check(b.L.ll_history_batch_cell_map_device_view(b.h, self.sequence, self.kind, C.byref(p), C.byref(k), C.byref(n), C.byref(nc)),
-              "ll_history_batch_cell_map_device_view")
-        if n.value == 0:
-            return torch.zeros((0, 4), dtype=torch.float32, device=f"cuda:{device}"), torch.zeros(0, dtype=torch.int64, device=f"cuda:{device}")
-        pts = torch.as_tensor(_DeviceView(p.value, n.value), device=f"cuda:{device}").clone()
-        keys = torch.as_tensor(_DeviceView64(k.value, n.value), device=f"cuda:{device}").clone()
-        return pts, keys
+    def _map(self):
+        return self.batch.L, "ll_history_batch_cell_map_", (self.batch.h, self.sequence, self.kind)
 
     def extract_cells_into(self, cell_ijk, dst: "Cell_map"):
         """Cell_map.extract_cells for this slot: the one-request form of History_buffer_batch.extract_cells.  (Not named extract_cells:
@@ -761,45 +753,31 @@ class _DeviceView64:
         self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "<i8", "data": (int(address), False), "version": 2}
 
 
-class Cell_map:
+class Cell_map(_Handle, _Cell_map_readers):
     """Points_cloud_map<float> (cell_map_keyframe.hpp:477-790) as used by the "cube" matching mode, resident on the
     device (include/loam_livox_hip.h, ll_cellmap_*): append_cloud, find_cells_in_radius + if_pt_in_fov + per-cell
     VoxelGrid (laser_mapping.hpp:475-513)."""
 
+    _destroy = "ll_cellmap_destroy"
+
     def __init__(self, max_points: int = 1 << 20, resolution: float = 1.0, minimum_revisit_threshold: int = 2**31 - 1, device: int = 0,
                  _borrowed=None):
-        self.L = capi.load()
+        super().__init__()
         self.owned = _borrowed is None
         self.resolution = resolution
         self.max_points = int(max_points)
         if self.owned:
-            self.h = C.c_void_p()
             check(self.L.ll_cellmap_create(device, max_points, resolution, minimum_revisit_threshold, C.byref(self.h)), "ll_cellmap_create")
         else:
             self.h = C.c_void_p(_borrowed)
 
     def close(self):
-        if getattr(self, "h", None) and self.owned:
-            self.L.ll_cellmap_destroy(self.h)
-        self.h = None
+        if not getattr(self, "owned", True):
+            self.h = None   # borrowed (History_buffer.cell_map): the history destroys it
+        super().close()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def device_view(self, device: int = 0):
-        """(points (n, 4) float32, cell keys (n,) int64) as torch DEVICE tensors, copied device-to-device out of the handle's arrays
-        (which the next append rewrites): the input of multigpu.gather_cell_maps, no host hop"""
-        import torch
-        p, k, n, nc = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(0)
-        check(self.L.ll_cellmap_device_view(self.h, C.byref(p), C.byref(k), C.byref(n), C.byref(nc)), "ll_cellmap_device_view")
-        if n.value == 0:
-            return torch.zeros((0, 4), dtype=torch.float32, device=f"cuda:{device}"), torch.zeros(0, dtype=torch.int64, device=f"cuda:{device}")
-        pts = torch.as_tensor(_DeviceView(p.value, n.value), device=f"cuda:{device}").clone()
-        keys = torch.as_tensor(_DeviceView64(k.value, n.value), device=f"cuda:{device}").clone()
-        return pts, keys
+    def _map(self):
+        return self.L, "ll_cellmap_", (self.h,)
 
     def reserve(self, max_points: int) -> None:
         """room for max_points points (no-op when not larger); content, revisit stamps and frame counter are kept"""
@@ -835,12 +813,6 @@ class Cell_map:
         check(self.L.ll_cellmap_append_touched(self.h, ptr(cloud), cloud.shape[0], int(min_points), ptr(ijk), cap, C.byref(n)),
               "ll_cellmap_append_touched")
         return ijk[:n.value].copy()
-
-    def stats(self):
-        """(cells, points, m_current_frame_idx)"""
-        nc, npts, fr = C.c_int64(0), C.c_int64(0), C.c_int32(0)
-        check(self.L.ll_cellmap_stats(self.h, C.byref(nc), C.byref(npts), C.byref(fr)), "ll_cellmap_stats")
-        return nc.value, npts.value, fr.value
 
     def query_filter(self, pose, radius: float, maximum_in_fov_angle: float, leaf: float, down_sample_replace: int = 1):
         """Returns (concatenated per-cell filtered cloud [n,4], number of selected cells)."""
@@ -878,43 +850,22 @@ class Cell_map:
     def keyframe_images(self, roi_ratio: float = 0.9):
         """Maps_keyframe::analyze over the cells of this map (cell_map_keyframe.hpp:1385-1493): dict(images [4,60,60] =
         line, plane, line_roi, plane_roi; ratio_nonzero [4]; eigen_R [2,3,3]; n_vectors [4]; centre [3]; roi_range)."""
-        img = np.zeros((4, 60, 60), np.float32)
-        ratio, R, nv, cr = np.zeros(4, np.float32), np.zeros((2, 3, 3), np.float32), np.zeros(4, np.int32), np.zeros(4, np.float32)
-        check(self.L.ll_cellmap_keyframe_images(self.h, roi_ratio, ptr(img), ptr(ratio), ptr(R), ptr(nv), ptr(cr)), "ll_cellmap_keyframe_images")
-        return dict(images=img, ratio_nonzero=ratio, eigen_R=R, n_vectors=nv, centre=cr[:3].copy(), roi_range=float(cr[3]))
-
-    def dump(self):
-        """(xyz [n,3] in (cell, insertion) order, cell indices [c,3], first point of each cell [c+1], last-update frame [c])"""
-        nc, npts, _ = self.stats()
-        xyzi = np.zeros((max(npts, 1), 4), np.float32)
-        ijk = np.zeros((max(nc, 1), 3), np.int32)
-        start = np.zeros(nc + 1, np.int32)
-        last = np.zeros(max(nc, 1), np.int32)
-        check(self.L.ll_cellmap_dump(self.h, ptr(xyzi), xyzi.shape[0], ptr(ijk), ptr(start), ptr(last), ijk.shape[0]), "ll_cellmap_dump")
-        return xyzi[:npts, :3].copy(), ijk[:nc].copy(), start, last[:nc].copy()
+        out = _keyframe_outputs()
+        check(self.L.ll_cellmap_keyframe_images(self.h, roi_ratio, *map(ptr, out)), "ll_cellmap_keyframe_images")
+        return _keyframe_result(*out)
 
 
-class Scene_aligner:
+class Scene_aligner(_Handle):
     """The device route of Scene_alignment::find_tranfrom_of_two_mappings (scene_alignment.hpp:269-391; ll_scene_align_*): one registrar,
     one map, one voxel filter, the selected clouds and their filtered forms, kept between calls and grown from initial_points.  No point of either key
     frame crosses to the host."""
 
+    _destroy = "ll_scene_align_destroy"
+
     def __init__(self, initial_points: int = 1 << 16, device: int = 0):
-        self.L = capi.load()
-        self.h = C.c_void_p()
+        super().__init__()
         check(self.L.ll_scene_align_create(device, int(initial_points), C.byref(self.h)), "ll_scene_align_create")
         self.params = capi.scene_align_default_params()
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ll_scene_align_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def run(self, keyframe_a: "Cell_map", keyframe_b: "Cell_map"):
         """(pose float64[7] = m_q_w_curr, m_t_w_curr; m_inlier_threshold; the reports of the registrations run)"""
@@ -932,43 +883,28 @@ class Scene_aligner:
     def work(self) -> np.ndarray:
         """test tap (ll_scene_align_work) on the last run: bytes of point data copied between host and device, host waits,
         registrations run, enqueues of the selection step"""
-        out = np.zeros(4, np.int64)
-        check(self.L.ll_scene_align_work(self.h, ptr(out)), "ll_scene_align_work")
-        return out
+        return self._tap("ll_scene_align_work")
 
 
-class Keyframe_bank:
+class Keyframe_bank(_Handle):
     """The key-frame descriptor bank (ll_keyframe_bank_*): the line and plane direction image of every processed key frame stay on the
     device with their norms; match answers "these (new, old) pairs" in one launch chain and one host wait, with keyframe_similarity's
     floats bit for bit.  An entry's id is its position in the order of the adds; the capacity doubles on demand."""
 
+    _destroy = "ll_keyframe_bank_destroy"
+
     def __init__(self, initial_entries: int = 256, device: int = 0):
-        self.L = capi.load()
-        self.h = C.c_void_p()
+        super().__init__()
         check(self.L.ll_keyframe_bank_create(device, int(initial_entries), C.byref(self.h)), "ll_keyframe_bank_create")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ll_keyframe_bank_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __len__(self):
         return int(check(self.L.ll_keyframe_bank_size(self.h), "ll_keyframe_bank_size"))
 
     def add_cell_map(self, cell_map: "Cell_map", roi_ratio: float = 0.9):
         """(Cell_map.keyframe_images( roi_ratio ) of the map, the id of the new entry): images 0 and 1 go into the bank device to device"""
-        img = np.zeros((4, 60, 60), np.float32)
-        ratio, R, nv, cr = np.zeros(4, np.float32), np.zeros((2, 3, 3), np.float32), np.zeros(4, np.int32), np.zeros(4, np.float32)
-        eid = C.c_int64(-1)
-        check(self.L.ll_keyframe_bank_add_cellmap(self.h, cell_map.h, roi_ratio, ptr(img), ptr(ratio), ptr(R), ptr(nv), ptr(cr), C.byref(eid)),
-              "ll_keyframe_bank_add_cellmap")
-        return dict(images=img, ratio_nonzero=ratio, eigen_R=R, n_vectors=nv, centre=cr[:3].copy(), roi_range=float(cr[3])), int(eid.value)
+        out, eid = _keyframe_outputs(), C.c_int64(-1)
+        check(self.L.ll_keyframe_bank_add_cellmap(self.h, cell_map.h, roi_ratio, *map(ptr, out), C.byref(eid)), "ll_keyframe_bank_add_cellmap")
+        return _keyframe_result(*out), int(eid.value)
 
     def add_images(self, img_line, img_plane) -> int:
         """an entry from two 60 x 60 host images; returns its id"""
@@ -1002,9 +938,7 @@ class Keyframe_bank:
 
     def work(self) -> np.ndarray:
         """test tap (ll_keyframe_bank_work) on the last match: enqueues, host waits, image bytes copied between host and device, pairs"""
-        out = np.zeros(4, np.int64)
-        check(self.L.ll_keyframe_bank_work(self.h, ptr(out)), "ll_keyframe_bank_work")
-        return out
+        return self._tap("ll_keyframe_bank_work")
 
 
 def map_refine_affine(pose_ori, pose_opm):
@@ -1016,26 +950,16 @@ def map_refine_affine(pose_ori, pose_opm):
     return R, T
 
 
-class Map_refine:
+class Map_refine(_Handle):
     """The key-frame map refinement (ll_map_refine_*): Mapping_refine of ceres_pose_graph_3d.hpp:368-538 over key-frame clouds that stay
     on the device.  add_cloud filters an accumulated cloud into the store and returns its id (its position in the order of the adds);
     refine moves and filters any selection of them in one launch chain and one host wait; merge filters the last outputs as one cloud."""
 
+    _destroy = "ll_map_refine_destroy"
+
     def __init__(self, initial_points: int = 1 << 20, device: int = 0):
-        self.L = capi.load()
-        self.h = C.c_void_p()
+        super().__init__()
         check(self.L.ll_map_refine_create(device, int(initial_points), C.byref(self.h)), "ll_map_refine_create")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ll_map_refine_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __len__(self):
         return int(check(self.L.ll_map_refine_size(self.h), "ll_map_refine_size"))
@@ -1071,16 +995,12 @@ class Map_refine:
 
     def cloud(self, cloud_id: int) -> np.ndarray:
         """a stored cloud [n, 4], read back"""
-        n = C.c_int64(0)
-        check(self.L.ll_map_refine_cloud(self.h, int(cloud_id), None, 0, C.byref(n)), "ll_map_refine_cloud")
-        out = np.zeros((int(n.value), 4), np.float32)
-        check(self.L.ll_map_refine_cloud(self.h, int(cloud_id), ptr(out), len(out), C.byref(n)), "ll_map_refine_cloud")
-        return out
+        return self._read_cloud("ll_map_refine_cloud", cloud_id)
 
     def run(self, ids, poses_ori, poses_opm, leaf: float = 0.2, transform_first: bool = False):
         """(offsets int64[n_sel + 1], status int32[n_sel]) of a run whose outputs stay on the device"""
         ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-        a, b = np.ascontiguousarray(poses_ori, np.float64).reshape(-1, 7), np.ascontiguousarray(poses_opm, np.float64).reshape(-1, 7)
+        a, b = _poses(poses_ori, -1), _poses(poses_opm, -1)
         if len(a) != len(ids) or len(b) != len(ids):
             raise ValueError("a pose pair per selected id")
         offsets, status = np.zeros(len(ids) + 1, np.int64), np.zeros(len(ids), np.int32)
@@ -1109,23 +1029,22 @@ class Map_refine:
     def work(self) -> np.ndarray:
         """test tap (ll_map_refine_work) on the last add / run / merge and its fetch: the host's enqueue calls (the sort and the scan one
         each), host waits, bytes between host and device, points of the chain"""
-        out = np.zeros(4, np.int64)
-        check(self.L.ll_map_refine_work(self.h, ptr(out)), "ll_map_refine_work")
-        return out
+        return self._tap("ll_map_refine_work")
 
 
-class Pose_graph:
+class Pose_graph(_Handle):
     """The pose-graph optimiser (ll_pose_graph_*): Ceres_pose_graph_3d::pose_graph_optimization (ceres_pose_graph_3d.hpp:336-352) for
     any number of independent graphs in one launch and one host wait.  A graph is a dict: poses [N, 7] {qx, qy, qz, qw, tx, ty, tz}
     (pose 0 is held constant), ab [E, 2] pose ids of every edge, meas [E, 7] in the pose layout, and optionally information [E, 36].
     The handle's capacities grow on demand (the handle is created again, larger: it keeps nothing between calls)."""
 
+    _destroy = "ll_pose_graph_destroy"
+
     def __init__(self, max_graphs: int = 16, max_poses: int = 4096, max_edges: int = 8192, max_envelope_blocks: int = 1 << 16, device: int = 0,
                  params=None):
-        self.L = capi.load()
+        super().__init__()
         self.device = device
         self.params = params if params is not None else capi.pose_graph_default_params()
-        self.h = None
         self._create([int(max_graphs), int(max_poses), int(max_edges), int(max_envelope_blocks)])
 
     def _create(self, capacity):
@@ -1133,17 +1052,6 @@ class Pose_graph:
         h = C.c_void_p()
         check(self.L.ll_pose_graph_create(self.device, *capacity, C.byref(h)), "ll_pose_graph_create")
         self.h, self.capacity = h, list(capacity)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ll_pose_graph_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def envelope_blocks(n_poses: int, ab) -> int:
@@ -1195,9 +1103,7 @@ class Pose_graph:
 
     def work(self) -> np.ndarray:
         """test tap (ll_pose_graph_work) on the last solve: enqueues, host waits, envelope blocks, graphs"""
-        out = np.zeros(4, np.int64)
-        check(self.L.ll_pose_graph_work(self.h, ptr(out)), "ll_pose_graph_work")
-        return out
+        return self._tap("ll_pose_graph_work")
 
 
 def _q_mul(a, b):
@@ -1250,26 +1156,16 @@ def keyframe_similarity(img_a, img_b, device: int = 0) -> float:
     return float(out.value)
 
 
-class Map_buffer:
+class Map_buffer(_Handle):
     """m_laser_cloud_{corner,surf}_from_map + their kd-trees (laser_mapping.hpp:539-546) as device grids."""
+
+    _destroy = "ll_map_destroy"
 
     CORNER, SURF = 0, 1
 
     def __init__(self, device: int = 0):
-        self.L = capi.load()
-        self.h = C.c_void_p()
+        super().__init__()
         check(self.L.ll_map_create(device, C.byref(self.h)), "ll_map_create")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ll_map_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def setInputCloud(self, kind: int, cloud: np.ndarray, cell_size: float = 0.0):
         cloud = np.ascontiguousarray(cloud, np.float32)
@@ -1311,13 +1207,14 @@ class Map_buffer:
         return float(ms.value)
 
 
-class Point_cloud_registration:
+class Point_cloud_registration(_Handle):
     """Device-backed Point_cloud_registration.  Configuration fields keep the reference names
     (point_cloud_registration.hpp:45-103); poses are the m_q_w_*/m_t_w_* pairs packed as float64[7]."""
 
+    _destroy = "ll_reg_destroy"
+
     def __init__(self, max_scans: int = 1, max_features: int = 24000, device: int = 0):
-        self.L = capi.load()
-        self.h = C.c_void_p()
+        super().__init__()
         check(self.L.ll_reg_create(device, max_scans, max_features, C.byref(self.h)), "ll_reg_create")
         self.params = capi.reg_default_params()
         self.max_scans = max_scans
@@ -1327,17 +1224,6 @@ class Point_cloud_registration:
         self.m_para_buffer_incremental = ident.copy()
         self.report = RegReport()
         self.m_inlier_threshold = 0.0
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ll_reg_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def find_out_incremental_transfrom(self, map_buffer: Map_buffer, laserCloudCornerStack: np.ndarray,
                                        laserCloudSurfStack: np.ndarray) -> int:
@@ -1353,7 +1239,9 @@ class Point_cloud_registration:
         self.m_inlier_threshold = rep.inlier_threshold
         return ret
 
-    def solve_batch(self, map_buffer: Map_buffer, corners: list, surfs: list, poses_last: np.ndarray, poses_curr: np.ndarray):
+    @staticmethod
+    def _pack_features(corners: list, surfs: list):
+        """ragged feature clouds as the library takes them: (n, corner [n, stride, 4], counts [n], stride, and the same of the surfaces)"""
         n = len(corners)
         nc = np.array([len(c) for c in corners], np.int32)
         ns = np.array([len(s) for s in surfs], np.int32)
@@ -1363,8 +1251,12 @@ class Point_cloud_registration:
         for i in range(n):
             cbuf[i, :nc[i]] = corners[i]
             sbuf[i, :ns[i]] = surfs[i]
-        pl = np.ascontiguousarray(poses_last, np.float64).reshape(n, 7)
-        pc = np.ascontiguousarray(poses_curr, np.float64).reshape(n, 7).copy()
+        return n, cbuf, nc, sc, sbuf, ns, ss
+
+    def solve_batch(self, map_buffer: Map_buffer, corners: list, surfs: list, poses_last: np.ndarray, poses_curr: np.ndarray):
+        n, cbuf, nc, sc, sbuf, ns, ss = self._pack_features(corners, surfs)
+        pl = _poses(poses_last, n)
+        pc = _poses(poses_curr, n).copy()
         pi = np.tile(np.array([0, 0, 0, 1, 0, 0, 0], np.float64), (n, 1))
         reps = (RegReport * n)()
         res = np.zeros(n, np.int32)
@@ -1374,89 +1266,66 @@ class Point_cloud_registration:
 
     def upload_features(self, corners: list, surfs: list):
         """Host feature clouds -> the registrar's HBM buffers (the upload half of solve_batch)."""
-        n = len(corners)
-        nc = np.array([len(c) for c in corners], np.int32)
-        ns = np.array([len(s) for s in surfs], np.int32)
-        sc, ss = max(1, int(nc.max())), max(1, int(ns.max()))
-        cbuf = np.zeros((n, sc, 4), np.float32)
-        sbuf = np.zeros((n, ss, 4), np.float32)
-        for i in range(n):
-            cbuf[i, :nc[i]] = corners[i]
-            sbuf[i, :ns[i]] = surfs[i]
+        n, cbuf, nc, sc, sbuf, ns, ss = self._pack_features(corners, surfs)
         check(self.L.ll_reg_upload_features(self.h, n, ptr(cbuf), ptr(nc), sc, ptr(sbuf), ptr(ns), ss), "ll_reg_upload_features")
         return n
 
+    def _enqueue(self, name: str, sources, n_scans: int, poses_last, poses_curr, heads=(), frame_index=()):
+        """the eight enqueues: the entry point's own handles and settings (`sources`: the map or the table of maps, the extractor, the
+        filters), the number of scans (and the heads of a merged scan), the parameters (and the frame indices of a map per slot), the
+        two pose blocks; no completion flag"""
+        pl, pc = _poses(poses_last, n_scans), _poses(poses_curr, n_scans)
+        self._call(name, *sources, n_scans, *heads, C.byref(self.params), *frame_index, ptr(pl), ptr(pc), None)
+
     def enqueue_uploaded(self, map_buffer: Map_buffer, n_scans: int, poses_last, poses_curr):
-        pl = np.ascontiguousarray(poses_last, np.float64).reshape(n_scans, 7)
-        pc = np.ascontiguousarray(poses_curr, np.float64).reshape(n_scans, 7)
-        check(self.L.ll_reg_enqueue_uploaded(self.h, map_buffer.h, n_scans, C.byref(self.params), ptr(pl), ptr(pc), None),
-              "ll_reg_enqueue_uploaded")
+        self._enqueue("ll_reg_enqueue_uploaded", (map_buffer.h,), n_scans, poses_last, poses_curr)
 
     def enqueue_fe(self, map_buffer: Map_buffer, fe: Livox_laser, n_scans: int, poses_last, poses_curr):
-        pl = np.ascontiguousarray(poses_last, np.float64).reshape(n_scans, 7)
-        pc = np.ascontiguousarray(poses_curr, np.float64).reshape(n_scans, 7)
-        check(self.L.ll_reg_enqueue_fe(self.h, map_buffer.h, fe.h, n_scans, C.byref(self.params), ptr(pl), ptr(pc), None),
-              "ll_reg_enqueue_fe")
+        self._enqueue("ll_reg_enqueue_fe", (map_buffer.h, fe.h), n_scans, poses_last, poses_curr)
 
     def enqueue_fe_merged(self, map_buffer: Map_buffer, fe: Livox_laser, n_scans: int, heads: int, poses_last, poses_curr):
         """Mid-100 (laser_feature_extractor.hpp:348-358): registrar scan b = the selected features of extractor slots
         b * heads ... b * heads + heads - 1, concatenated on the device (corner clouds together, surface clouds together)."""
-        pl = np.ascontiguousarray(poses_last, np.float64).reshape(n_scans, 7)
-        pc = np.ascontiguousarray(poses_curr, np.float64).reshape(n_scans, 7)
-        check(self.L.ll_reg_enqueue_fe_merged(self.h, map_buffer.h, fe.h, n_scans, int(heads), C.byref(self.params), ptr(pl), ptr(pc), None),
-              "ll_reg_enqueue_fe_merged")
+        self._enqueue("ll_reg_enqueue_fe_merged", (map_buffer.h, fe.h), n_scans, poses_last, poses_curr, heads=(int(heads),))
 
     def enqueue_fe_downsampled(self, map_buffer: Map_buffer, fe: Livox_laser, vox_corner: "VoxelGrid", vox_surf: "VoxelGrid",
                                line_res: float, plane_res: float, n_scans: int, poses_last, poses_curr):
         """m_if_input_downsample_mode (laser_mapping.hpp:1367-1373): voxel-filter the selected features on the device, then
         register them."""
-        pl = np.ascontiguousarray(poses_last, np.float64).reshape(n_scans, 7)
-        pc = np.ascontiguousarray(poses_curr, np.float64).reshape(n_scans, 7)
-        check(self.L.ll_reg_enqueue_fe_downsampled(self.h, map_buffer.h, fe.h, vox_corner.h, vox_surf.h, line_res, plane_res, n_scans,
-                                                   C.byref(self.params), ptr(pl), ptr(pc), None), "ll_reg_enqueue_fe_downsampled")
+        self._enqueue("ll_reg_enqueue_fe_downsampled", (map_buffer.h, fe.h, vox_corner.h, vox_surf.h, line_res, plane_res), n_scans, poses_last, poses_curr)
 
-    def _maps_args(self, maps, n_scans: int, poses_last, poses_curr, frame_index):
-        """the handle table, poses and frame indices of a map-per-slot enqueue (None in maps = an idle slot)"""
+    def _maps_args(self, maps, n_scans: int, frame_index):
+        """the handle table and the frame indices of a map-per-slot enqueue (None in maps = an idle slot)"""
         if len(maps) != n_scans:
             raise ValueError(f"maps has {len(maps)} entries for {n_scans} scans")
-        tab = (C.c_void_p * n_scans)(*[None if m is None else m.h for m in maps])
-        pl = np.ascontiguousarray(poses_last, np.float64).reshape(n_scans, 7)
-        pc = np.ascontiguousarray(poses_curr, np.float64).reshape(n_scans, 7)
         fi = None
         if frame_index is not None:
             fi = np.ascontiguousarray(frame_index, np.int32).reshape(n_scans)
-        return tab, pl, pc, fi
+        return _handle_table(maps), (ptr(fi),)
 
     def enqueue_fe_maps(self, maps, fe: Livox_laser, n_scans: int, poses_last, poses_curr, frame_index=None):
         """enqueue_fe with a map per slot (ll_reg_enqueue_fe_maps): scan b is registered against maps[b] (a Map_buffer, or None for an
         idle slot) with frame_index[b] (None: params.current_frame_index for every slot); the start-up gate is decided per slot."""
-        tab, pl, pc, fi = self._maps_args(maps, n_scans, poses_last, poses_curr, frame_index)
-        check(self.L.ll_reg_enqueue_fe_maps(self.h, tab, fe.h, n_scans, C.byref(self.params), None if fi is None else ptr(fi), ptr(pl), ptr(pc), None),
-              "ll_reg_enqueue_fe_maps")
+        tab, fi = self._maps_args(maps, n_scans, frame_index)
+        self._enqueue("ll_reg_enqueue_fe_maps", (tab, fe.h), n_scans, poses_last, poses_curr, frame_index=fi)
 
     def enqueue_fe_downsampled_maps(self, maps, fe: Livox_laser, vox_corner: "VoxelGrid", vox_surf: "VoxelGrid", line_res: float, plane_res: float,
                                     n_scans: int, poses_last, poses_curr, frame_index=None):
         """enqueue_fe_downsampled with a map per slot (ll_reg_enqueue_fe_downsampled_maps)"""
-        tab, pl, pc, fi = self._maps_args(maps, n_scans, poses_last, poses_curr, frame_index)
-        check(self.L.ll_reg_enqueue_fe_downsampled_maps(self.h, tab, fe.h, vox_corner.h, vox_surf.h, line_res, plane_res, n_scans,
-                                                        C.byref(self.params), None if fi is None else ptr(fi), ptr(pl), ptr(pc), None),
-              "ll_reg_enqueue_fe_downsampled_maps")
+        tab, fi = self._maps_args(maps, n_scans, frame_index)
+        self._enqueue("ll_reg_enqueue_fe_downsampled_maps", (tab, fe.h, vox_corner.h, vox_surf.h, line_res, plane_res), n_scans, poses_last, poses_curr,
+                      frame_index=fi)
 
     def enqueue_spin(self, map_buffer: Map_buffer, spin: "Spinning_laser", n_scans: int, poses_last, poses_curr):
         """enqueue_fe for a spinning-lidar handle: corner stack = its less-sharp cloud, surface stack = its less-flat cloud, read where
         the extractor left them (ll_reg_enqueue_spin).  params.if_motion_deblur must be 0."""
-        pl = np.ascontiguousarray(poses_last, np.float64).reshape(n_scans, 7)
-        pc = np.ascontiguousarray(poses_curr, np.float64).reshape(n_scans, 7)
-        check(self.L.ll_reg_enqueue_spin(self.h, map_buffer.h, spin.h, n_scans, C.byref(self.params), ptr(pl), ptr(pc), None),
-              "ll_reg_enqueue_spin")
+        self._enqueue("ll_reg_enqueue_spin", (map_buffer.h, spin.h), n_scans, poses_last, poses_curr)
 
     def enqueue_spin_downsampled(self, map_buffer: Map_buffer, spin: "Spinning_laser", vox_corner: "VoxelGrid", vox_surf: "VoxelGrid",
                                  line_res: float, plane_res: float, n_scans: int, poses_last, poses_curr):
         """enqueue_fe_downsampled for a spinning-lidar handle (m_if_input_downsample_mode, laser_mapping.hpp:1367-1373)"""
-        pl = np.ascontiguousarray(poses_last, np.float64).reshape(n_scans, 7)
-        pc = np.ascontiguousarray(poses_curr, np.float64).reshape(n_scans, 7)
-        check(self.L.ll_reg_enqueue_spin_downsampled(self.h, map_buffer.h, spin.h, vox_corner.h, vox_surf.h, line_res, plane_res, n_scans,
-                                                     C.byref(self.params), ptr(pl), ptr(pc), None), "ll_reg_enqueue_spin_downsampled")
+        self._enqueue("ll_reg_enqueue_spin_downsampled", (map_buffer.h, spin.h, vox_corner.h, vox_surf.h, line_res, plane_res), n_scans, poses_last,
+                      poses_curr)
 
     def collect(self, n_scans: int):
         pc = np.zeros((n_scans, 7), np.float64)
@@ -1501,20 +1370,16 @@ class Point_cloud_registration:
         check(self.L.ll_reg_set_profiling(self.h, int(enable)), "ll_reg_set_profiling")
 
     def debug_worklists(self, n_scans=1):
-        out = np.zeros(4, np.int64)
-        check(self.L.ll_reg_debug_worklists(self.h, int(n_scans), ptr(out)), "ll_reg_debug_worklists")
+        out = self._tap("ll_reg_debug_worklists", int(n_scans))
         return int(out[0] + out[2]), int(out[1] + out[3])
 
     def debug_worklists_by_kind(self, n_scans=1):
         """((corner searched, corner re-sorted), (surface searched, surface re-sorted)) of the last ICP iteration"""
-        out = np.zeros(4, np.int64)
-        check(self.L.ll_reg_debug_worklists(self.h, int(n_scans), ptr(out)), "ll_reg_debug_worklists")
+        out = self._tap("ll_reg_debug_worklists", int(n_scans))
         return (int(out[0]), int(out[1])), (int(out[2]), int(out[3]))
 
     def debug_cycles(self, scan: int = 0):
-        out = np.zeros(16, np.int64)
-        check(self.L.ll_reg_debug_cycles(self.h, scan, ptr(out)), "ll_reg_debug_cycles")
-        return out
+        return self._tap("ll_reg_debug_cycles", scan, n=16)
 
     def kernel_times(self):
         ms = np.zeros(3, np.float32)
@@ -1527,7 +1392,7 @@ class Point_cloud_registration:
         of every accepted scan, moved to the map frame with its pose, are appended to the torch DEVICE tensor `out`
         ((capacity, 4) float32, contiguous) from row n_used on.  Returns the new row count."""
         acc = np.ascontiguousarray(accept, np.int32)
-        ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        ps = _poses(poses, -1)
         assert out.is_contiguous() and out.shape[1] == 4 and acc.shape[0] >= n_scans and ps.shape[0] >= n_scans
         n = C.c_int64(int(n_used))
         check(self.L.ll_cloud_transform_fe_device(self.h, fe.h, int(n_scans), int(kind), ptr(acc), ptr(ps), C.c_void_p(out.data_ptr()),
@@ -1538,7 +1403,7 @@ class Point_cloud_registration:
                                      n_used: int) -> int:
         """append_to_submap_device for a spinning-lidar handle: cloud `which` (Spinning_laser.FULL .. LESS_FLAT) of every accepted scan"""
         acc = np.ascontiguousarray(accept, np.int32)
-        ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        ps = _poses(poses, -1)
         assert out.is_contiguous() and out.shape[1] == 4 and acc.shape[0] >= n_scans and ps.shape[0] >= n_scans
         n = C.c_int64(int(n_used))
         check(self.L.ll_cloud_transform_spin_device(self.h, spin.h, int(n_scans), int(which), ptr(acc), ptr(ps), C.c_void_p(out.data_ptr()),

@@ -17,6 +17,18 @@ import numpy as np
 from .api import History_buffer, History_buffer_batch, Livox_laser, Map_buffer, Point_cloud_registration, Spinning_laser, VoxelGrid
 
 
+def _set_registrar_params(p, *, scan_points, icp_max_iterations, ceres_max_iterations, max_allow_incre_R, max_allow_incre_T, max_allow_final_cost,
+                          init_accumulate_frames, minimum_icp_R_diff, minimum_icp_T_diff, maximum_residual_blocks, subsample_seed, **others) -> None:
+    """the registrar's parameters from the arguments of Laser_mapping of the same names (others: the arguments the registrar does not take)"""
+    p.icp_max_iterations, p.ceres_max_iterations = icp_max_iterations, ceres_max_iterations
+    p.para_max_angular_rate, p.para_max_speed, p.max_final_cost = max_allow_incre_R, max_allow_incre_T, max_allow_final_cost
+    p.mapping_init_accumulate_frames = init_accumulate_frames
+    p.minimum_icp_R_diff, p.minimum_icp_T_diff = minimum_icp_R_diff, minimum_icp_T_diff  # PCR:94-95
+    # optimization/maximum_residual_blocks (200 in the shipped configs): sub-sampling on a reproducible stream; 0 = keep all
+    p.maximum_allow_residual_block = maximum_residual_blocks if maximum_residual_blocks > 0 else scan_points
+    p.subsample_seed = subsample_seed if maximum_residual_blocks > 0 else 0
+
+
 class Laser_mapping:
     """lidar_type (common/lidar_type of the feature node, laser_feature_extractor.hpp:831-851): "livox" (default) runs the Livox
     extractor; any other value runs the spinning-lidar one (scan_line 16 or 64, minimum_range, mapping_plane_resolution: the feature
@@ -71,14 +83,10 @@ class Laser_mapping:
                 self.history.set_cell_map_async(True)
         self.m_if_input_downsample_mode = input_downsample_mode
         self.history_add_t_step, self.history_add_angle_step = history_add_t_step, history_add_angle_step
-        p = self.reg.params
-        p.icp_max_iterations, p.ceres_max_iterations = icp_max_iterations, ceres_max_iterations
-        p.para_max_angular_rate, p.para_max_speed, p.max_final_cost = max_allow_incre_R, max_allow_incre_T, max_allow_final_cost
-        p.mapping_init_accumulate_frames = init_accumulate_frames
-        p.minimum_icp_R_diff, p.minimum_icp_T_diff = minimum_icp_R_diff, minimum_icp_T_diff  # PCR:94-95
-        # optimization/maximum_residual_blocks (200 in the shipped configs): sub-sampling on a reproducible stream; 0 = keep all
-        p.maximum_allow_residual_block = maximum_residual_blocks if maximum_residual_blocks > 0 else scan_points
-        p.subsample_seed = subsample_seed if maximum_residual_blocks > 0 else 0
+        _set_registrar_params(self.reg.params, scan_points=scan_points, icp_max_iterations=icp_max_iterations, ceres_max_iterations=ceres_max_iterations,
+                              max_allow_incre_R=max_allow_incre_R, max_allow_incre_T=max_allow_incre_T, max_allow_final_cost=max_allow_final_cost,
+                              init_accumulate_frames=init_accumulate_frames, minimum_icp_R_diff=minimum_icp_R_diff,
+                              minimum_icp_T_diff=minimum_icp_T_diff, maximum_residual_blocks=maximum_residual_blocks, subsample_seed=subsample_seed)
         self.m_current_frame_index = 0
         self.pose = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)  # m_q_w_curr / m_t_w_curr
         self.map_sizes = (0, 0)
@@ -415,13 +423,7 @@ class Laser_mapping_batch:
         self.line_res, self.plane_res = a["line_res"], a["plane_res"]
         self.m_if_input_downsample_mode = a["input_downsample_mode"]
         self.history_add_t_step, self.history_add_angle_step = a["history_add_t_step"], a["history_add_angle_step"]
-        p = self.reg.params
-        p.icp_max_iterations, p.ceres_max_iterations = a["icp_max_iterations"], a["ceres_max_iterations"]
-        p.para_max_angular_rate, p.para_max_speed, p.max_final_cost = a["max_allow_incre_R"], a["max_allow_incre_T"], a["max_allow_final_cost"]
-        p.mapping_init_accumulate_frames = a["init_accumulate_frames"]
-        p.minimum_icp_R_diff, p.minimum_icp_T_diff = a["minimum_icp_R_diff"], a["minimum_icp_T_diff"]
-        p.maximum_allow_residual_block = a["maximum_residual_blocks"] if a["maximum_residual_blocks"] > 0 else scan_points
-        p.subsample_seed = a["subsample_seed"] if a["maximum_residual_blocks"] > 0 else 0
+        _set_registrar_params(self.reg.params, **a)
         self.frame_index = np.zeros(S, np.int32)                                  # m_current_frame_index of every sequence
         self.poses = np.tile(np.array([0, 0, 0, 1, 0, 0, 0], np.float64), (S, 1))  # m_q_w_curr / m_t_w_curr
         self.map_sizes = [(0, 0)] * S

@@ -79,6 +79,10 @@ struct Quaterniond_map {
     double &y() { return p[1]; }
     double &z() { return p[2]; }
     double &w() { return p[3]; }
+    double x() const { return p[0]; }
+    double y() const { return p[1]; }
+    double z() const { return p[2]; }
+    double w() const { return p[3]; }
     Quaterniond_map &operator=(const Quaterniond &q)
     {
         for (int i = 0; i < 4; i++) p[i] = q.c[i];
@@ -95,6 +99,7 @@ struct Vector3d_map {
     double *p;
     explicit Vector3d_map(double *q) : p(q) {}
     double &operator()(int i) { return p[i]; }
+    double operator()(int i) const { return p[i]; }
     Vector3d_map &operator=(const Vector3d &v)
     {
         for (int i = 0; i < 3; i++) p[i] = v.c[i];
@@ -175,6 +180,85 @@ inline void xyzi_to_cloud(const float *v, int n, Cloud &c)
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// What the classes below share.
+//
+// Ownership: a class that owns an ll_* handle holds it in a Handle, which destroys it exactly once.  A Handle moves and does not
+// copy, and so does its class; a moved-from object holds null, and the library refuses its calls ("null handle", thrown by check).
+template <class T, void (*Destroy)(T *)>
+struct Destroyer {
+    void operator()(T *h) const { Destroy(h); }
+};
+template <class T, void (*Destroy)(T *)>
+using Handle = std::unique_ptr<T, Destroyer<T, Destroy>>;
+
+// The one way a handle is made, in a constructor, on first use, or larger than the one before (which is destroyed first):
+// create( &raw ) wraps the ll_*_create call.  The process' runtime hints come first, so no call site applies them.
+template <class H, class Create>
+inline void make_handle(H &h, const char *what, Create create)
+{
+    h.reset();
+    runtime_hints();
+    typename H::pointer raw = nullptr;
+    check(create(&raw), what);
+    h.reset(raw);
+}
+
+// The one way a cloud is read back, size then fill: call( buffer, capacity in points ) wraps the C call and answers the number of
+// points; it is asked with ( nullptr, 0 ) first and, unless the cloud is empty, with a buffer of that size.  A negative answer throws
+// through check with the entry point's name.
+template <class Call>
+inline std::vector<float> read_xyzi(const char *what, Call call)
+{
+    const int64_t n = call((float *)nullptr, (int64_t)0);
+    if (n < 0) check(-1, what);
+    std::vector<float> v((size_t)n * 4);
+    if (n > 0 && call(v.data(), n) < 0) check(-1, what);
+    return v;
+}
+template <class Cloud, class Call>
+inline void read_cloud(const char *what, Cloud &out, Call call)
+{
+    const std::vector<float> v = read_xyzi(what, call);
+    xyzi_to_cloud(v.data(), (int)(v.size() / 4), out);
+}
+
+// A pose in the C ABI's order {qx,qy,qz,qw,tx,ty,tz}, from and to a quaternion read as q.x() and a vector read as t( i ): the
+// look-alikes above, their _map views and Eigen's types.
+template <class Q, class V>
+inline void to_pose7(const Q &q, const V &t, double out[7])
+{
+    out[0] = q.x(), out[1] = q.y(), out[2] = q.z(), out[3] = q.w();
+    for (int i = 0; i < 3; i++) out[4 + i] = t(i);
+}
+template <class Q, class V>
+inline void from_pose7(const double in[7], Q &q, V &t)
+{
+    q.x() = in[0], q.y() = in[1], q.z() = in[2], q.w() = in[3];
+    for (int i = 0; i < 3; i++) t(i) = in[4 + i];
+}
+
+// cell indices as the int32 {i, j, k} triples of the C ABI, appended to ijk
+inline void pack_cells(const std::vector<std::array<int, 3>> &cells, std::vector<int32_t> &ijk)
+{
+    for (const std::array<int, 3> &c : cells)
+        for (size_t d = 0; d < 3; d++) ijk.push_back((int32_t)c[d]);
+}
+// lists laid end to end: list r is [ off[r], off[r + 1] )
+template <class T>
+inline std::vector<int64_t> csr_offsets(const std::vector<std::vector<T>> &lists)
+{
+    std::vector<int64_t> off(lists.size() + 1, 0);
+    for (size_t r = 0; r < lists.size(); r++) off[r + 1] = off[r] + (int64_t)lists[r].size();
+    return off;
+}
+// the points of a cloud argument; the C ABI wants a readable pointer for an empty one too
+inline const float *xyzi_or_dummy(const std::vector<float> &v)
+{
+    static const float dummy[4] = {0, 0, 0, 0};
+    return v.empty() ? dummy : v.data();
+}
+
+// ------------------------------------------------------------------------------------------------------------
 class Livox_laser {
    public:
     // public tunables of the reference class (livox_feature_extractor.hpp:143-167); set them before the first
@@ -197,11 +281,6 @@ class Livox_laser {
     };
     std::vector<Pt_infos> m_pts_info_vec;
 
-    ~Livox_laser()
-    {
-        if (h_) ll_fe_destroy(h_);
-    }
-
     // std::vector<pcl::PointCloud<PointXYZI>> extract_laser_features(cloud, time_stamp), LFE:722: the petal clouds of
     // split_laser_scan (LFE:657-719) -- a new cloud whenever the petal angle changes, the last petal dropped (:681), points
     // masked 000 / too-near / nan removed, intensity = idx / N (set_intensity(e_I_motion_blur), :283-286), empty petals
@@ -215,15 +294,15 @@ class Livox_laser {
         m_input_points_size = n;
         first_of_.clear();
         int32_t n_clouds = 0;
-        check(ll_fe_extract(h_, raw_.data(), n, time_stamp, &n_clouds), "ll_fe_extract");
+        check(ll_fe_extract(h_.get(), raw_.data(), n, time_stamp, &n_clouds), "ll_fe_extract");
         std::vector<int32_t> type(n), label(n);
         std::vector<float> depth(n), curv(n), view(n), ts(n), pang(n);
-        check(ll_fe_labels(h_, 0, type.data(), label.data(), depth.data(), nullptr, curv.data(), view.data(), ts.data(), pang.data()),
+        check(ll_fe_labels(h_.get(), 0, type.data(), label.data(), depth.data(), nullptr, curv.data(), view.data(), ts.data(), pang.data()),
               "ll_fe_labels");
         m_pts_info_vec.resize(n);
         for (int i = 0; i < n; i++) m_pts_info_vec[i] = Pt_infos{type[i], label[i], i, ts[i], depth[i], curv[i], view[i]};
         int32_t ns = 0, cl = 0, npc = 0;
-        check(ll_fe_splits(h_, 0, nullptr, &ns, &cl, &npc, nullptr, nullptr, nullptr, nullptr), "ll_fe_splits");
+        check(ll_fe_splits(h_.get(), 0, nullptr, &ns, &cl, &npc, nullptr, nullptr, nullptr, nullptr), "ll_fe_splits");
         std::vector<Cloud> out;
         if (cl == 0) return out;  // fewer than 6 split entries (LFE:572, 759-762)
         int scan_idx = 0;
@@ -284,7 +363,7 @@ class Livox_laser {
         std::vector<int32_t> ci(n), si(n), fi(n);
         std::vector<float> cc((size_t)n * 4), sc((size_t)n * 4);
         int32_t nc = 0, ns = 0, nf = 0;
-        check(ll_fe_select(h_, minimum_blur, maximum_blur, ci.data(), &nc, si.data(), &ns, fi.data(), &nf, cc.data(), sc.data()),
+        check(ll_fe_select(h_.get(), minimum_blur, maximum_blur, ci.data(), &nc, si.data(), &ns, fi.data(), &nf, cc.data(), sc.data()),
               "ll_fe_select");
         xyzi_to_cloud(cc.data(), nc, pc_corners);
         xyzi_to_cloud(sc.data(), ns, pc_surface);
@@ -315,8 +394,7 @@ class Livox_laser {
         p.max_points = max_points;
         p.max_scans = 1;
         p.piecewise_number = piecewise_number;
-        runtime_hints();
-        check(ll_fe_create(&p, &h_), "ll_fe_create");
+        make_handle(h_, "ll_fe_create", [&](ll_fe **out) { return ll_fe_create(&p, out); });
     }
     static size_t hash_xyz(float x, float y, float z)
     {
@@ -330,7 +408,7 @@ class Livox_laser {
         uint64_t h = (uint64_t)a * 0x9E3779B97F4A7C15ull ^ ((uint64_t)b << 21) * 0xC2B2AE3D27D4EB4Full ^ (uint64_t)c * 0x165667B19E3779F9ull;
         return (size_t)(h ^ (h >> 29));
     }
-    ll_fe *h_ = nullptr;
+    Handle<ll_fe, ll_fe_destroy> h_;
     std::vector<float> raw_;
     std::vector<int> first_of_;
 };
@@ -349,28 +427,16 @@ class Spinning_laser {
     int device = 0;
     int max_points = 0;             // 0: sized for the first scan seen (grown on demand)
     int max_line_points = 8192;
-    Spinning_laser() = default;
-    Spinning_laser(const Spinning_laser &) = delete;
-    Spinning_laser &operator=(const Spinning_laser &) = delete;
-    ~Spinning_laser()
-    {
-        if (h_) ll_spin_destroy(h_);
-    }
 
     template <class Cloud>
     void extract(const Cloud &in, Cloud &full, Cloud &sharp, Cloud &less_sharp, Cloud &flat, Cloud &less_flat)
     {
-        const std::vector<float> raw = cloud_to_xyzi(in);
-        const int n = (int)in.points.size();
-        ensure_handle(n);
-        const float dummy[4] = {0, 0, 0, 0};
-        const int st = ll_spin_extract(h_, n ? raw.data() : dummy, n);
-        check(st, "ll_spin_extract");
+        const int st = extract_device(in);
         if (st != LL_SPIN_STATUS_OK) throw std::runtime_error("ll_spin_extract: a line holds more less-flat points than max_line_points");
         Cloud *outs[5] = {&full, &sharp, &less_sharp, &flat, &less_flat};
         for (int which = 0; which < 5; which++) {
             int32_t m = 0;
-            check(ll_spin_cloud(h_, 0, which, buf_.data(), nullptr, &m), "ll_spin_cloud");
+            check(ll_spin_cloud(h_.get(), 0, which, buf_.data(), nullptr, &m), "ll_spin_cloud");
             xyzi_to_cloud(buf_.data(), m, *outs[which]);
         }
     }
@@ -385,20 +451,17 @@ class Spinning_laser {
         const std::vector<float> raw = cloud_to_xyzi(in);
         const int n = (int)in.points.size();
         ensure_handle(n);
-        const float dummy[4] = {0, 0, 0, 0};
-        const int st = ll_spin_extract(h_, n ? raw.data() : dummy, n);
+        const int st = ll_spin_extract(h_.get(), xyzi_or_dummy(raw), n);
         check(st, "ll_spin_extract");
         return st;
     }
-    ll_spin *handle() { return h_; }  // null before the first extraction
+    ll_spin *handle() { return h_.get(); }  // null before the first extraction
     int capacity() const { return cap_; }
 
    private:
     void ensure_handle(int n)
     {
         if (h_ && n <= cap_) return;
-        if (h_) ll_spin_destroy(h_);
-        h_ = nullptr;
         ll_spin_params p;
         ll_spin_default_params(&p);
         p.scan_line = scan_line;
@@ -409,11 +472,10 @@ class Spinning_laser {
         p.max_points = cap_;
         p.max_scans = 1;
         p.max_line_points = max_line_points;
-        runtime_hints();
-        check(ll_spin_create(&p, &h_), "ll_spin_create");
+        make_handle(h_, "ll_spin_create", [&](ll_spin **out) { return ll_spin_create(&p, out); });
         buf_.assign((size_t)cap_ * 4, 0.f);
     }
-    ll_spin *h_ = nullptr;
+    Handle<ll_spin, ll_spin_destroy> h_;
     int cap_ = 0;
     std::vector<float> buf_;
 };
@@ -450,10 +512,6 @@ class VoxelGrid {
         }
         return *this;
     }
-    ~VoxelGrid()
-    {
-        if (h_) ll_voxel_destroy(h_);
-    }
     void setLeafSize(float lx, float ly, float lz)
     {
         leaf_[0] = lx;
@@ -474,21 +532,18 @@ class VoxelGrid {
             return;
         }
         if (!h_ || n > cap_) {
-            if (h_) ll_voxel_destroy(h_);
-            h_ = nullptr;
             cap_ = n > max_points ? n : max_points;
-            runtime_hints();
-            check(ll_voxel_create(device, 1, cap_, &h_), "ll_voxel_create");
+            make_handle(h_, "ll_voxel_create", [&](ll_voxel **out) { return ll_voxel_create(device, 1, cap_, out); });
         }
         std::vector<float> out(in_.size());
         int32_t n_out = 0, st = 0;
-        check(ll_voxel_filter(h_, 1, in_.data(), &n, n, leaf_, out.data(), &n_out, &st), "ll_voxel_filter");
+        check(ll_voxel_filter(h_.get(), 1, in_.data(), &n, n, leaf_, out.data(), &n_out, &st), "ll_voxel_filter");
         status = st;
         xyzi_to_cloud(out.data(), n_out, output);
     }
 
    private:
-    ll_voxel *h_ = nullptr;
+    Handle<ll_voxel, ll_voxel_destroy> h_;
     int cap_ = 0;
     float leaf_[3] = {0.4f, 0.4f, 0.4f};
     std::vector<float> in_;
@@ -503,15 +558,10 @@ class History_buffer {
    public:
     History_buffer(int maximum_history_size, int max_points_per_frame, float line_res, float plane_res, int device = 0)
     {
-        runtime_hints();
-        check(ll_history_create(device, maximum_history_size, max_points_per_frame, line_res, plane_res, &h_), "ll_history_create");
+        make_handle(h_, "ll_history_create", [&](ll_history **out) {
+            return ll_history_create(device, maximum_history_size, max_points_per_frame, line_res, plane_res, out);
+        });
     }
-    ~History_buffer()
-    {
-        if (h_) ll_history_destroy(h_);
-    }
-    History_buffer(const History_buffer &) = delete;
-    History_buffer &operator=(const History_buffer &) = delete;
 
     // "Add new frame" (laser_mapping.hpp:1417-1478): features in the sensor frame, pose = {qx,qy,qz,qw,tx,ty,tz} of the
     // accepted registration.  Returns true when the frame was pushed (false: "Reject add history").
@@ -521,7 +571,7 @@ class History_buffer {
     {
         const std::vector<float> c = cloud_to_xyzi(corner_stack), s = cloud_to_xyzi(surf_stack);
         int32_t added = 0;
-        check(ll_history_add(h_, c.data(), (int32_t)(c.size() / 4), s.data(), (int32_t)(s.size() / 4), pose, history_add_t_step,
+        check(ll_history_add(h_.get(), c.data(), (int32_t)(c.size() / 4), s.data(), (int32_t)(s.size() / 4), pose, history_add_t_step,
                              history_add_angle_step, &added),
               "ll_history_add");
         return added != 0;
@@ -531,44 +581,41 @@ class History_buffer {
     {
         if (!spin.handle()) throw std::runtime_error("History_buffer::add: the Spinning_laser has not extracted a scan");
         int32_t added = 0;
-        check(ll_history_add_spin(h_, spin.handle(), 0, pose, history_add_t_step, history_add_angle_step, &added), "ll_history_add_spin");
+        check(ll_history_add_spin(h_.get(), spin.handle(), 0, pose, history_add_t_step, history_add_angle_step, &added), "ll_history_add_spin");
         return added != 0;
     }
     // The add-frame rule (laser_mapping.hpp:1439-1451) reads the node's m_q_w_curr / m_t_w_curr, which is still the pose
     // BEFORE the registration whose result add() receives: hand it over first (applies to the next add only).
-    void set_gate_pose(const double pose_before_registration[7]) { check(ll_history_set_gate_pose(h_, pose_before_registration), "ll_history_set_gate_pose"); }
+    void set_gate_pose(const double pose_before_registration[7]) { check(ll_history_set_gate_pose(h_.get(), pose_before_registration), "ll_history_set_gate_pose"); }
     // update_buff_for_matching(): concatenation of the history -> VoxelGrid -> search grids of `map`
     void refresh(ll_map *map, int64_t *n_corner = nullptr, int64_t *n_surf = nullptr)
     {
-        check(ll_history_refresh(h_, map, n_corner, n_surf), "ll_history_refresh");
+        check(ll_history_refresh(h_.get(), map, n_corner, n_surf), "ll_history_refresh");
     }
     // m_laser_cloud_corner_from_map_last / m_laser_cloud_surf_from_map_last of the last refresh (for publishing / saving)
     template <class Cloud>
     void map_cloud(int kind, Cloud &out)
     {
-        const int64_t n = ll_history_map_cloud(h_, kind, nullptr, 0);
-        std::vector<float> v((size_t)(n > 0 ? n : 0) * 4);
-        if (n > 0 && ll_history_map_cloud(h_, kind, v.data(), n) < 0) check(-1, "ll_history_map_cloud");
-        xyzi_to_cloud(v.data(), (int)n, out);
+        read_cloud("ll_history_map_cloud", out, [&](float *xyzi, int64_t capacity) { return ll_history_map_cloud(h_.get(), kind, xyzi, capacity); });
     }
-    int size() const { return ll_history_size(h_); }
+    int size() const { return ll_history_size(h_.get()); }
 
     // m_pt_cell_map_corners / m_pt_cell_map_planes (laser_mapping.hpp:274-275, 617-624) for m_matching_mode == 1: once
     // enabled, every add() also appends the frame to the two cell maps (laser_mapping.hpp:1492-1493)
     void enable_cell_map(int64_t max_points, float m_pt_cell_resolution = 1.0f, int m_para_threshold_cell_revisit = 5000)
     {
-        check(ll_history_enable_cell_map(h_, max_points, m_pt_cell_resolution, m_para_threshold_cell_revisit), "ll_history_enable_cell_map");
+        check(ll_history_enable_cell_map(h_.get(), max_points, m_pt_cell_resolution, m_para_threshold_cell_revisit), "ll_history_enable_cell_map");
     }
     // m_matching_mode == 0 never reads the cell maps between frames (laser_mapping.hpp:1492-1493 only appends): feed them beside the mapping
     // loop, on a service thread of the handle, as the reference runs its own map services on threads (:568-594).  Every reader
     // (refresh_cells, cell_map_size, cell_map) waits for the frames handed over so far; sync_cell_maps() does only that.
-    void set_cell_map_async(bool enable = true) { check(ll_history_set_cell_map_async(h_, enable ? 1 : 0), "ll_history_set_cell_map_async"); }
-    void sync_cell_maps() { check(ll_history_sync_cell_maps(h_), "ll_history_sync_cell_maps"); }
+    void set_cell_map_async(bool enable = true) { check(ll_history_set_cell_map_async(h_.get(), enable ? 1 : 0), "ll_history_set_cell_map_async"); }
+    void sync_cell_maps() { check(ll_history_sync_cell_maps(h_.get()), "ll_history_sync_cell_maps"); }
     // the cell map of one feature kind (borrowed: valid as long as this object), e.g. for ll_cellmap_device_view -- the input of a multi-GPU
     // gather of cell maps
     ll_cellmap *cell_map(int kind)
     {
-        ll_cellmap *c = ll_history_cell_map(h_, kind);
+        ll_cellmap *c = ll_history_cell_map(h_.get(), kind);
         if (!c) check(-1, "ll_history_cell_map");
         return c;
     }
@@ -577,20 +624,20 @@ class History_buffer {
                        float m_maximum_search_range_surface = 100.0f, float m_maximum_in_fov_angle = 30.0f, int m_down_sample_replace = 1,
                        int64_t *n_corner = nullptr, int64_t *n_surf = nullptr)
     {
-        check(ll_history_refresh_cells(h_, map, pose, m_maximum_search_range_corner, m_maximum_search_range_surface, m_maximum_in_fov_angle,
+        check(ll_history_refresh_cells(h_.get(), map, pose, m_maximum_search_range_corner, m_maximum_search_range_surface, m_maximum_in_fov_angle,
                                        m_down_sample_replace, n_corner, n_surf),
               "ll_history_refresh_cells");
     }
     // Points_cloud_map::get_cells_size() and the number of points held, per feature kind (0 corner, 1 surface)
     void cell_map_size(int kind, int64_t *n_cells, int64_t *n_points)
     {
-        ll_cellmap *c = ll_history_cell_map(h_, kind);
+        ll_cellmap *c = ll_history_cell_map(h_.get(), kind);
         if (!c) check(-1, "ll_history_cell_map");
         check(ll_cellmap_stats(c, n_cells, n_points, nullptr), "ll_cellmap_stats");
     }
 
    private:
-    ll_history *h_ = nullptr;
+    Handle<ll_history, ll_history_destroy> h_;
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -604,34 +651,28 @@ class History_batch {
     History_batch(int n_sequences, int maximum_history_size, int max_points_per_frame, float line_res, float plane_res, int device = 0)
         : n_(n_sequences)
     {
-        runtime_hints();
-        check(ll_history_batch_create(device, n_sequences, maximum_history_size, max_points_per_frame, line_res, plane_res, &h_),
-              "ll_history_batch_create");
+        make_handle(h_, "ll_history_batch_create", [&](ll_history_batch **out) {
+            return ll_history_batch_create(device, n_sequences, maximum_history_size, max_points_per_frame, line_res, plane_res, out);
+        });
     }
-    ~History_batch()
-    {
-        if (h_) ll_history_batch_destroy(h_);
-    }
-    History_batch(const History_batch &) = delete;
-    History_batch &operator=(const History_batch &) = delete;
 
     // slot s takes scan s of the extractor; added (optional): n_sequences flags, 1 where the frame was pushed
     void add(ll_fe *fe, const double *poses, const double *gate_poses = nullptr, const int32_t *active = nullptr,
              double history_add_t_step = 0.0, double history_add_angle_step = 0.0, int32_t *added = nullptr)
     {
-        check(ll_history_batch_add_fe(h_, fe, active, poses, gate_poses, history_add_t_step, history_add_angle_step, added), "ll_history_batch_add_fe");
+        check(ll_history_batch_add_fe(h_.get(), fe, active, poses, gate_poses, history_add_t_step, history_add_angle_step, added), "ll_history_batch_add_fe");
     }
     // slot s takes cloud s of the two filters (the down-sampled stacks of the last enqueue_fe_maps with filters)
     void add(ll_voxel *vox_corner, ll_voxel *vox_surf, const double *poses, const double *gate_poses = nullptr, const int32_t *active = nullptr,
              double history_add_t_step = 0.0, double history_add_angle_step = 0.0, int32_t *added = nullptr)
     {
-        check(ll_history_batch_add_voxel(h_, vox_corner, vox_surf, active, poses, gate_poses, history_add_t_step, history_add_angle_step, added),
+        check(ll_history_batch_add_voxel(h_.get(), vox_corner, vox_surf, active, poses, gate_poses, history_add_t_step, history_add_angle_step, added),
               "ll_history_batch_add_voxel");
     }
     // update_buff_for_matching() of every active slot: new search grids of both kinds in maps[s]
     void refresh(ll_map *const *maps, const int32_t *active = nullptr, int64_t *n_corner = nullptr, int64_t *n_surf = nullptr)
     {
-        check(ll_history_batch_refresh(h_, maps, active, n_corner, n_surf), "ll_history_batch_refresh");
+        check(ll_history_batch_refresh(h_.get(), maps, active, n_corner, n_surf), "ll_history_batch_refresh");
     }
     // update_buff_for_matching() with m_matching_mode == 1 for every active slot, at poses [n_sequences][7]: the cells of the slot's cell
     // maps in range and in the field of view, each through the VoxelGrid (and replaced by its leaves with m_down_sample_replace),
@@ -640,35 +681,32 @@ class History_batch {
                        float m_maximum_search_range_surface = 100.0f, float m_maximum_in_fov_angle = 30.0f, int m_down_sample_replace = 1,
                        int64_t *n_corner = nullptr, int64_t *n_surf = nullptr)
     {
-        check(ll_history_batch_refresh_cells(h_, maps, active, poses, m_maximum_search_range_corner, m_maximum_search_range_surface,
+        check(ll_history_batch_refresh_cells(h_.get(), maps, active, poses, m_maximum_search_range_corner, m_maximum_search_range_surface,
                                              m_maximum_in_fov_angle, m_down_sample_replace, n_corner, n_surf),
               "ll_history_batch_refresh_cells");
     }
-    void cell_match_work(int64_t out[8]) { check(ll_history_batch_cell_match_work(h_, out), "ll_history_batch_cell_match_work"); }
+    void cell_match_work(int64_t out[8]) { check(ll_history_batch_cell_match_work(h_.get(), out), "ll_history_batch_cell_match_work"); }
     template <class Cloud>
     void map_cloud(int sequence, int kind, Cloud &out)
     {
-        const int64_t n = ll_history_batch_map_cloud(h_, sequence, kind, nullptr, 0);
-        if (n < 0) check(-1, "ll_history_batch_map_cloud");
-        std::vector<float> v((size_t)n * 4);
-        if (n > 0 && ll_history_batch_map_cloud(h_, sequence, kind, v.data(), n) < 0) check(-1, "ll_history_batch_map_cloud");
-        xyzi_to_cloud(v.data(), (int)n, out);
+        read_cloud("ll_history_batch_map_cloud", out,
+                   [&](float *xyzi, int64_t capacity) { return ll_history_batch_map_cloud(h_.get(), sequence, kind, xyzi, capacity); });
     }
-    int size(int sequence) const { return ll_history_batch_size(h_, sequence); }
+    int size(int sequence) const { return ll_history_batch_size(h_.get(), sequence); }
     int n_sequences() const { return n_; }
-    ll_history_batch *handle() { return h_; }
+    ll_history_batch *handle() { return h_.get(); }
 
     // m_pt_cell_map_corners / m_pt_cell_map_planes of every slot (laser_mapping.hpp:274-275, 617-624): from here on every active slot
     // of add() appends its filtered frame to its two cell maps, pushed or not.  An add costs the new points; the stored points are put
     // in order by the first read after it (cell_map_stats / cell_map_dump / cell_map_device_view, or sync_cell_maps()).
     void enable_cell_maps(int64_t initial_points_per_map, float cell_resolution = 1.0f, int threshold_cell_revisit = 5000)
     {
-        check(ll_history_batch_enable_cell_maps(h_, initial_points_per_map, cell_resolution, threshold_cell_revisit), "ll_history_batch_enable_cell_maps");
+        check(ll_history_batch_enable_cell_maps(h_.get(), initial_points_per_map, cell_resolution, threshold_cell_revisit), "ll_history_batch_enable_cell_maps");
     }
-    void sync_cell_maps() { check(ll_history_batch_sync_cell_maps(h_), "ll_history_batch_sync_cell_maps"); }
+    void sync_cell_maps() { check(ll_history_batch_sync_cell_maps(h_.get()), "ll_history_batch_sync_cell_maps"); }
     void cell_map_stats(int sequence, int kind, int64_t *n_cells, int64_t *n_points, int32_t *frame_idx = nullptr)
     {
-        check(ll_history_batch_cell_map_stats(h_, sequence, kind, n_cells, n_points, frame_idx), "ll_history_batch_cell_map_stats");
+        check(ll_history_batch_cell_map_stats(h_.get(), sequence, kind, n_cells, n_points, frame_idx), "ll_history_batch_cell_map_stats");
     }
     // the layouts of ll_cellmap_dump: xyzi [n_points][4], cell_ijk [n_cells][3], cell_start [n_cells + 1], cell_last_update [n_cells]
     void cell_map_dump(int sequence, int kind, std::vector<float> &xyzi, std::vector<int32_t> &cell_ijk, std::vector<int32_t> &cell_start,
@@ -680,7 +718,7 @@ class History_batch {
         cell_ijk.assign((size_t)(nc > 0 ? nc : 1) * 3, 0);
         cell_start.assign((size_t)nc + 1, 0);
         cell_last_update.assign((size_t)(nc > 0 ? nc : 1), 0);
-        check(ll_history_batch_cell_map_dump(h_, sequence, kind, xyzi.data(), np > 0 ? np : 1, cell_ijk.data(), cell_start.data(),
+        check(ll_history_batch_cell_map_dump(h_.get(), sequence, kind, xyzi.data(), np > 0 ? np : 1, cell_ijk.data(), cell_start.data(),
                                              cell_last_update.data(), nc > 0 ? nc : 1),
               "ll_history_batch_cell_map_dump");
         xyzi.resize((size_t)np * 4);
@@ -691,7 +729,7 @@ class History_batch {
     void cell_map_device_view(int sequence, int kind, const float **dev_xyz0, const uint64_t **dev_point_keys, int64_t *n_points,
                               int64_t *n_cells = nullptr)
     {
-        check(ll_history_batch_cell_map_device_view(h_, sequence, kind, dev_xyz0, dev_point_keys, n_points, n_cells),
+        check(ll_history_batch_cell_map_device_view(h_.get(), sequence, kind, dev_xyz0, dev_point_keys, n_points, n_cells),
               "ll_history_batch_cell_map_device_view");
     }
     // Maps_keyframe's view of the shared cells (cell_map_keyframe.hpp:1243-1261) for several slots in one call: request r copies the
@@ -707,15 +745,14 @@ class History_batch {
         const size_t R = sequences.size();
         if (cells.size() != R || dst.size() != R) throw std::invalid_argument("History_batch::extract_cells: one cell list and one destination per sequence");
         std::vector<int32_t> seq(sequences.begin(), sequences.end()), ijk;
-        std::vector<int64_t> off(R + 1, 0), n_found(R > 0 ? R : 1, 0), n_pts(R > 0 ? R : 1, 0);
+        const std::vector<int64_t> off = csr_offsets(cells);
+        std::vector<int64_t> n_found(R > 0 ? R : 1, 0), n_pts(R > 0 ? R : 1, 0);
         std::vector<ll_cellmap *> maps(R > 0 ? R : 1, nullptr);
         for (size_t r = 0; r < R; r++) {
-            for (const std::array<int, 3> &c : cells[r])
-                for (int d = 0; d < 3; d++) ijk.push_back((int32_t)c[(size_t)d]);
-            off[r + 1] = off[r] + (int64_t)cells[r].size();
+            pack_cells(cells[r], ijk);
             maps[r] = dst[r] ? dst[r]->handle() : nullptr;
         }
-        check(ll_history_batch_extract_cells(h_, kind, (int32_t)R, seq.data(), off.data(), ijk.empty() ? nullptr : ijk.data(), maps.data(), n_found.data(),
+        check(ll_history_batch_extract_cells(h_.get(), kind, (int32_t)R, seq.data(), off.data(), ijk.empty() ? nullptr : ijk.data(), maps.data(), n_found.data(),
                                              n_pts.data()),
               "ll_history_batch_extract_cells");
         for (size_t r = 0; r < R; r++) dst[r]->holds_at_least(n_pts[r]);
@@ -729,32 +766,32 @@ class History_batch {
     // that call's extractor.  Thin wrappers of the C ABI, which documents them.
     void enable_scan_log(int maximum_history_size, int64_t initial_scans)
     {
-        check(ll_history_batch_enable_scan_log(h_, maximum_history_size, initial_scans), "ll_history_batch_enable_scan_log");
+        check(ll_history_batch_enable_scan_log(h_.get(), maximum_history_size, initial_scans), "ll_history_batch_enable_scan_log");
     }
-    void log_full(ll_fe *fe, const int32_t *active = nullptr) { check(ll_history_batch_log_full_fe(h_, fe, active), "ll_history_batch_log_full_fe"); }
+    void log_full(ll_fe *fe, const int32_t *active = nullptr) { check(ll_history_batch_log_full_fe(h_.get(), fe, active), "ll_history_batch_log_full_fe"); }
     int64_t hand_over(int sequence)
     {
         int64_t id = 0;
-        check(ll_history_batch_scan_log_hand_over(h_, sequence, &id), "ll_history_batch_scan_log_hand_over");
+        check(ll_history_batch_scan_log_hand_over(h_.get(), sequence, &id), "ll_history_batch_scan_log_hand_over");
         return id;
     }
     void drop_groups(const std::vector<int64_t> &group_ids)
     {
-        check(ll_history_batch_scan_log_drop(h_, (int64_t)group_ids.size(), group_ids.empty() ? nullptr : group_ids.data()), "ll_history_batch_scan_log_drop");
+        check(ll_history_batch_scan_log_drop(h_.get(), (int64_t)group_ids.size(), group_ids.empty() ? nullptr : group_ids.data()), "ll_history_batch_scan_log_drop");
     }
     // the group's points {x, y, z, intensity}, scan after scan
     std::vector<float> read_group(int64_t group_id)
     {
-        int64_t n = 0;
-        check(ll_history_batch_scan_log_read(h_, group_id, nullptr, 0, &n), "ll_history_batch_scan_log_read");
-        std::vector<float> v((size_t)n * 4);
-        if (n > 0) check(ll_history_batch_scan_log_read(h_, group_id, v.data(), n, &n), "ll_history_batch_scan_log_read");
-        return v;
+        return read_xyzi("ll_history_batch_scan_log_read", [&](float *xyzi, int64_t capacity) {
+            int64_t n = 0;
+            const int rc = ll_history_batch_scan_log_read(h_.get(), group_id, xyzi, capacity, &n);
+            return rc < 0 ? (int64_t)rc : n;
+        });
     }
-    void scan_log_work(int64_t out[4]) { check(ll_history_batch_scan_log_work(h_, out), "ll_history_batch_scan_log_work"); }
+    void scan_log_work(int64_t out[4]) { check(ll_history_batch_scan_log_work(h_.get(), out), "ll_history_batch_scan_log_work"); }
 
    private:
-    ll_history_batch *h_ = nullptr;
+    Handle<ll_history_batch, ll_history_batch_destroy> h_;
     int n_ = 0;
 };
 
@@ -768,21 +805,15 @@ class Points_cloud_map {
     explicit Points_cloud_map(int64_t max_points, float resolution = 1.0f, int m_minimum_revisit_threshold = 2147483647, int device = 0)
         : capacity_(max_points)
     {
-        runtime_hints();
-        check(ll_cellmap_create(device, max_points, resolution, m_minimum_revisit_threshold, &h_), "ll_cellmap_create");
+        make_handle(h_, "ll_cellmap_create",
+                    [&](ll_cellmap **out) { return ll_cellmap_create(device, max_points, resolution, m_minimum_revisit_threshold, out); });
     }
-    ~Points_cloud_map()
-    {
-        if (h_) ll_cellmap_destroy(h_);
-    }
-    Points_cloud_map(const Points_cloud_map &) = delete;
-    Points_cloud_map &operator=(const Points_cloud_map &) = delete;
 
     template <class Cloud>
     void append_cloud(const Cloud &cloud)  // :619-672 (intensity is not kept, :82)
     {
         const std::vector<float> v = cloud_to_xyzi(cloud);
-        check(ll_cellmap_append(h_, v.data(), (int32_t)(v.size() / 4)), "ll_cellmap_append");
+        check(ll_cellmap_append(h_.get(), v.data(), (int32_t)(v.size() / 4)), "ll_cellmap_append");
     }
     // append_cloud( pts, &cell_vec ) (:619-672, what the mapping node calls when loop closure is on, laser_mapping.hpp:1442): the
     // reference's cell_vec is a set of cell POINTERS; the cells live on the device here, so the set holds their integer cell
@@ -798,7 +829,7 @@ class Points_cloud_map {
         const int32_t n = (int32_t)(v.size() / 4);
         std::vector<int32_t> ijk((size_t)(n > 0 ? n : 1) * 3);  // a cloud of n points touches at most n cells
         int64_t n_touched = 0;
-        check(ll_cellmap_append_touched(h_, v.data(), n, 3, ijk.data(), (int64_t)(ijk.size() / 3), &n_touched), "ll_cellmap_append_touched");
+        check(ll_cellmap_append_touched(h_.get(), v.data(), n, 3, ijk.data(), (int64_t)(ijk.size() / 3), &n_touched), "ll_cellmap_append_touched");
         cell_vec->clear();
         const int64_t n_listed = n_touched < (int64_t)(ijk.size() / 3) ? n_touched : (int64_t)(ijk.size() / 3);  // (a short buffer truncates; this one never is)
         for (int64_t i = 0; i < n_listed; i++) cell_vec->insert(Cell_index{ijk[3 * i], ijk[3 * i + 1], ijk[3 * i + 2]});
@@ -807,7 +838,7 @@ class Points_cloud_map {
     // revisit stamps and frame counter kept (no-op when not larger).
     void reserve(int64_t max_points)
     {
-        check(ll_cellmap_reserve(h_, max_points), "ll_cellmap_reserve");
+        check(ll_cellmap_reserve(h_.get(), max_points), "ll_cellmap_reserve");
         if (max_points > capacity_) capacity_ = max_points;  // (reserve_for doubles from the capacity the map really has)
     }
     // Maps_keyframe's view of the shared cells (:1243-1261: a key frame holds pointers to the map's cells and reads them as they are
@@ -817,11 +848,11 @@ class Points_cloud_map {
     // the cell it had here.  Returns the cells found; *n_points: the points copied.
     int64_t extract_cells(const std::vector<std::array<int, 3>> &cells, Points_cloud_map &dst, int64_t *n_points = nullptr)
     {
-        std::vector<int32_t> ijk(cells.size() * 3);
-        for (size_t i = 0; i < cells.size(); i++)
-            for (int d = 0; d < 3; d++) ijk[3 * i + d] = (int32_t)cells[i][(size_t)d];
+        std::vector<int32_t> ijk;
+        pack_cells(cells, ijk);
         int64_t n_found = 0, n_pts = 0;
-        check(ll_cellmap_extract_cells(h_, ijk.empty() ? nullptr : ijk.data(), (int64_t)cells.size(), dst.h_, &n_found, &n_pts), "ll_cellmap_extract_cells");
+        check(ll_cellmap_extract_cells(h_.get(), ijk.empty() ? nullptr : ijk.data(), (int64_t)cells.size(), dst.h_.get(), &n_found, &n_pts),
+              "ll_cellmap_extract_cells");
         if (n_pts > dst.capacity_) dst.capacity_ = n_pts;
         if (n_points) *n_points = n_pts;
         return n_found;
@@ -834,34 +865,33 @@ class Points_cloud_map {
     Cloud extract_specify_points(Feature_type select_type)
     {
         if (select_type != e_feature_line && select_type != e_feature_plane) check(-1, "extract_specify_points: only e_feature_line and e_feature_plane are selected on the device");
-        int64_t n_line = 0, n_plane = 0;
-        check(ll_cellmap_feature_clouds(h_, nullptr, 0, &n_line, nullptr, 0, &n_plane, nullptr), "ll_cellmap_feature_clouds");
         const bool line = select_type == e_feature_line;
-        std::vector<float> v((size_t)(line ? n_line : n_plane) * 4);
-        float *buf = v.empty() ? nullptr : v.data();
-        check(ll_cellmap_feature_clouds(h_, line ? buf : nullptr, line ? (int64_t)(v.size() / 4) : 0, &n_line, line ? nullptr : buf,
-                                        line ? 0 : (int64_t)(v.size() / 4), &n_plane, nullptr), "ll_cellmap_feature_clouds");
         Cloud out;
-        xyzi_to_cloud(v.data(), (int)(v.size() / 4), out);
+        read_cloud("ll_cellmap_feature_clouds", out, [&](float *xyzi, int64_t capacity) {
+            int64_t n_line = 0, n_plane = 0;
+            const int rc = ll_cellmap_feature_clouds(h_.get(), line ? xyzi : nullptr, line ? capacity : 0, &n_line, line ? nullptr : xyzi,
+                                                     line ? 0 : capacity, &n_plane, nullptr);
+            return rc < 0 ? (int64_t)rc : line ? n_line : n_plane;
+        });
         return out;
     }
     // Maps_keyframe::get_center (:1291-1301): the float mean of the cell centres, cells in ascending cell order
     void get_center(float centre[3])
     {
         int64_t n_line = 0, n_plane = 0;
-        check(ll_cellmap_feature_clouds(h_, nullptr, 0, &n_line, nullptr, 0, &n_plane, centre), "ll_cellmap_feature_clouds");
+        check(ll_cellmap_feature_clouds(h_.get(), nullptr, 0, &n_line, nullptr, 0, &n_plane, centre), "ll_cellmap_feature_clouds");
     }
     // the stored points ({x, y, z, 0}, ordered by (cell, insertion)) and the 64-bit cell key of every point where they lie on the device;
     // valid until the next call that changes the map
     void device_view(const float **dev_xyz0, const uint64_t **dev_point_keys, int64_t *n_points, int64_t *n_cells = nullptr)
     {
-        check(ll_cellmap_device_view(h_, dev_xyz0, dev_point_keys, n_points, n_cells), "ll_cellmap_device_view");
+        check(ll_cellmap_device_view(h_.get(), dev_xyz0, dev_point_keys, n_points, n_cells), "ll_cellmap_device_view");
     }
     // grows the capacity (doubling) so that n_more points fit: the reference's map grows on the heap without bound
     void reserve_for(size_t n_more)
     {
         int64_t n_pts = 0, cap = capacity_;
-        check(ll_cellmap_stats(h_, nullptr, &n_pts, nullptr), "ll_cellmap_stats");
+        check(ll_cellmap_stats(h_.get(), nullptr, &n_pts, nullptr), "ll_cellmap_stats");
         if (cap <= 0) cap = 1;
         while (cap < n_pts + (int64_t)n_more) cap *= 2;
         if (cap != capacity_) reserve(cap);
@@ -873,15 +903,13 @@ class Points_cloud_map {
     void find_cells_in_radius_filtered(const double pose[7], float radius, float leaf, Cloud &out)
     {
         int64_t n_sel = 0, n_out = 0;
-        check(ll_cellmap_query_filter(h_, pose, radius, 360.0f, leaf, 0, &n_sel, &n_out), "ll_cellmap_query_filter");
-        std::vector<float> v((size_t)(n_out > 0 ? n_out : 0) * 4);
-        if (n_out > 0 && ll_cellmap_result(h_, v.data(), n_out) < 0) check(-1, "ll_cellmap_result");
-        xyzi_to_cloud(v.data(), (int)n_out, out);
+        check(ll_cellmap_query_filter(h_.get(), pose, radius, 360.0f, leaf, 0, &n_sel, &n_out), "ll_cellmap_query_filter");
+        read_cloud("ll_cellmap_result", out, [&](float *xyzi, int64_t capacity) { return xyzi ? ll_cellmap_result(h_.get(), xyzi, capacity) : n_out; });
     }
     int64_t get_cells_size() const  // :551-554
     {
         int64_t n = 0;
-        check(ll_cellmap_stats(h_, &n, nullptr, nullptr), "ll_cellmap_stats");
+        check(ll_cellmap_stats(h_.get(), &n, nullptr, nullptr), "ll_cellmap_stats");
         return n;
     }
     // m_feature_type / m_feature_vector of every cell, in ascending cell-index order
@@ -890,14 +918,14 @@ class Points_cloud_map {
         const int64_t n = get_cells_size();
         feature_type.assign((size_t)n, 0);
         feature_vector.assign((size_t)n * 3, 0.f);
-        check(ll_cellmap_features(h_, feature_type.data(), feature_vector.data(), nullptr, nullptr, nullptr, n), "ll_cellmap_features");
+        check(ll_cellmap_features(h_.get(), feature_type.data(), feature_vector.data(), nullptr, nullptr, nullptr, n), "ll_cellmap_features");
     }
     // m_feature_img_line, m_feature_img_plane, m_feature_img_line_roi, m_feature_img_plane_roi (60 x 60 each, row = phi bin)
     // and m_ratio_nonzero_line / _plane of the four histograms; the map stands for the key frame's cell set
     void analyze(std::vector<float> &images, float ratio_nonzero[4], float roi_ratio = 0.9f)
     {
         images.assign((size_t)4 * 60 * 60, 0.f);
-        check(ll_cellmap_keyframe_images(h_, roi_ratio, images.data(), ratio_nonzero, nullptr, nullptr, nullptr), "ll_cellmap_keyframe_images");
+        check(ll_cellmap_keyframe_images(h_.get(), roi_ratio, images.data(), ratio_nonzero, nullptr, nullptr, nullptr), "ll_cellmap_keyframe_images");
     }
     // Maps_keyframe::max_similiarity_of_two_image (:1155-1196) of two 60 x 60 images
     static float max_similiarity_of_two_image(const float *img_a, const float *img_b, int device = 0)
@@ -906,7 +934,7 @@ class Points_cloud_map {
         check(ll_keyframe_similarity(device, img_a, img_b, &s), "ll_keyframe_similarity");
         return s;
     }
-    ll_cellmap *handle() { return h_; }
+    ll_cellmap *handle() { return h_.get(); }
     // the library raised the capacity itself (History_batch::extract_cells into this map): reserve_for doubles from what the map has
     void holds_at_least(int64_t n_points)
     {
@@ -914,7 +942,7 @@ class Points_cloud_map {
     }
 
    private:
-    ll_cellmap *h_ = nullptr;
+    Handle<ll_cellmap, ll_cellmap_destroy> h_;
     int64_t capacity_ = 0;
 };
 
@@ -1002,8 +1030,9 @@ class Handle_pool {
 };
 
 // ------------------------------------------------------------------------------------------------------------
-class Point_cloud_registration {
-   public:
+// The part of Point_cloud_registration that copies as plain values: the class copies it as a whole, so a field added here is copied
+// without being named anywhere.
+struct Point_cloud_registration_fields {
     // configuration fields with the reference names and defaults (point_cloud_registration.hpp:45-103)
     int ICP_PLANE = 1, ICP_LINE = 1;
     int IF_LINE_FEATURE_CHECK = 0, IF_PLANE_FEATURE_CHECK = 0;  // PCR:46,48
@@ -1032,8 +1061,6 @@ class Point_cloud_registration {
     double m_para_buffer_RT[7] = {0, 0, 0, 1, 0, 0, 0};
     double m_para_buffer_RT_last[7] = {0, 0, 0, 1, 0, 0, 0};
     double m_para_buffer_incremental[7] = {0, 0, 0, 1, 0, 0, 0};
-    Quaterniond_map m_q_w_incre = Quaterniond_map(m_para_buffer_incremental);
-    Vector3d_map m_t_w_incre = Vector3d_map(m_para_buffer_incremental + 4);
     Quaterniond m_q_w_curr, m_q_w_last;
     Vector3d m_t_w_curr, m_t_w_last;
     double m_inlier_threshold = 0, m_angular_diff = 0, m_t_diff = 0;
@@ -1041,6 +1068,13 @@ class Point_cloud_registration {
     struct Opt_summary : ll_reg_report {
         int num_residual_blocks = 0;
         Opt_summary() : ll_reg_report() {}
+        static Opt_summary from(const ll_reg_report &rep)
+        {
+            Opt_summary s;
+            static_cast<ll_reg_report &>(s) = rep;
+            s.num_residual_blocks = rep.n_blocks_last;
+            return s;
+        }
         std::string BriefReport() const
         {
             char b[256];
@@ -1053,6 +1087,13 @@ class Point_cloud_registration {
     Opt_summary summary, m_final_opt_summary;
     int device = 0;
     int max_features = 100000;
+};
+
+class Point_cloud_registration : public Point_cloud_registration_fields {
+   public:
+    // views of this object's own m_para_buffer_incremental (PCR:55-56): a copy keeps its own
+    Quaterniond_map m_q_w_incre = Quaterniond_map(m_para_buffer_incremental);
+    Vector3d_map m_t_w_incre = Vector3d_map(m_para_buffer_incremental + 4);
 
     Point_cloud_registration()
     {
@@ -1061,40 +1102,12 @@ class Point_cloud_registration {
         m_q_w_curr.setIdentity();
         m_t_w_curr.setZero();
     }
-    // the maps refer to this object's own buffer: copies re-seat them
-    Point_cloud_registration(const Point_cloud_registration &o) { *this = o; }
+    // a copy takes the fields; it borrows a registrar of its own on first use
+    Point_cloud_registration(const Point_cloud_registration &o) : Point_cloud_registration_fields(o) {}
     Point_cloud_registration &operator=(const Point_cloud_registration &o)
     {
-        if (this == &o) return *this;
-        ICP_PLANE = o.ICP_PLANE, ICP_LINE = o.ICP_LINE;
-        IF_LINE_FEATURE_CHECK = o.IF_LINE_FEATURE_CHECK, IF_PLANE_FEATURE_CHECK = o.IF_PLANE_FEATURE_CHECK;
-        m_if_motion_deblur = o.m_if_motion_deblur, m_current_frame_index = o.m_current_frame_index;
-        m_mapping_init_accumulate_frames = o.m_mapping_init_accumulate_frames, m_last_time_stamp = o.m_last_time_stamp;
-        m_para_max_angular_rate = o.m_para_max_angular_rate, m_para_max_speed = o.m_para_max_speed, m_max_final_cost = o.m_max_final_cost;
-        m_para_icp_max_iterations = o.m_para_icp_max_iterations, m_para_cere_max_iterations = o.m_para_cere_max_iterations;
-        m_para_cere_prerun_times = o.m_para_cere_prerun_times;
-        m_minimum_pt_time_stamp = o.m_minimum_pt_time_stamp, m_maximum_pt_time_stamp = o.m_maximum_pt_time_stamp;
-        m_minimum_icp_R_diff = o.m_minimum_icp_R_diff, m_minimum_icp_T_diff = o.m_minimum_icp_T_diff;
-        m_inliner_dis = o.m_inliner_dis, m_inlier_ratio = o.m_inlier_ratio;
-        m_maximum_dis_plane_for_match = o.m_maximum_dis_plane_for_match, m_maximum_dis_line_for_match = o.m_maximum_dis_line_for_match;
-        m_maximum_allow_residual_block = o.m_maximum_allow_residual_block, m_subsample_seed = o.m_subsample_seed;
-        m_if_verbose_screen_printf = o.m_if_verbose_screen_printf;
-        m_logger_common = o.m_logger_common, m_logger_pcd = o.m_logger_pcd, m_logger_timer = o.m_logger_timer, m_timer = o.m_timer;
-        for (int i = 0; i < 7; i++) {
-            m_para_buffer_RT[i] = o.m_para_buffer_RT[i];
-            m_para_buffer_RT_last[i] = o.m_para_buffer_RT_last[i];
-            m_para_buffer_incremental[i] = o.m_para_buffer_incremental[i];
-        }
-        m_q_w_curr = o.m_q_w_curr, m_q_w_last = o.m_q_w_last, m_t_w_curr = o.m_t_w_curr, m_t_w_last = o.m_t_w_last;
-        m_inlier_threshold = o.m_inlier_threshold, m_angular_diff = o.m_angular_diff, m_t_diff = o.m_t_diff;
-        summary = o.summary, m_final_opt_summary = o.m_final_opt_summary;
-        device = o.device, max_features = o.max_features;
+        Point_cloud_registration_fields::operator=(o);
         return *this;
-    }
-
-    ~Point_cloud_registration()
-    {
-        if (reg_) Handle_pool::instance().release(reg_);
     }
 
     // float refine_blur(in_blur, min_blur, max_blur), PCR:128-141
@@ -1150,15 +1163,12 @@ class Point_cloud_registration {
     {
         if (!spin.handle()) throw std::runtime_error("find_out_incremental_transfrom: the Spinning_laser has not extracted a scan");
         const int need = spin.capacity() > max_features ? spin.capacity() : max_features;
-        if (reg_ && reg_cap_ < need) {
-            Handle_pool::instance().release(reg_);
-            reg_ = nullptr;
-        }
-        if (!reg_) reg_ = Handle_pool::instance().acquire(device, reg_cap_ = need);
+        if (reg_ && reg_cap_ < need) reg_.reset();  // too small: back to the pool
+        ll_reg *reg = registrar(need);
         ll_reg_params p;
         fill_params(p);
         pose_from_members();
-        check(ll_reg_enqueue_spin(reg_, map(), spin.handle(), 1, &p, m_para_buffer_RT_last, m_para_buffer_RT, m_para_buffer_incremental),
+        check(ll_reg_enqueue_spin(reg, map(), spin.handle(), 1, &p, m_para_buffer_RT_last, m_para_buffer_RT, m_para_buffer_incremental),
               "ll_reg_enqueue_spin");
         return collect();
     }
@@ -1191,7 +1201,7 @@ class Point_cloud_registration {
     template <class CloudPtr>
     int register_scan(CloudPtr scan_corner, CloudPtr scan_surf, std::unique_lock<std::mutex> *held_until_enqueued)
     {
-        if (!reg_) reg_ = Handle_pool::instance().acquire(device, reg_cap_ = max_features);
+        ll_reg *reg = registrar(max_features);
         ll_map *m = map();
         const std::vector<float> c = cloud_to_xyzi(*scan_corner), s = cloud_to_xyzi(*scan_surf);
         ll_reg_params p;
@@ -1199,10 +1209,8 @@ class Point_cloud_registration {
         pose_from_members();
         // ll_reg_solve in its three steps (upload the scan's features, enqueue = pin the map snapshots + launch, collect)
         const int32_t nc = (int32_t)(c.size() / 4), ns = (int32_t)(s.size() / 4);
-        const float dummy[4] = {0, 0, 0, 0};
-        check(ll_reg_upload_features(reg_, 1, nc ? c.data() : dummy, &nc, nc > 0 ? nc : 1, ns ? s.data() : dummy, &ns, ns > 0 ? ns : 1),
-              "ll_reg_upload_features");
-        check(ll_reg_enqueue_uploaded(reg_, m, 1, &p, m_para_buffer_RT_last, m_para_buffer_RT, m_para_buffer_incremental), "ll_reg_enqueue_uploaded");
+        check(ll_reg_upload_features(reg, 1, xyzi_or_dummy(c), &nc, nc > 0 ? nc : 1, xyzi_or_dummy(s), &ns, ns > 0 ? ns : 1), "ll_reg_upload_features");
+        check(ll_reg_enqueue_uploaded(reg, m, 1, &p, m_para_buffer_RT_last, m_para_buffer_RT, m_para_buffer_incremental), "ll_reg_enqueue_uploaded");
         if (held_until_enqueued) held_until_enqueued->unlock();
         return collect();
     }
@@ -1237,13 +1245,12 @@ class Point_cloud_registration {
     {
         ll_reg_report rep;
         int32_t ret = 0;
-        check(ll_reg_collect(reg_, 1, m_para_buffer_RT, m_para_buffer_incremental, &rep, &ret), "ll_reg_collect");
+        check(ll_reg_collect(reg_.get(), 1, m_para_buffer_RT, m_para_buffer_incremental, &rep, &ret), "ll_reg_collect");
         members_from_pose();
         m_inlier_threshold = rep.inlier_threshold;
         m_angular_diff = rep.angular_diff_deg;
         m_t_diff = rep.t_diff;
-        static_cast<ll_reg_report &>(summary) = rep;
-        summary.num_residual_blocks = rep.n_blocks_last;
+        summary = Opt_summary::from(rep);
         if (ret == 1 && !rep.gated) m_final_opt_summary = summary;  // PCR:574
         if (ret == 0) m_last_time_stamp = m_minimum_pt_time_stamp;   // PCR:569
         return ret;
@@ -1277,11 +1284,11 @@ class Point_cloud_registration {
     template <class Cloud>
     unsigned int pointcloudAssociateToMap(const Cloud &pc_in, Cloud &pt_out, int /*if_undistore*/ = 0)
     {
-        if (!reg_) reg_ = Handle_pool::instance().acquire(device, reg_cap_ = max_features);
+        ll_reg *reg = registrar(max_features);
         pose_from_members();
         const std::vector<float> in = cloud_to_xyzi(pc_in);
         std::vector<float> out(in.size());
-        check(ll_cloud_transform(reg_, in.data(), out.data(), (int)(in.size() / 4), m_para_buffer_RT), "ll_cloud_transform");
+        check(ll_cloud_transform(reg, in.data(), out.data(), (int)(in.size() / 4), m_para_buffer_RT), "ll_cloud_transform");
         xyzi_to_cloud(out.data(), (int)(in.size() / 4), pt_out);
         return (unsigned int)(in.size() / 4);
     }
@@ -1289,18 +1296,15 @@ class Point_cloud_registration {
    private:
     void pose_from_members()
     {
-        m_para_buffer_RT[0] = m_q_w_curr.x(), m_para_buffer_RT[1] = m_q_w_curr.y(), m_para_buffer_RT[2] = m_q_w_curr.z(), m_para_buffer_RT[3] = m_q_w_curr.w();
-        m_para_buffer_RT_last[0] = m_q_w_last.x(), m_para_buffer_RT_last[1] = m_q_w_last.y(), m_para_buffer_RT_last[2] = m_q_w_last.z(),
-        m_para_buffer_RT_last[3] = m_q_w_last.w();
-        for (int i = 0; i < 3; i++) {
-            m_para_buffer_RT[4 + i] = m_t_w_curr(i);
-            m_para_buffer_RT_last[4 + i] = m_t_w_last(i);
-        }
+        to_pose7(m_q_w_curr, m_t_w_curr, m_para_buffer_RT);
+        to_pose7(m_q_w_last, m_t_w_last, m_para_buffer_RT_last);
     }
-    void members_from_pose()
+    void members_from_pose() { from_pose7(m_para_buffer_RT, m_q_w_curr, m_t_w_curr); }
+    // the registrar borrowed from the pool, of `capacity` features when this call is the one that borrows it
+    ll_reg *registrar(int capacity)
     {
-        m_q_w_curr.x() = m_para_buffer_RT[0], m_q_w_curr.y() = m_para_buffer_RT[1], m_q_w_curr.z() = m_para_buffer_RT[2], m_q_w_curr.w() = m_para_buffer_RT[3];
-        for (int i = 0; i < 3; i++) m_t_w_curr(i) = m_para_buffer_RT[4 + i];
+        if (!reg_) reg_.reset(Handle_pool::instance().acquire(device, reg_cap_ = capacity));
+        return reg_.get();
     }
     template <class Cloud>
     void upload_if_changed(Handle_pool::Shared_map &sm, int kind, const Cloud &c)
@@ -1320,8 +1324,7 @@ class Point_cloud_registration {
         if (k.n == now.n && k.hash == now.hash && k.generation == ll_map_generation(sm.map, kind)) return;  // same contents, still the published structure
         int64_t gen = -1;  // the generation of OUR publication, reported from inside the map's lock
         if (now.n == 0) {
-            const float none[4] = {0, 0, 0, 0};
-            check(ll_map_upload_gen(sm.map, kind, none, 4, 0, 0.0f, &gen), "ll_map_upload");
+            check(ll_map_upload_gen(sm.map, kind, xyzi_or_dummy(std::vector<float>()), 4, 0, 0.0f, &gen), "ll_map_upload");
         } else {
             // ll_map_upload takes x, y, z at any float stride: a point type whose coordinates are three consecutive floats
             // (pcl::PointXYZI: 8 floats per point) goes as it lies, without a staging copy
@@ -1338,8 +1341,11 @@ class Point_cloud_registration {
         now.generation = gen;  // (not ll_map_generation() now: a refresh may have published in between, and the key would then vouch for it)
         k = now;
     }
-    ll_reg *reg_ = nullptr;
-    int reg_cap_ = 0;  // the feature capacity reg_ was acquired with
+    struct Give_back {
+        void operator()(ll_reg *r) const { Handle_pool::instance().release(r); }
+    };
+    std::unique_ptr<ll_reg, Give_back> reg_;  // borrowed from Handle_pool, given back with this object
+    int reg_cap_ = 0;                         // the feature capacity reg_ was acquired with
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1408,7 +1414,8 @@ inline ll_pose_graph_summary pose_graph_optimization(MapOfPoses &poses, VectorOf
     std::vector<double> x;
     for (MapOfPoses::const_iterator it = poses.begin(); it != poses.end(); ++it) {
         index[it->first] = (int)index.size();
-        const double row[7] = {it->second.q.x(), it->second.q.y(), it->second.q.z(), it->second.q.w(), it->second.p(0), it->second.p(1), it->second.p(2)};
+        double row[7];
+        to_pose7(it->second.q, it->second.p, row);
         x.insert(x.end(), row, row + 7);
     }
     const int64_t n = (int64_t)poses.size(), e = (int64_t)constraints.size();
@@ -1420,7 +1427,8 @@ inline ll_pose_graph_summary pose_graph_optimization(MapOfPoses &poses, VectorOf
         if (!index.count(c.id_begin) || !index.count(c.id_end)) check(-1, "pose_graph_optimization: a constraint names a pose that is not in the map");
         const int a = index[c.id_begin], b = index[c.id_end];
         ab.push_back(a), ab.push_back(b);
-        const double row[7] = {c.t_be.q.x(), c.t_be.q.y(), c.t_be.q.z(), c.t_be.q.w(), c.t_be.p(0), c.t_be.p(1), c.t_be.p(2)};
+        double row[7];
+        to_pose7(c.t_be.q, c.t_be.p, row);
         meas.insert(meas.end(), row, row + 7);
         for (int i = 0; i < 6; i++)
             for (int j = 0; j < 6; j++) info.push_back(c.information(i, j));
@@ -1429,19 +1437,13 @@ inline ll_pose_graph_summary pose_graph_optimization(MapOfPoses &poses, VectorOf
     }
     int64_t blocks = 1;
     for (int64_t k = 1; k < n; k++) blocks += (k - 1) - first[(size_t)k] + 1;
-    runtime_hints();
-    ll_pose_graph *h = nullptr;
-    check(ll_pose_graph_create(device, 1, n, e > 0 ? e : 1, blocks, &h), "ll_pose_graph_create");
+    Handle<ll_pose_graph, ll_pose_graph_destroy> h;
+    make_handle(h, "ll_pose_graph_create", [&](ll_pose_graph **out) { return ll_pose_graph_create(device, 1, n, e > 0 ? e : 1, blocks, out); });
     const int64_t pose_offsets[2] = {0, n}, edge_offsets[2] = {0, e};
-    const int rc = ll_pose_graph_solve(h, nullptr, 1, pose_offsets, x.data(), edge_offsets, ab.data(), meas.data(), info.data(), &summary);
-    const std::string why = rc < 0 ? ll_last_error() : "";
-    ll_pose_graph_destroy(h);
-    if (rc < 0) throw std::runtime_error("ll_pose_graph_solve: " + why);
+    check(ll_pose_graph_solve(h.get(), nullptr, 1, pose_offsets, x.data(), edge_offsets, ab.data(), meas.data(), info.data(), &summary),
+          "ll_pose_graph_solve");  // (h goes on both ways out, after the error's text is taken)
     size_t k = 0;
-    for (MapOfPoses::iterator it = poses.begin(); it != poses.end(); ++it, k++) {
-        it->second.q.x() = x[7 * k], it->second.q.y() = x[7 * k + 1], it->second.q.z() = x[7 * k + 2], it->second.q.w() = x[7 * k + 3];
-        for (int i = 0; i < 3; i++) it->second.p(i) = x[7 * k + 4 + i];
-    }
+    for (MapOfPoses::iterator it = poses.begin(); it != poses.end(); ++it, k++) from_pose7(&x[7 * k], it->second.q, it->second.p);
     return summary;
 }
 
@@ -1495,12 +1497,6 @@ class Scene_alignment {
 
     Scene_alignment() {}
     explicit Scene_alignment(std::string path) { init(path); }
-    ~Scene_alignment()
-    {
-        if (h_) ll_scene_align_destroy(h_);
-    }
-    Scene_alignment(const Scene_alignment &) = delete;
-    Scene_alignment &operator=(const Scene_alignment &) = delete;
 
     void set_downsample_resolution(const float &line_res, const float &plane_res)  // :55-62
     {
@@ -1525,10 +1521,7 @@ class Scene_alignment {
         (void)if_save;
         (void)mapping_save_path;
         if (!keyframe_a || !keyframe_b) check(-1, "Scene_alignment::find_tranfrom_of_two_mappings: null key frame");
-        if (!h_) {
-            runtime_hints();
-            check(ll_scene_align_create(device, initial_points, &h_), "ll_scene_align_create");
-        }
+        if (!h_) make_handle(h_, "ll_scene_align_create", [&](ll_scene_align **out) { return ll_scene_align_create(device, initial_points, out); });
         ll_scene_align_params p;
         ll_scene_align_default_params(&p);
         p.line_res = m_line_res;
@@ -1541,23 +1534,17 @@ class Scene_alignment {
         double pose[7], thr = 0.0;
         ll_reg_report rep[3];
         int32_t n_rep = 0;
-        check(ll_scene_align_run(h_, keyframe_a->handle(), keyframe_b->handle(), &p, pose, &thr, rep, &n_rep), "ll_scene_align_run");
-        m_pc_reg.m_q_w_curr.x() = pose[0], m_pc_reg.m_q_w_curr.y() = pose[1], m_pc_reg.m_q_w_curr.z() = pose[2], m_pc_reg.m_q_w_curr.w() = pose[3];
-        for (int i = 0; i < 3; i++) m_pc_reg.m_t_w_curr(i) = pose[4 + i];
+        check(ll_scene_align_run(h_.get(), keyframe_a->handle(), keyframe_b->handle(), &p, pose, &thr, rep, &n_rep), "ll_scene_align_run");
+        from_pose7(pose, m_pc_reg.m_q_w_curr, m_pc_reg.m_t_w_curr);
         m_pc_reg.m_inlier_threshold = thr;
         reports.clear();
-        for (int i = 0; i < n_rep; i++) {
-            Point_cloud_registration::Opt_summary s;
-            static_cast<ll_reg_report &>(s) = rep[i];
-            s.num_residual_blocks = rep[i].n_blocks_last;
-            reports.push_back(s);
-        }
+        for (int i = 0; i < n_rep; i++) reports.push_back(Point_cloud_registration::Opt_summary::from(rep[i]));
         if (n_rep > 0) m_pc_reg.summary = m_pc_reg.m_final_opt_summary = reports.back();
         pair_idx++;
         return thr;
     }
     // test tap (ll_scene_align_work) on the last call
-    void work(int64_t out[4]) { check(ll_scene_align_work(h_, out), "ll_scene_align_work"); }
+    void work(int64_t out[4]) { check(ll_scene_align_work(h_.get(), out), "ll_scene_align_work"); }
 
     // :97-129: the loop constraint s_idx -> t_idx from the poses of the two key frames and the alignment's inverted transform:
     // q_res = q_b^-1 icp_q^-1 q_a, t_res = q_b^-1 ( icp_q^-1 ( t_a - icp_t ) - t_b ).  fp64 on the host, Eigen's operation order.
@@ -1585,7 +1572,7 @@ class Scene_alignment {
     }
 
    private:
-    ll_scene_align *h_ = nullptr;
+    Handle<ll_scene_align, ll_scene_align_destroy> h_;
     int registrar_init_ = 0;
 };
 
@@ -1598,22 +1585,15 @@ class Keyframe_bank {
    public:
     explicit Keyframe_bank(int64_t initial_entries = 256, int device = 0)
     {
-        runtime_hints();
-        check(ll_keyframe_bank_create(device, initial_entries, &h_), "ll_keyframe_bank_create");
+        make_handle(h_, "ll_keyframe_bank_create", [&](ll_keyframe_bank **out) { return ll_keyframe_bank_create(device, initial_entries, out); });
     }
-    ~Keyframe_bank()
-    {
-        if (h_) ll_keyframe_bank_destroy(h_);
-    }
-    Keyframe_bank(const Keyframe_bank &) = delete;
-    Keyframe_bank &operator=(const Keyframe_bank &) = delete;
 
     // Points_cloud_map::analyze with the same outputs; the key frame's line and plane image also become a new entry, whose id is returned
     int64_t add(Points_cloud_map &keyframe, std::vector<float> &images, float ratio_nonzero[4], float roi_ratio = 0.9f)
     {
         images.assign((size_t)4 * 60 * 60, 0.f);
         int64_t id = -1;
-        check(ll_keyframe_bank_add_cellmap(h_, keyframe.handle(), roi_ratio, images.data(), ratio_nonzero, nullptr, nullptr, nullptr, &id),
+        check(ll_keyframe_bank_add_cellmap(h_.get(), keyframe.handle(), roi_ratio, images.data(), ratio_nonzero, nullptr, nullptr, nullptr, &id),
               "ll_keyframe_bank_add_cellmap");
         return id;
     }
@@ -1621,24 +1601,24 @@ class Keyframe_bank {
     int64_t add(const float *img_line, const float *img_plane)
     {
         int64_t id = -1;
-        check(ll_keyframe_bank_add_images(h_, img_line, img_plane, &id), "ll_keyframe_bank_add_images");
+        check(ll_keyframe_bank_add_images(h_.get(), img_line, img_plane, &id), "ll_keyframe_bank_add_images");
         return id;
     }
-    int64_t size() const { return ll_keyframe_bank_size(h_); }
+    int64_t size() const { return ll_keyframe_bank_size(h_.get()); }
     // sim_line[p], sim_plane[p] of ( ids_a[p] = the new key frame, ids_b[p] = the old one )
     void match(const std::vector<int64_t> &ids_a, const std::vector<int64_t> &ids_b, std::vector<float> &sim_line, std::vector<float> &sim_plane)
     {
         if (ids_a.size() != ids_b.size()) check(-1, "Keyframe_bank::match: ids_a and ids_b differ in length");
         sim_line.assign(ids_a.size(), 0.f);
         sim_plane.assign(ids_a.size(), 0.f);
-        check(ll_keyframe_bank_match(h_, (int64_t)ids_a.size(), ids_a.data(), ids_b.data(), sim_line.data(), sim_plane.data()), "ll_keyframe_bank_match");
+        check(ll_keyframe_bank_match(h_.get(), (int64_t)ids_a.size(), ids_a.data(), ids_b.data(), sim_line.data(), sim_plane.data()), "ll_keyframe_bank_match");
     }
     // test tap (ll_keyframe_bank_work) on the last match
-    void work(int64_t out[4]) { check(ll_keyframe_bank_work(h_, out), "ll_keyframe_bank_work"); }
-    ll_keyframe_bank *handle() { return h_; }
+    void work(int64_t out[4]) { check(ll_keyframe_bank_work(h_.get(), out), "ll_keyframe_bank_work"); }
+    ll_keyframe_bank *handle() { return h_.get(); }
 
    private:
-    ll_keyframe_bank *h_ = nullptr;
+    Handle<ll_keyframe_bank, ll_keyframe_bank_destroy> h_;
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1661,12 +1641,6 @@ class Mapping_refine {
     int m_step_skip = 2;
 
     explicit Mapping_refine(int64_t initial_points = 1 << 20, int device = 0) : initial_points_(initial_points), device_(device) {}
-    ~Mapping_refine()
-    {
-        if (h_) ll_map_refine_destroy(h_);
-    }
-    Mapping_refine(const Mapping_refine &) = delete;
-    Mapping_refine &operator=(const Mapping_refine &) = delete;
 
     void set_down_sample_resolution(float res) { m_down_sample_res = res; }
     // ( laser_mapping.hpp:902 ) kept, not used: nothing is written
@@ -1689,8 +1663,9 @@ class Mapping_refine {
 #pragma clang fp contract(off)
 #endif
         float R[9], T[3];
-        const double ori[7] = {q_ori.x(), q_ori.y(), q_ori.z(), q_ori.w(), t_ori(0), t_ori(1), t_ori(2)};
-        const double opm[7] = {q_opm.x(), q_opm.y(), q_opm.z(), q_opm.w(), t_opm(0), t_opm(1), t_opm(2)};
+        double ori[7], opm[7];
+        to_pose7(q_ori, t_ori, ori);
+        to_pose7(q_opm, t_opm, opm);
         check(ll_map_refine_affine(ori, opm, R, T), "ll_map_refine_affine");
         std::vector<V> out(raw_pt_vec.size());
         for (size_t k = 0; k < raw_pt_vec.size(); k++) {
@@ -1732,10 +1707,9 @@ class Mapping_refine {
         Cloud out;
         if (!h_) return out;
         int64_t n = 0;
-        check(ll_map_refine_merge(h_, m_down_sample_res, &n, nullptr), "ll_map_refine_merge");
-        std::vector<float> v((size_t)(n > 0 ? n : 1) * 4);
-        check(ll_map_refine_fetch_merged(h_, v.data(), n), "ll_map_refine_fetch_merged");
-        xyzi_to_cloud(v.data(), (int)n, out);
+        check(ll_map_refine_merge(h_.get(), m_down_sample_res, &n, nullptr), "ll_map_refine_merge");
+        read_cloud("ll_map_refine_fetch_merged", out,
+                   [&](float *xyzi, int64_t capacity) { return xyzi ? (int64_t)ll_map_refine_fetch_merged(h_.get(), xyzi, capacity) : n; });
         return out;
     }
     // ll_map_refine_add_logged: request r is the concatenation of the logged scans of groups_per_request[r] (ids of
@@ -1744,18 +1718,13 @@ class Mapping_refine {
     std::vector<int64_t> add_logged(History_batch &batch, const std::vector<std::vector<int64_t> > &groups_per_request, float leaf,
                                     std::vector<int64_t> *n_kept = nullptr, std::vector<int32_t> *status = nullptr)
     {
-        if (!h_) {
-            runtime_hints();
-            check(ll_map_refine_create(device_, initial_points_, &h_), "ll_map_refine_create");
-        }
+        ensure();
         const size_t R = groups_per_request.size();
-        std::vector<int64_t> off(R + 1, 0), gids, ids(R > 0 ? R : 1, -1), kept(R > 0 ? R : 1, 0);
+        const std::vector<int64_t> off = csr_offsets(groups_per_request);
+        std::vector<int64_t> gids, ids(R > 0 ? R : 1, -1), kept(R > 0 ? R : 1, 0);
         std::vector<int32_t> st(R > 0 ? R : 1, 0);
-        for (size_t r = 0; r < R; r++) {
-            gids.insert(gids.end(), groups_per_request[r].begin(), groups_per_request[r].end());
-            off[r + 1] = (int64_t)gids.size();
-        }
-        check(ll_map_refine_add_logged(h_, batch.handle(), (int64_t)R, off.data(), gids.empty() ? nullptr : gids.data(), leaf, ids.data(), kept.data(),
+        for (size_t r = 0; r < R; r++) gids.insert(gids.end(), groups_per_request[r].begin(), groups_per_request[r].end());
+        check(ll_map_refine_add_logged(h_.get(), batch.handle(), (int64_t)R, off.data(), gids.empty() ? nullptr : gids.data(), leaf, ids.data(), kept.data(),
                                        st.data()),
               "ll_map_refine_add_logged");
         ids.resize(R), kept.resize(R), st.resize(R);
@@ -1764,11 +1733,15 @@ class Mapping_refine {
         return ids;
     }
     // test tap (ll_map_refine_work) on the last run and its fetch
-    void work(int64_t out[4]) { check(ll_map_refine_work(h_, out), "ll_map_refine_work"); }
-    ll_map_refine *handle() { return h_; }
+    void work(int64_t out[4]) { check(ll_map_refine_work(h_.get(), out), "ll_map_refine_work"); }
+    ll_map_refine *handle() { return h_.get(); }
 
    private:
     static void check_arg(const char *what) { throw std::runtime_error(what); }
+    void ensure()  // the handle is made by the first call that needs it
+    {
+        if (!h_) make_handle(h_, "ll_map_refine_create", [&](ll_map_refine **out) { return ll_map_refine_create(device_, initial_points_, out); });
+    }
 
     int64_t stored_id(int key, const Cloud &c)
     {
@@ -1776,7 +1749,7 @@ class Mapping_refine {
         if (it != ids_.end() && it->second.second == c.points.size()) return it->second.first;
         const std::vector<float> v = cloud_to_xyzi(c);
         int64_t id = -1;
-        check(ll_map_refine_add_stored(h_, v.empty() ? nullptr : v.data(), (int64_t)c.points.size(), &id), "ll_map_refine_add_stored");
+        check(ll_map_refine_add_stored(h_.get(), v.empty() ? nullptr : v.data(), (int64_t)c.points.size(), &id), "ll_map_refine_add_stored");
         ids_[key] = std::make_pair(id, c.points.size());
         return id;
     }
@@ -1786,10 +1759,7 @@ class Mapping_refine {
     {
         if (map_idx_pc.size() != poses_ori.size() || map_idx_pc.size() != poses_opm.size())   // ( the asserts of :461-462, :508-509 )
             check_arg("Mapping_refine: map_idx_pc, poses_ori and poses_opm differ in size");
-        if (!h_) {
-            runtime_hints();
-            check(ll_map_refine_create(device_, initial_points_, &h_), "ll_map_refine_create");
-        }
+        ensure();
         std::vector<int64_t> ids;
         std::vector<double> ori, opm;
         for (size_t k = 0; k < keys.size(); k++) {
@@ -1797,17 +1767,19 @@ class Mapping_refine {
             Ceres_pose_graph_3d::MapOfPoses::const_iterator a = poses_ori.find(keys[k]), b = poses_opm.find(keys[k]);
             if (pc == map_idx_pc.end() || a == poses_ori.end() || b == poses_opm.end()) check_arg("Mapping_refine: an id is missing from a map");
             ids.push_back(stored_id(keys[k], pc->second));
-            const double ra[7] = {a->second.q.x(), a->second.q.y(), a->second.q.z(), a->second.q.w(), a->second.p(0), a->second.p(1), a->second.p(2)};
-            const double rb[7] = {b->second.q.x(), b->second.q.y(), b->second.q.z(), b->second.q.w(), b->second.p(0), b->second.p(1), b->second.p(2)};
+            double ra[7], rb[7];
+            to_pose7(a->second.q, a->second.p, ra);
+            to_pose7(b->second.q, b->second.p, rb);
             ori.insert(ori.end(), ra, ra + 7);
             opm.insert(opm.end(), rb, rb + 7);
         }
         std::vector<int64_t> offsets(keys.size() + 1, 0);
         std::vector<int32_t> status(keys.size() + 1, 0);
-        check(ll_map_refine_run(h_, mode, (int64_t)keys.size(), ids.data(), ori.data(), opm.data(), m_down_sample_res, offsets.data(), status.data()),
+        check(ll_map_refine_run(h_.get(), mode, (int64_t)keys.size(), ids.data(), ori.data(), opm.data(), m_down_sample_res, offsets.data(), status.data()),
               "ll_map_refine_run");
-        std::vector<float> v((size_t)(offsets.back() > 0 ? offsets.back() : 1) * 4);
-        check(ll_map_refine_fetch(h_, v.data(), offsets.back()), "ll_map_refine_fetch");
+        const std::vector<float> v = read_xyzi("ll_map_refine_fetch", [&](float *xyzi, int64_t capacity) {
+            return xyzi ? (int64_t)ll_map_refine_fetch(h_.get(), xyzi, capacity) : offsets.back();
+        });
         std::vector<Cloud> out(keys.size());
         for (size_t k = 0; k < keys.size(); k++) xyzi_to_cloud(v.data() + 4 * offsets[k], (int)(offsets[k + 1] - offsets[k]), out[k]);
         return out;
@@ -1815,7 +1787,7 @@ class Mapping_refine {
 
     int64_t initial_points_;
     int device_;
-    ll_map_refine *h_ = nullptr;
+    Handle<ll_map_refine, ll_map_refine_destroy> h_;
     std::map<int, std::pair<int64_t, size_t> > ids_;  // key of map_idx_pc -> (id in the store, points it had when uploaded)
 };
 

@@ -24,9 +24,18 @@
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "loam_livox_hip.h"
+
+// The two entry points behind Point_cloud_registration::m_if_compute_information are referenced weakly: the header's registration path
+// names them, and a program that never sets the member must keep linking against whatever it linked against before (an older build of
+// the library, a test stand-in of the C ABI).  Setting the member without them throws.
+extern "C" {
+int ll_reg_set_information(ll_reg *r, int32_t enable) __attribute__((weak));
+int ll_reg_information(ll_reg *r, int32_t n_scans, ll_reg_information_record *out) __attribute__((weak));
+}
 
 // The registrar's pose members (m_q_w_curr, m_t_w_curr, m_q_w_last, m_t_w_last, m_q_w_incre, m_t_w_incre,
 // point_cloud_registration.hpp:53-56,75-76) are Eigen objects in the reference and the node assigns Eigen objects to them
@@ -1030,6 +1039,107 @@ class Handle_pool {
 };
 
 // ------------------------------------------------------------------------------------------------------------
+// Registration information (ll_reg_information, DESIGN "Registration information"): host arithmetic on the 36 numbers of a scan's
+// Gauss-Newton matrix.  The adapter has no Eigen of its own, so the eigen decomposition is a cyclic Jacobi.
+
+// Eigenvalues (ascending, w[6]) and eigenvectors (the COLUMNS of V, row-major: V[i * 6 + k] = component i of vector k) of the symmetric
+// 6 x 6 matrix H (row-major; the upper triangle is read).  Cyclic Jacobi: every sweep annihilates the 15 off-diagonal entries in turn by
+// plane rotations, until the off-diagonal norm is below 2^-52 of the diagonal's (a handful of sweeps; convergence is quadratic).
+// Returns the sweeps taken.
+inline int symmetric_eigen6(const double H[36], double w[6], double V[36])
+{
+    double a[36];
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            a[i * 6 + j] = i <= j ? H[i * 6 + j] : H[j * 6 + i];
+            V[i * 6 + j] = i == j ? 1.0 : 0.0;
+        }
+    int sweep = 0;
+    for (; sweep < 60; sweep++) {
+        double off = 0.0, diag = 0.0;
+        for (int i = 0; i < 6; i++) {
+            diag += a[i * 6 + i] * a[i * 6 + i];
+            for (int j = i + 1; j < 6; j++) off += a[i * 6 + j] * a[i * 6 + j];
+        }
+        if (off == 0.0 || off <= 4.9303806576313238e-32 * diag) break;  // 2^-104: |off| <= 2^-52 |diag|
+        for (int p = 0; p < 5; p++)
+            for (int q = p + 1; q < 6; q++) {
+                const double apq = a[p * 6 + q];
+                if (apq == 0.0) continue;
+                const double theta = (a[q * 6 + q] - a[p * 6 + p]) / (2.0 * apq);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+                for (int k = 0; k < 6; k++) {  // A <- A J
+                    const double akp = a[k * 6 + p], akq = a[k * 6 + q];
+                    a[k * 6 + p] = c * akp - sn * akq;
+                    a[k * 6 + q] = sn * akp + c * akq;
+                }
+                for (int k = 0; k < 6; k++) {  // A <- J^T A
+                    const double apk = a[p * 6 + k], aqk = a[q * 6 + k];
+                    a[p * 6 + k] = c * apk - sn * aqk;
+                    a[q * 6 + k] = sn * apk + c * aqk;
+                }
+                a[p * 6 + q] = a[q * 6 + p] = 0.0;  // (what the rotation was chosen for)
+                for (int k = 0; k < 6; k++) {  // V <- V J
+                    const double vkp = V[k * 6 + p], vkq = V[k * 6 + q];
+                    V[k * 6 + p] = c * vkp - sn * vkq;
+                    V[k * 6 + q] = sn * vkp + c * vkq;
+                }
+            }
+    }
+    for (int i = 0; i < 6; i++) w[i] = a[i * 6 + i];
+    for (int i = 0; i < 5; i++) {  // ascending, the vectors with their values
+        int m = i;
+        for (int j = i + 1; j < 6; j++)
+            if (w[j] < w[m]) m = j;
+        if (m != i) {
+            std::swap(w[i], w[m]);
+            for (int k = 0; k < 6; k++) std::swap(V[k * 6 + i], V[k * 6 + m]);
+        }
+    }
+    return sweep;
+}
+
+// H of the solver's tangent d = [d_rot; d_t] of the increment as the information of the scan's pose in the map frame, ordered
+// translation then rotation vector (radians) like the pose graph's residual: with R = R(pose_last) a step d moves the pose by
+// xi = T d, T = [[0, R], [2 R, 0]], hence H_pose = T^-T H T^-1 with T^-1 = [[0, R^T / 2], [R^T, 0]].  pose_last = (qx, qy, qz, qw, t).
+inline void information_in_pose_frame(const double H[36], const double pose_last[7], double H_pose[36])
+{
+    const double x = pose_last[0], y = pose_last[1], z = pose_last[2], w = pose_last[3];
+    const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w),     2 * (x * z + y * w),
+                         2 * (x * y + z * w),     1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                         2 * (x * z - y * w),     2 * (y * z + x * w),     1 - 2 * (x * x + y * y)};
+    double Ti[36] = {0};
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            Ti[i * 6 + 3 + j] = 0.5 * R[j * 3 + i];  // d_rot = R^T theta / 2
+            Ti[(3 + i) * 6 + j] = R[j * 3 + i];      // d_t = R^T dt
+        }
+    double HT[36];
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            double v = 0.0;
+            for (int k = 0; k < 6; k++) v += H[i * 6 + k] * Ti[k * 6 + j];
+            HT[i * 6 + j] = v;
+        }
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            double v = 0.0;
+            for (int k = 0; k < 6; k++) v += Ti[k * 6 + i] * HT[k * 6 + j];
+            H_pose[i * 6 + j] = v;
+        }
+}
+
+// what Point_cloud_registration::information() returns
+struct Registration_information {
+    double H[36], g[6], cost;           // ll_reg_information_record: solver tangent [d_rot; d_t]
+    int n_line, n_plane, status;        // blocks summed; 0 computed, 1 gated / no iteration / empty scan, 2 aborted solve
+    double eigenvalues[6];              // of H, ascending
+    double eigenvectors[36];            // columns, row-major (symmetric_eigen6)
+    double H_pose[36];                  // information_in_pose_frame( H, the pose the registration started from )
+};
+
+// ------------------------------------------------------------------------------------------------------------
 // The part of Point_cloud_registration that copies as plain values: the class copies it as a whole, so a field added here is copied
 // without being named anywhere.
 struct Point_cloud_registration_fields {
@@ -1038,6 +1148,7 @@ struct Point_cloud_registration_fields {
     int IF_LINE_FEATURE_CHECK = 0, IF_PLANE_FEATURE_CHECK = 0;  // PCR:46,48
     int line_search_num = 5, plane_search_num = 5;              // PCR:45,47 (the device search is fixed at k = 5)
     int m_if_motion_deblur = 0;
+    int m_if_compute_information = 0;  // 1: every registration also leaves information() (not in the reference; off: no call more)
     int m_current_frame_index = 0;
     int m_mapping_init_accumulate_frames = 100;
     float m_last_time_stamp = 0;
@@ -1085,6 +1196,8 @@ struct Point_cloud_registration_fields {
         std::string FullReport() const { return BriefReport(); }
     };
     Opt_summary summary, m_final_opt_summary;
+    ll_reg_information_record m_information_record = {};  // of the last registration made with m_if_compute_information
+    int m_information_valid = 0;
     int device = 0;
     int max_features = 100000;
 };
@@ -1168,8 +1281,11 @@ class Point_cloud_registration : public Point_cloud_registration_fields {
         ll_reg_params p;
         fill_params(p);
         pose_from_members();
-        check(ll_reg_enqueue_spin(reg, map(), spin.handle(), 1, &p, m_para_buffer_RT_last, m_para_buffer_RT, m_para_buffer_incremental),
-              "ll_reg_enqueue_spin");
+        {
+            Information_switch sw(reg, m_if_compute_information);
+            check(ll_reg_enqueue_spin(reg, map(), spin.handle(), 1, &p, m_para_buffer_RT_last, m_para_buffer_RT, m_para_buffer_incremental),
+                  "ll_reg_enqueue_spin");
+        }
         return collect();
     }
 
@@ -1196,8 +1312,44 @@ class Point_cloud_registration : public Point_cloud_registration_fields {
               "ll_reg_enqueue_fe_downsampled_maps");
     }
 
+    // The information of the last registration made with m_if_compute_information = 1: the Gauss-Newton matrix of its last
+    // linearisation (ll_reg_information), its eigen decomposition and the same matrix in the pose's own frame.  This object registers
+    // one scan per call, so scan must be 0.
+    Registration_information information(int scan = 0) const
+    {
+        if (scan != 0) throw std::runtime_error("information: this object registers one scan per call (scan must be 0)");
+        if (!m_information_valid) throw std::runtime_error("information: no registration was made with m_if_compute_information = 1");
+        Registration_information out;
+        const ll_reg_information_record &r = m_information_record;
+        std::memcpy(out.H, r.H, sizeof(out.H));
+        std::memcpy(out.g, r.g, sizeof(out.g));
+        out.cost = r.cost;
+        out.n_line = r.n_line, out.n_plane = r.n_plane, out.status = r.status;
+        symmetric_eigen6(out.H, out.eigenvalues, out.eigenvectors);
+        information_in_pose_frame(out.H, m_para_buffer_RT_last, out.H_pose);
+        return out;
+    }
+
     // void pointAssociateToMap ... see below
    private:
+    // ll_reg_set_information around ONE enqueue: the switch is read by the enqueue, and the registrar goes back to a pool whose other
+    // borrowers did not ask.  Nothing is called when the member is 0.
+    struct Information_switch {
+        ll_reg *r;
+        Information_switch(ll_reg *reg, int on) : r(on ? reg : nullptr)
+        {
+            if (!r) return;
+            if (!&ll_reg_set_information || !&ll_reg_information)
+                throw std::runtime_error("m_if_compute_information: this program is linked against a library without ll_reg_set_information");
+            check(ll_reg_set_information(r, 1), "ll_reg_set_information");
+        }
+        ~Information_switch()
+        {
+            if (r) (void)ll_reg_set_information(r, 0);
+        }
+        Information_switch(const Information_switch &) = delete;
+        Information_switch &operator=(const Information_switch &) = delete;
+    };
     template <class CloudPtr>
     int register_scan(CloudPtr scan_corner, CloudPtr scan_surf, std::unique_lock<std::mutex> *held_until_enqueued)
     {
@@ -1210,7 +1362,10 @@ class Point_cloud_registration : public Point_cloud_registration_fields {
         // ll_reg_solve in its three steps (upload the scan's features, enqueue = pin the map snapshots + launch, collect)
         const int32_t nc = (int32_t)(c.size() / 4), ns = (int32_t)(s.size() / 4);
         check(ll_reg_upload_features(reg, 1, xyzi_or_dummy(c), &nc, nc > 0 ? nc : 1, xyzi_or_dummy(s), &ns, ns > 0 ? ns : 1), "ll_reg_upload_features");
-        check(ll_reg_enqueue_uploaded(reg, m, 1, &p, m_para_buffer_RT_last, m_para_buffer_RT, m_para_buffer_incremental), "ll_reg_enqueue_uploaded");
+        {
+            Information_switch sw(reg, m_if_compute_information);
+            check(ll_reg_enqueue_uploaded(reg, m, 1, &p, m_para_buffer_RT_last, m_para_buffer_RT, m_para_buffer_incremental), "ll_reg_enqueue_uploaded");
+        }
         if (held_until_enqueued) held_until_enqueued->unlock();
         return collect();
     }
@@ -1246,6 +1401,11 @@ class Point_cloud_registration : public Point_cloud_registration_fields {
         ll_reg_report rep;
         int32_t ret = 0;
         check(ll_reg_collect(reg_.get(), 1, m_para_buffer_RT, m_para_buffer_incremental, &rep, &ret), "ll_reg_collect");
+        m_information_valid = 0;
+        if (m_if_compute_information) {  // (no device work: the records came back with the collect)
+            check(ll_reg_information(reg_.get(), 1, &m_information_record), "ll_reg_information");
+            m_information_valid = 1;
+        }
         members_from_pose();
         m_inlier_threshold = rep.inlier_threshold;
         m_angular_diff = rep.angular_diff_deg;

@@ -926,6 +926,35 @@ int ll_cloud_transform_fe_device(ll_reg *r, ll_fe *fe, int32_t n_scans, int32_t 
 int ll_reg_set_profiling(ll_reg *r, int32_t enable);
 int ll_reg_kernel_times(ll_reg *r, float ms[3], int32_t launches[3]);
 
+/* Information matrix of a registration, per scan: how well the answer is constrained.  The reference has no such output; the
+ * definition is this project's (DESIGN "Registration information").  For a scan in which at least one ICP iteration ran,
+ *     H = sum rho' J^T J,   g = sum rho' J^T r,   cost = 1/2 sum rho(|r|^2)
+ * over the candidate blocks of the scan's LAST ICP iteration (every candidate the block build left active, corner queries then surface
+ * queries), evaluated at the increment that iteration returned, in the solver's tangent d = [d_rot(3); d_t(3)]:
+ * R_inc+ = Exp(2 d_rot) R_inc, t_inc+ = t_inc + d_t.  The sub-sampling drop and the inlier prune of the solve are NOT applied (the
+ * pruned set never leaves the solver's registers; outliers are down-weighted by the Huber term as in every evaluation).  A scan's
+ * record does not depend on its slot, the batch size, the solver or search form, or the single-map against the map-per-slot form.
+ *   H       full symmetric 6 x 6, row-major;  g, cost: the gradient and the cost of the same evaluation
+ *   n_line, n_plane   blocks summed
+ *   status  0 computed (a rejected scan too: the caller has the accept flag); 1 not computed -- the scan was gated (PCR:199), no ICP
+ *           iteration ran, or the scan had no feature -- H, g, cost zero; 2 the solve was aborted (ll_reg_report.aborted), all zero
+ * (The record type cannot share the name of the entry point that fills it, so it carries the suffix _record.)
+ * ll_reg_set_information(r, 1) holds from the next enqueue on (default 0: nothing is launched, allocated or copied).  With it on,
+ * every enqueue launches one more kernel behind the last ICP iteration and ll_reg_collect brings the records back in the copy and the
+ * one wait it makes anyway.  ll_reg_information copies the records of the last collected enqueue to out[n_scans]; it refuses -- and
+ * leaves the handle usable -- a null handle or output, n_scans other than the last enqueue's, a call before ll_reg_collect, and a
+ * call after an enqueue made with the switch off.  ll_reg_information_time: with ll_reg_set_profiling, the kernel's time in the last
+ * collected enqueue (milliseconds; 0 when it did not run). */
+typedef struct {
+    double H[36];
+    double g[6];
+    double cost;
+    int32_t n_line, n_plane, status, reserved;
+} ll_reg_information_record;
+int ll_reg_set_information(ll_reg *r, int32_t enable);
+int ll_reg_information(ll_reg *r, int32_t n_scans, ll_reg_information_record *out);
+int ll_reg_information_time(ll_reg *r, float *ms);
+
 /* Builds compiled with -DLL_SOLVE_TIMING accumulate shader-clock counts per solver phase of scan slot `scan`:
  * [0] cost evaluations, [1] LM controller, [2] L1 pass, [3] de-duplication, [4] rank select, [5] total, [6] flag census,
  * [7] prune, [8] epilogue (plane-table path: table build); [9] counts how often the L1 pass took the values its last prerun

@@ -1369,6 +1369,32 @@ class Point_cloud_registration(_Handle):
     def set_profiling(self, enable: bool = True):
         check(self.L.ll_reg_set_profiling(self.h, int(enable)), "ll_reg_set_profiling")
 
+    def set_information(self, enable: bool = True):
+        """ll_reg_set_information: from the next enqueue on, every registration also leaves the Gauss-Newton matrix of its last
+        linearisation per scan (information()); off by default, and nothing is launched, allocated or copied while it is off"""
+        check(self.L.ll_reg_set_information(self.h, int(bool(enable))), "ll_reg_set_information")
+
+    def information(self, n_scans: int = 1) -> list:
+        """The records of the last collected enqueue (made with set_information on), one dict per scan: H [6, 6] = sum rho' J^T J, g [6]
+        and cost of the scan's last linearisation in the solver's tangent [d_rot(3); d_t(3)] (R_inc+ = Exp(2 d_rot) R_inc), n_line /
+        n_plane blocks summed, status (0 computed, 1 gated / no iteration / empty scan, 2 aborted solve: H zero), and the
+        eigenvalues (ascending) and eigenvectors (columns) of H.  No device work: ll_reg_collect brought the records back."""
+        recs = (capi.RegInformation * n_scans)()
+        check(self.L.ll_reg_information(self.h, int(n_scans), recs), "ll_reg_information")
+        out = []
+        for r in recs:
+            H = np.array(r.H, np.float64).reshape(6, 6)
+            w, v = np.linalg.eigh(H)
+            out.append({"H": H, "g": np.array(r.g, np.float64), "cost": float(r.cost), "n_line": int(r.n_line), "n_plane": int(r.n_plane),
+                        "status": int(r.status), "eigenvalues": w, "eigenvectors": v})
+        return out
+
+    def information_time(self) -> float:
+        """with set_profiling: milliseconds of the information kernel in the last collected enqueue (0.0 when it did not run)"""
+        ms = C.c_float(0.0)
+        check(self.L.ll_reg_information_time(self.h, C.byref(ms)), "ll_reg_information_time")
+        return float(ms.value)
+
     def debug_worklists(self, n_scans=1):
         out = self._tap("ll_reg_debug_worklists", int(n_scans))
         return int(out[0] + out[2]), int(out[1] + out[3])
@@ -1416,3 +1442,19 @@ class Point_cloud_registration(_Handle):
         p = np.ascontiguousarray(self.m_pose_w_curr if pose is None else pose, np.float64)
         check(self.L.ll_cloud_transform(self.h, ptr(pc_in), ptr(out), pc_in.shape[0], ptr(p)), "ll_cloud_transform")
         return out
+
+
+def information_in_pose_frame(H, pose_last) -> np.ndarray:
+    """Point_cloud_registration.information()'s H, given in the solver's tangent d = [d_rot; d_t] of the increment, as the information of
+    the scan's POSE in the map frame, ordered translation then rotation vector (radians): the order of the pose graph's residual.
+    With R = R(pose_last), a step d moves the pose by xi = [dt_map; theta_map] = T d, T = [[0, R], [2 R, 0]] (R_curr+ = Exp(2 R d_rot) R_curr,
+    t_curr+ = t_curr + R d_t), hence H_pose = T^-T H T^-1 with T^-1 = [[0, R^T / 2], [R^T, 0]].  36 numbers: host arithmetic."""
+    H = np.asarray(H, np.float64).reshape(6, 6)
+    x, y, z, w = (float(v) for v in np.asarray(pose_last, np.float64).reshape(7)[:4])
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    Ti = np.zeros((6, 6))
+    Ti[0:3, 3:6] = 0.5 * R.T
+    Ti[3:6, 0:3] = R.T
+    return Ti.T @ H @ Ti

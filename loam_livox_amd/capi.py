@@ -50,6 +50,12 @@ class RegReport(C.Structure):
                 ("lm_iterations_total", C.c_int32), ("accepted", C.c_int32), ("gated", C.c_int32), ("aborted", C.c_int32)]
 
 
+class RegInformation(C.Structure):
+    """ll_reg_information_record"""
+    _fields_ = [("H", C.c_double * 36), ("g", C.c_double * 6), ("cost", C.c_double), ("n_line", C.c_int32), ("n_plane", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SceneAlignParams(C.Structure):
     _fields_ = [("line_res", C.c_float), ("plane_res", C.c_float), ("maximum_icp_iteration", C.c_int32), ("accepted_threshold", C.c_float),
                 ("maximum_residual_block", C.c_int32), ("registrar_init", C.c_int32), ("subsample_seed", C.c_int32)]
@@ -119,6 +125,9 @@ SYMBOLS = {
     "ll_cloud_transform_fe_device": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "ll_reg_set_profiling": (_i32, [_vp, _i32]),
     "ll_reg_kernel_times": (_i32, [_vp, _vp, _vp]),
+    "ll_reg_set_information": (_i32, [_vp, _i32]),
+    "ll_reg_information": (_i32, [_vp, _i32, _vp]),
+    "ll_reg_information_time": (_i32, [_vp, C.POINTER(_f)]),
     "ll_reg_debug_cycles": (_i32, [_vp, _i32, _vp]),
     "ll_reg_debug_worklists": (_i32, [_vp, _i32, _vp]),
     "ll_voxel_create": (_i32, [_i32, _i32, _i32, C.POINTER(_vp)]),

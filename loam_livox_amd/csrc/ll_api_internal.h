@@ -20,6 +20,7 @@
 #include "../../include/loam_livox_hip.h"
 #include "ll_device.h"
 #include "ll_reg_core.h"
+#include "ll_reg_info_core.h"
 #include "ll_cellmap.h"
 #include "ll_voxel.h"
 #include "ll_spin.h"
@@ -134,10 +135,16 @@ struct ll_reg {
     // profiling
     std::vector<hipEvent_t> ev;   // pairs
     std::vector<int> ev_class;
-    float prof_ms[3] = {0, 0, 0};
-    int prof_launches[3] = {0, 0, 0};
+    float prof_ms[4] = {0, 0, 0, 0};  // k-NN + build, solver, finalize, information (class 3: ll_reg_information_time)
+    int prof_launches[4] = {0, 0, 0, 0};
     double *d_pose_tmp = nullptr;
     int uploaded_scans = 0;  // scans covered by the last ll_reg_upload_features
+    // information matrix per scan (ll_reg_set_information): nothing is allocated, launched or copied while the switch is off
+    int info_enable = 0;
+    int info_enqueued = 0;   // the last enqueue launched reg_information_kernel
+    int info_collected = 0;  // ll_reg_collect has run since the last enqueue
+    InfoRecord *d_info = nullptr;     // [max_scans]
+    std::vector<InfoRecord> h_info;   // the last collect's records
 };
 
 // ---------------------------------------------------------------------------------------------------- voxel grid

@@ -116,7 +116,7 @@ extern "C" void ll_reg_destroy(ll_reg *r)
     (void)hipSetDevice(r->device);
     RegDev &d = r->dev;
     void *ptrs[] = {d.state, d.blk_f, d.blk_av, d.blk_id, d.pl_tab, d.blk_flag, d.nn, d.qperm, d.qsorted, d.qperm_c, d.qw, d.ref_q, d.ref_p, d.ref_s, d.blk_flag0, d.work_search, d.work_build, d.work_cnt, d.work_off, d.grp_ctl, d.solve_order, d.grp_part, d.grp_xch, d.blk_l1, d.hash, d.dbg_idx, d.dbg_d2,
-                    r->d_corner, r->d_surf, r->d_nc, r->d_ns, r->d_pose_tmp, r->d_map_tab};
+                    r->d_corner, r->d_surf, r->d_nc, r->d_ns, r->d_pose_tmp, r->d_map_tab, r->d_info};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : r->ev) (void)hipEventDestroy(e);
@@ -154,6 +154,38 @@ extern "C" int ll_reg_set_profiling(ll_reg *r, int32_t enable)
 {
     if (!r) return set_err("ll_reg_set_profiling", "null handle");
     r->profiling = enable ? 1 : 0;
+    return 0;
+}
+
+extern "C" int ll_reg_set_information(ll_reg *r, int32_t enable)
+{
+    if (!r) return set_err("ll_reg_set_information", "null handle");
+    if (enable && !r->d_info) {  // (the first time the switch goes on: a registrar that never asks pays nothing)
+        HC(hipSetDevice(r->device));
+        DM(r->d_info, (size_t)r->max_scans);
+        r->h_info.resize((size_t)r->max_scans);
+    }
+    r->info_enable = enable ? 1 : 0;  // read by the next enqueue
+    return 0;
+}
+
+extern "C" int ll_reg_information(ll_reg *r, int32_t n_scans, ll_reg_information_record *out)
+{
+    static_assert(sizeof(ll_reg_information_record) == sizeof(InfoRecord), "ll_reg_information_record is the device record");
+    if (!r) return set_err("ll_reg_information", "null handle");
+    if (!out) return set_err("ll_reg_information", "null output");
+    if (!r->info_collected) return set_err("ll_reg_information", "no registration has been collected since the last enqueue (call ll_reg_collect first)");
+    if (!r->info_enqueued) return set_err("ll_reg_information", "the last enqueue was made with the information switch off (ll_reg_set_information)");
+    if (n_scans != r->last_n_scans) return set_err("ll_reg_information", "n_scans differs from the last enqueue's");
+    memcpy(out, r->h_info.data(), (size_t)n_scans * sizeof(InfoRecord));
+    return 0;
+}
+
+extern "C" int ll_reg_information_time(ll_reg *r, float *ms)
+{
+    if (!r) return set_err("ll_reg_information_time", "null handle");
+    if (!ms) return set_err("ll_reg_information_time", "null output");
+    *ms = r->prof_ms[3];  // (0 without ll_reg_set_profiling, or when the last collected enqueue had the switch off)
     return 0;
 }
 
@@ -290,6 +322,8 @@ static int reg_begin(ll_reg *r, const ll_reg_params *prm, int *debug = nullptr)
     r->pinned[0].reset();
     r->pinned[1].reset();
     r->pinned_maps.clear();
+    r->info_enqueued = 0;
+    r->info_collected = 0;
     return 0;
 }
 
@@ -340,8 +374,16 @@ static int reg_size_check(const char *where, const ll_reg *r, const ll_reg_param
     return 0;
 }
 
-static int reg_finish(ll_reg *r, int n_scans, PinGuard &pin_guard)
+// gc / gs: the grids every scan ran against, or map_tab: the device table of a map per slot (then gc / gs are not read)
+static int reg_finish(ll_reg *r, int n_scans, PinGuard &pin_guard, const Grid &gc, const Grid &gs, const Grid *map_tab)
 {
+    if (r->info_enable) {
+        // here the states still hold the last iteration's increment and pose_last, and the map snapshots are pinned
+        prof_begin(r, 3);
+        launch_reg_information(r->dev, r->rc, gc, gs, map_tab, r->d_info, n_scans, r->stream);
+        prof_end(r);
+        r->info_enqueued = 1;
+    }
     prof_begin(r, 2);
     launch_reg_finalize(r->dev, r->rc, n_scans, r->stream);
     prof_end(r);
@@ -415,7 +457,7 @@ static int reg_enqueue(const char *where, ll_reg *r, const ll_map *map, int n_sc
             prof_end(r);
         }
     }
-    return reg_finish(r, n_scans, pin_guard);
+    return reg_finish(r, n_scans, pin_guard, mk0.grid, mk1.grid, nullptr);
 }
 
 extern "C" int ll_reg_collect(ll_reg *r, int32_t n_scans, double *poses_curr, double *poses_incre, ll_reg_report *reports,
@@ -425,7 +467,10 @@ extern "C" int ll_reg_collect(ll_reg *r, int32_t n_scans, double *poses_curr, do
     if (n_scans < 1 || n_scans > r->max_scans) return set_err("ll_reg_collect", "n_scans out of range");
     HC(hipSetDevice(r->device));
     HC(hipMemcpyAsync(r->h_state.data(), r->dev.state, (size_t)n_scans * sizeof(RegState), hipMemcpyDeviceToHost, r->stream));
+    if (r->info_enqueued)  // the records ride in the same wait
+        HC(hipMemcpyAsync(r->h_info.data(), r->d_info, (size_t)r->last_n_scans * sizeof(InfoRecord), hipMemcpyDeviceToHost, r->stream));
     HC(hipStreamSynchronize(r->stream));
+    r->info_collected = 1;
     r->pinned[0].reset();  // the solve has left the device: its map snapshots may be recycled
     r->pinned[1].reset();
     r->pinned_maps.clear();
@@ -456,7 +501,7 @@ extern "C" int ll_reg_collect(ll_reg *r, int32_t n_scans, double *poses_curr, do
         }
     }
     if (r->profiling) {
-        for (int k = 0; k < 3; k++) {
+        for (int k = 0; k < 4; k++) {
             r->prof_ms[k] = 0.f;
             r->prof_launches[k] = 0;
         }
@@ -685,7 +730,8 @@ static int reg_enqueue_maps(const char *where, ll_reg *r, const ll_map *const *m
             prof_end(r);
         }
     }
-    return reg_finish(r, n_scans, pin_guard);
+    const Grid none{};
+    return reg_finish(r, n_scans, pin_guard, none, none, r->d_map_tab);
 }
 
 extern "C" int ll_reg_enqueue_fe_maps(ll_reg *r, const ll_map *const *maps, ll_fe *fe, int32_t n_scans, const ll_reg_params *prm,

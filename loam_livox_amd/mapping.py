@@ -14,7 +14,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .api import History_buffer, History_buffer_batch, Livox_laser, Map_buffer, Point_cloud_registration, Spinning_laser, VoxelGrid
+from .api import (History_buffer, History_buffer_batch, Livox_laser, Map_buffer, Point_cloud_registration, Spinning_laser, VoxelGrid,
+                  information_in_pose_frame)
 
 
 def _set_registrar_params(p, *, scan_points, icp_max_iterations, ceres_max_iterations, max_allow_incre_R, max_allow_incre_T, max_allow_final_cost,
@@ -27,6 +28,18 @@ def _set_registrar_params(p, *, scan_points, icp_max_iterations, ceres_max_itera
     # optimization/maximum_residual_blocks (200 in the shipped configs): sub-sampling on a reproducible stream; 0 = keep all
     p.maximum_allow_residual_block = maximum_residual_blocks if maximum_residual_blocks > 0 else scan_points
     p.subsample_seed = subsample_seed if maximum_residual_blocks > 0 else 0
+
+
+def _with_pose_frame(info: dict, pose_last) -> dict:
+    """a registrar's information record plus H_pose: H in the frame of the pose the registration started from (translation, then rotation vector)"""
+    info = dict(info)
+    info["H_pose"] = information_in_pose_frame(info["H"], pose_last)
+    return info
+
+
+def _degenerate_directions(info: dict, min_eigenvalue: float) -> np.ndarray:
+    weak = info["eigenvalues"] < float(min_eigenvalue)
+    return np.ascontiguousarray(info["eigenvectors"][:, weak].T)
 
 
 class Laser_mapping:
@@ -47,7 +60,8 @@ class Laser_mapping:
                  maximum_search_range_corner: float = 100.0, maximum_search_range_surface: float = 100.0,
                  maximum_in_fov_angle: float = 30.0, down_sample_replace: int = 1, cell_map_max_points: int = 1 << 21,
                  loop_closure_if_enable: int = 0, loop_closure: dict | None = None, keep_cell_maps: bool = False,
-                 lidar_type: str = "livox", scan_line: int = 16, minimum_range: float = 0.1, mapping_plane_resolution: float = 0.8):
+                 lidar_type: str = "livox", scan_line: int = 16, minimum_range: float = 0.1, mapping_plane_resolution: float = 0.8,
+                 information: bool = False):
         self.lidar_type = lidar_type
         self._spin = lidar_type != "livox"
         if self._spin:
@@ -64,6 +78,12 @@ class Laser_mapping:
         self._prefetched = None  # (the array object that was prefetched, its time stamp, handle)
         self._scan_points, self._device = scan_points, device
         self.reg = Point_cloud_registration(max_scans=1, max_features=scan_points, device=device)
+        # information: every frame's registration also leaves the Gauss-Newton matrix of its last linearisation (last_information:
+        # Point_cloud_registration.information()'s dict plus H_pose, the same in the pose's own frame); poses are the same bits either way
+        self._information = bool(information)
+        self.last_information = None
+        if self._information:
+            self.reg.set_information(True)
         self.map = Map_buffer(device=device)
         self.vox = (VoxelGrid(scan_points, 1, device=device), VoxelGrid(scan_points, 1, device=device))
         self.history = History_buffer(maximum_history_size, scan_points, line_res, plane_res, device=device)
@@ -122,6 +142,19 @@ class Laser_mapping:
         cloud = self.reg.pointcloudAssociateToMap(full, self.pose) if len(full) else full
         self.keyframes.add_scan(cloud, self.pose, self.m_current_frame_index, history_added=history_added)
         self.loops += self.keyframes.process_waiting()
+
+    def _read_information(self, pose_last) -> None:
+        """the record of the registration just collected, with H in the frame of the pose it started from"""
+        if self._information:
+            self.last_information = _with_pose_frame(self.reg.information(1)[0], pose_last)
+
+    def degenerate_directions(self, min_eigenvalue: float) -> np.ndarray:
+        """The eigenvectors [k, 6] of the last frame's H (solver tangent [d_rot; d_t]) whose eigenvalue lies below min_eigenvalue: the
+        directions the frame's registration left unconstrained.  The caller names the value: rotation and translation rows carry
+        different units, so any built-in threshold would be a guess."""
+        if self.last_information is None:
+            raise RuntimeError("degenerate_directions needs information=True and a registered frame")
+        return _degenerate_directions(self.last_information, min_eigenvalue)
 
     def sync(self) -> None:
         """every frame handed to the cell maps' service thread has been appended (keep_cell_maps in matching mode 0)"""
@@ -194,6 +227,7 @@ class Laser_mapping:
             self._extract(self._fe_pair[other], next_xyzi, next_time_stamp)
             self._prefetched = (next_xyzi, next_time_stamp, self._fe_pair[other], next_scan_id)
         res, pc, _, reps = reg.collect(1)
+        self._read_information(self.pose)
         flags = getattr(reg, "debug_flags", 0)
         if reps[0].aborted:
             self.aborted_solves += 1
@@ -205,6 +239,7 @@ class Laser_mapping:
             reg.set_debug_flags(flags | 32)
             self._enqueue(fe, pose)
             res, pc, _, reps = reg.collect(1)
+            self._read_information(self.pose)  # the repeat's record replaces the aborted one
             reg.set_debug_flags(flags)
         self.last_report = reps[0]
         t1 = time.perf_counter()
@@ -265,6 +300,7 @@ class Laser_mapping:
         reg.m_pose_w_curr = self.pose.copy()
         reg.m_para_buffer_incremental = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)  # a fresh Point_cloud_registration per scan (:1348)
         res = reg.find_out_incremental_transfrom(self.map, corner_stack, surf_stack)
+        self._read_information(self.pose)
         self.last_report = reg.report
         if not res:  # :1413-1416
             return 0
@@ -379,6 +415,10 @@ class Laser_mapping_batch:
         self._scan_points = scan_points
         self.fe = Livox_laser(max_points=scan_points, max_scans=S, device=device, piecewise_number=1)
         self.reg = Point_cloud_registration(max_scans=S, max_features=scan_points, device=device)
+        self._information = bool(a["information"])  # Laser_mapping's: last_information[s] is slot s's record of its last frame
+        self.last_information = [None] * S
+        if self._information:
+            self.reg.set_information(True)
         self.vox = (VoxelGrid(scan_points, S, device=device), VoxelGrid(scan_points, S, device=device))
         self.maps = [Map_buffer(device=device) for _ in range(S)]
         self.batched_history, self.cell_maps, self.cell_matching = bool(batched_history), bool(cell_maps), bool(cell_matching)
@@ -447,6 +487,12 @@ class Laser_mapping_batch:
             self.rounds.close()
         for h in [self.fe, self.reg, self.vox[0], self.vox[1]] + self.maps + ([self.history_batch] if self.batched_history else self.histories):
             h.close()
+
+    def degenerate_directions(self, sequence: int, min_eigenvalue: float) -> np.ndarray:
+        """Laser_mapping.degenerate_directions for one sequence's last frame"""
+        if self.last_information[sequence] is None:
+            raise RuntimeError("degenerate_directions needs information=True and a registered frame of that sequence")
+        return _degenerate_directions(self.last_information[sequence], min_eigenvalue)
 
     def sync(self) -> None:
         """every accepted frame is in the cell maps and their stores are in order (cell_maps=True; otherwise nothing to wait for)"""
@@ -568,6 +614,7 @@ class Laser_mapping_batch:
         maps = [self.maps[s] if active[s] else None for s in range(S)]
         self._enqueue(maps, fi)
         res, pc, _, reps = reg.collect(S)
+        infos = reg.information(S) if self._information else None
         flags = getattr(reg, "debug_flags", 0)
         again = [s for s in range(S) if active[s] and reps[s].aborted]
         self.aborted_solves += len(again)
@@ -577,15 +624,20 @@ class Laser_mapping_batch:
             reg.set_debug_flags(flags | 32)
             self._enqueue([self.maps[s] if s in again else None for s in range(S)], fi)
             res2, pc2, _, reps2 = reg.collect(S)
+            infos2 = reg.information(S) if self._information else None
             reg.set_debug_flags(flags)
             for s in again:
                 res[s], pc[s], reps[s] = res2[s], pc2[s], reps2[s]
+                if infos is not None:
+                    infos[s] = infos2[s]  # the repeat's record replaces the aborted one
         t1 = time.perf_counter()
         jobs = []
         for s in range(S):
             if not active[s]:
                 continue
             self.last_reports[s] = reps[s]
+            if infos is not None:
+                self.last_information[s] = _with_pose_frame(infos[s], self.poses[s])
             out[s] = 1 if res[s] else 0
             if res[s]:  # :1413-1416
                 jobs.append((s, self.poses[s].copy(), pc[s].copy()))

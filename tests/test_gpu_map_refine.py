@@ -1,5 +1,9 @@
 """-m gpu: the key-frame map refinement on the device (api.Map_refine over ll_map_refine_*) against the oracle's VoxelGrid composed with
-the numpy move of tests/map_refine_inputs.py -- float bits, counts and status, no tolerance.  Reads nothing of the reference."""
+the numpy move of tests/map_refine_inputs.py -- float bits, counts and status, no tolerance.  Reads nothing of the reference.
+The ragged set runs the chain at up to 40 selections of filtered clouds; mi.many_selections and mi.last_voxel_at_the_end, stored as
+given, run it past the 256-selection trips of mr_offsets_kernel, with wavefronts of mr_head_kernel over many selections, at the
+selection counts where the sort width changes, at the MR_CHUNK bounds, with non-finite rows inside filtered selections and with no
+sentinel behind the last voxel."""
 import numpy as np
 import pytest
 
@@ -169,6 +173,128 @@ def test_far_from_the_origin(gpu_lib):
             st, want = mi.expected(stored[cid][1], ori[s], opm[s], mi.RUN_LEAF, transform_first)
             assert mr.status[s] == st == 0 and same(clouds[s], want), (raw[cid][0], transform_first)
             assert np.abs(clouds[s][:, :2]).min() > 4900.0
+    mr.close()
+
+
+# ---- where the chain changes form: trips of mr_offsets_kernel, wavefronts of many selections, sort widths, chunk bounds, the keys' end ------
+def stored(store, **kw):
+    """a handle that holds `store` as given (add_stored): id = position"""
+    mr = Map_refine(**kw)
+    for k, cloud in enumerate(store):
+        assert mr.add_stored(cloud) == k
+        assert mr.work().tolist() == ([1, 1, 16 * len(cloud), len(cloud)] if len(cloud) else [0, 0, 0, 0])
+    return mr
+
+
+def assert_run(mr, ids, ori, opm, want, transform_first, what=()):
+    """a run over ids equals want = [(status, cloud)] in bits; -> the clouds"""
+    clouds = mr.refine(ids, ori, opm, mi.RUN_LEAF, transform_first)
+    assert len(clouds) == len(want)
+    for s, (st, cloud) in enumerate(want):
+        assert mr.status[s] == st and same(clouds[s], cloud), (*what, transform_first, s, ids[s])
+    return clouds
+
+
+@pytest.fixture(scope="module")
+def many(gpu_lib):
+    """mi.many_selections, the oracle's results of the 600 in both modes and the conditions they meet -- all before the device is touched --
+    then the set on a handle: made once, shared, not changed"""
+    store, ids, ori, opm = mi.many_selections(83)
+    want = mi.expected_run(store, ids, ori, opm)
+    figures = {tf: mi.many_conditions(store, ids, want[tf]) for tf in (False, True)}
+    mr = stored(store, initial_points=1 << 12)
+    for k, cloud in enumerate(store):                                    # kept as given, non-finite rows included
+        assert same(mr.cloud(k), cloud), k
+    yield dict(mr=mr, store=store, ids=ids, ori=ori, opm=opm, want=want, figures=figures)
+    mr.close()
+
+
+@pytest.mark.parametrize("transform_first", [False, True])
+def test_600_selections_in_one_run(many, transform_first):
+    mr, store, ids, ori, opm = (many[k] for k in ("mr", "store", "ids", "ori", "opm"))
+    print("many_selections:", many["figures"][transform_first])
+    clouds = assert_run(mr, ids, ori, opm, many["want"][transform_first], transform_first)
+    work = mr.work()
+    assert work[0] == 15 and work[1] == 2 and work[3] == sum(len(store[c]) for c in ids)
+    st, want = mi.filtered(np.concatenate(clouds), mi.RUN_LEAF)
+    assert same(mr.merge(mi.RUN_LEAF), want) and mr.merge_status == st
+
+
+@pytest.mark.parametrize("n_sel", [2, 3, 4, 7, 8, 255, 256, 257, 511, 512, 513])
+def test_selection_counts_where_the_sort_width_changes(many, n_sel):
+    """32 + sel_bits key bits are sorted, 2^sel_bits >= n_sel + 1: at 3, 7, 255 and 511 selections the sentinel's low bits are n_sel itself"""
+    mr, ids, ori, opm = (many[k] for k in ("mr", "ids", "ori", "opm"))
+    for transform_first in (False, True):
+        assert_run(mr, ids[:n_sel], ori[:n_sel], opm[:n_sel], many["want"][transform_first][:n_sel], transform_first, (n_sel,))
+
+
+def test_shrinking_back_after_growth_leaves_nothing_behind(many):
+    store, ids, ori, opm = (many[k] for k in ("store", "ids", "ori", "opm"))
+    mr, fresh = stored(store, initial_points=1 << 10), stored(store, initial_points=1 << 10)
+    few = [mi.MANY_2049, 5, mi.MANY_CUBE, mi.MANY_NAN, 0]               # two work items, finite and non-finite rows, handed back, empty
+    for transform_first in (False, True):
+        want5 = [mi.expected(store[c], ori[s], opm[s], mi.RUN_LEAF, transform_first) for s, c in enumerate(few)]
+        assert [st for st, _ in want5] == [0, 0, 1, 2, 0]
+        first = assert_run(mr, few, ori[:5], opm[:5], want5, transform_first, ("before",))
+        grown = assert_run(mr, ids, ori, opm, many["want"][transform_first], transform_first, ("grown",))
+        third = assert_run(mr, few, ori[:5], opm[:5], want5, transform_first, ("after",))
+        alone = fresh.refine(ids, ori, opm, mi.RUN_LEAF, transform_first)
+        assert all(same(a, b) for a, b in zip(first, third)) and all(same(a, b) for a, b in zip(grown, alone))
+        assert np.array_equal(mr.status, [st for st, _ in want5])
+    mr.close()
+    fresh.close()
+
+
+def test_selections_of_one_two_and_four_chunks(many):
+    mr, store, ids, ori, opm = (many[k] for k in ("mr", "store", "ids", "ori", "opm"))
+    at = sorted(mi.MANY_CHUNK_AT)                                        # the selections that hold the 2048-, 2049- and 4096-point clouds
+    mi.packed_voxel_is_one_point(store)                                  # from the oracle: the voxel across the work-item bound is one point
+    for transform_first in (False, True):
+        want = many["want"][transform_first]
+        for s in at:
+            assert want[s][0] == 0 and 0 < len(want[s][1]) <= len(store[ids[s]])
+            assert_run(mr, [ids[s]], ori[s:s + 1], opm[s:s + 1], [want[s]], transform_first, ("alone",))
+            assert mr.work()[3] == len(store[ids[s]])
+        assert_run(mr, [ids[s] for s in at], ori[at], opm[at], [want[s] for s in at], transform_first, ("together",))
+
+
+@pytest.mark.parametrize("cnt", [1, 7, 8, 9, 16])
+def test_last_voxel_ends_at_the_last_key(gpu_lib, cnt):
+    """mr_centroid reads keys eight at a time up to `total`: here the last voxel's cnt keys are the last keys of the chain"""
+    store = mi.last_voxel_at_the_end(cnt)
+    n_finite = sum(mi.finite_count(c) for c in store)
+    assert n_finite == sum(len(c) for c in store) and all(len(c) > 0 for c in store)     # no point is a sentinel ...
+    mr = stored(store, initial_points=1 << 10)
+    for ori, opm in (mi.poses(2, 89), (np.stack([mi.IDENTITY] * 2),) * 2):
+        want = mi.expected_run(store, [0, 1], ori, opm)
+        assert all(st == 0 for tf in want for st, _ in want[tf])                        # ... and no selection is empty or handed back
+        for transform_first in (False, True):
+            assert_run(mr, [0, 1], ori, opm, want[transform_first], transform_first, (cnt,))
+            assert mr.work()[3] == n_finite
+    packed = mi.in_voxel(store[1], mi.LAST_VOXEL_AT)
+    for transform_first in (False, True):                               # under the identity pair the last output row is the packed voxel
+        last = want[transform_first][1][1][-1:]
+        assert packed.sum() == cnt and mi.in_voxel(last, mi.LAST_VOXEL_AT).all()
+        assert np.array_equal(bits(last[:, :3]), bits(mi.filtered(store[1][packed], mi.RUN_LEAF)[1][:, :3]))
+    mr.close()
+
+
+def test_add_cloud_hands_back_non_finite_rows_and_a_run_filters_them(gpu_lib):
+    rng = np.random.default_rng(97)
+    cloud = rng.uniform(-15, 15, (60, 4)).astype(np.float32)
+    cloud[0, :3], cloud[1, :3] = -15.0, 15.0                             # a 30 m extent: 30001^3 > 2^31 leaves of 1 mm
+    bad = np.arange(60) % 7 == 3
+    cloud[bad, rng.integers(0, 3, int(bad.sum()))] = rng.choice(np.array([np.nan, np.inf, -np.inf], np.float32), int(bad.sum()))
+    assert 0 < mi.finite_count(cloud) < 60 and mi.filtered(cloud, 0.001)[0] == 1
+    mr = Map_refine(initial_points=1 << 10)
+    assert mr.add_cloud(np.ones((5, 4), np.float32), mi.ADD_LEAF) == (0, 1, 0)
+    assert mr.add_cloud(cloud, 0.001) == (1, 60, 1)
+    assert same(mr.cloud(1), cloud)
+    ori, opm = mi.poses(2, 101)
+    want = mi.expected_run([np.ones((1, 4), np.float32), cloud], [1, 0], ori, opm)
+    for transform_first in (False, True):
+        assert want[transform_first][0][0] == 0 and 0 < len(want[transform_first][0][1]) <= mi.finite_count(cloud)
+        assert_run(mr, [1, 0], ori, opm, want[transform_first], transform_first)
     mr.close()
 
 

@@ -207,6 +207,32 @@ def test_add_logged_equals_add_cloud_of_the_host_concatenation(gpu_lib, runs):
     ref.close()
 
 
+def test_add_logged_past_256_requests(gpu_lib, runs):
+    """300 requests are 300 selections of one MR_FILTER_ONLY chain: mr_offsets_kernel makes two trips, and the requests that hold points
+    sit at the chain's first and last selection and on both sides of the trip bound"""
+    from loam_livox_amd.api import Map_refine
+    rig, groups, _, _ = runs(3, 32)   # (a run of its own: its groups are consumed here)
+    live = [k for k, (_, w) in enumerate(groups) if w is not None]
+    named = {0: live[:1], 255: live[1:3], 256: live[3:4], 299: live[4:6]}
+    requests = [[groups[k][0] for k in named.get(r, [])] for r in range(300)]
+    wants = [cat([sc for k in named.get(r, []) for sc in groups[k][1]]) for r in range(300)]
+    assert all(len(wants[r]) > 0 for r in named) and sum(len(w) > 0 for w in wants) == 4
+    mr, ref = Map_refine(1 << 12), Map_refine(1 << 12)
+    in_use = int(rig.hb.scan_log_work()[2])
+    ids, kept, status = mr.add_logged(rig.hb, requests, 0.5)
+    work = mr.work().tolist()
+    assert ids.tolist() == list(range(300)) and len(mr) == 300
+    for r, w in enumerate(wants):
+        cid, n_kept, st = ref.add_cloud(w, 0.5)
+        assert (int(ids[r]), int(kept[r]), int(status[r])) == (cid, n_kept, st), r
+        assert (n_kept > 0 and st == 0) if r in named else (n_kept == 0 and st == 2), r
+        assert np.array_equal(bits(mr.cloud(r)), bits(ref.cloud(cid))), (r, "stored cloud in bits")
+    assert work[1] == 1                                                            # one host wait whatever n_req is
+    assert rig.hb.scan_log_work()[2] == in_use - sum(len(groups[k][1]) for ks in named.values() for k in ks)
+    mr.close()
+    ref.close()
+
+
 def test_refusals_leave_both_handles_usable(gpu_lib, cropped):
     from loam_livox_amd.api import History_buffer, History_buffer_batch, Map_refine
     scans_of, poses = cropped

@@ -6,7 +6,10 @@ Affine and move: ll_map_refine_affine and mr_move give, bit for bit, what the re
 time, compiled against oracle/ref_stubs/ll_stub_eigen.h; skipped where the reference is absent) and what the numpy restatement of
 tests/map_refine_inputs.py gives -- the restatement the GPU tier uses.
 Chain: the per-point and per-voxel text of ll_map_refine_core.h, run on the CPU by the driver over the plan the C ABI makes, gives in
-both modes and for merge the oracle's VoxelGrid composed with the numpy move, on the ragged set of clouds."""
+both modes and for merge the oracle's VoxelGrid composed with the numpy move, on the ragged set of clouds -- and on the sets the GPU
+tier runs where the device chain changes form (mi.many_selections, mi.last_voxel_at_the_end): the host loop has no trips, wavefronts or
+sort widths, so what this tier shows of them is that the expected values and the conditions the GPU tier asserts on them hold, and that
+the shared core text agrees with the oracle on selections of finite and non-finite rows."""
 import ctypes as C
 import os
 import re
@@ -258,6 +261,54 @@ def test_driver_runs_clean_under_the_sanitizers(tmp_path, ragged, chain_runs):
         _, status, clouds = run_chain(exe, str(tmp_path), mode, mi.RUN_LEAF, stored, ids, ori, opm)   # (asserts exit status 0, empty stderr)
         assert np.array_equal(status, chain_runs[mode][1])
         assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(clouds, chain_runs[mode][2]))
+
+
+# ------------------------------------------------------------------------------------------------ the sets of the GPU tier's form changes
+@pytest.fixture(scope="module")
+def many():
+    """mi.many_selections and the oracle's results in both modes: made once, shared, not changed"""
+    store, ids, ori, opm = mi.many_selections(83)
+    return store, ids, ori, opm, mi.expected_run(store, ids, ori, opm)
+
+
+def chain_equals(driver, tmp, store, ids, ori, opm, want):
+    for mode in (0, 1):
+        offsets, status, clouds = run_chain(driver, tmp, mode, mi.RUN_LEAF, store, ids, ori, opm)
+        assert offsets[-1] == sum(len(c) for _, c in want[bool(mode)])
+        for s, (st, cloud) in enumerate(want[bool(mode)]):
+            assert status[s] == st and clouds[s].shape == cloud.shape and np.array_equal(bits(clouds[s]), bits(cloud)), (mode, s, ids[s])
+
+
+def test_many_selections_hold_what_the_gpu_tier_rests_on(many):
+    store, ids, _, _, want = many
+    for tf in (False, True):
+        figures = mi.many_conditions(store, ids, want[tf])
+        assert figures["points"] > figures["valid"] > 20000, figures
+    # the sizes the set was built for: tiny clouds, several of 1-3 points, every fifth with finite and non-finite rows
+    tiny = store[:mi.N_TINY]
+    assert all(1 <= len(c) <= 70 for c in tiny) and sorted(len(tiny[k]) for k in mi.TINY_FEW) == [1, 1, 2, 2, 3, 3]
+    assert all((0 < mi.finite_count(c) < len(c)) == (k % 5 == 0) for k, c in enumerate(tiny))
+    assert [len(store[ids[s]]) for s in mi.MANY_FEW_AT] == [1, 2, 3, 1, 2, 3] * 2 + [1, 2, 3, 1]
+    mi.packed_voxel_is_one_point(store)
+
+
+def test_chain_equals_the_oracle_on_many_selections(driver, many, tmp_path):
+    store, ids, ori, opm, want = many
+    chain_equals(driver, str(tmp_path), store, ids, ori, opm, want)
+
+
+@pytest.mark.parametrize("cnt", [1, 7, 8, 9, 16])
+def test_chain_equals_the_oracle_where_the_last_voxel_ends_the_keys(driver, tmp_path, cnt):
+    store = mi.last_voxel_at_the_end(cnt)
+    assert all(mi.finite_count(c) == len(c) > 0 for c in store)
+    for ori, opm in (mi.poses(2, 89), (np.stack([mi.IDENTITY] * 2),) * 2):
+        want = mi.expected_run(store, [0, 1], ori, opm)
+        assert all(st == 0 for tf in want for st, _ in want[tf])        # nothing is empty or handed back: no sentinel in the chain
+        chain_equals(driver, str(tmp_path), store, [0, 1], ori, opm, want)
+    for tf in (False, True):                                            # (the identity pair's results) the last row is the packed voxel
+        last = want[tf][1][1][-1:]
+        assert mi.in_voxel(store[1], mi.LAST_VOXEL_AT).sum() == cnt and mi.in_voxel(last, mi.LAST_VOXEL_AT).all()
+        assert np.array_equal(bits(last[:, :3]), bits(mi.filtered(store[1][mi.in_voxel(store[1], mi.LAST_VOXEL_AT)], mi.RUN_LEAF)[1][:, :3]))
 
 
 # ------------------------------------------------------------------------------------------------ refusals

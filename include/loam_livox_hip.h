@@ -306,7 +306,16 @@ int ll_reg_set_debug_knn_iteration(ll_reg *r, int32_t icp_iteration);
  * Small scans (at most 1024 corner + surface queries in the largest scan of a batch: voxel-filtered clouds, laser_mapping.hpp:1367-1373)
  * take a solver of their own, one wavefront per scan in batches of 512 scans or more and four below (ll_reg_small_kernels.hip):
  * bit 15 = off (such scans on the 512-thread solver: A/B; results agree to rounding, counts exactly); bit 16 / bit 17 = one / four
- * wavefronts per scan whatever the batch size, both = two (tests); bit 18 = its workgroups in scan order instead of longest first (A/B). */
+ * wavefronts per scan whatever the batch size, both = two (tests); bit 18 = its workgroups in scan order instead of longest first (A/B).
+ * Batches whose surface queries take the tile search in every ICP iteration search, from iteration 4 on, only the queries that have
+ * moved out of the order budget of their last search (the others provably keep their list): bit 19 = every query in every iteration
+ * (A/B, tests; the environment switch LL_KNN_SPARSE_FROM moves the first such iteration).  Same result bits either way; the
+ * iteration whose lists ll_reg_debug_knn records (bit 0) searches every query, so that every list is written. */
+/* Test tap: what the solver reads of scan slot `scan` after a registration -- per corner / surface query the neighbour record
+ * {three positions in the cell-sorted map, "five found inside the radius"} (4 ints) and the block flag as built (1 byte).  Unlike the
+ * lists of ll_reg_debug_knn, which only searched queries write, these are the values of the last ICP iteration whichever iteration
+ * established them.  NULL to skip. */
+int ll_reg_debug_blocks(ll_reg *r, int32_t scan, int32_t *corner_nn4, uint8_t *corner_flag, int32_t *surf_nn4, uint8_t *surf_flag);
 
 /* ------------------------------------------------------------------------------------------------------------
  * VoxelGrid  (SURVEY 8(f) row 1).  pcl::VoxelGrid<pcl::PointXYZI> as hku-mars/loam_livox uses it:

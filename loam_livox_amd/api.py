@@ -1343,12 +1343,13 @@ class Point_cloud_registration(_Handle):
                   reuse_from_iter1: bool = False, no_solver_groups: bool = False,
                   test_group_abort: bool = False, no_knn_coop: bool = False, no_knn_tile: bool = False,
                   knn_tile_with_reuse: bool = False, knn_tile_small_batches: bool = False, no_line_cache: bool = False,
-                  no_small_solver: bool = False, small_solver_waves: int = 0, no_solve_order: bool = False):
+                  no_small_solver: bool = False, small_solver_waves: int = 0, no_solve_order: bool = False, no_knn_sparse: bool = False):
         flags = (int(bool(enable)) | (2 if force_general_solver else 0) | (4 if no_knn_reuse else 0) | (8 if reuse_from_iter1 else 0)
                  | (32 if no_solver_groups else 0)
                  | (128 if test_group_abort else 0) | (256 if no_knn_coop else 0) | (512 if no_knn_tile else 0)
                  | (1024 if knn_tile_with_reuse else 0) | (2048 if knn_tile_small_batches else 0) | (4096 if no_line_cache else 0)
-                 | (32768 if no_small_solver else 0) | {0: 0, 1: 65536, 4: 131072, 2: 65536 | 131072}[int(small_solver_waves)] | (262144 if no_solve_order else 0))
+                 | (32768 if no_small_solver else 0) | {0: 0, 1: 65536, 4: 131072, 2: 65536 | 131072}[int(small_solver_waves)] | (262144 if no_solve_order else 0)
+                 | (524288 if no_knn_sparse else 0))
         self.set_debug_flags(flags)
 
     def set_debug_flags(self, flags: int):
@@ -1365,6 +1366,14 @@ class Point_cloud_registration(_Handle):
         si, sd = np.zeros((n_surf, 5), np.int32), np.zeros((n_surf, 5), np.float32)
         check(self.L.ll_reg_debug_knn(self.h, scan, ptr(ci), ptr(cd), ptr(si), ptr(sd)), "ll_reg_debug_knn")
         return ci, cd, si, sd
+
+    def debug_blocks(self, scan: int, n_corner: int, n_surf: int):
+        """what the solver reads of a scan after a registration: (corner nn [n, 4], corner flag [n], surface nn, surface flag) -- the
+        neighbour positions + found flag and the block flag as built, whichever ICP iteration established them"""
+        cn, cf = np.zeros((n_corner, 4), np.int32), np.zeros(n_corner, np.uint8)
+        sn, sf = np.zeros((n_surf, 4), np.int32), np.zeros(n_surf, np.uint8)
+        check(self.L.ll_reg_debug_blocks(self.h, scan, ptr(cn), ptr(cf), ptr(sn), ptr(sf)), "ll_reg_debug_blocks")
+        return cn, cf, sn, sf
 
     def set_profiling(self, enable: bool = True):
         check(self.L.ll_reg_set_profiling(self.h, int(enable)), "ll_reg_set_profiling")

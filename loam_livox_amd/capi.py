@@ -119,6 +119,7 @@ SYMBOLS = {
     "ll_reg_enqueue_fe_merged": (_i32, [_vp, _vp, _vp, _i32, _i32, C.POINTER(RegParams), _vp, _vp, _vp]),
     "ll_reg_collect": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "ll_reg_debug_knn": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "ll_reg_debug_blocks": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "ll_reg_set_debug": (_i32, [_vp, _i32]),
     "ll_reg_set_debug_knn_iteration": (_i32, [_vp, _i32]),
     "ll_cloud_transform": (_i32, [_vp, _vp, _vp, _i32, _vp]),

@@ -432,6 +432,19 @@ static int reg_enqueue(const char *where, ll_reg *r, const ll_map *map, int n_sc
     // 7.2 ms without the tile search
     if (r->rc.knn_tile == 2 && max_ns > LL_KNN_TILE_SEG) r->rc.knn_tile = 1;
     if (r->rc.knn_tile == 2) r->rc.knn_reuse = 0;
+    // ... until the late iterations, where most lists provably hold (profiles/knn_sparse_gate.json: 23 % of the C2 batch's surface queries
+    // have left their order budget at ICP iteration 4, 4 % at iteration 9): from LL_KNN_SPARSE_FROM on, one streaming pass compares every query with
+    // the 16-byte record its last search left and the tile search takes the rest, compacted into whole wavefronts in cell order
+    // (ll_knn_kernels.hip; the round-3 form that lost against searching everything sent them to per-lane ring searches).  The records
+    // lie in the cell order, so they start once it is final (knn_tile_last_sort).  Not where a query changes without moving
+    // (sub-sampling), where the block is more than the list (PCA checks) or where the tile kernel does not transform (motion deblur);
+    // debug bit 19 restores the search of everything (A/B, tests).
+    r->rc.knn_sparse_from = 0;
+    if (r->rc.knn_tile == 2 && !(debug & 524288) && !prm->subsample_seed && !r->rc.check_line_pca && !r->rc.check_plane_pca && !r->rc.if_motion_deblur) {
+        static const int from_env = getenv("LL_KNN_SPARSE_FROM") ? atoi(getenv("LL_KNN_SPARSE_FROM")) : 0;  // (A/B runs of unmodified drivers)
+        const int from = from_env > 0 ? from_env : LL_KNN_SPARSE_FROM;
+        r->rc.knn_sparse_from = from > r->rc.knn_tile_last_sort + 1 ? from : r->rc.knn_tile_last_sort + 1;
+    }
     // Small batches leave most of the chip idle with one workgroup per scan: spread each scan's cost evaluations over a
     // group of LL_GRP workgroups (ll_reg_solve_fast.h, group_*).  Compact scans only; the others run on the group's first.
     // A scan whose records (nearly) fit one CU's LDS cache gains nothing from it and pays ~3.5 us per exchange: voxel-filtered
@@ -925,6 +938,23 @@ extern "C" int ll_reg_debug_knn(ll_reg *r, int32_t scan, int32_t *corner_idx5, f
     D2H_OPT(corner_d25, r->dev.dbg_d2 + base, (size_t)nc * 5, float);
     D2H_OPT(surf_idx5, r->dev.dbg_idx + base + (size_t)r->dev.cap_c * 5, (size_t)ns * 5, int);
     D2H_OPT(surf_d25, r->dev.dbg_d2 + base + (size_t)r->dev.cap_c * 5, (size_t)ns * 5, float);
+    return 0;
+}
+
+extern "C" int ll_reg_debug_blocks(ll_reg *r, int32_t scan, int32_t *corner_nn4, uint8_t *corner_flag, int32_t *surf_nn4, uint8_t *surf_flag)
+{
+    if (!r) return set_err("ll_reg_debug_blocks", "null handle");
+    if (scan < 0 || scan >= r->max_scans) return set_err("ll_reg_debug_blocks", "scan out of range");
+    HC(hipSetDevice(r->device));
+    HC(hipStreamSynchronize(r->stream));
+    int nc = 0, ns = 0;
+    HC(hipMemcpy(&nc, r->dev.n_corner + scan, sizeof(int), hipMemcpyDeviceToHost));
+    HC(hipMemcpy(&ns, r->dev.n_surf + scan, sizeof(int), hipMemcpyDeviceToHost));
+    const size_t base = (size_t)scan * r->dev.cap;
+    D2H_OPT(corner_nn4, reinterpret_cast<const int *>(r->dev.nn + base), (size_t)nc * 4, int);
+    D2H_OPT(corner_flag, r->dev.blk_flag0 + base, (size_t)nc, unsigned char);
+    D2H_OPT(surf_nn4, reinterpret_cast<const int *>(r->dev.nn + base + r->dev.cap_c), (size_t)ns * 4, int);
+    D2H_OPT(surf_flag, r->dev.blk_flag0 + base + r->dev.cap_c, (size_t)ns, unsigned char);
     return 0;
 }
 

@@ -23,6 +23,10 @@ namespace ll {
 #define LL_KNN_TILE_MIN_SURF 1024   // batches whose largest scan has at least this many surface queries (below: the wavefront-per-query search)
 #define LL_KNN_TILE_SEG 24576       // queries one sorting workgroup orders (1024 threads x 24); a multiple of the tile kernel's workgroup
 #define LL_KNN_TILE_MAX_SURF (4 * LL_KNN_TILE_SEG)  // ... and at most this many: larger scans are sorted in segments (Mid-100: three heads)
+#define LL_KNN_SPARSE_FROM 4        // first ICP iteration whose tile search takes only the queries that left their list's order budget
+                                    // (RegConst::knn_sparse_from; profiles/knn_sparse_gate.json: the unsettled share per iteration; measured at B = 256
+                                    //  with three batches in flight: from 5 -> 54.5 / 55.3 k scans/s, from 4 -> 55.8 / 55.9 k, from 3 -> 55.4 / 55.6 k,
+                                    //  every query in every iteration 52.9 / 53.3 k)
 
 // Small scans (voxel-filtered feature clouds: a few hundred residual blocks) have a solver of their own (ll_reg_small_kernels.hip)
 #define LL_SMALL_MAX_BLOCKS 2048     // batches whose largest scan has at most this many corner + surface queries (more than 1024: eight wavefronts per scan)
@@ -142,6 +146,8 @@ struct RegConst {
     int knn_tile;        // surface searches by the tile kernel (ll_knn_tile.h): 0 = off (A/B), 1 = wherever the per-lane search of ALL surface
                          // queries would run (ICP iterations before knn_reuse_from, or every iteration without reuse), 2 = every ICP iteration
                          // (the reuse machinery is then off: a tile search of everything costs less than classifying + searching the lists)
+    int knn_sparse_from; // knn_tile == 2 only: from this ICP iteration on the tile search takes only the surface queries that have moved
+                         // out of their list's order budget (reg_knn_classify_kernel, ll_knn_kernels.hip); 0 = every query in every iteration
     unsigned int subsample_seed;  // a13 (0 = off)
     int max_blocks;               // maximum_allow_residual_block
     float max_d2_line, max_d2_plane;      // compared against fp32 squared distances (PCR:254,353)
@@ -182,6 +188,9 @@ struct RegDev {
     int *work_cnt;                // [B][2 kinds][2] lengths of this ICP iteration's work lists (search, re-sorted) per scan and kind:
                                   // work_search / work_build hold (scan * cap + slot) entries, dense inside the scan-and-kind's own
                                   // segment [scan * cap + kind * cap_c, ...); one atomic per re-query workgroup and list reserves a range
+                                  // (a registration that takes the tile search in every ICP iteration, ll_knn_kernels.hip: [b][0][0] = length of
+                                  // the scan's list of unsettled surface positions in work_build, [b][0][1] = sum of those lengths over the
+                                  // iterations so far, [b][1][iter & 1] = length of the lane kernel's list in work_search)
     int n_chunks;                 // chunks of 256 queries (RQ_THREADS) per (scan, kind): the re-query kernel's grid
     int4 *nn;                     // [B][cap]  neighbour positions (cell-sorted order) + found flag (K6a -> K6b)
     unsigned short *qperm;        // [B][cap_s] surface queries of a scan ordered by the map cell they fall into at ICP iteration 0 (reg_qsort_kernel)

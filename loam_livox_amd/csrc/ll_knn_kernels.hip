@@ -262,15 +262,99 @@ __global__ __launch_bounds__(QC_THREADS) void reg_qsort_corner_kernel(RegDev rd,
 // of their lanes -- nearly all of them queries on the map's outer walls, a centimetre outside the grid: tile_query now adopts the
 // nearest cell for them).
 #define KT_LIST_BUILD_ONLY 0x80000000u  // list entry: slot | this bit when the neighbours are stored and only build_one is left
-template <bool FUSED>
-__global__ __launch_bounds__(KT_THREADS) __attribute__((amdgpu_waves_per_eu(FUSED ? 6 : 5, 8)))  // (the gather of rd.qw costs the sixth)
-void reg_knn_tile_kernel(RegDev rd, RegConst rc, Grid gs, int iter, int surf_blocks)
+// MODE (late ICP iterations of a registration without sub-sampling, PCA checks or motion deblur: rc.knn_sparse_from, ll_api_reg.hip):
+//   KT_DENSE  : every query of the scan, 64 consecutive positions of the cell order per wavefront (the form of every iteration before)
+//   KT_RECORD : the same, and every query leaves its REUSE RECORD {position in the map frame, m_strong} (ll_knn_core.h KnnRef) at its
+//               place in the cell order (the surface half of rd.ref_q): while the query stays within m_strong of that position a
+//               new search returns the same five neighbours in the same order, so rd.nn and rd.blk_flag0 of its slot hold as they are
+//   KT_SPARSE : only the positions reg_knn_classify_kernel has listed (rd.work_build, surface half; rd.work_cnt[4 b]): the queries
+//               that have left their budget, up to 64 list entries per wavefront (the KT_SPARSE index space below).  Searched queries
+//               renew their record.  A lane the tile does not settle gets the budget 0: it is searched in every iteration.
+#define KT_DENSE 0
+#define KT_RECORD 1
+#define KT_SPARSE 2
+// KT_SPARSE takes another index space.  A late iteration lists a few per cent of a scan's queries: a dozen wavefronts per scan, each
+// a chain of two to four rounds.  One workgroup range per scan, as the dense forms have it, spent 75 - 100 us per B = 256 launch on
+// that (17 k workgroups that find nothing between the 2 k that do, and no second wavefront on a SIMD to hide a chain behind).  So the
+// wavefronts of all scans are ONE index space: every workgroup sums the scans' list lengths (p1 <= KT_SPARSE_MAX_SCANS scans from p0
+// on per launch: a table in LDS), and its wavefronts stride over (scan, 64 entries) units, all of them busy from the first cycle.
+// With few entries altogether a unit is 32 or 16 entries (the other lanes idle): more and shorter chains -- fewer cells per
+// wavefront, fewer rounds -- while there are SIMDs left to put them on.  The launch is bound by those chains, not by wavefront
+// slots: four wavefronts per SIMD, 128 registers.
+#define KT_SPARSE_MAX_SCANS 1024
+#define KT_SPARSE_WAVES 4096  // units the launch tries to have at least (the chip holds 6 144 wavefronts of the dense form)
+// p0 = workgroups per scan (KT_SPARSE: first scan of the launch), p1: KT_SPARSE only, scans of the launch
+template <bool FUSED, int MODE>
+__global__ __launch_bounds__(KT_THREADS) __attribute__((amdgpu_waves_per_eu(MODE == KT_SPARSE ? 4 : (FUSED ? 6 : 5), 8)))  // (the gather of rd.qw costs the sixth)
+void reg_knn_tile_kernel(RegDev rd, RegConst rc, Grid gs, int iter, int p0, int p1)
 {
     __shared__ float4 s_tile[KT_THREADS / 64][LL_TILE_CAP + 4];
-    const int bid = blockIdx.x;
-    const int b = bid / surf_blocks, sblk = bid - b * surf_blocks;
+    __shared__ int s_off[MODE == KT_SPARSE ? KT_SPARSE_MAX_SCANS + 1 : 1];  // KT_SPARSE: first unit of every scan of this launch, and the number of units
+    __shared__ int s_part[2][KT_THREADS / 64];
+    int unit = 0, n_units = 0, E = 64;
+    if (MODE == KT_SPARSE) {
+        constexpr int PER = KT_SPARSE_MAX_SCANS / KT_THREADS;
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        int cnt[PER], sum = 0;
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            const int sc = tid * PER + k;
+            cnt[k] = sc < p1 ? rd.work_cnt[4 * (p0 + sc)] : 0;
+            sum += cnt[k];
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+        if (lane == 0) s_part[0][wave] = sum;
+        __syncthreads();
+        int total = 0;
+        for (int w = 0; w < KT_THREADS / 64; w++) total += s_part[0][w];
+        if (total == 0) return;  // (uniform)
+        E = total >= 64 * KT_SPARSE_WAVES ? 64 : (total >= 32 * KT_SPARSE_WAVES ? 32 : 16);  // entries per unit
+        int units = 0;
+#pragma unroll
+        for (int k = 0; k < PER; k++) units += (cnt[k] + E - 1) / E;
+        int incl = units;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int y = __shfl_up(incl, off);
+            if (lane >= off) incl += y;
+        }
+        if (lane == 63) s_part[1][wave] = incl;
+        __syncthreads();
+        int base = incl - units;
+        for (int w = 0; w < wave; w++) base += s_part[1][w];
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            const int sc = tid * PER + k;
+            if (sc < p1) s_off[sc] = base;
+            base += (cnt[k] + E - 1) / E;
+        }
+        if (tid == KT_THREADS - 1) s_off[p1] = base;
+        __syncthreads();
+        n_units = s_off[p1];
+        unit = (int)blockIdx.x * (KT_THREADS / 64) + wave;  // (uniform per wavefront)
+        if (unit >= n_units) return;
+    }
+    do {
+    int b, i;  // the scan, and the lane's position in its cell order
+    bool valid;
+    if (MODE == KT_SPARSE) {
+        int lo = 0, hi = p1;  // the scan of this unit: the last one with s_off[scan] <= unit (scans without entries tie with their successor)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_off[mid] <= unit) lo = mid; else hi = mid;
+        }
+        b = p0 + lo;
+        const int lane = threadIdx.x & 63, at = (unit - s_off[lo]) * E + lane;
+        valid = lane < E && at < rd.work_cnt[4 * b];
+        i = valid ? rd.work_build[(size_t)b * rd.cap + rd.cap_c + at] : 0;
+    } else {
+        const int bid = blockIdx.x;
+        b = bid / p0;
+        i = (bid - b * p0) * KT_THREADS + threadIdx.x;
+        valid = false;  // (set behind the loads)
+    }
     const RegState *st = rd.state + b;
-    const int i = sblk * KT_THREADS + threadIdx.x;  // position in the scan's cell order
     // The order entry and the sorted feature are read side by side (round 5: order -> feature gather, two dependent round trips), with a
     // clamped index ahead of the bounds test (the arrays hold cap_s entries per scan).  (Hoisting the pose and the done / count words
     // into the same batch with explicit scalar loads was measured: no change at six wavefronts per SIMD.)
@@ -279,9 +363,13 @@ void reg_knn_tile_kernel(RegDev rd, RegConst rc, Grid gs, int iter, int surf_blo
     const int pq = (int)rd.qperm[(size_t)b * rd.cap_s + ic];
     float4 feat = make_float4(0.f, 0.f, 0.f, 0.f);
     if (FUSED) feat = rd.qsorted[(size_t)b * rd.cap_s + ic];
-    if (done || (i & ~63) >= nS) return;  // (whole wavefronts)
+    if (MODE == KT_SPARSE) {
+        if (done) continue;  // (its list is empty anyway: the classification pass skips it)
+    } else {
+        if (done || (i & ~63) >= nS) return;  // (whole wavefronts)
+        valid = i < nS;
+    }
     const size_t sb = (size_t)b * rd.cap;
-    const bool valid = i < nS;
     const bool compact = !rc.force_general && padded_block_count(nC, nS) <= LL_TABLE_MAX_BLOCKS;  // scan_is_compact
 #ifdef LL_TILE_TIMING
     // instrumented build: wall clocks of this wavefront per phase, added to the scan's RegState::dbg_cycles by lane 0 --
@@ -293,7 +381,8 @@ void reg_knn_tile_kernel(RegDev rd, RegConst rc, Grid gs, int iter, int surf_blo
     long long tw = t_begin;
 #endif
     // segment base + index in the segment; the segment is the same for the whole wavefront (LL_KNN_TILE_SEG is a multiple of 64): scalar
-    const int seg_base = (__builtin_amdgcn_readfirstlane(i) / LL_KNN_TILE_SEG) * LL_KNN_TILE_SEG;
+    // (KT_SPARSE: scans of one segment only)
+    const int seg_base = MODE == KT_SPARSE ? 0 : (__builtin_amdgcn_readfirstlane(i) / LL_KNN_TILE_SEG) * LL_KNN_TILE_SEG;
     const int q = valid ? seg_base + pq : 0;
     const int slot = rd.cap_c + q;
     float4 pw;
@@ -338,6 +427,15 @@ void reg_knn_tile_kernel(RegDev rd, RegConst rc, Grid gs, int iter, int surf_blo
         LL_TT(10, tw);
     }
     if (listed && !fin && FUSED) rd.qw[sb + slot] = pw;
+    if (MODE != KT_DENSE && valid) {
+        float m_strong = 0.0f;
+        if (fin) {
+            KnnRef ref;
+            knn5_make_ref(r, pw.x, pw.y, pw.z, max_d2, ref);
+            m_strong = ref.m_strong;
+        }
+        rd.ref_q[sb + rd.cap_c + i] = make_float4(pw.x, pw.y, pw.z, m_strong);
+    }
     const unsigned long long lm = __ballot(listed);
     if (lm) {  // (uniform) one atomic per wavefront reserves its entries
         const int lane = threadIdx.x & 63;
@@ -356,6 +454,72 @@ void reg_knn_tile_kernel(RegDev rd, RegConst rc, Grid gs, int iter, int surf_blo
     if ((threadIdx.x & 63) == 0 && LL_TILE_TIMING != 2)
         for (int k_ = 0; k_ < 16; k_++) atomicAdd((unsigned long long *)&rd.state[b].dbg_cycles[k_], (unsigned long long)tt[k_]);
 #endif
+    } while (MODE == KT_SPARSE && (unit += (int)gridDim.x * (KT_THREADS / 64)) < n_units);
+}
+
+// Which surface queries the tile search of this ICP iteration has to take (rc.knn_sparse_from): one streaming pass over the scan's
+// cell order.  Per position: the sorted feature through the current pose exactly as reg_knn_tile_kernel<true, ..> transforms it, its
+// displacement from the reuse record left at that position (knn5_ref_delta), and the test against the record's order budget
+// m_strong.  Inside the budget a new search would return the list the slot already holds (ll_knn_core.h KnnRef) and nothing is
+// written; every other position -- a non-finite displacement too -- is appended to the scan's list (rd.work_build, surface half;
+// counter rd.work_cnt[4 b], cleared by the lane kernel of the iteration before).  One workgroup per KS_PER x KS_THREADS consecutive
+// positions and one reservation per workgroup, its entries in cell order, so 64 neighbouring entries still share map cells.  The
+// order of the workgroups' ranges is the order their atomics were served in; results go to each query's own slot and do not depend on it.
+#define KS_THREADS 256
+#define KS_PER 4
+__global__ __launch_bounds__(KS_THREADS) void reg_knn_classify_kernel(RegDev rd)
+{
+    __shared__ int s_cnt[KS_PER * (KS_THREADS / 64)];  // [slice * waves + wave]
+    __shared__ int s_base;
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const RegState *st = rd.state + b;
+    if (st->done) return;
+    const int nS = rd.n_surf[b];
+    const int p0 = (int)blockIdx.x * KS_PER * KS_THREADS;
+    if (p0 >= nS) return;
+    const size_t sb = (size_t)b * rd.cap;
+    float4 ft[KS_PER], rq[KS_PER];
+#pragma unroll
+    for (int u = 0; u < KS_PER; u++) {  // (all loads in flight together)
+        const int pos = p0 + u * KS_THREADS + tid;
+        const int pc = pos < nS ? pos : nS - 1;
+        ft[u] = rd.qsorted[(size_t)b * rd.cap_s + pc];
+        rq[u] = rd.ref_q[sb + rd.cap_c + pc];
+    }
+    unsigned long long m[KS_PER];
+    bool open[KS_PER];
+#pragma unroll
+    for (int u = 0; u < KS_PER; u++) {
+        const int pos = p0 + u * KS_THREADS + tid;
+        float pw[3];
+        transform_plain(st, ft[u], pw);
+        KnnRef ref;
+        ref.qx = rq[u].x;
+        ref.qy = rq[u].y;
+        ref.qz = rq[u].z;
+        const float delta = knn5_ref_delta(ref, pw[0], pw[1], pw[2]);  // NaN for a non-finite query: listed
+        open[u] = pos < nS && !(delta < rq[u].w);
+        m[u] = __ballot(open[u]);
+        if (lane == 0) s_cnt[u * (KS_THREADS / 64) + wave] = (int)__popcll(m[u]);
+    }
+    __syncthreads();
+    int off[KS_PER], total = 0;
+#pragma unroll
+    for (int u = 0; u < KS_PER; u++) {
+        off[u] = 0;
+        for (int w = 0; w < KS_THREADS / 64; w++) {
+            const int c = s_cnt[u * (KS_THREADS / 64) + w];
+            if (w == wave) off[u] = total;  // everything in the slices before, then the earlier wavefronts of this one
+            total += c;
+        }
+    }
+    if (total == 0) return;  // (uniform)
+    if (tid == 0) s_base = atomicAdd(&rd.work_cnt[4 * b], total);
+    __syncthreads();
+    int *list = rd.work_build + sb + rd.cap_c + s_base;
+#pragma unroll
+    for (int u = 0; u < KS_PER; u++)
+        if (open[u]) list[off[u] + (int)__popcll(m[u] & ((1ull << lane) - 1ull))] = p0 + u * KS_THREADS + tid;
 }
 
 // What the tile kernel does not do.  First corner_blocks workgroups per scan (scan fastest): the scan's CORNER queries, 64 per wavefront in
@@ -442,7 +606,13 @@ __global__ __launch_bounds__(KL_THREADS) void reg_knn_lane_kernel(RegDev rd, Reg
     if (rd.state[b].done) return;
     const size_t sb = (size_t)b * rd.cap;
     const int n = rd.work_cnt[4 * b + 2 + (iter & 1)];
-    if (lblk == 0 && threadIdx.x == 0) rd.work_cnt[4 * b + 2 + ((iter & 1) ^ 1)] = 0;  // the other counter, for the next ICP iteration's tile kernel
+    if (lblk == 0 && threadIdx.x == 0) {
+        rd.work_cnt[4 * b + 2 + ((iter & 1) ^ 1)] = 0;  // the other counter, for the next ICP iteration's tile kernel
+        // ... and the length of the list its classification pass appends to: this iteration's has been read (it is added to the next
+        // word, which nothing else uses in a registration that takes the tile search in every iteration: the tap of ll_reg_debug_worklists)
+        rd.work_cnt[4 * b + 1] += rd.work_cnt[4 * b];
+        rd.work_cnt[4 * b] = 0;
+    }
     if (n <= KL_COOP_PER * list_blocks) {
         for (int k = lblk; k < n; k += list_blocks) {
             const unsigned int e = (unsigned int)rd.work_search[sb + rd.cap_c + k];
@@ -503,10 +673,30 @@ void launch_reg_knn_tile(const RegDev &rd, const RegConst &rc, const Grid &gc, c
     // appends to, so only a registration's first search needs a memset (ten fill launches per registration were 1 % of a step)
     if (iter == 0) (void)hipMemsetAsync(rd.work_cnt, 0, (size_t)n_scans * 4 * sizeof(int), s);
     if (fused) {
-        hipLaunchKernelGGL(reg_knn_tile_kernel<true>, dim3((unsigned int)(sbk * n_scans)), dim3(KT_THREADS), 0, s, rd, rc, gs, iter, sbk);
+        // late iterations (rc.knn_sparse_from, set by the caller for fused batches only): the iteration before the first sparse one
+        // leaves every query's reuse record, from then on a classification pass lists the queries whose list may have changed and
+        // the tile search takes those alone (the grid covers the worst case: every query listed)
+        const dim3 tgrid((unsigned int)(sbk * n_scans)), tblock(KT_THREADS);
+        // (the ICP iteration whose neighbour lists the debug tap records searches every query, so that every list is written: in the
+        //  record-writing form when it is a late one -- the records it renews are as good as any, and no result bit depends on the form)
+        const bool tap = rc.debug_knn && iter == rc.debug_knn_iter;
+        if (rc.knn_sparse_from > 0 && iter >= rc.knn_sparse_from && !tap) {
+            hipLaunchKernelGGL(reg_knn_classify_kernel, dim3((unsigned int)((max_ns + KS_PER * KS_THREADS - 1) / (KS_PER * KS_THREADS)), (unsigned int)n_scans),
+                               dim3(KS_THREADS), 0, s, rd);
+            for (int scan0 = 0; scan0 < n_scans; scan0 += KT_SPARSE_MAX_SCANS) {
+                const int ns = n_scans - scan0 < KT_SPARSE_MAX_SCANS ? n_scans - scan0 : KT_SPARSE_MAX_SCANS;
+                // (every query listed: sbk workgroups' worth of units per scan; beyond 2 048 workgroups -- more wavefronts than the chip holds -- they stride)
+                const long long worst = (long long)sbk * ns;
+                hipLaunchKernelGGL((reg_knn_tile_kernel<true, KT_SPARSE>), dim3((unsigned int)(worst < 2048 ? worst : 2048)), tblock, 0, s, rd, rc, gs, iter, scan0, ns);
+            }
+        } else if (rc.knn_sparse_from > 0 && iter >= rc.knn_sparse_from - 1) {
+            hipLaunchKernelGGL((reg_knn_tile_kernel<true, KT_RECORD>), tgrid, tblock, 0, s, rd, rc, gs, iter, sbk, 0);
+        } else {
+            hipLaunchKernelGGL((reg_knn_tile_kernel<true, KT_DENSE>), tgrid, tblock, 0, s, rd, rc, gs, iter, sbk, 0);
+        }
         hipLaunchKernelGGL(reg_knn_lane_kernel<true>, dim3((unsigned int)((cb + lb) * n_scans)), dim3(KL_THREADS), 0, s, rd, rc, gc, gs, iter, n_scans, cb, lb);
     } else {
-        hipLaunchKernelGGL(reg_knn_tile_kernel<false>, dim3((unsigned int)(sbk * n_scans)), dim3(KT_THREADS), 0, s, rd, rc, gs, iter, sbk);
+        hipLaunchKernelGGL((reg_knn_tile_kernel<false, KT_DENSE>), dim3((unsigned int)(sbk * n_scans)), dim3(KT_THREADS), 0, s, rd, rc, gs, iter, sbk, 0);
         hipLaunchKernelGGL(reg_knn_lane_kernel<false>, dim3((unsigned int)((cb + lb) * n_scans)), dim3(KL_THREADS), 0, s, rd, rc, gc, gs, iter, n_scans, cb, lb);
     }
 }

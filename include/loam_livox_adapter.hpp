@@ -35,6 +35,10 @@
 extern "C" {
 int ll_reg_set_information(ll_reg *r, int32_t enable) __attribute__((weak));
 int ll_reg_information(ll_reg *r, int32_t n_scans, ll_reg_information_record *out) __attribute__((weak));
+// ... and the deskewed clouds (if_undistore = 1): used only by callers that ask for them
+int ll_reg_interpolation(ll_reg *r, int32_t n_scans, double *theta, double *omega_hat9, double *pose_last7, double *pose_incre7) __attribute__((weak));
+int ll_cloud_undistort(ll_reg *r, int32_t slot, const float *in_xyzi, float *out_xyzi, int32_t n) __attribute__((weak));
+int ll_history_set_undistort(ll_history *h, ll_reg *r, int32_t slot) __attribute__((weak));
 }
 
 // The registrar's pose members (m_q_w_curr, m_t_w_curr, m_q_w_last, m_t_w_last, m_q_w_incre, m_t_w_incre,
@@ -596,6 +600,13 @@ class History_buffer {
     // The add-frame rule (laser_mapping.hpp:1439-1451) reads the node's m_q_w_curr / m_t_w_curr, which is still the pose
     // BEFORE the registration whose result add() receives: hand it over first (applies to the next add only).
     void set_gate_pose(const double pose_before_registration[7]) { check(ll_history_set_gate_pose(h_.get(), pose_before_registration), "ll_history_set_gate_pose"); }
+    // g_if_undistore = 1 for the next add() of clouds (laser_mapping.hpp:1424,1430): it moves them with the pose interpolated at every
+    // point's time stamp, from the registration `reg` (Point_cloud_registration::handle()) collected last; `pose` keeps gating.
+    void set_undistort(ll_reg *reg, int slot = 0)
+    {
+        if (!&ll_history_set_undistort) throw std::runtime_error("set_undistort: this program is linked against a library without ll_history_set_undistort");
+        check(ll_history_set_undistort(h_.get(), reg, slot), "ll_history_set_undistort");
+    }
     // update_buff_for_matching(): concatenation of the history -> VoxelGrid -> search grids of `map`
     void refresh(ll_map *map, int64_t *n_corner = nullptr, int64_t *n_surf = nullptr)
     {
@@ -1402,6 +1413,7 @@ class Point_cloud_registration : public Point_cloud_registration_fields {
         int32_t ret = 0;
         check(ll_reg_collect(reg_.get(), 1, m_para_buffer_RT, m_para_buffer_incremental, &rep, &ret), "ll_reg_collect");
         m_information_valid = 0;
+        m_interp_valid = 0;
         if (m_if_compute_information) {  // (no device work: the records came back with the collect)
             check(ll_reg_information(reg_.get(), 1, &m_information_record), "ll_reg_information");
             m_information_valid = 1;
@@ -1420,13 +1432,40 @@ class Point_cloud_registration : public Point_cloud_registration_fields {
 
     // void pointAssociateToMap(pi, po, interpolate_s = 1.0, if_undistore = 0), PCR:622-661.  The node calls it per point
     // with g_if_undistore == 0 (laser_mapping.hpp:80, 1424, 1430): p_w = q_w_curr * p + t_w_curr in double, stored to
-    // float, with Eigen's rotation formula  v + w (2 q x v) + q x (2 q x v).  The Rodrigues-interpolated form needs the
-    // increment of the registration in progress and lives on the device only (if_undistore != 0 throws).
+    // float, with Eigen's rotation formula  v + w (2 q x v) + q x (2 q x v).  The Rodrigues-interpolated form (PCR:633-654,
+    // if_undistore != 0 with m_if_motion_deblur and interpolate_s != 1) runs on the host with the state of the last registration,
+    // fetched once per registration (ll_reg_interpolation): the arithmetic of ll_reg_core.h point_to_map_undistort.
     template <class P>
     void pointAssociateToMap(P const *const pi, P *const po, double interpolate_s = 1.0, int if_undistore = 0)
     {
-        if (!(m_if_motion_deblur == 0 || if_undistore == 0 || interpolate_s == 1.0))
-            throw std::runtime_error("pointAssociateToMap: the motion-deblur interpolation (PCR:633-654) is only available inside the registrar");
+        if (!(m_if_motion_deblur == 0 || if_undistore == 0 || interpolate_s == 1.0)) {
+            fetch_interpolation();
+            const double s = interpolate_s;
+            const double T[3] = {m_interp_incre[4] * (s * 1.0), m_interp_incre[5] * (s * 1.0), m_interp_incre[6] * (s * 1.0)};  // PCR:641
+            const double th = m_interp_theta * s;
+            const double sn = std::sin(th), cs1 = 1.0 - std::cos(th);
+            const double pc[3] = {(double)pi->x, (double)pi->y, (double)pi->z};
+            double inner[3];
+            for (int i = 0; i < 3; i++) {  // PCR:642-645
+                double acc = 0.0;
+                for (int j = 0; j < 3; j++) {
+                    const double rij = ((i == j) ? 1.0 : 0.0) + sn * m_interp_hat[i * 3 + j] + cs1 * m_interp_hat_sq[i * 3 + j];
+                    acc += rij * pc[j];
+                }
+                inner[i] = acc + T[i];
+            }
+            const double *q = m_interp_last;  // PCR:646
+            double uv[3] = {q[1] * inner[2] - q[2] * inner[1], q[2] * inner[0] - q[0] * inner[2], q[0] * inner[1] - q[1] * inner[0]};
+            uv[0] += uv[0];
+            uv[1] += uv[1];
+            uv[2] += uv[2];
+            const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
+            po->x = (float)((inner[0] + q[3] * uv[0] + c[0]) + q[4]);
+            po->y = (float)((inner[1] + q[3] * uv[1] + c[1]) + q[5]);
+            po->z = (float)((inner[2] + q[3] * uv[2] + c[2]) + q[6]);
+            po->intensity = pi->intensity;
+            return;
+        }
         const double qx = m_q_w_curr.x(), qy = m_q_w_curr.y(), qz = m_q_w_curr.z(), qw = m_q_w_curr.w();
         const double v[3] = {(double)pi->x, (double)pi->y, (double)pi->z};
         double uv[3] = {qy * v[2] - qz * v[1], qz * v[0] - qx * v[2], qx * v[1] - qy * v[0]};
@@ -1442,18 +1481,45 @@ class Point_cloud_registration : public Point_cloud_registration_fields {
 
     // unsigned int pointcloudAssociateToMap(pc_in, pt_out, if_undistore = 0), PCR:673-685
     template <class Cloud>
-    unsigned int pointcloudAssociateToMap(const Cloud &pc_in, Cloud &pt_out, int /*if_undistore*/ = 0)
+    unsigned int pointcloudAssociateToMap(const Cloud &pc_in, Cloud &pt_out, int if_undistore = 0)
     {
         ll_reg *reg = registrar(max_features);
         pose_from_members();
         const std::vector<float> in = cloud_to_xyzi(pc_in);
         std::vector<float> out(in.size());
+        if (if_undistore != 0 && m_if_motion_deblur != 0) {  // PCR:627: every point with the pose interpolated at its time stamp
+            if (!&ll_cloud_undistort) throw std::runtime_error("pointcloudAssociateToMap: this program is linked against a library without ll_cloud_undistort");
+            check(ll_cloud_undistort(reg, 0, in.data(), out.data(), (int)(in.size() / 4)), "ll_cloud_undistort");
+            xyzi_to_cloud(out.data(), (int)(in.size() / 4), pt_out);
+            return (unsigned int)(in.size() / 4);
+        }
         check(ll_cloud_transform(reg, in.data(), out.data(), (int)(in.size() / 4), m_para_buffer_RT), "ll_cloud_transform");
         xyzi_to_cloud(out.data(), (int)(in.size() / 4), pt_out);
         return (unsigned int)(in.size() / 4);
     }
 
+    // the registrar this object registers with (History_buffer::set_undistort); null before the first call that needs one
+    ll_reg *handle() { return reg_.get(); }
+
    private:
+    // m_interpolatation_theta / _omega_hat / _omega_hat_sq_2 (PCR:58,66-68), m_q_w_last / m_t_w_last and the increment of the last
+    // collected registration, fetched by the first per-point call after it
+    double m_interp_theta = 0.0, m_interp_hat[9] = {}, m_interp_hat_sq[9] = {}, m_interp_last[7] = {0, 0, 0, 1, 0, 0, 0}, m_interp_incre[7] = {0, 0, 0, 1, 0, 0, 0};
+    int m_interp_valid = 0;
+    void fetch_interpolation()
+    {
+        if (m_interp_valid) return;
+        if (!&ll_reg_interpolation) throw std::runtime_error("pointAssociateToMap: this program is linked against a library without ll_reg_interpolation");
+        if (!reg_) throw std::runtime_error("pointAssociateToMap: if_undistore needs a registration (find_out_incremental_transfrom) first");
+        check(ll_reg_interpolation(reg_.get(), 1, &m_interp_theta, m_interp_hat, m_interp_last, m_interp_incre), "ll_reg_interpolation");
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                double a = 0;
+                for (int k = 0; k < 3; k++) a += m_interp_hat[i * 3 + k] * m_interp_hat[k * 3 + j];
+                m_interp_hat_sq[i * 3 + j] = a;
+            }
+        m_interp_valid = 1;
+    }
     void pose_from_members()
     {
         to_pose7(m_q_w_curr, m_t_w_curr, m_para_buffer_RT);

@@ -396,6 +396,13 @@ int ll_history_add_voxel(ll_history *h, ll_voxel *vox_corner, ll_voxel *vox_surf
  * ll_history_add* call (it applies to the next add only); without it the registered pose gates as well, which gives the
  * same pushes as long as both steps are 0.0 (the reference's fixed values). */
 int ll_history_set_gate_pose(ll_history *h, const double pose[7]);
+/* g_if_undistore = 1 for the next ll_history_add / _add_fe / _add_voxel only (laser_mapping.hpp:1424,1430:
+ * pointAssociateToMap( ..., refine_blur( intensity ), g_if_undistore ) on both down-sampled clouds): that add moves its two clouds with
+ * the state slot `slot` of r's last collected registration left (see "Deskewed clouds" below) instead of with `pose`; `pose` still
+ * serves the add-frame rule and the cell maps' bookkeeping.  The state is copied on the device into memory of this handle when this
+ * is called, so r may be enqueued again at once; the host waits for nothing.  ll_history_add_spin refuses an add after it (and
+ * drops it): the spinning extractor's intensity is no time stamp (laser_feature_extractor.hpp:502). */
+int ll_history_set_undistort(ll_history *h, ll_reg *r, int32_t slot);
 int ll_history_refresh(ll_history *h, ll_map *map, int64_t *n_map_corner, int64_t *n_map_surf);
 int32_t ll_history_size(const ll_history *h);
 /* the match buffer clouds of the last refresh (host copy, for inspection / tests): returns the number of points written */
@@ -928,6 +935,37 @@ int ll_cloud_transform(ll_reg *r, const float *in_xyzi, float *out_xyzi, int32_t
  * be exceeded. */
 int ll_cloud_transform_fe_device(ll_reg *r, ll_fe *fe, int32_t n_scans, int32_t kind, const int32_t *accept, const double *poses7,
                                  float *dev_out_xyzi, int64_t capacity_points, int64_t *n_points);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Deskewed clouds: pointAssociateToMap / pointcloudAssociateToMap with if_undistore = 1
+ * (point_cloud_registration.hpp:622-661, 673-685; the node's g_if_undistore = 1, laser_mapping.hpp:1424,1430,1442,1582,1587).
+ * Every point (x, y, z, time stamp) moves with the pose interpolated at its time stamp: s = refine_blur (:128-141, float),
+ * s == 1 or if_motion_deblur == 0 -> q_curr p + t_curr (:627-630); otherwise (:641-646)
+ *     p_w = q_last ( (I + sin(s theta) hat + (1 - cos(s theta)) hat^2) p + s t_incre ) + t_last,   double math, float store,
+ * with theta / hat from compute_interpolatation_rodrigue (:607-620) of the registration's increment.  A time stamp below
+ * minimum_pt_time_stamp gives s < 0, which is not clamped (the reference extrapolates); a non-finite s counts as 1 (:137).
+ * The intensity is copied (:659).  These are the numbers the registrar's own searches moved the features with (:247-248),
+ * operation for operation.
+ *
+ * All of them use the state the last COLLECTED registration on r left in slot `slot` (scan b of the batch), and are refused
+ * before a first ll_reg_collect, while an enqueue is uncollected, and for slots beyond that registration's n_scans.
+ *   if_motion_deblur == 0 in that registration: the plain transform with the slot's pose_curr, bit for bit (:627).
+ *   a gated slot (report.gated: :199, nothing was estimated): identity increment, theta 0, zero matrices -- the plain
+ *     transform with pose_last, bit for bit.
+ *   a rejected slot (result 0, :561-573): pose_curr = pose_last, and the increment of its last ICP iteration stays in place, as
+ *     in the reference object.  The node never reaches its "Add new frame" for such a scan (laser_mapping.hpp:1405-1411).
+ *
+ * ll_reg_interpolation: m_interpolatation_theta, m_interpolatation_omega_hat (row-major 3x3), m_q_w_last / m_t_w_last and
+ * m_q_w_incre / m_t_w_incre (x y z w, t) of slots 0 .. n_scans-1; any output may be NULL.  No device work.
+ * ll_cloud_undistort: pointcloudAssociateToMap( in, out, 1 ) (:673-685) for a host cloud. */
+int ll_reg_interpolation(ll_reg *r, int32_t n_scans, double *theta, double *omega_hat9, double *pose_last7, double *pose_incre7);
+int ll_cloud_undistort(ll_reg *r, int32_t slot, const float *in_xyzi, float *out_xyzi, int32_t n);
+/* ll_cloud_transform_fe_device with if_undistore = 1: slot b's selection of `kind` (0 corner, 1 surface, 2 the full selection,
+ * laser_feature_extractor.hpp:246,255: intensity = time stamp) moves with slot b's state -- there is no poses7 -- and is appended
+ * to dev_out_xyzi from *n_points on, in one launch for the batch.  Fails, leaving *n_points and the buffer untouched, if the
+ * capacity would be exceeded. */
+int ll_cloud_undistort_fe_device(ll_reg *r, ll_fe *fe, int32_t n_scans, int32_t kind, const int32_t *accept, float *dev_out_xyzi,
+                                 int64_t capacity_points, int64_t *n_points);
 
 /* HIP-event timing of the kernels launched by the last enqueue/solve on this handle (milliseconds, summed
  * over launches) and launch counts: [0] knn+block-build, [1] solver, [2] finalize. Enabled by

@@ -143,6 +143,14 @@ class Livox_laser(_Handle):
         return dict(corner_idx=ci[:nc.value].copy(), surf_idx=si[:ns.value].copy(), full_idx=fi[:nf.value].copy(),
                     pc_corners=cc[:nc.value].copy(), pc_surface=sc[:ns.value].copy())
 
+    def full_selection(self, scan: int = 0) -> np.ndarray:
+        """the positions of the full cloud select_batch() left in slot `scan` (ascending), and nothing else: one count and one index array
+        cross the bus (ll_fe_selection with its other outputs NULL)"""
+        fi = np.zeros(self.params.max_points, np.int32)
+        nf = C.c_int32(0)
+        check(self.L.ll_fe_selection(self.h, int(scan), None, None, None, None, ptr(fi), C.byref(nf), None, None), "ll_fe_selection")
+        return fi[:nf.value].copy()
+
     def pts_info(self, scan: int = 0):
         """m_pts_info_vec as a dict of arrays."""
         n = self._n[scan]
@@ -432,6 +440,11 @@ class History_buffer(_Handle):
         """the node's pose before the registration whose result the next add() receives (laser_mapping.hpp:1439-1451)"""
         p = np.ascontiguousarray(pose, np.float64)
         check(self.L.ll_history_set_gate_pose(self.h, ptr(p)), "ll_history_set_gate_pose")
+
+    def set_undistort(self, reg: "Point_cloud_registration", slot: int = 0) -> None:
+        """g_if_undistore = 1 for the next add() / add_fe() / add_voxel() only (laser_mapping.hpp:1424,1430): that add moves its clouds with the
+        pose interpolated at every point's time stamp, from the state slot `slot` of reg's last collected registration left"""
+        check(self.L.ll_history_set_undistort(self.h, reg.h, int(slot)), "ll_history_set_undistort")
 
     def map_cloud(self, kind: int) -> np.ndarray:
         return self._read_counted_cloud("ll_history_map_cloud", kind)
@@ -1445,9 +1458,32 @@ class Point_cloud_registration(_Handle):
                                                     int(out.shape[0]), C.byref(n)), "ll_cloud_transform_spin_device")
         return int(n.value)
 
-    def pointcloudAssociateToMap(self, pc_in: np.ndarray, pose: np.ndarray | None = None) -> np.ndarray:
+    def interpolation(self, n_scans: int = 1) -> dict:
+        """ll_reg_interpolation: what compute_interpolatation_rodrigue (PCR:607-620) left in the slots of the last collected registration:
+        dict(theta [n], omega_hat [n, 3, 3], pose_last [n, 7], pose_incre [n, 7]).  A gated slot: theta 0, zero matrix, identity increment."""
+        n = int(n_scans)
+        th, hat, pl, pi = np.zeros(n), np.zeros((n, 3, 3)), np.zeros((n, 7)), np.zeros((n, 7))
+        check(self.L.ll_reg_interpolation(self.h, n, ptr(th), ptr(hat), ptr(pl), ptr(pi)), "ll_reg_interpolation")
+        return {"theta": th, "omega_hat": hat, "pose_last": pl, "pose_incre": pi}
+
+    def cloud_undistort_fe_device(self, fe: "Livox_laser", n_scans: int, kind: int, accept: np.ndarray, out, n_used: int) -> int:
+        """append_to_submap_device with if_undistore = 1: the `kind` selection (0 corner, 1 surface, 2 full) of every accepted slot moves with
+        that slot's state of the last collected registration (no poses argument).  Returns the new row count."""
+        acc = np.ascontiguousarray(accept, np.int32)
+        assert out.is_contiguous() and out.shape[1] == 4 and acc.shape[0] >= n_scans
+        n = C.c_int64(int(n_used))
+        check(self.L.ll_cloud_undistort_fe_device(self.h, fe.h, int(n_scans), int(kind), ptr(acc), C.c_void_p(out.data_ptr()), int(out.shape[0]),
+                                                  C.byref(n)), "ll_cloud_undistort_fe_device")
+        return int(n.value)
+
+    def pointcloudAssociateToMap(self, pc_in: np.ndarray, pose: np.ndarray | None = None, if_undistore: int = 0, slot: int = 0) -> np.ndarray:
+        """PCR:673-685.  if_undistore = 1: every point with the pose interpolated at its time stamp, from slot `slot` of the last collected
+        registration (`pose` is not used)."""
         pc_in = capi.as_f32(pc_in, 4)
         out = np.empty_like(pc_in)
+        if if_undistore:
+            check(self.L.ll_cloud_undistort(self.h, int(slot), ptr(pc_in), ptr(out), pc_in.shape[0]), "ll_cloud_undistort")
+            return out
         p = np.ascontiguousarray(self.m_pose_w_curr if pose is None else pose, np.float64)
         check(self.L.ll_cloud_transform(self.h, ptr(pc_in), ptr(out), pc_in.shape[0], ptr(p)), "ll_cloud_transform")
         return out

@@ -124,6 +124,9 @@ SYMBOLS = {
     "ll_reg_set_debug_knn_iteration": (_i32, [_vp, _i32]),
     "ll_cloud_transform": (_i32, [_vp, _vp, _vp, _i32, _vp]),
     "ll_cloud_transform_fe_device": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "ll_reg_interpolation": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "ll_cloud_undistort": (_i32, [_vp, _i32, _vp, _vp, _i32]),
+    "ll_cloud_undistort_fe_device": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _vp]),
     "ll_reg_set_profiling": (_i32, [_vp, _i32]),
     "ll_reg_kernel_times": (_i32, [_vp, _vp, _vp]),
     "ll_reg_set_information": (_i32, [_vp, _i32]),
@@ -147,6 +150,7 @@ SYMBOLS = {
     "ll_history_size": (_i32, [_vp]),
     "ll_history_map_cloud": (_i64, [_vp, _i32, _vp, _i64]),
     "ll_history_set_gate_pose": (_i32, [_vp, _vp]),
+    "ll_history_set_undistort": (_i32, [_vp, _vp, _i32]),
     "ll_history_map_cloud_device": (_i32, [_vp, _i32, _vp, _vp]),
     "ll_history_batch_create": (_i32, [_i32, _i32, _i32, _i32, _f, _f, C.POINTER(_vp)]),
     "ll_history_batch_destroy": (None, [_vp]),

@@ -161,9 +161,10 @@ extern "C" void ll_history_destroy(ll_history *h)
             if (h->stage[k][i]) (void)hipFree(h->stage[k][i]);
     for (int k = 0; k < 2; k++) cellmap_release(h->cells[k]);
     if (h->hp_table) (void)hipHostFree(h->hp_table);
-    void *ptrs[] = {h->frames[0], h->frames[1], h->d_map[0], h->d_map[1], h->d_in, h->d_xf, h->d_concat, h->d_n, h->d_pose, h->d_cmap[0], h->d_cmap[1], h->d_table};
+    void *ptrs[] = {h->frames[0], h->frames[1], h->d_map[0], h->d_map[1], h->d_in, h->d_xf, h->d_concat, h->d_n, h->d_pose, h->d_cmap[0], h->d_cmap[1], h->d_table, h->d_und};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    if (h->ev_und) (void)hipEventDestroy(h->ev_und);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -176,7 +177,10 @@ static int history_filter_kind(ll_history *h, int kind, const float4 *d_src, int
 {
     *n_out = 0;
     if (n <= 0) return 0;
-    launch_cloud_transform(d_src, h->d_xf, n, h->d_pose, h->stream);  // laser_mapping.hpp:1421-1431
+    if (h->use_und)  // g_if_undistore = 1: every point with the pose interpolated at its time stamp (PCR:641-646)
+        launch_cloud_undistort(h->d_und, nullptr, UndistortJob{0, n, 0, 0}, 1, n, d_src, nullptr, nullptr, h->d_xf, h->stream);
+    else
+        launch_cloud_transform(d_src, h->d_xf, n, h->d_pose, h->stream);  // laser_mapping.hpp:1421-1431
     HC(hipMemcpyAsync(h->d_n, &n, sizeof(int), hipMemcpyHostToDevice, h->stream));
     const float leaf[3] = {h->res[kind], h->res[kind], h->res[kind]};
     const char *err = nullptr;
@@ -246,6 +250,8 @@ static int history_add_common(ll_history *h, const float4 *d_corner, int n_corne
     // history_add_t_step = history_add_angle_step = 0, the reference's fixed values: every frame is pushed).
     const double *gp = h->has_gate ? h->gate : pose;
     h->has_gate = false;
+    h->use_und = h->has_und;  // one-shot too (ll_history_set_undistort): this add's two clouds move with the registration's record
+    h->has_und = false;
     const bool push = history_add_frame(gp, h->last_q, h->last_t, h->size, h->max_hist, t_step, angle_step);
     if (added) *added = push ? 1 : 0;
     if (!push && !h->cells[0]) return 0;
@@ -271,6 +277,27 @@ extern "C" int ll_history_set_gate_pose(ll_history *h, const double pose[7])
     if (!h || !pose) return set_err("ll_history_set_gate_pose", "null argument");
     for (int i = 0; i < 7; i++) h->gate[i] = pose[i];
     h->has_gate = true;
+    return 0;
+}
+
+// g_if_undistore = 1 for the next add (laser_mapping.hpp:1424,1430): slot `slot` of the registration r collected last.  The record is copied
+// on the registrar's stream into memory of this handle -- the registrar's next enqueue may follow at once -- and this handle's stream
+// waits for the copy on the device; the host waits for nothing.
+extern "C" int ll_history_set_undistort(ll_history *h, ll_reg *r, int32_t slot)
+{
+    static const char *where = "ll_history_set_undistort";
+    if (!h || !r) return set_err(where, "null argument");
+    if (r->device != h->device) return set_err(where, "registrar lives on another device");
+    if (slot < 0) return set_err(where, "negative slot");
+    if (reg_undistort_records(where, r, slot + 1)) return -1;
+    if (!h->d_und) {
+        DM(h->d_und, 1);
+        HC(hipEventCreateWithFlags(&h->ev_und, hipEventDisableTiming));
+    }
+    HC(hipMemcpyAsync(h->d_und, r->d_und + slot, sizeof(UndistortRec), hipMemcpyDeviceToDevice, r->stream));
+    HC(hipEventRecord(h->ev_und, r->stream));
+    HC(hipStreamWaitEvent(h->stream, h->ev_und, 0));
+    h->has_und = true;
     return 0;
 }
 
@@ -320,6 +347,11 @@ extern "C" int ll_history_add_spin(ll_history *h, ll_spin *sp, int32_t scan, con
                                    double history_add_angle_step, int32_t *added)
 {
     if (!h || !sp || !pose) return set_err("ll_history_add_spin", "null argument");
+    if (h->has_und) {  // (dropped with the refusal: the handle goes on with plain adds)
+        h->has_und = false;
+        return set_err("ll_history_add_spin", "ll_history_set_undistort does not apply: the spinning extractor writes intensity = scanID + scanPeriod * relTime "
+                                              "(laser_feature_extractor.hpp:502), which is no time stamp of refine_blur (point_cloud_registration.hpp:128-141)");
+    }
     SpinView v;
     spin_view(sp, &v);
     if (v.device != h->device) return set_err("ll_history_add_spin", "extractor lives on another device");

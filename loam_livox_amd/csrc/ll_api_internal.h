@@ -145,6 +145,11 @@ struct ll_reg {
     int info_collected = 0;  // ll_reg_collect has run since the last enqueue
     InfoRecord *d_info = nullptr;     // [max_scans]
     std::vector<InfoRecord> h_info;   // the last collect's records
+    // deskewed clouds (ll_cloud_undistort*, ll_history_set_undistort): nothing is allocated, launched or copied before the first of them
+    int collected_scans = 0;          // slots the last ll_reg_collect brought back (0: an enqueue is uncollected, or none was made)
+    UndistortRec *d_und = nullptr;    // [max_scans] the collected registration's records (reg_undistort_records)
+    UndistortJob *d_und_jobs = nullptr;  // [max_scans] job table of a batched launch
+    int und_valid = 0;                // d_und holds the records of the registration collected last
 };
 
 // ---------------------------------------------------------------------------------------------------- voxel grid
@@ -208,6 +213,12 @@ struct ll_history {
     double last_q[4] = {0, 0, 0, 1}, last_t[3] = {0, 0, 0};  // m_last_his_add_q / m_last_his_add_t
     double gate[7] = {0, 0, 0, 1, 0, 0, 0};                   // ll_history_set_gate_pose: the node's pose BEFORE the registration
     bool has_gate = false;
+    // ll_history_set_undistort: the next add moves its clouds with this record (a copy this handle owns, made on the registrar's stream;
+    // ev_und orders this handle's stream behind the copy).  Both allocated by the first call.
+    UndistortRec *d_und = nullptr;
+    hipEvent_t ev_und = nullptr;
+    bool has_und = false;
+    bool use_und = false;  // the add in progress was preceded by the setter
     int64_t n_map[2] = {0, 0};
     float4 *d_map[2] = {nullptr, nullptr};   // filtered match buffer of the last refresh
     // m_pt_cell_map_corners / m_pt_cell_map_planes (laser_mapping.hpp:274-275), ll_history_enable_cell_map
@@ -275,6 +286,7 @@ int map_rebuild_boxed(ll_map *m, int kind, const float *d_raw, int stride, int64
 int reg_enqueue_device_clouds(const char *where, ll_reg *r, const ll_map *map, const float4 *d_corner, const int *d_n_corner, int n_corner,
                               const float4 *d_surf, const int *d_n_surf, int n_surf, const ll_reg_params *prm, const double pose_last[7],
                               const double pose_curr[7], const double pose_incre[7]);
+int reg_undistort_records(const char *where, ll_reg *r, int n_slots);
 // ll_api_cellmap.hip
 void cellmap_release(ll_cellmap *c);
 int cellmap_make_room(ll_cellmap *c, int64_t max_points, const char *where);

@@ -116,7 +116,7 @@ extern "C" void ll_reg_destroy(ll_reg *r)
     (void)hipSetDevice(r->device);
     RegDev &d = r->dev;
     void *ptrs[] = {d.state, d.blk_f, d.blk_av, d.blk_id, d.pl_tab, d.blk_flag, d.nn, d.qperm, d.qsorted, d.qperm_c, d.qw, d.ref_q, d.ref_p, d.ref_s, d.blk_flag0, d.work_search, d.work_build, d.work_cnt, d.work_off, d.grp_ctl, d.solve_order, d.grp_part, d.grp_xch, d.blk_l1, d.hash, d.dbg_idx, d.dbg_d2,
-                    r->d_corner, r->d_surf, r->d_nc, r->d_ns, r->d_pose_tmp, r->d_map_tab, r->d_info};
+                    r->d_corner, r->d_surf, r->d_nc, r->d_ns, r->d_pose_tmp, r->d_map_tab, r->d_info, r->d_und, r->d_und_jobs};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : r->ev) (void)hipEventDestroy(e);
@@ -324,6 +324,8 @@ static int reg_begin(ll_reg *r, const ll_reg_params *prm, int *debug = nullptr)
     r->pinned_maps.clear();
     r->info_enqueued = 0;
     r->info_collected = 0;
+    r->collected_scans = 0;
+    r->und_valid = 0;
     return 0;
 }
 
@@ -484,6 +486,7 @@ extern "C" int ll_reg_collect(ll_reg *r, int32_t n_scans, double *poses_curr, do
         HC(hipMemcpyAsync(r->h_info.data(), r->d_info, (size_t)r->last_n_scans * sizeof(InfoRecord), hipMemcpyDeviceToHost, r->stream));
     HC(hipStreamSynchronize(r->stream));
     r->info_collected = 1;
+    r->collected_scans = n_scans < r->last_n_scans ? n_scans : r->last_n_scans;
     r->pinned[0].reset();  // the solve has left the device: its map snapshots may be recycled
     r->pinned[1].reset();
     r->pinned_maps.clear();
@@ -1090,5 +1093,107 @@ extern "C" int ll_cloud_transform(ll_reg *r, const float *in_xyzi, float *out_xy
     HC(hipStreamSynchronize(r->stream));
     (void)hipFree(d_in);
     (void)hipFree(d_out);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- deskewed clouds
+// pointAssociateToMap / pointcloudAssociateToMap with if_undistore = 1 (point_cloud_registration.hpp:622-661, 673-685) after the
+// registration has been collected.  The solver states are the next enqueue's to overwrite, so the first call after a collect copies
+// what the formula needs into records of this handle (undistort_snapshot_kernel, on the registrar's stream: ordered behind the
+// registration and ahead of the next upload); every later call until the next enqueue reuses them.
+int ll::reg_undistort_records(const char *where, ll_reg *r, int n_slots)
+{
+    if (!r->collected_scans) return set_err(where, "no registration has been collected since the last enqueue (call ll_reg_collect first)");
+    if (n_slots < 1 || n_slots > r->last_n_scans) return set_err(where, "slot beyond the last registration's n_scans");
+    HC(hipSetDevice(r->device));
+    if (!r->d_und) {
+        DM(r->d_und, (size_t)r->max_scans);
+        DM(r->d_und_jobs, (size_t)r->max_scans);
+    }
+    if (!r->und_valid) {
+        launch_undistort_snapshot(r->dev.state, 0, r->last_n_scans, r->rc, r->d_und, r->stream);
+        HC(hipGetLastError());
+        r->und_valid = 1;
+    }
+    return 0;
+}
+
+extern "C" int ll_reg_interpolation(ll_reg *r, int32_t n_scans, double *theta, double *omega_hat9, double *pose_last7, double *pose_incre7)
+{
+    static const char *where = "ll_reg_interpolation";
+    if (!r) return set_err(where, "null handle");
+    if (!r->collected_scans) return set_err(where, "no registration has been collected since the last enqueue (call ll_reg_collect first)");
+    if (n_scans < 1 || n_scans > r->collected_scans) return set_err(where, "n_scans beyond the last collected registration's");
+    for (int b = 0; b < n_scans; b++) {
+        const RegState &s = r->h_state[b];
+        const bool gated = s.gated != 0;  // no increment was estimated (PCR:199): identity
+        if (theta) theta[b] = gated ? 0.0 : s.interp_theta;
+        for (int i = 0; i < 9 && omega_hat9; i++) omega_hat9[9 * b + i] = gated ? 0.0 : s.hat[i];
+        for (int i = 0; i < 7 && pose_last7; i++) pose_last7[7 * b + i] = s.pose_last[i];
+        for (int i = 0; i < 7 && pose_incre7; i++) pose_incre7[7 * b + i] = gated ? (i == 3 ? 1.0 : 0.0) : s.inc[i];
+    }
+    return 0;
+}
+
+extern "C" int ll_cloud_undistort(ll_reg *r, int32_t slot, const float *in_xyzi, float *out_xyzi, int32_t n)
+{
+    static const char *where = "ll_cloud_undistort";
+    if (!r || (n > 0 && (!in_xyzi || !out_xyzi))) return set_err(where, "null argument");
+    if (slot < 0) return set_err(where, "negative slot");
+    if (reg_undistort_records(where, r, slot + 1)) return -1;
+    if (n <= 0) return 0;
+    float4 *d_in = nullptr, *d_out = nullptr;
+    DM(d_in, (size_t)n);
+    DM(d_out, (size_t)n);
+    hipError_t e = hipMemcpyAsync(d_in, in_xyzi, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, r->stream);
+    if (e == hipSuccess) {
+        const UndistortJob one{slot, n, 0, 0};
+        launch_cloud_undistort(r->d_und, nullptr, one, 1, n, d_in, nullptr, nullptr, d_out, r->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_xyzi, d_out, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, r->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return set_err(where, hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int ll_cloud_undistort_fe_device(ll_reg *r, ll_fe *fe, int32_t n_scans, int32_t kind, const int32_t *accept, float *dev_out_xyzi,
+                                            int64_t capacity_points, int64_t *n_points)
+{
+    static const char *where = "ll_cloud_undistort_fe_device";
+    if (!r || !fe || !accept || !dev_out_xyzi || !n_points) return set_err(where, "null argument");
+    if (fe->prm.device != r->device) return set_err(where, "extractor lives on another device");
+    if (n_scans < 0 || n_scans > fe->prm.max_scans || kind < 0 || kind > 2 || *n_points < 0) return set_err(where, "bad argument");
+    if (n_scans == 0) return 0;
+    if (kind == 2 && !fe->dev.full_idx) return set_err(where, "the extractor keeps no full selection");
+    if (reg_undistort_records(where, r, n_scans)) return -1;
+    HC(hipStreamSynchronize(fe->stream));
+    std::vector<int> cnt((size_t)n_scans);
+    HC(hipMemcpy(cnt.data(), kind == 0 ? fe->dev.n_corner : kind == 1 ? fe->dev.n_surf : fe->dev.n_full, (size_t)n_scans * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<UndistortJob> jobs;
+    int64_t at = *n_points;
+    int max_n = 0;
+    for (int b = 0; b < n_scans; b++) {
+        if (!accept[b] || cnt[b] <= 0) continue;
+        if (cnt[b] > fe->dev.stride) return set_err(where, "selection count exceeds the extractor stride");
+        jobs.push_back(UndistortJob{b, cnt[b], (long long)b * fe->dev.stride, (long long)at});
+        at += cnt[b];
+        max_n = cnt[b] > max_n ? cnt[b] : max_n;
+    }
+    if (at > capacity_points) return set_err(where, "device buffer too small");
+    if (!jobs.empty()) {
+        HC(hipMemcpyAsync(r->d_und_jobs, jobs.data(), jobs.size() * sizeof(UndistortJob), hipMemcpyHostToDevice, r->stream));
+        const UndistortJob none{0, 0, 0, 0};
+        if (kind == 2)
+            launch_cloud_undistort(r->d_und, r->d_und_jobs, none, (int)jobs.size(), max_n, fe->dev.xyzi, fe->dev.full_idx, fe->dev.tstamp, (float4 *)dev_out_xyzi, r->stream);
+        else
+            launch_cloud_undistort(r->d_und, r->d_und_jobs, none, (int)jobs.size(), max_n, kind == 0 ? fe->dev.corner_feat : fe->dev.surf_feat, nullptr, nullptr,
+                                   (float4 *)dev_out_xyzi, r->stream);
+        HC(hipGetLastError());
+        HC(hipStreamSynchronize(r->stream));  // (the job table is host memory of this call; the caller reads the buffer on a stream of its own)
+    }
+    *n_points = at;
     return 0;
 }

@@ -245,6 +245,25 @@ void launch_reg_solve_maps(const RegDev &rd, const RegConst &rc, const Grid *map
 void launch_reg_solve_small_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, int cls, int max_nc, int max_ns, int iter, hipStream_t s);
 void launch_reg_finalize(const RegDev &rd, const RegConst &rc, int n_scans, hipStream_t s);
 void launch_cloud_transform(const float4 *in, float4 *out, int n, const double *d_pose, hipStream_t s);
+// Deskewed clouds (pointAssociateToMap with g_if_undistore = 1, PCR:622-661).  What one slot of a COLLECTED registration left for it,
+// copied out of RegState into a record its consumer owns (the next enqueue overwrites the states): 304 bytes per slot.
+struct UndistortRec {
+    double pose_last[7], pose_curr[7], inc_t[3];
+    double theta, hat[9], hat_sq[9];  // m_interpolatation_* (PCR:58,66-68)
+    int deblur;                       // if_motion_deblur of the registration
+    float min_ts, max_ts;             // its time range (PCR:53-54)
+    int pad;
+};
+struct UndistortJob {  // one slot of a cloud_undistort_kernel launch
+    int rec, n;                  // its record, its points
+    long long src_off, dst_off;  // first point in src / dst
+};
+// recs[first + k] <- state[first + k], k < n.  A gated slot gets the identity increment: both poses = pose_last, theta 0, zero matrices.
+void launch_undistort_snapshot(const RegState *state, int first, int n, const RegConst &rc, UndistortRec *recs, hipStream_t s);
+// grid (ceil(max_n / 256), n_slots): slot b moves jobs[b].n points with recs[jobs[b].rec].  d_jobs == nullptr: the one slot `one`.
+// pick != nullptr: point i of a slot is src[src_off + pick[src_off + i]] with intensity pick_w[same] (the extractor's full selection).
+void launch_cloud_undistort(const UndistortRec *recs, const UndistortJob *d_jobs, const UndistortJob &one, int n_slots, int max_n, const float4 *src,
+                            const int *pick, const float *pick_w, float4 *dst, hipStream_t s);
 #define LL_HIST_CONCAT_MAX 1023  // frames one history_concat_kernel launch gathers (longer histories: the per-frame copies)
 void launch_history_concat(const float4 *frames, const int2 *d_table, int n_seg, int total, float4 *out, hipStream_t s);
 void launch_reg_merge_heads(const float4 *fe_corner, const float4 *fe_surf, const int *fe_nc, const int *fe_ns, int fe_stride, int heads,

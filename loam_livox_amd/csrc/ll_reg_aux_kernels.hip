@@ -55,6 +55,70 @@ void launch_cloud_transform(const float4 *in, float4 *out, int n, const double *
     hipLaunchKernelGGL(cloud_transform_kernel, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n, d_pose);
 }
 
+// Deskewed clouds, step 1: the constants of a collected registration out of the solver states into records the consumer owns
+// (the states are overwritten by the next enqueue's upload).  One lane per slot.
+__global__ void undistort_snapshot_kernel(const RegState *state, int first, int n, int deblur, float min_ts, float max_ts, UndistortRec *recs)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const RegState *st = state + first + k;
+    UndistortRec *o = recs + first + k;
+    const bool gated = st->gated != 0;  // PCR:199: no increment was estimated -- identity, I p + 0 is exact
+    for (int i = 0; i < 7; i++) {
+        o->pose_last[i] = st->pose_last[i];
+        o->pose_curr[i] = gated ? st->pose_last[i] : st->pose_curr[i];
+    }
+    for (int i = 0; i < 3; i++) o->inc_t[i] = gated ? 0.0 : st->inc[4 + i];
+    o->theta = gated ? 0.0 : st->interp_theta;
+    for (int i = 0; i < 9; i++) {
+        o->hat[i] = gated ? 0.0 : st->hat[i];
+        o->hat_sq[i] = gated ? 0.0 : st->hat_sq[i];
+    }
+    o->deblur = deblur;
+    o->min_ts = min_ts;
+    o->max_ts = max_ts;
+    o->pad = 0;
+}
+void launch_undistort_snapshot(const RegState *state, int first, int n, const RegConst &rc, UndistortRec *recs, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(undistort_snapshot_kernel, dim3((n + 63) / 64), dim3(64), 0, s, state, first, n, rc.if_motion_deblur, rc.min_ts, rc.max_ts, recs);
+}
+
+// Deskewed clouds, step 2: pointcloudAssociateToMap( in, out, if_undistore = 1 ) (PCR:673-685) for the slots of a batch in one launch.
+// One lane per point; blockIdx.y = slot.  The slot's job and its record are indexed by the block index alone, so they arrive through
+// scalar loads, once per wavefront, ahead of the per-point work.  32 bytes of traffic per point and, in the Rodrigues branch, the fp64
+// sin / cos of point_to_map_undistort (the library's: the bits the registrar's searches computed).  Intensity copied (PCR:659).
+__global__ __launch_bounds__(256) void cloud_undistort_kernel(const UndistortRec *__restrict__ recs, const UndistortJob *__restrict__ jobs, UndistortJob one,
+                                                              const float4 *__restrict__ src, const int *__restrict__ pick, const float *__restrict__ pick_w,
+                                                              float4 *__restrict__ dst)
+{
+    const UndistortJob j = jobs ? jobs[blockIdx.y] : one;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= j.n) return;
+    const UndistortRec &c = recs[j.rec];
+    float4 v;
+    if (pick) {  // a selection by position (the extractor's full cloud): point pick[i] of the slot, its time stamp from the plane beside it
+        const int k = pick[j.src_off + i];
+        v = src[j.src_off + k];
+        v.w = pick_w[j.src_off + k];  // intensity := time stamp, LFE:246,255
+    } else {
+        v = src[j.src_off + i];
+    }
+    float o[3];
+    point_to_map_undistort(c.pose_last, c.pose_curr, c.inc_t, c.theta, c.hat, c.hat_sq, c.deblur, c.min_ts, c.max_ts, v, o);
+    dst[j.dst_off + i] = make_float4(o[0], o[1], o[2], v.w);
+}
+void launch_cloud_undistort(const UndistortRec *recs, const UndistortJob *d_jobs, const UndistortJob &one, int n_slots, int max_n, const float4 *src,
+                            const int *pick, const float *pick_w, float4 *dst, hipStream_t s)
+{
+    if (n_slots <= 0 || max_n <= 0) return;
+    for (int first = 0; first < n_slots; first += 65535) {  // (grid.y is a 16-bit dimension)
+        const int ny = n_slots - first < 65535 ? n_slots - first : 65535;
+        hipLaunchKernelGGL(cloud_undistort_kernel, dim3((max_n + 255) / 256, ny), dim3(256), 0, s, recs, d_jobs ? d_jobs + first : nullptr, one, src, pick, pick_w, dst);
+    }
+}
+
 // Mid-100: the selected features of `heads` consecutive extractor slots (the lidars of one sweep) become ONE registrar scan,
 // corner clouds and surface clouds each concatenated in head order (laser_feature_extractor.hpp:348-358), device to device.
 // grid (chunks of the extractor stride, n_scans * heads, 2 kinds).  Points beyond the registrar's capacity are not written;

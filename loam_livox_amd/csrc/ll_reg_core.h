@@ -101,6 +101,82 @@ LL_HD float refine_blur(int deblur, float in_blur, float min_blur, float max_blu
     return res;
 }
 
+// compute_interpolatation_rodrigue, PCR:607-620 (Eigen AngleAxis from the increment's quaternion q = (x, y, z, w)): the angle, the
+// normalised axis' cross-product matrix (row-major) and its square
+LL_HD void interp_rodrigues(const double q[4], double *theta, double hat[9], double hat_sq[9])
+{
+    double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+    double axis[3];
+    if (n != 0.0) {
+        *theta = 2.0 * atan2(n, fabs(q[3]));  // the angle from |vec| and |w| ...
+        if (q[3] < 0) n = -n;                 // ... then the axis turned for w < 0: (axis, theta) is the rotation of q, as slerp's shorter arc
+        axis[0] = q[0] / n;
+        axis[1] = q[1] / n;
+        axis[2] = q[2] / n;
+    } else {
+        *theta = 0.0;
+        axis[0] = 1.0;
+        axis[1] = 0.0;
+        axis[2] = 0.0;
+    }
+    const double an = sqrt(dot3(axis, axis));
+    axis[0] /= an;
+    axis[1] /= an;
+    axis[2] /= an;
+    for (int i = 0; i < 9; i++) hat[i] = 0.0;
+    hat[1] = -axis[2];
+    hat[3] = axis[2];
+    hat[2] = axis[1];
+    hat[6] = -axis[1];
+    hat[5] = -axis[0];
+    hat[7] = axis[0];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            double s = 0;
+            for (int k = 0; k < 3; k++) s += hat[i * 3 + k] * hat[k * 3 + j];
+            hat_sq[i * 3 + j] = s;
+        }
+}
+
+// pointAssociateToMap with its undistort branch (point_cloud_registration.hpp:622-661): the point p = (x, y, z, time stamp) moves with
+// the pose interpolated at its time stamp.  s = refine_blur (float, :625); deblur off or s == 1 -> the end-of-scan pose (:627-630);
+// otherwise (:641-646)  R_s = I + sin(s theta) hat + (1 - cos(s theta)) hat_sq,  out = q_last (R_s p + s t_inc) + t_last, double math,
+// float store.  theta / hat / hat_sq are what compute_interpolatation_rodrigue (:607-620) left for the increment.  A negative s
+// (a stamp before min_ts) is not clamped: the reference extrapolates.  The registrar's searches (transform_query) and the deskewed
+// clouds (cloud_undistort_kernel, the adapter's per-point form) share this one function, operation for operation.
+// P4: float4 on the device; any {x, y, z, w} of floats where this header is built without the HIP vector types.
+template <class P4>
+LL_HD void point_to_map_undistort(const double pose_last[7], const double pose_curr[7], const double inc_t[3], double theta, const double hat[9],
+                                  const double hat_sq[9], int deblur, float min_ts, float max_ts, const P4 &p, float out[3])
+{
+    const float sblur = refine_blur(deblur, p.w, min_ts, max_ts);  // PCR:247,625
+    if (deblur == 0 || (double)sblur == 1.0) {
+        point_to_map(pose_curr, p.x, p.y, p.z, out);  // PCR:629
+    } else {
+        // Rodrigues interpolation, PCR:641-646
+        const double s = (double)sblur;
+        const double T[3] = {inc_t[0] * (s * 1.0), inc_t[1] * (s * 1.0), inc_t[2] * (s * 1.0)};
+        const double th = theta * s;
+        const double sn = sin(th), cs1 = 1.0 - cos(th);
+        const double pc[3] = {(double)p.x, (double)p.y, (double)p.z};
+        double inner[3], o[3];
+        LL_UNROLL
+        for (int i = 0; i < 3; i++) {
+            double acc = 0.0;
+            LL_UNROLL
+            for (int j = 0; j < 3; j++) {
+                const double rij = ((i == j) ? 1.0 : 0.0) + sn * hat[i * 3 + j] + cs1 * hat_sq[i * 3 + j];
+                acc += rij * pc[j];
+            }
+            inner[i] = acc + T[i];
+        }
+        quat_rot(pose_last, inner, o);
+        out[0] = (float)(o[0] + pose_last[4]);
+        out[1] = (float)(o[1] + pose_last[5]);
+        out[2] = (float)(o[2] + pose_last[6]);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- a13: sub-sampling
 // point_cloud_registration.hpp:232-238, 339-345 (features) and :438-458 (residual blocks) drop work at random when a scan
 // has more than 2 x / 1 x maximum_allow_residual_block of it.  The reference draws from mt19937(random_device), which

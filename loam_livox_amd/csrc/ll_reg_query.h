@@ -139,32 +139,8 @@ __device__ __forceinline__ void transform_query(const RegState *st, const RegCon
 {
     pw[0] = pw[1] = pw[2] = NAN;  // non-finite features are skipped (PCR:242-245; surface: defined deviation)
     if (!(ll_isfinite(f.x) && ll_isfinite(f.y) && ll_isfinite(f.z))) return;
-    const float sblur = refine_blur(rc.if_motion_deblur, f.w, rc.min_ts, rc.max_ts);  // PCR:247
-    if (rc.if_motion_deblur == 0 || (double)sblur == 1.0) {
-        point_to_map(st->pose_curr, f.x, f.y, f.z, pw);  // PCR:629
-    } else {
-        // Rodrigues interpolation, PCR:641-646
-        const double s = (double)sblur;
-        const double T[3] = {st->inc[4] * (s * 1.0), st->inc[5] * (s * 1.0), st->inc[6] * (s * 1.0)};
-        const double th = st->interp_theta * s;
-        const double sn = sin(th), cs1 = 1.0 - cos(th);
-        const double pc[3] = {(double)f.x, (double)f.y, (double)f.z};
-        double inner[3], o[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            double acc = 0.0;
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                const double rij = ((i == j) ? 1.0 : 0.0) + sn * st->hat[i * 3 + j] + cs1 * st->hat_sq[i * 3 + j];
-                acc += rij * pc[j];
-            }
-            inner[i] = acc + T[i];
-        }
-        quat_rot(st->pose_last, inner, o);
-        pw[0] = (float)(o[0] + st->pose_last[4]);
-        pw[1] = (float)(o[1] + st->pose_last[5]);
-        pw[2] = (float)(o[2] + st->pose_last[6]);
-    }
+    // PCR:247, 622-661 (ll_reg_core.h: the arithmetic the deskewed clouds share)
+    point_to_map_undistort(st->pose_last, st->pose_curr, &st->inc[4], st->interp_theta, st->hat, st->hat_sq, rc.if_motion_deblur, rc.min_ts, rc.max_ts, f, pw);
 }
 
 __device__ __forceinline__ float4 load_feature(const RegDev &rd, int b, int kind, int q)

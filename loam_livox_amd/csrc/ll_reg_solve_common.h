@@ -52,37 +52,7 @@ __device__ __forceinline__ void wave_sum_acc(const double (&acc)[LL_NACC], doubl
 // compute_interpolatation_rodrigue, PCR:607-620 (Eigen AngleAxis from quaternion)
 __device__ inline void compute_interp(const double q[4], RegState *st)
 {
-    double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
-    double axis[3];
-    if (q[3] < 0) n = -n;
-    if (n != 0.0) {
-        st->interp_theta = 2.0 * atan2(n, fabs(q[3]));
-        axis[0] = q[0] / n;
-        axis[1] = q[1] / n;
-        axis[2] = q[2] / n;
-    } else {
-        st->interp_theta = 0.0;
-        axis[0] = 1.0;
-        axis[1] = 0.0;
-        axis[2] = 0.0;
-    }
-    const double an = sqrt(dot3(axis, axis));
-    axis[0] /= an;
-    axis[1] /= an;
-    axis[2] /= an;
-    for (int i = 0; i < 9; i++) st->hat[i] = 0.0;
-    st->hat[1] = -axis[2];
-    st->hat[3] = axis[2];
-    st->hat[2] = axis[1];
-    st->hat[6] = -axis[1];
-    st->hat[5] = -axis[0];
-    st->hat[7] = axis[0];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            double s = 0;
-            for (int k = 0; k < 3; k++) s += st->hat[i * 3 + k] * st->hat[k * 3 + j];
-            st->hat_sq[i * 3 + j] = s;
-        }
+    interp_rodrigues(q, &st->interp_theta, st->hat, st->hat_sq);  // (ll_reg_core.h: the arithmetic, shared with the host tier)
 }
 
 // pose composition, convergence test and per-iteration report (PCR:509-531); lane 0 only

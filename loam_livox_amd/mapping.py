@@ -42,6 +42,12 @@ def _degenerate_directions(info: dict, min_eigenvalue: float) -> np.ndarray:
     return np.ascontiguousarray(info["eigenvectors"][:, weak].T)
 
 
+def _point_time_stamp(current_time: float, idx, time_internal_pts: float):
+    """the extractor's stamp of point idx (livox_feature_extractor.hpp:482; ll_fe_core.h point_time_stamp), operation for operation;
+    idx: one position or an array of them -> float32"""
+    return (np.float64(current_time) + (np.asarray(idx).astype(np.float32) * np.float32(time_internal_pts)).astype(np.float64)).astype(np.float32)
+
+
 class Laser_mapping:
     """lidar_type (common/lidar_type of the feature node, laser_feature_extractor.hpp:831-851): "livox" (default) runs the Livox
     extractor; any other value runs the spinning-lidar one (scan_line 16 or 64, minimum_range, mapping_plane_resolution: the feature
@@ -61,9 +67,16 @@ class Laser_mapping:
                  maximum_in_fov_angle: float = 30.0, down_sample_replace: int = 1, cell_map_max_points: int = 1 << 21,
                  loop_closure_if_enable: int = 0, loop_closure: dict | None = None, keep_cell_maps: bool = False,
                  lidar_type: str = "livox", scan_line: int = 16, minimum_range: float = 0.1, mapping_plane_resolution: float = 0.8,
-                 information: bool = False):
+                 information: bool = False, if_motion_deblur: int = 0, if_undistort: int = 0):
         self.lidar_type = lidar_type
         self._spin = lidar_type != "livox"
+        # if_motion_deblur: the registrar's switch and the frame's time range (laser_mapping.hpp:1336-1347).  if_undistort: g_if_undistore --
+        # the history frames, the full cloud and the published clouds move with the pose interpolated at every point's time stamp
+        # (:1424,1430,1442).  Both 0: the loop makes exactly the calls it makes without them.
+        self.if_motion_deblur, self.if_undistort = int(bool(if_motion_deblur)), int(bool(if_undistort))
+        if self._spin and (self.if_motion_deblur or self.if_undistort):
+            raise ValueError(f'lidar_type "{lidar_type}" (spinning lidar): if_motion_deblur and if_undistort must be 0 -- the spinning extractor\'s '
+                             "intensity is scanID + scanPeriod * relTime (laser_feature_extractor.hpp:502), no time stamp")
         if self._spin:
             if matching_mode or keep_cell_maps or loop_closure_if_enable:
                 raise ValueError(f'lidar_type "{lidar_type}" (spinning lidar) runs in history mode only: matching_mode, keep_cell_maps and '
@@ -107,6 +120,8 @@ class Laser_mapping:
                               max_allow_incre_R=max_allow_incre_R, max_allow_incre_T=max_allow_incre_T, max_allow_final_cost=max_allow_final_cost,
                               init_accumulate_frames=init_accumulate_frames, minimum_icp_R_diff=minimum_icp_R_diff,
                               minimum_icp_T_diff=minimum_icp_T_diff, maximum_residual_blocks=maximum_residual_blocks, subsample_seed=subsample_seed)
+        if self.if_motion_deblur:
+            self.reg.params.if_motion_deblur = 1
         self.m_current_frame_index = 0
         self.pose = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)  # m_q_w_curr / m_t_w_curr
         self.map_sizes = (0, 0)
@@ -139,7 +154,10 @@ class Laser_mapping:
         history's add answered for this scan (:1446-1448) -- the scan's full cloud joins m_laser_cloud_full_history with it (:1456)"""
         full = np.ascontiguousarray(full_xyzi, np.float32)
         full = full[np.isfinite(full[:, :3]).all(axis=1)]
-        cloud = self.reg.pointcloudAssociateToMap(full, self.pose) if len(full) else full
+        if self.if_undistort:  # :1442, pointcloudAssociateToMap( full, full_out, g_if_undistore )
+            cloud = self.reg.pointcloudAssociateToMap(full, self.pose, if_undistore=1) if len(full) else full
+        else:
+            cloud = self.reg.pointcloudAssociateToMap(full, self.pose) if len(full) else full
         self.keyframes.add_scan(cloud, self.pose, self.m_current_frame_index, history_added=history_added)
         self.loops += self.keyframes.process_waiting()
 
@@ -216,6 +234,11 @@ class Laser_mapping:
             fe = self._fe_pair[0]
             self._extract(fe, xyzi, time_stamp)
         self.fe = fe  # the handle that holds this frame's features (history add, key frames)
+        if self.if_motion_deblur:  # find_min_max_intensity( full ), :1336-1347: from the previous frame's last stamp to this frame's
+            full_idx = fe.full_selection(0)  # (ascending: the last one carries the largest stamp)
+            max_t = float(_point_time_stamp(time_stamp, int(full_idx[-1]), fe.params.time_internal_pts)) if len(full_idx) else 0.0
+            reg.params.minimum_pt_time_stamp, reg.params.maximum_pt_time_stamp = self.m_last_time_stamp, max_t
+            self.m_last_time_stamp = max_t
         reg.params.current_frame_index = self.m_current_frame_index  # init_pointcloud_registration runs before the increment
         self.m_current_frame_index += 1
         pose = self.pose[None]
@@ -248,6 +271,8 @@ class Laser_mapping:
         if not res[0]:  # :1413-1416
             return 0
         self.history.set_gate_pose(self.pose)  # m_q_w_curr is still the pre-registration pose at LM:1439-1451
+        if self.if_undistort:
+            self.history.set_undistort(reg, 0)  # :1424,1430
         if self.m_if_input_downsample_mode:
             added = self.history.add_voxel(self.vox[0], self.vox[1], 0, pc[0], self.history_add_t_step, self.history_add_angle_step)
         elif self._spin:
@@ -257,7 +282,12 @@ class Laser_mapping:
         self.pose = pc[0].copy()  # :1496-1500
         if self.keyframes is not None:
             tk = time.perf_counter()
-            self._keyframe_step(np.asarray(xyzi, np.float32)[fe.get_features(0.0, 1.0)["full_idx"]], bool(added))  # /pc2_full of this scan
+            full_idx = fe.get_features(0.0, 1.0)["full_idx"]
+            full = np.asarray(xyzi, np.float32)[full_idx]  # /pc2_full of this scan
+            if self.if_undistort:  # the feature node publishes it with intensity := time stamp (LFE:246,255), which the deskew reads
+                full = full.copy()
+                full[:, 3] = _point_time_stamp(time_stamp, full_idx, fe.params.time_internal_pts)
+            self._keyframe_step(full, bool(added))
             self.full_map_s += time.perf_counter() - tk
         t2 = time.perf_counter()
         if self.m_matching_mode:  # update_buff_for_matching (service thread in the node), synchronous here
@@ -306,6 +336,8 @@ class Laser_mapping:
             return 0
         self.history.set_gate_pose(self.pose)  # m_q_w_curr is still the pre-registration pose at LM:1439-1451
         self.pose = np.array(reg.m_pose_w_curr, np.float64)
+        if self.if_undistort:
+            self.history.set_undistort(reg, 0)  # :1424,1430
         added = self.history.add(corner_stack, surf_stack, self.pose, self.history_add_t_step, self.history_add_angle_step)
         if self.keyframes is not None:
             self._keyframe_step(full, bool(added))

@@ -39,6 +39,9 @@ int ll_reg_information(ll_reg *r, int32_t n_scans, ll_reg_information_record *ou
 int ll_reg_interpolation(ll_reg *r, int32_t n_scans, double *theta, double *omega_hat9, double *pose_last7, double *pose_incre7) __attribute__((weak));
 int ll_cloud_undistort(ll_reg *r, int32_t slot, const float *in_xyzi, float *out_xyzi, int32_t n) __attribute__((weak));
 int ll_history_set_undistort(ll_history *h, ll_reg *r, int32_t slot) __attribute__((weak));
+// ... and motion deblur with a map per slot
+int ll_reg_set_time_ranges(ll_reg *r, const float *minimum_pt_time_stamp, const float *maximum_pt_time_stamp, int32_t n_scans) __attribute__((weak));
+int ll_history_batch_set_undistort(ll_history_batch *h, ll_reg *r) __attribute__((weak));
 }
 
 // The registrar's pose members (m_q_w_curr, m_t_w_curr, m_q_w_last, m_t_w_last, m_q_w_incre, m_t_w_incre,
@@ -689,6 +692,14 @@ class History_batch {
         check(ll_history_batch_add_voxel(h_.get(), vox_corner, vox_surf, active, poses, gate_poses, history_add_t_step, history_add_angle_step, added),
               "ll_history_batch_add_voxel");
     }
+    // g_if_undistore = 1 for the next add() (laser_mapping.hpp:1424,1430), History_buffer::set_undistort for all slots: active slot s moves
+    // its clouds with the state slot s of the registration `reg` collected last left; poses / gate_poses keep serving the add-frame rule.
+    void set_undistort(ll_reg *reg)
+    {
+        if (!&ll_history_batch_set_undistort)
+            throw std::runtime_error("set_undistort: this program is linked against a library without ll_history_batch_set_undistort");
+        check(ll_history_batch_set_undistort(h_.get(), reg), "ll_history_batch_set_undistort");
+    }
     // update_buff_for_matching() of every active slot: new search grids of both kinds in maps[s]
     void refresh(ll_map *const *maps, const int32_t *active = nullptr, int64_t *n_corner = nullptr, int64_t *n_surf = nullptr)
     {
@@ -1304,7 +1315,14 @@ class Point_cloud_registration : public Point_cloud_registration_fields {
     // maps[b] (nullptr = idle slot) with frame_index[b] (nullptr = m_current_frame_index for every slot), the start-up gate decided
     // per slot.  The batch handles are the caller's C handles (a registrar created with max_scans >= n_scans; voxel filters with
     // max_clouds >= n_scans); this object contributes its configuration fields.  Collect with ll_reg_collect( reg, n_scans, ... ).
-    // m_if_motion_deblur must be 0 (the call throws otherwise).
+    // m_if_motion_deblur = 1 needs set_time_ranges( reg, ... ) in front of the call (which throws otherwise).
+    // set_time_ranges: a time range per scan for the NEXT enqueue_fe_maps on `reg` only (ll_reg_set_time_ranges) -- slot b runs from
+    // minimum_pt_time_stamp[b] to maximum_pt_time_stamp[b] where a registration reads m_minimum_pt_time_stamp / m_maximum_pt_time_stamp.
+    static void set_time_ranges(ll_reg *reg, const float *minimum_pt_time_stamp, const float *maximum_pt_time_stamp, int n_scans)
+    {
+        if (!&ll_reg_set_time_ranges) throw std::runtime_error("set_time_ranges: this program is linked against a library without ll_reg_set_time_ranges");
+        check(ll_reg_set_time_ranges(reg, minimum_pt_time_stamp, maximum_pt_time_stamp, n_scans), "ll_reg_set_time_ranges");
+    }
     void enqueue_fe_maps(ll_reg *reg, const ll_map *const *maps, ll_fe *fe, int n_scans, const int32_t *frame_index, const double *poses_last,
                          const double *poses_curr) const
     {

@@ -96,6 +96,10 @@ int ll_fe_upload_async(ll_fe *h, int32_t first_scan, int32_t n_scans, const floa
 int ll_fe_extract_batch(ll_fe *h, int32_t n_scans); /* asynchronous on the handle's stream */
 /* piece >= 0: use the device-computed piece-wise window `piece`; piece < 0: explicit [minimum,maximum]_blur */
 int ll_fe_select_batch(ll_fe *h, int32_t n_scans, int32_t piece, float minimum_blur, float maximum_blur);
+/* last_position[b], b < n_scans: the last (largest: a selection is ascending) position of slot b's selection of `kind` (0 corner,
+ * 1 surface, 2 full) after ll_fe_select_batch, -1 where the selection is empty.  One small launch and one copy of n_scans ints: what a
+ * motion-deblur frame's time range needs of the full selection (laser_mapping.hpp:1336) without downloading it. */
+int ll_fe_selection_last(ll_fe *h, int32_t n_scans, int32_t kind, int32_t *last_position);
 /* The selection ll_fe_select_batch left in slot `scan`: what ll_fe_select returns for slot 0 (get_features' outputs,
  * livox_feature_extractor.hpp:219-272), for any slot of a batch.  Output buffers sized max_points; NULL to skip.  Synchronises. */
 int ll_fe_selection(ll_fe *h, int32_t scan, int32_t *corner_idx, int32_t *n_corner, int32_t *surf_idx, int32_t *n_surf,
@@ -353,8 +357,25 @@ int ll_reg_enqueue_fe_downsampled(ll_reg *r, const ll_map *map, ll_fe *fe, ll_vo
  *   results                  slot b's pose, increment, result and report are those of ll_reg_enqueue_fe[_downsampled] for that scan
  *                            alone (n_scans = 1) against maps[b] with that frame index, bit for bit, whatever n_scans is: the solver form
  *                            is chosen per slot as for the scan alone.
- * Refused: null arguments, a map on another device, n_scans out of range, prm->if_motion_deblur != 0 (all before anything is
- * launched), and a batch with a running scan beyond the compact solver's size (Mid-100 sweeps). */
+ * Refused: null arguments, a map on another device, n_scans out of range, prm->if_motion_deblur != 0 without a time range per scan
+ * (below; all before anything is launched), and a batch with a running scan beyond the compact solver's size (Mid-100 sweeps).
+ *
+ * MOTION DEBLUR WITH A MAP PER SLOT needs ll_reg_set_time_ranges in front of the enqueue: lock-step sequences run from their own
+ * previous frame's last stamp to this frame's (laser_mapping.hpp:1336-1347), so the params' one pair per batch cannot serve them.
+ *   ll_reg_set_time_ranges   one-shot, like ll_history_set_gate_pose: the next ll_reg_enqueue_fe_maps / _downsampled_maps takes the
+ *                            table, whether it succeeds or is refused.  Slot b of that enqueue uses (minimum[b], maximum[b])
+ *                            wherever a registration reads the params' minimum_pt_time_stamp / maximum_pt_time_stamp -- searches,
+ *                            residual blocks, the *_mb solver, the information record, the deskew records (ll_reg_interpolation,
+ *                            ll_cloud_undistort*, ll_history[_batch]_set_undistort) -- and the params' own pair is not read.  A
+ *                            running slot gives the bits of ll_reg_enqueue_fe[_downsampled] for that scan alone with its range in
+ *                            the params.  With if_motion_deblur == 0 the table is taken and not used.
+ *   refused                  null arrays, n_scans < 1 or > max_scans; the next _maps enqueue when its n_scans differs; ANY single-map
+ *                            enqueue while a table is pending (the table is dropped, not silently ignored); a running scan that the
+ *                            single-map entry points would hand to the general solver (beyond 61 440 padded blocks, or the
+ *                            force-general debug switch): the "compact solver" refusal above, before a kernel is launched.
+ * The pairs wait in pinned host memory and go up with the enqueue's other per-scan data on the registrar's stream: no host wait is
+ * added.  Nothing is allocated before the first call. */
+int ll_reg_set_time_ranges(ll_reg *r, const float *minimum_pt_time_stamp, const float *maximum_pt_time_stamp, int32_t n_scans);
 int ll_reg_enqueue_fe_maps(ll_reg *r, const ll_map *const *maps, ll_fe *fe, int32_t n_scans, const ll_reg_params *prm,
                            const int32_t *frame_index, const double *poses_last, const double *poses_curr, const double *poses_incre);
 int ll_reg_enqueue_fe_downsampled_maps(ll_reg *r, const ll_map *const *maps, ll_fe *fe, ll_voxel *vox_corner, ll_voxel *vox_surf,
@@ -441,6 +462,12 @@ int ll_history_batch_add_voxel(ll_history_batch *h, ll_voxel *vox_corner, ll_vox
                                double history_add_angle_step, int32_t *added);
 int ll_history_batch_add_fe(ll_history_batch *h, ll_fe *fe, const int32_t *active, const double *poses7, const double *gate_poses7,
                             double history_add_t_step, double history_add_angle_step, int32_t *added);
+/* g_if_undistore = 1 for the next ll_history_batch_add_voxel / _add_fe only, the batch form of ll_history_set_undistort: that add
+ * moves active slot s's two clouds with the state slot s of r's last collected registration left ("Deskewed clouds" below) instead of
+ * with poses7[s], all slots in one launch; poses7 / gate_poses7 still serve the add-frame rule and the cell maps.  The S records are
+ * copied on the device into memory of this handle when this is called, so r may be enqueued again at once; the host waits for nothing.
+ * Refused before a first ll_reg_collect, while an enqueue is uncollected, and when r's last registration had fewer than n_sequences scans. */
+int ll_history_batch_set_undistort(ll_history_batch *h, ll_reg *r);
 int ll_history_batch_refresh(ll_history_batch *h, ll_map *const *maps, const int32_t *active, int64_t *n_map_corner,
                              int64_t *n_map_surf);
 int32_t ll_history_batch_size(const ll_history_batch *h, int32_t sequence);
@@ -949,6 +976,7 @@ int ll_cloud_transform_fe_device(ll_reg *r, ll_fe *fe, int32_t n_scans, int32_t 
  *
  * All of them use the state the last COLLECTED registration on r left in slot `slot` (scan b of the batch), and are refused
  * before a first ll_reg_collect, while an enqueue is uncollected, and for slots beyond that registration's n_scans.
+ *   the time range is the registration's: the params' pair, or slot b's own pair after ll_reg_set_time_ranges (a map per slot).
  *   if_motion_deblur == 0 in that registration: the plain transform with the slot's pose_curr, bit for bit (:627).
  *   a gated slot (report.gated: :199, nothing was estimated): identity increment, theta 0, zero matrices -- the plain
  *     transform with pose_last, bit for bit.

@@ -151,6 +151,13 @@ class Livox_laser(_Handle):
         check(self.L.ll_fe_selection(self.h, int(scan), None, None, None, None, ptr(fi), C.byref(nf), None, None), "ll_fe_selection")
         return fi[:nf.value].copy()
 
+    def selection_last(self, n_scans: int, kind: int = 2) -> np.ndarray:
+        """the last (largest) position of every slot's selection of `kind` (0 corner, 1 surface, 2 full) after select_batch(), int32
+        [n_scans], -1 where the selection is empty (ll_fe_selection_last: one small launch, n_scans ints across the bus)"""
+        last = np.zeros(int(n_scans), np.int32)
+        check(self.L.ll_fe_selection_last(self.h, int(n_scans), int(kind), ptr(last)), "ll_fe_selection_last")
+        return last
+
     def pts_info(self, scan: int = 0):
         """m_pts_info_vec as a dict of arrays."""
         n = self._n[scan]
@@ -501,6 +508,11 @@ class History_buffer_batch(_Handle):
         check(self.L.ll_history_batch_add_fe(self.h, fe.h, ptr(act), ptr(poses), ptr(gate), history_add_t_step, history_add_angle_step,
                                              ptr(added)), "ll_history_batch_add_fe")
         return added.astype(bool)
+
+    def set_undistort(self, reg: "Point_cloud_registration") -> None:
+        """g_if_undistore = 1 for the next add_voxel() / add_fe() only (History_buffer.set_undistort for all slots): active slot s moves its
+        clouds with the state slot s of reg's last collected registration left; poses / gate_poses still serve the add rule"""
+        check(self.L.ll_history_batch_set_undistort(self.h, reg.h), "ll_history_batch_set_undistort")
 
     def refresh(self, maps, active=None):
         """maps: n_sequences Map_buffer (None allowed for an inactive slot).  Returns (n_corner [S], n_surf [S]) of the match buffers."""
@@ -1306,6 +1318,15 @@ class Point_cloud_registration(_Handle):
         """m_if_input_downsample_mode (laser_mapping.hpp:1367-1373): voxel-filter the selected features on the device, then
         register them."""
         self._enqueue("ll_reg_enqueue_fe_downsampled", (map_buffer.h, fe.h, vox_corner.h, vox_surf.h, line_res, plane_res), n_scans, poses_last, poses_curr)
+
+    def set_time_ranges(self, min_ts, max_ts) -> None:
+        """ll_reg_set_time_ranges: a time range per scan for the NEXT enqueue_fe_maps / enqueue_fe_downsampled_maps only -- slot b runs
+        over (min_ts[b], max_ts[b]) wherever a registration reads params.minimum_pt_time_stamp / maximum_pt_time_stamp, which is what
+        params.if_motion_deblur = 1 needs with a map per slot.  A single-map enqueue with a table pending is refused."""
+        lo, hi = np.ascontiguousarray(min_ts, np.float32).reshape(-1), np.ascontiguousarray(max_ts, np.float32).reshape(-1)
+        if len(lo) != len(hi):
+            raise ValueError(f"{len(lo)} minimum and {len(hi)} maximum time stamps")
+        check(self.L.ll_reg_set_time_ranges(self.h, ptr(lo), ptr(hi), len(lo)), "ll_reg_set_time_ranges")
 
     def _maps_args(self, maps, n_scans: int, frame_index):
         """the handle table and the frame indices of a map-per-slot enqueue (None in maps = an idle slot)"""

@@ -87,6 +87,7 @@ SYMBOLS = {
     "ll_fe_labels": (_i32, [_vp, _i32] + [_vp] * 8),
     "ll_fe_splits": (_i32, [_vp, _i32, _vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _vp, _vp, _vp]),
     "ll_fe_select": (_i32, [_vp, _f, _f, _vp, C.POINTER(_i32), _vp, C.POINTER(_i32), _vp, C.POINTER(_i32), _vp, _vp]),
+    "ll_fe_selection_last": (_i32, [_vp, _i32, _i32, _vp]),
     "ll_fe_selection": (_i32, [_vp, _i32, _vp, C.POINTER(_i32), _vp, C.POINTER(_i32), _vp, C.POINTER(_i32), _vp, _vp]),
     "ll_fe_upload": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp]),
     "ll_fe_upload_async": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp]),
@@ -151,6 +152,8 @@ SYMBOLS = {
     "ll_history_map_cloud": (_i64, [_vp, _i32, _vp, _i64]),
     "ll_history_set_gate_pose": (_i32, [_vp, _vp]),
     "ll_history_set_undistort": (_i32, [_vp, _vp, _i32]),
+    "ll_history_batch_set_undistort": (_i32, [_vp, _vp]),
+    "ll_reg_set_time_ranges": (_i32, [_vp, _vp, _vp, _i32]),
     "ll_history_map_cloud_device": (_i32, [_vp, _i32, _vp, _vp]),
     "ll_history_batch_create": (_i32, [_i32, _i32, _i32, _i32, _f, _f, C.POINTER(_vp)]),
     "ll_history_batch_destroy": (None, [_vp]),

@@ -120,7 +120,7 @@ extern "C" void ll_fe_destroy(ll_fe *h)
     void *ptrs[] = {h->d_xyzi, h->d_npts, h->d_time0, d.type, d.label, d.depth2, d.polar2, d.curv, d.view, d.tstamp,
                     d.polar_angle, d.img, d.flags, d.cand, d.split_idx, d.petal_first, d.petal_last, d.run_angle, d.info,
                     d.corner_idx, d.surf_idx, d.full_idx, d.corner_feat, d.surf_feat, d.n_corner, d.n_surf, d.n_full,
-                    d.n_ambig, d.ambig_list};
+                    d.n_ambig, d.ambig_list, h->d_last};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (h->hp_npts) (void)hipHostFree(h->hp_npts);
@@ -363,6 +363,26 @@ extern "C" int ll_fe_select(ll_fe *h, float minimum_blur, float maximum_blur, in
     D2H_OPT(full_idx, h->dev.full_idx, nf, int);
     D2H_OPT(corner_xyzi, h->dev.corner_feat, nc, float4);
     D2H_OPT(surf_xyzi, h->dev.surf_feat, ns, float4);
+    return 0;
+}
+
+// The last (largest: a selection is ascending) position of every slot's selection of `kind` (0 corner, 1 surface, 2 full), -1 where it
+// is empty: what the time range of a motion-deblur frame needs of the full selection (laser_mapping.hpp:1336: its largest stamp), as
+// one small launch and one copy of n_scans ints instead of a selection per slot.
+extern "C" int ll_fe_selection_last(ll_fe *h, int32_t n_scans, int32_t kind, int32_t *last_position)
+{
+    static const char *where = "ll_fe_selection_last";
+    if (!h) return set_err(where, "null handle");
+    if (!last_position) return set_err(where, "null argument");
+    if (n_scans < 1 || n_scans > h->prm.max_scans) return set_err(where, "n_scans out of range");
+    if (kind < 0 || kind > 2) return set_err(where, "kind must be 0 (corner), 1 (surface) or 2 (full)");
+    if (kind == 2 && !h->dev.full_idx) return set_err(where, "the extractor keeps no full selection");
+    HC(hipSetDevice(h->prm.device));
+    if (!h->d_last) DM(h->d_last, (size_t)h->prm.max_scans);
+    launch_fe_selection_last(h->dev, n_scans, kind, h->d_last, h->stream);
+    HC(hipGetLastError());
+    HC(hipMemcpyAsync(last_position, h->d_last, (size_t)n_scans * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HC(hipStreamSynchronize(h->stream));
     return 0;
 }
 

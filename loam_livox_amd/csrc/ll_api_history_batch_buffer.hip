@@ -73,9 +73,10 @@ extern "C" void ll_history_batch_destroy(ll_history_batch *h)
         voxel_free(h->vm[k]);
     }
     void *dev[] = {h->frames[0], h->frames[1], h->d_xf, h->d_nxf, h->d_concat, h->d_map, h->d_add, h->d_cnt, h->d_ref, h->d_mm, h->d_grid,
-                   h->d_nvalid, h->keys, h->keys2, h->vals, h->vals2, h->counts, h->tmp, h->d_cq_tab, h->d_cx_in, h->d_cx_out, h->d_cx_dst};
+                   h->d_nvalid, h->keys, h->keys2, h->vals, h->vals2, h->counts, h->tmp, h->d_cq_tab, h->d_cx_in, h->d_cx_out, h->d_cx_dst, h->d_und};
     for (void *p : dev)
         if (p) (void)hipFree(p);
+    if (h->ev_und) (void)hipEventDestroy(h->ev_und);
     for (int k = 0; k < 2; k++) hb_store_free(h->st[k]);
     hb_full_free(h);
     hb_scan_log_free(h);
@@ -129,9 +130,18 @@ extern "C" int32_t ll_history_batch_size(const ll_history_batch *h, int32_t sequ
     return (h && sequence >= 0 && sequence < h->S) ? h->size[sequence] : -1;
 }
 
-// slots 0 .. S-1 of a device-resident producer
+// one-shot (ll_history_batch_set_undistort): the records pending for the next add, taken by that add whatever becomes of it -- the
+// first thing both entry points do with their handle, ahead of their own refusals
+static bool history_batch_take_undistort(ll_history_batch *h)
+{
+    const bool und = h && h->has_und;
+    if (h) h->has_und = false;
+    return und;
+}
+
+// slots 0 .. S-1 of a device-resident producer; und: this add's clouds move with the registration's records (h->d_und)
 static int history_batch_add_common(const char *where, ll_history_batch *h, const FeatView &v, const int32_t *active, const double *poses7,
-                                    const double *gate_poses7, double t_step, double angle_step, int32_t *added)
+                                    const double *gate_poses7, double t_step, double angle_step, int32_t *added, bool und)
 {
     const int S = h->S;
     HC(hipSetDevice(h->device));
@@ -175,7 +185,10 @@ static int history_batch_add_common(const char *where, ll_history_batch *h, cons
     }
     if (n_work == 0) return 0;
     HC(hipMemcpyAsync(h->d_add, h->hp_add, (size_t)S * sizeof(HbAddSlot), hipMemcpyHostToDevice, h->stream));
-    launch_hb_transform(v.corner, v.n_corner, v.stride_c, v.surf, v.n_surf, v.stride_s, h->d_add, S, h->max_pts, h->d_xf, h->d_nxf, h->stream);  // :1421-1431
+    if (und)  // g_if_undistore = 1: every point with the pose interpolated at its time stamp (PCR:641-646); the poses still serve the rule and the cell maps
+        launch_hb_transform_undistort(v.corner, v.n_corner, v.stride_c, v.surf, v.n_surf, v.stride_s, h->d_add, h->d_und, S, h->max_pts, h->d_xf, h->d_nxf, h->stream);
+    else
+        launch_hb_transform(v.corner, v.n_corner, v.stride_c, v.surf, v.n_surf, v.stride_s, h->d_add, S, h->max_pts, h->d_xf, h->d_nxf, h->stream);  // :1421-1431
     const char *err = nullptr;
     for (int k = 0; k < 2; k++) {  // :1434-1437
         const float leaf[3] = {h->res[k], h->res[k], h->res[k]};
@@ -211,20 +224,42 @@ extern "C" int ll_history_batch_add_voxel(ll_history_batch *h, ll_voxel *vc, ll_
                                           const double *gate_poses7, double history_add_t_step, double history_add_angle_step, int32_t *added)
 {
     static const char *where = "ll_history_batch_add_voxel";
+    const bool und = history_batch_take_undistort(h);
     if (!h || !vc || !vs || !poses7) return set_err(where, "null argument");
     if (vc->device != h->device || vs->device != h->device) return set_err(where, "handles live on different devices");
     if (vc->dev.max_clouds < h->S || vs->dev.max_clouds < h->S) return set_err(where, "the voxel filters hold fewer clouds than n_sequences");
-    return history_batch_add_common(where, h, feat_view(vc, vs), active, poses7, gate_poses7, history_add_t_step, history_add_angle_step, added);
+    return history_batch_add_common(where, h, feat_view(vc, vs), active, poses7, gate_poses7, history_add_t_step, history_add_angle_step, added, und);
 }
 
 extern "C" int ll_history_batch_add_fe(ll_history_batch *h, ll_fe *fe, const int32_t *active, const double *poses7, const double *gate_poses7,
                                        double history_add_t_step, double history_add_angle_step, int32_t *added)
 {
     static const char *where = "ll_history_batch_add_fe";
+    const bool und = history_batch_take_undistort(h);
     if (!h || !fe || !poses7) return set_err(where, "null argument");
     if (fe->prm.device != h->device) return set_err(where, "extractor lives on another device");
     if (fe->prm.max_scans < h->S) return set_err(where, "the extractor holds fewer scans than n_sequences");
-    return history_batch_add_common(where, h, feat_view(fe), active, poses7, gate_poses7, history_add_t_step, history_add_angle_step, added);
+    return history_batch_add_common(where, h, feat_view(fe), active, poses7, gate_poses7, history_add_t_step, history_add_angle_step, added, und);
+}
+
+// g_if_undistore = 1 for the next add (laser_mapping.hpp:1424,1430), the batch form of ll_history_set_undistort: slot s of the registration
+// r collected last moves sequence s's clouds.  The S records are copied on the registrar's stream into memory of this handle -- the
+// registrar's next enqueue may follow at once -- and this handle's stream waits for the copy on the device; the host waits for nothing.
+extern "C" int ll_history_batch_set_undistort(ll_history_batch *h, ll_reg *r)
+{
+    static const char *where = "ll_history_batch_set_undistort";
+    if (!h || !r) return set_err(where, "null argument");
+    if (r->device != h->device) return set_err(where, "registrar lives on another device");
+    if (reg_undistort_records(where, r, h->S)) return -1;  // (refuses an uncollected enqueue and a registration of fewer than S scans)
+    if (!h->d_und) {
+        DM(h->d_und, (size_t)h->S);
+        HC(hipEventCreateWithFlags(&h->ev_und, hipEventDisableTiming));
+    }
+    HC(hipMemcpyAsync(h->d_und, r->d_und, (size_t)h->S * sizeof(UndistortRec), hipMemcpyDeviceToDevice, r->stream));
+    HC(hipEventRecord(h->ev_und, r->stream));
+    HC(hipStreamWaitEvent(h->stream, h->ev_und, 0));
+    h->has_und = true;
+    return 0;
 }
 
 void hb_sizes_out(const ll_history_batch *h, int64_t *n_map_corner, int64_t *n_map_surf)

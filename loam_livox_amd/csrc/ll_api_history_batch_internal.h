@@ -64,6 +64,11 @@ struct ll_history_batch {
     std::vector<int64_t> n_map[2];           // [S]
     // tables: pinned host copies and their device mirrors
     HbAddSlot *hp_add = nullptr, *d_add = nullptr;  // [S]
+    // ll_history_batch_set_undistort: the next add moves slot s's clouds with record s (copies this handle owns, made on the registrar's
+    // stream; ev_und orders this handle's stream behind them).  Both allocated by the first call.
+    UndistortRec *d_und = nullptr;                  // [S]
+    hipEvent_t ev_und = nullptr;
+    bool has_und = false;
     int *hp_cnt = nullptr, *d_cnt = nullptr;        // host [4 S]: input counts [2][S], filtered counts [2][S]; device [2][S] filtered counts
     char *hp_ref = nullptr, *d_ref = nullptr;       // refresh: int active[S], int n_concat[2][S], (16-byte aligned) HbSeg segs[2 S max_hist]
     size_t ref_seg_off = 0, ref_bytes = 0;

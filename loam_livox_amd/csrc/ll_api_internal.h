@@ -79,6 +79,7 @@ struct ll_fe {
     // kernel of the batch in flight could be enqueued
     int *hp_npts = nullptr;
     double *hp_time0 = nullptr;
+    int *d_last = nullptr;  // [max_scans] ll_fe_selection_last: the last position of every slot's selection (allocated by the first call)
 };
 
 // ============================================================================================== map
@@ -150,6 +151,10 @@ struct ll_reg {
     UndistortRec *d_und = nullptr;    // [max_scans] the collected registration's records (reg_undistort_records)
     UndistortJob *d_und_jobs = nullptr;  // [max_scans] job table of a batched launch
     int und_valid = 0;                // d_und holds the records of the registration collected last
+    // a time range per scan (ll_reg_set_time_ranges): nothing is allocated, launched or copied before the first call
+    float2 *hp_ts = nullptr, *d_ts = nullptr;  // [max_scans] {minimum, maximum time stamp}: pinned host staging, device table
+    int ts_pending = 0;               // n_scans of the table waiting for the next enqueue (one-shot; 0: none)
+    int ts_last = 0;                  // the last enqueue ran with motion deblur on d_ts (its deskew records take their ranges from it)
 };
 
 // ---------------------------------------------------------------------------------------------------- voxel grid

@@ -2,6 +2,7 @@
 // ll_reg_collect, the debug taps, ll_cloud_transform*.  This file owns the ordering of the registrar's stream behind the feature
 // producers and the map-snapshot pins of the solve in flight.
 #include "ll_api_internal.h"
+#include "ll_reg_query.h"  // padded_block_count, LL_TABLE_MAX_BLOCKS: the host's refusal and the solver kernels count a scan's blocks alike
 
 extern "C" void ll_reg_default_params(ll_reg_params *p)
 {
@@ -116,9 +117,10 @@ extern "C" void ll_reg_destroy(ll_reg *r)
     (void)hipSetDevice(r->device);
     RegDev &d = r->dev;
     void *ptrs[] = {d.state, d.blk_f, d.blk_av, d.blk_id, d.pl_tab, d.blk_flag, d.nn, d.qperm, d.qsorted, d.qperm_c, d.qw, d.ref_q, d.ref_p, d.ref_s, d.blk_flag0, d.work_search, d.work_build, d.work_cnt, d.work_off, d.grp_ctl, d.solve_order, d.grp_part, d.grp_xch, d.blk_l1, d.hash, d.dbg_idx, d.dbg_d2,
-                    r->d_corner, r->d_surf, r->d_nc, r->d_ns, r->d_pose_tmp, r->d_map_tab, r->d_info, r->d_und, r->d_und_jobs};
+                    r->d_corner, r->d_surf, r->d_nc, r->d_ns, r->d_pose_tmp, r->d_map_tab, r->d_info, r->d_und, r->d_und_jobs, r->d_ts};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    if (r->hp_ts) (void)hipHostFree(r->hp_ts);
     for (hipEvent_t e : r->ev) (void)hipEventDestroy(e);
     if (r->ev_wait) (void)hipEventDestroy(r->ev_wait);
     if (r->stream) (void)hipStreamDestroy(r->stream);
@@ -186,6 +188,27 @@ extern "C" int ll_reg_information_time(ll_reg *r, float *ms)
     if (!r) return set_err("ll_reg_information_time", "null handle");
     if (!ms) return set_err("ll_reg_information_time", "null output");
     *ms = r->prof_ms[3];  // (0 without ll_reg_set_profiling, or when the last collected enqueue had the switch off)
+    return 0;
+}
+
+// A time range per scan for the next enqueue with a map per slot (lock-step sequences: every slot runs from its own previous frame's
+// last stamp to this frame's, laser_mapping.hpp:1336-1347).  One-shot like ll_history_set_gate_pose: the next ll_reg_enqueue_fe_maps /
+// ll_reg_enqueue_fe_downsampled_maps takes the table, whether it succeeds or is refused.  The pairs wait in pinned memory and go up
+// with that enqueue's other per-scan data.
+extern "C" int ll_reg_set_time_ranges(ll_reg *r, const float *minimum_pt_time_stamp, const float *maximum_pt_time_stamp, int32_t n_scans)
+{
+    static const char *where = "ll_reg_set_time_ranges";
+    if (!r) return set_err(where, "null handle");
+    if (!minimum_pt_time_stamp || !maximum_pt_time_stamp) return set_err(where, "null argument");
+    if (n_scans < 1 || n_scans > r->max_scans) return set_err(where, "n_scans out of range");
+    if (!r->hp_ts) {
+        HC(hipSetDevice(r->device));
+        HC(hipHostMalloc((void **)&r->hp_ts, (size_t)r->max_scans * sizeof(float2), hipHostMallocDefault));
+        DM(r->d_ts, (size_t)r->max_scans);
+    }
+    // (the staging is free: the enqueue that read it last has drained the stream behind its copy, reg_exchange_counts)
+    for (int b = 0; b < n_scans; b++) r->hp_ts[b] = make_float2(minimum_pt_time_stamp[b], maximum_pt_time_stamp[b]);
+    r->ts_pending = n_scans;
     return 0;
 }
 
@@ -326,6 +349,7 @@ static int reg_begin(ll_reg *r, const ll_reg_params *prm, int *debug = nullptr)
     r->info_collected = 0;
     r->collected_scans = 0;
     r->und_valid = 0;
+    r->ts_last = 0;
     return 0;
 }
 
@@ -377,12 +401,13 @@ static int reg_size_check(const char *where, const ll_reg *r, const ll_reg_param
 }
 
 // gc / gs: the grids every scan ran against, or map_tab: the device table of a map per slot (then gc / gs are not read)
-static int reg_finish(ll_reg *r, int n_scans, PinGuard &pin_guard, const Grid &gc, const Grid &gs, const Grid *map_tab)
+// ts_tab: the device table of a time range per scan (a map per slot with motion deblur), else nullptr
+static int reg_finish(ll_reg *r, int n_scans, PinGuard &pin_guard, const Grid &gc, const Grid &gs, const Grid *map_tab, const float2 *ts_tab = nullptr)
 {
     if (r->info_enable) {
         // here the states still hold the last iteration's increment and pose_last, and the map snapshots are pinned
         prof_begin(r, 3);
-        launch_reg_information(r->dev, r->rc, gc, gs, map_tab, r->d_info, n_scans, r->stream);
+        launch_reg_information(r->dev, r->rc, gc, gs, map_tab, r->d_info, n_scans, r->stream, ts_tab);
         prof_end(r);
         r->info_enqueued = 1;
     }
@@ -395,6 +420,17 @@ static int reg_finish(ll_reg *r, int n_scans, PinGuard &pin_guard, const Grid &g
 }
 
 // ---- one map for the batch -----------------------------------------------------------------------------------------------------------
+// The first thing every single-map entry point does with its handle: a table of time ranges that is pending (ll_reg_set_time_ranges)
+// is dropped and the call refused, whatever else the call would have been refused for -- not silently ignored, and never left for a
+// later enqueue: a caller that set a range per scan expects a map per slot behind it.
+static int reg_refuse_pending_ranges(const char *where, ll_reg *r)
+{
+    if (!r || !r->ts_pending) return 0;
+    r->ts_pending = 0;
+    return set_err(where, "a table of time ranges is pending (ll_reg_set_time_ranges): it applies to the entry points with a map per slot "
+                          "only and has been dropped");
+}
+
 // common launch sequence; reg_bind has set the feature pointers in r->dev
 static int reg_enqueue(const char *where, ll_reg *r, const ll_map *map, int n_scans, const ll_reg_params *prm, const double *poses_last,
                        const double *poses_curr, const double *poses_incre, const int *known_counts = nullptr)
@@ -645,6 +681,7 @@ extern "C" int ll_reg_enqueue_fe(ll_reg *r, const ll_map *map, ll_fe *fe, int32_
                                  const double *poses_last, const double *poses_curr, const double *poses_incre)
 {
     static const char *where = "ll_reg_enqueue_fe";
+    if (reg_refuse_pending_ranges(where, r)) return -1;
     if (!r || !fe) return set_err(where, "null handle");
     if (fe->prm.device != r->device) return set_err(where, "extractor lives on another device");
     if (reg_fe_fits(where, r, fe, n_scans)) return -1;
@@ -655,13 +692,24 @@ extern "C" int ll_reg_enqueue_fe(ll_reg *r, const ll_map *map, ll_fe *fe, int32_
 
 // ---- a map per slot ---------------------------------------------------------------------------------------------------------------
 // what can be refused before anything is launched
+// the pending table of time ranges, taken by this enqueue whatever becomes of it (one-shot): its n_scans, or 0 when none was set
+static int reg_take_time_ranges(ll_reg *r)
+{
+    const int n = r->ts_pending;
+    r->ts_pending = 0;
+    return n;
+}
+
+// ts_n: what reg_take_time_ranges answered
 static int reg_maps_check(const char *where, ll_reg *r, const ll_map *const *maps, int n_scans, const ll_reg_params *prm, const double *poses_last,
-                          const double *poses_curr)
+                          const double *poses_curr, int ts_n)
 {
     if (!r || !maps) return set_err(where, "null argument");
     if (reg_params_check(where, r, n_scans, prm, poses_last, poses_curr)) return -1;
-    if (prm->if_motion_deblur)
-        return set_err(where, "motion deblur is not supported with a map per slot (if_motion_deblur must be 0): register such scans through the single-map entry points");
+    if (ts_n && ts_n != n_scans) return set_err(where, "the table of time ranges was set for another n_scans (ll_reg_set_time_ranges): dropped");
+    if (prm->if_motion_deblur && !ts_n)
+        return set_err(where, "motion deblur is not supported with a map per slot without a time range per scan (if_motion_deblur must be 0, or "
+                              "ll_reg_set_time_ranges in front of this call): the params' range is one pair for the batch");
     for (int b = 0; b < n_scans; b++)
         if (maps[b] && maps[b]->device != r->device) return set_err(where, "map lives on another device");
     return 0;
@@ -669,9 +717,13 @@ static int reg_maps_check(const char *where, ll_reg *r, const ll_map *const *map
 
 // reg_enqueue with a map per slot; reg_bind has set the feature pointers in r->dev and reg_maps_check passed.  The gate of PCR:199 is
 // decided per slot from that slot's map and frame index; maps[b] == nullptr is an idle slot (comes back gated).
+// deblur (reg_maps_check: only with a table of time ranges taken, r->hp_ts[0 .. n_scans)): the reference's *_mb problem per slot, slot b
+// over its own range -- the searches as below, the transform and the block constants with the slot's range, and solve_big<1> for every
+// running slot (ll_reg_big_maps_kernels.hip), which is what the single-map entry points give a deblur scan of any size.
 static int reg_enqueue_maps(const char *where, ll_reg *r, const ll_map *const *maps, int n_scans, const ll_reg_params *prm, const int32_t *frame_index,
                             const double *poses_last, const double *poses_curr, const double *poses_incre)
 {
+    const bool deblur = prm->if_motion_deblur != 0;
     if (reg_begin(r, prm)) return -1;
     PinGuard pin_guard{r};
     r->rc.knn_tile = 0;   // (no table form: their work items are not bound to one scan per workgroup; the lists are the same bit for bit)
@@ -708,6 +760,13 @@ static int reg_enqueue_maps(const char *where, ll_reg *r, const ll_map *const *m
     }
     r->last_gated = n_run ? 0 : 1;
     r->last_n_scans = n_scans;
+    if (deblur) {  // the ranges go up with the states and the grid table, ahead of the one wait reg_exchange_counts makes anyway
+        HC(hipMemcpyAsync(r->d_ts, r->hp_ts, (size_t)n_scans * sizeof(float2), hipMemcpyHostToDevice, r->stream));
+        // d_ts is rewritten HERE, behind reg_begin, and nowhere else: reg_undistort_records reads it lazily after the collect, and reg_begin
+        // has just cleared und_valid / collected_scans -- an upload inside ll_reg_set_time_ranges could change the ranges under the records
+        // of a registration that is still being read (a setter followed by a refused enqueue)
+        r->ts_last = 1;
+    }
     if (reg_exchange_counts(r, n_scans, true)) return -1;
     int max_nc = 0, max_ns = 0;  // over the slots that run: the others launch nothing
     RegMapsClasses cls{};        // ... and per solver form (reg_maps_class: the form each scan would get alone)
@@ -729,7 +788,22 @@ static int reg_enqueue_maps(const char *where, ll_reg *r, const ll_map *const *m
     for (int c = 0; c < 2; c++) cls.max_ns[c] = max_tot[c] - cls.max_nc[c];
     if (reg_size_check(where, r, prm, max_nc, max_ns, "")) return -1;
     r->rc.solve_group = cls.n[3] ? LL_GRP : 1;  // (here: whether the grouped solver's bookkeeping is needed; the launcher sets it per launch)
-    if (n_run) {
+    if (deblur) {  // no size classes: every running slot takes solve_big<1> on one workgroup
+        r->rc.solve_group = 1;
+        for (int b = 0; b < n_scans; b++)  // scan_is_compact (ll_reg_query.h) on the host's counts, through the definitions the kernel reads
+            if (!r->h_state[b].done && (r->rc.force_general || padded_block_count(r->h_nc[b], r->h_ns[b]) > LL_TABLE_MAX_BLOCKS))
+                return set_err(where, "a scan of this batch is beyond the compact solver's size (or the general solver was forced): not supported with a map "
+                                      "per slot, register such scans through the single-map entry points");
+        for (int it = 0; n_run && it < prm->icp_max_iterations; it++) {
+            r->rc.xch_epoch = it + 1;
+            prof_begin(r, 0);
+            launch_reg_knn_build_maps(r->dev, r->rc, r->d_map_tab, n_scans, it, max_nc, max_ns, r->stream, r->d_ts);
+            prof_end(r);
+            prof_begin(r, 1);
+            launch_reg_solve_big_maps(r->dev, r->rc, r->d_map_tab, r->d_ts, n_scans, r->stream);
+            prof_end(r);
+        }
+    } else if (n_run) {
         if ((cls.n[2] && !reg_solve_fast_eligible(r->rc, cls.max_nc[2], cls.max_ns[2])) || (cls.n[3] && !reg_solve_fast_eligible(r->rc, cls.max_nc[3], cls.max_ns[3])))
             return set_err(where, "a scan of this batch is beyond the compact solver's size (or the general solver was forced): not supported with a map "
                                   "per slot, register such scans through the single-map entry points");
@@ -747,15 +821,16 @@ static int reg_enqueue_maps(const char *where, ll_reg *r, const ll_map *const *m
         }
     }
     const Grid none{};
-    return reg_finish(r, n_scans, pin_guard, none, none, r->d_map_tab);
+    return reg_finish(r, n_scans, pin_guard, none, none, r->d_map_tab, deblur ? r->d_ts : nullptr);
 }
 
 extern "C" int ll_reg_enqueue_fe_maps(ll_reg *r, const ll_map *const *maps, ll_fe *fe, int32_t n_scans, const ll_reg_params *prm,
                                       const int32_t *frame_index, const double *poses_last, const double *poses_curr, const double *poses_incre)
 {
     static const char *where = "ll_reg_enqueue_fe_maps";
+    const int ts_n = r ? reg_take_time_ranges(r) : 0;
     if (!r || !fe) return set_err(where, "null handle");
-    if (reg_maps_check(where, r, maps, n_scans, prm, poses_last, poses_curr)) return -1;
+    if (reg_maps_check(where, r, maps, n_scans, prm, poses_last, poses_curr, ts_n)) return -1;
     if (fe->prm.device != r->device) return set_err(where, "extractor lives on another device");
     if (reg_fe_fits(where, r, fe, n_scans)) return -1;
     HC(hipSetDevice(r->device));
@@ -793,6 +868,7 @@ int ll::reg_enqueue_device_clouds(const char *where, ll_reg *r, const ll_map *ma
                                   const float4 *d_surf, const int *d_n_surf, int n_surf, const ll_reg_params *prm, const double pose_last[7],
                                   const double pose_curr[7], const double pose_incre[7])
 {
+    if (reg_refuse_pending_ranges(where, r)) return -1;
     HC(hipSetDevice(r->device));
     const FeatView v{d_corner, d_surf, d_n_corner, d_n_surf, n_corner > 0 ? n_corner : 1, n_surf > 0 ? n_surf : 1, {nullptr, nullptr}};
     if (reg_bind(r, v)) return -1;
@@ -805,6 +881,7 @@ extern "C" int ll_reg_enqueue_fe_downsampled(ll_reg *r, const ll_map *map, ll_fe
                                              const double *poses_curr, const double *poses_incre)
 {
     static const char *where = "ll_reg_enqueue_fe_downsampled";
+    if (reg_refuse_pending_ranges(where, r)) return -1;
     if (!r || !fe || !vc || !vs) return set_err(where, "null handle");
     if (fe->prm.device != r->device) return set_err(where, "handles live on different devices");
     if (reg_voxel_check(where, r, vc, vs)) return -1;
@@ -821,8 +898,9 @@ extern "C" int ll_reg_enqueue_fe_downsampled_maps(ll_reg *r, const ll_map *const
                                                   const double *poses_last, const double *poses_curr, const double *poses_incre)
 {
     static const char *where = "ll_reg_enqueue_fe_downsampled_maps";
+    const int ts_n = r ? reg_take_time_ranges(r) : 0;
     if (!r || !fe || !vc || !vs) return set_err(where, "null handle");
-    if (reg_maps_check(where, r, maps, n_scans, prm, poses_last, poses_curr)) return -1;
+    if (reg_maps_check(where, r, maps, n_scans, prm, poses_last, poses_curr, ts_n)) return -1;
     if (fe->prm.device != r->device) return set_err(where, "handles live on different devices");
     if (reg_voxel_check(where, r, vc, vs)) return -1;
     if (n_scans > vc->dev.max_clouds || n_scans > vs->dev.max_clouds) return set_err(where, "n_scans exceeds the voxel filters' max_clouds");
@@ -876,6 +954,7 @@ extern "C" int ll_reg_enqueue_fe_merged(ll_reg *r, const ll_map *map, ll_fe *fe,
                                         const double *poses_last, const double *poses_curr, const double *poses_incre)
 {
     static const char *where = "ll_reg_enqueue_fe_merged";
+    if (reg_refuse_pending_ranges(where, r)) return -1;
     if (!r || !fe) return set_err(where, "null handle");
     if (fe->prm.device != r->device) return set_err(where, "extractor lives on another device");
     if (heads < 1 || n_scans < 1 || n_scans > r->max_scans || (int64_t)n_scans * heads > fe->prm.max_scans)
@@ -896,6 +975,7 @@ extern "C" int ll_reg_enqueue_uploaded(ll_reg *r, const ll_map *map, int32_t n_s
                                        const double *poses_curr, const double *poses_incre)
 {
     static const char *where = "ll_reg_enqueue_uploaded";
+    if (reg_refuse_pending_ranges(where, r)) return -1;
     if (!r) return set_err(where, "null handle");
     if (n_scans < 1 || n_scans > r->uploaded_scans) return set_err(where, "no features uploaded for that many scans");
     HC(hipSetDevice(r->device));
@@ -908,6 +988,7 @@ extern "C" int ll_reg_solve_batch(ll_reg *r, const ll_map *map, int32_t n_scans,
                                   const ll_reg_params *prm, const double *poses_last, double *poses_curr, double *poses_incre,
                                   ll_reg_report *reports, int32_t *results)
 {
+    if (reg_refuse_pending_ranges("ll_reg_solve_batch", r)) return -1;  // (before the upload: the enqueue behind it would refuse anyway)
     if (ll_reg_upload_features(r, n_scans, corner_xyzi, n_corner, stride_corner, surf_xyzi, n_surf, stride_surf)) return -1;
     if (ll_reg_enqueue_uploaded(r, map, n_scans, prm, poses_last, poses_curr, poses_incre)) return -1;
     return ll_reg_collect(r, n_scans, poses_curr, poses_incre, reports, results);
@@ -1029,6 +1110,7 @@ extern "C" int ll_reg_enqueue_spin(ll_reg *r, const ll_map *map, ll_spin *sp, in
                                    const double *poses_last, const double *poses_curr, const double *poses_incre)
 {
     static const char *where = "ll_reg_enqueue_spin";
+    if (reg_refuse_pending_ranges(where, r)) return -1;
     SpinView v;
     if (reg_spin_check(where, r, sp, n_scans, prm, &v)) return -1;
     if (spin_handoff(sp, n_scans, &v)) return -1;
@@ -1042,6 +1124,7 @@ extern "C" int ll_reg_enqueue_spin_downsampled(ll_reg *r, const ll_map *map, ll_
                                                const double *poses_curr, const double *poses_incre)
 {
     static const char *where = "ll_reg_enqueue_spin_downsampled";
+    if (reg_refuse_pending_ranges(where, r)) return -1;
     if (!vc || !vs) return set_err(where, "null handle");
     SpinView v;
     if (reg_spin_check(where, r, sp, n_scans, prm, &v)) return -1;
@@ -1111,7 +1194,7 @@ int ll::reg_undistort_records(const char *where, ll_reg *r, int n_slots)
         DM(r->d_und_jobs, (size_t)r->max_scans);
     }
     if (!r->und_valid) {
-        launch_undistort_snapshot(r->dev.state, 0, r->last_n_scans, r->rc, r->d_und, r->stream);
+        launch_undistort_snapshot(r->dev.state, 0, r->last_n_scans, r->rc, r->d_und, r->stream, r->ts_last ? r->d_ts : nullptr);
         HC(hipGetLastError());
         r->und_valid = 1;
     }

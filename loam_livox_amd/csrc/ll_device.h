@@ -72,6 +72,8 @@ struct FeDev {
 void launch_fe_point(const FeDev &fb, const FeConst &fc, int n_scans, int max_n, hipStream_t s);
 void launch_fe_split(const FeDev &fb, int pieces, int n_scans, hipStream_t s);
 void launch_fe_select(const FeDev &fb, int n_scans, int piece, float min_blur, float max_blur, hipStream_t s);
+// d_last[b] = the last entry of slot b's selection of kind (0 corner, 1 surface, 2 full: fb.full_idx must exist), -1 where it is empty
+void launch_fe_selection_last(const FeDev &fb, int n_scans, int kind, int *d_last, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ map grid
 
@@ -225,7 +227,11 @@ int reg_solve_small_waves(const RegConst &rc, int n_scans, int max_nc, int max_n
 // A map per slot (ll_reg_enqueue_fe_maps): map_tab[2 b] / map_tab[2 b + 1] are the corner / surface grid of scan b, in device memory.
 // Per-lane or per-wavefront searches of every query in every ICP iteration (no tile search, no reuse lists), the small solver or
 // reg_solve_kernel's table form; the caller refuses motion deblur and batches beyond reg_solve_fast_eligible.
-void launch_reg_knn_build_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, int iter, int max_nc, int max_ns, hipStream_t s);
+// ts_tab (ll_reg_set_time_ranges; motion deblur with a map per slot): {minimum, maximum time stamp} of scan b at ts_tab[b], in device
+// memory; the transform and the block constants of scan b then read its pair where the single-map kernels read rc.min_ts / rc.max_ts.
+// nullptr: the launches of a map per slot without motion deblur, unchanged.
+void launch_reg_knn_build_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, int iter, int max_nc, int max_ns, hipStream_t s,
+                               const float2 *ts_tab = nullptr);
 // The solver form is chosen PER SLOT, as the single-map entry points would choose it for that scan alone (the forms group their sums
 // differently and agree to rounding only; a slot must give the bits of its own registration): class 0 = the small solver's
 // four-wavefront form (up to 1024 blocks; whatever the batch size: the one- and two-wavefront forms of large single-map batches are
@@ -242,6 +248,10 @@ struct RegMapsClasses {
     int grp_min;
 };
 void launch_reg_solve_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, const RegMapsClasses &cls, int iter, hipStream_t s);
+// Motion deblur with a map per slot: reg_solve_big_kernel<1>'s plane-table path (solve_big<1>) for every running scan, one workgroup each,
+// the surface map from map_tab[2 b + 1] and the time range from ts_tab[b] (ll_reg_big_maps_kernels.hip).  The caller has refused scans
+// that scan_is_compact would send to solve_general.
+void launch_reg_solve_big_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, const float2 *ts_tab, int n_scans, hipStream_t s);
 void launch_reg_solve_small_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, int cls, int max_nc, int max_ns, int iter, hipStream_t s);
 void launch_reg_finalize(const RegDev &rd, const RegConst &rc, int n_scans, hipStream_t s);
 void launch_cloud_transform(const float4 *in, float4 *out, int n, const double *d_pose, hipStream_t s);
@@ -259,7 +269,8 @@ struct UndistortJob {  // one slot of a cloud_undistort_kernel launch
     long long src_off, dst_off;  // first point in src / dst
 };
 // recs[first + k] <- state[first + k], k < n.  A gated slot gets the identity increment: both poses = pose_last, theta 0, zero matrices.
-void launch_undistort_snapshot(const RegState *state, int first, int n, const RegConst &rc, UndistortRec *recs, hipStream_t s);
+// ts_tab != nullptr: record k takes its time range from ts_tab[first + k] (a registration with a range per scan) instead of rc's.
+void launch_undistort_snapshot(const RegState *state, int first, int n, const RegConst &rc, UndistortRec *recs, hipStream_t s, const float2 *ts_tab = nullptr);
 // grid (ceil(max_n / 256), n_slots): slot b moves jobs[b].n points with recs[jobs[b].rec].  d_jobs == nullptr: the one slot `one`.
 // pick != nullptr: point i of a slot is src[src_off + pick[src_off + i]] with intensity pick_w[same] (the extractor's full selection).
 void launch_cloud_undistort(const UndistortRec *recs, const UndistortJob *d_jobs, const UndistortJob &one, int n_slots, int max_n, const float4 *src,

@@ -478,6 +478,17 @@ __global__ __launch_bounds__(SP_THREADS) void fe_select_kernel(FeDev fb, int pie
     }
 }
 
+// one lane per slot: the last entry of the slot's selection of `kind`, which fe_select_kernel writes in ascending order
+__global__ void fe_selection_last_kernel(FeDev fb, int n_scans, int kind, int *last)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_scans) return;
+    const int *idx = kind == 0 ? fb.corner_idx : kind == 1 ? fb.surf_idx : fb.full_idx;
+    int n = kind == 0 ? fb.n_corner[b] : kind == 1 ? fb.n_surf[b] : fb.n_full[b];
+    n = n < fb.stride ? n : fb.stride;
+    last[b] = n > 0 ? idx[(size_t)b * fb.stride + n - 1] : -1;
+}
+
 // ---- launch wrappers (called from ll_api.hip) --------------------------------------------------------------
 void launch_fe_point(const FeDev &fb, const FeConst &fc, int n_scans, int max_n, hipStream_t s)
 {
@@ -491,6 +502,10 @@ void launch_fe_split(const FeDev &fb, int pieces, int n_scans, hipStream_t s)
 void launch_fe_select(const FeDev &fb, int n_scans, int piece, float min_blur, float max_blur, hipStream_t s)
 {
     hipLaunchKernelGGL(fe_select_kernel, dim3(n_scans), dim3(SP_THREADS), 0, s, fb, piece, min_blur, max_blur);
+}
+void launch_fe_selection_last(const FeDev &fb, int n_scans, int kind, int *d_last, hipStream_t s)
+{
+    hipLaunchKernelGGL(fe_selection_last_kernel, dim3((n_scans + 63) / 64), dim3(64), 0, s, fb, n_scans, kind, d_last);
 }
 
 }  // namespace ll

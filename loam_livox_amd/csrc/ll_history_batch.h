@@ -38,6 +38,9 @@ struct HbGrid {
 
 void launch_hb_transform(const float4 *src_c, const int *n_c, int stride_c, const float4 *src_s, const int *n_s, int stride_s,
                          const HbAddSlot *tab, int n_slots, int max_pts, float4 *xf, int *n_xf, hipStream_t s);
+// the same with slot s's clouds moved by recs[s] (a registration's deskew records, ll_device.h) instead of tab[s].pose
+void launch_hb_transform_undistort(const float4 *src_c, const int *n_c, int stride_c, const float4 *src_s, const int *n_s, int stride_s,
+                                   const HbAddSlot *tab, const UndistortRec *recs, int n_slots, int max_pts, float4 *xf, int *n_xf, hipStream_t s);
 void launch_hb_scatter(const float4 *out_c, const int *n_out_c, const float4 *out_s, const int *n_out_s, int stride, const HbAddSlot *tab,
                        int n_slots, int max_pts, int ring_slots, float4 *frames_c, float4 *frames_s, int *cnt, hipStream_t s);
 void launch_hb_gather_frames(const float4 *frames_c, const float4 *frames_s, const HbSeg *segs, int n_seg, int max_pts, float4 *concat,

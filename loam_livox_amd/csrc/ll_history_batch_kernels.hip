@@ -25,6 +25,22 @@ namespace ll {
     } while (0)
 
 // ---- add ---------------------------------------------------------------------------------------------------------------------
+// what the two transform kernels below share: the points this block's (slot, kind) moves -- the cloud's count within the slot's capacity
+// and the producer's stride, 0 for a slot that does not work -- which the block's first thread also writes to n_xf[kind][slot]
+__device__ __forceinline__ int hb_transform_count(const int *n_c, const int *n_s, int stride, const HbAddSlot *tab, int n_slots, int max_pts, int *n_xf)
+{
+    const int s = blockIdx.y, kind = blockIdx.z;
+    int n = 0;
+    if (tab[s].work) {
+        n = kind ? n_s[s] : n_c[s];
+        n = n < 0 ? 0 : n;
+        n = n < max_pts ? n : max_pts;
+        n = n < stride ? n : stride;
+    }
+    if (blockIdx.x * 256 + threadIdx.x == 0) n_xf[kind * n_slots + s] = n;
+    return n;
+}
+
 // grid (chunks of 256 points, slots, 2 kinds): both clouds of every working slot into the map frame (laser_mapping.hpp:1421-1431)
 __global__ __launch_bounds__(256) void hb_transform_kernel(const float4 *src_c, const int *n_c, int stride_c, const float4 *src_s,
                                                            const int *n_s, int stride_s, const HbAddSlot *tab, int n_slots, int max_pts,
@@ -33,21 +49,31 @@ __global__ __launch_bounds__(256) void hb_transform_kernel(const float4 *src_c, 
     const int s = blockIdx.y, kind = blockIdx.z;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int stride = kind ? stride_s : stride_c;
-    int n = 0;
-    if (tab[s].work) {
-        n = kind ? n_s[s] : n_c[s];
-        n = n < 0 ? 0 : n;
-        n = n < max_pts ? n : max_pts;
-        n = n < stride ? n : stride;
-    }
-    if (i == 0) n_xf[kind * n_slots + s] = n;
-    if (i >= n) return;
+    if (i >= hb_transform_count(n_c, n_s, stride, tab, n_slots, max_pts, n_xf)) return;
     double p[7];
 #pragma unroll
     for (int k = 0; k < 7; k++) p[k] = tab[s].pose[k];
     const float4 v = (kind ? src_s : src_c)[(size_t)s * stride + i];
     float o[3];
     point_to_map(p, v.x, v.y, v.z, o);
+    xf[((size_t)kind * n_slots + s) * max_pts + i] = make_float4(o[0], o[1], o[2], v.w);
+}
+
+// The deskew form (ll_history_batch_set_undistort; g_if_undistore = 1, laser_mapping.hpp:1424,1430): slot s's clouds move with record
+// recs[s] of the registration -- every point with the pose interpolated at its time stamp, point_to_map_undistort as
+// cloud_undistort_kernel calls it -- instead of tab[s].pose.  The slot is the block's y index, so its record arrives through scalar loads.
+__global__ __launch_bounds__(256) void hb_transform_undistort_kernel(const float4 *src_c, const int *n_c, int stride_c, const float4 *src_s,
+                                                                     const int *n_s, int stride_s, const HbAddSlot *tab, const UndistortRec *__restrict__ recs,
+                                                                     int n_slots, int max_pts, float4 *xf, int *n_xf)
+{
+    const int s = blockIdx.y, kind = blockIdx.z;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int stride = kind ? stride_s : stride_c;
+    if (i >= hb_transform_count(n_c, n_s, stride, tab, n_slots, max_pts, n_xf)) return;
+    const UndistortRec &c = recs[s];
+    const float4 v = (kind ? src_s : src_c)[(size_t)s * stride + i];
+    float o[3];
+    point_to_map_undistort(c.pose_last, c.pose_curr, c.inc_t, c.theta, c.hat, c.hat_sq, c.deblur, c.min_ts, c.max_ts, v, o);
     xf[((size_t)kind * n_slots + s) * max_pts + i] = make_float4(o[0], o[1], o[2], v.w);
 }
 
@@ -192,6 +218,13 @@ void launch_hb_transform(const float4 *src_c, const int *n_c, int stride_c, cons
 {
     hipLaunchKernelGGL(hb_transform_kernel, dim3((max_pts + 255) / 256, n_slots, 2), dim3(256), 0, s, src_c, n_c, stride_c, src_s, n_s, stride_s,
                        tab, n_slots, max_pts, xf, n_xf);
+}
+
+void launch_hb_transform_undistort(const float4 *src_c, const int *n_c, int stride_c, const float4 *src_s, const int *n_s, int stride_s,
+                                   const HbAddSlot *tab, const UndistortRec *recs, int n_slots, int max_pts, float4 *xf, int *n_xf, hipStream_t s)
+{
+    hipLaunchKernelGGL(hb_transform_undistort_kernel, dim3((max_pts + 255) / 256, n_slots, 2), dim3(256), 0, s, src_c, n_c, stride_c, src_s, n_s,
+                       stride_s, tab, recs, n_slots, max_pts, xf, n_xf);
 }
 
 void launch_hb_scatter(const float4 *out_c, const int *n_out_c, const float4 *out_s, const int *n_out_s, int stride, const HbAddSlot *tab,

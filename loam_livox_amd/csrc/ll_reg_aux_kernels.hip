@@ -57,7 +57,8 @@ void launch_cloud_transform(const float4 *in, float4 *out, int n, const double *
 
 // Deskewed clouds, step 1: the constants of a collected registration out of the solver states into records the consumer owns
 // (the states are overwritten by the next enqueue's upload).  One lane per slot.
-__global__ void undistort_snapshot_kernel(const RegState *state, int first, int n, int deblur, float min_ts, float max_ts, UndistortRec *recs)
+__global__ void undistort_snapshot_kernel(const RegState *state, int first, int n, int deblur, float min_ts, float max_ts, const float2 *ts_tab,
+                                          UndistortRec *recs)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
@@ -75,14 +76,14 @@ __global__ void undistort_snapshot_kernel(const RegState *state, int first, int 
         o->hat_sq[i] = gated ? 0.0 : st->hat_sq[i];
     }
     o->deblur = deblur;
-    o->min_ts = min_ts;
-    o->max_ts = max_ts;
+    o->min_ts = ts_tab ? ts_tab[first + k].x : min_ts;  // (a registration with a time range per scan: ll_reg_set_time_ranges)
+    o->max_ts = ts_tab ? ts_tab[first + k].y : max_ts;
     o->pad = 0;
 }
-void launch_undistort_snapshot(const RegState *state, int first, int n, const RegConst &rc, UndistortRec *recs, hipStream_t s)
+void launch_undistort_snapshot(const RegState *state, int first, int n, const RegConst &rc, UndistortRec *recs, hipStream_t s, const float2 *ts_tab)
 {
     if (n <= 0) return;
-    hipLaunchKernelGGL(undistort_snapshot_kernel, dim3((n + 63) / 64), dim3(64), 0, s, state, first, n, rc.if_motion_deblur, rc.min_ts, rc.max_ts, recs);
+    hipLaunchKernelGGL(undistort_snapshot_kernel, dim3((n + 63) / 64), dim3(64), 0, s, state, first, n, rc.if_motion_deblur, rc.min_ts, rc.max_ts, ts_tab, recs);
 }
 
 // Deskewed clouds, step 2: pointcloudAssociateToMap( in, out, if_undistore = 1 ) (PCR:673-685) for the slots of a batch in one launch.

@@ -164,7 +164,8 @@ inline void info_reduce_serial(const double (*acc)[LL_NACC], int nt, double sum[
 namespace ll {
 // one workgroup of LL_INFO_THREADS per scan, behind the last ICP iteration and in front of reg_finalize_kernel; out[n_scans] in device
 // memory.  map_tab == nullptr: every scan against the grids gc / gs; otherwise scan b against map_tab[2 b] / map_tab[2 b + 1].
+// ts_tab (with map_tab and motion deblur only): scan b's time range is ts_tab[b] = {minimum, maximum} instead of rc's pair.
 void launch_reg_information(const RegDev &rd, const RegConst &rc, const Grid &gc, const Grid &gs, const Grid *map_tab, InfoRecord *out, int n_scans,
-                            hipStream_t s);
+                            hipStream_t s, const float2 *ts_tab = nullptr);
 }  // namespace ll
 #endif

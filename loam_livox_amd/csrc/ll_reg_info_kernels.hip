@@ -18,7 +18,7 @@ static_assert(LL_INFO_THREADS % 64 == 0, "whole wavefronts");
 
 template <int DEBLUR, bool TABLE>
 __global__ __launch_bounds__(LL_INFO_THREADS) void reg_information_kernel(RegDev rd, RegConst rc, Grid gc, Grid gs, const Grid *map_tab, InfoRecord *out,
-                                                                          int n_scans)
+                                                                          int n_scans, const float2 *ts_tab)
 {
     constexpr int W = LL_INFO_THREADS / 64;
     __shared__ double s_red[W][LL_NACC];
@@ -57,6 +57,11 @@ __global__ __launch_bounds__(LL_INFO_THREADS) void reg_information_kernel(RegDev
     s.cap_c = rd.cap_c;
     s.min_ts = rc.min_ts;
     s.max_ts = rc.max_ts;
+    if (TABLE && DEBLUR) {  // a time range per scan (ll_reg_set_time_ranges); behind the status test: idle and gated slots have left
+        const float2 ts = ts_tab[b];
+        s.min_ts = ts.x;
+        s.max_ts = ts.y;
+    }
     s.huber_a = rc.huber_a;
     double x[7];
 #pragma unroll
@@ -94,16 +99,18 @@ __global__ __launch_bounds__(LL_INFO_THREADS) void reg_information_kernel(RegDev
 }
 
 void launch_reg_information(const RegDev &rd, const RegConst &rc, const Grid &gc, const Grid &gs, const Grid *map_tab, InfoRecord *out, int n_scans,
-                            hipStream_t s)
+                            hipStream_t s, const float2 *ts_tab)
 {
     if (n_scans <= 0) return;
     const dim3 grid(n_scans), block(LL_INFO_THREADS);
-    if (map_tab)
-        hipLaunchKernelGGL((reg_information_kernel<0, true>), grid, block, 0, s, rd, rc, gc, gs, map_tab, out, n_scans);
+    if (map_tab && rc.if_motion_deblur)  // (the caller has a table of ranges: ll_reg_enqueue_fe_maps refuses deblur without one)
+        hipLaunchKernelGGL((reg_information_kernel<1, true>), grid, block, 0, s, rd, rc, gc, gs, map_tab, out, n_scans, ts_tab);
+    else if (map_tab)
+        hipLaunchKernelGGL((reg_information_kernel<0, true>), grid, block, 0, s, rd, rc, gc, gs, map_tab, out, n_scans, ts_tab);
     else if (rc.if_motion_deblur)
-        hipLaunchKernelGGL((reg_information_kernel<1, false>), grid, block, 0, s, rd, rc, gc, gs, map_tab, out, n_scans);
+        hipLaunchKernelGGL((reg_information_kernel<1, false>), grid, block, 0, s, rd, rc, gc, gs, map_tab, out, n_scans, ts_tab);
     else
-        hipLaunchKernelGGL((reg_information_kernel<0, false>), grid, block, 0, s, rd, rc, gc, gs, map_tab, out, n_scans);
+        hipLaunchKernelGGL((reg_information_kernel<0, false>), grid, block, 0, s, rd, rc, gc, gs, map_tab, out, n_scans, ts_tab);
 }
 
 }  // namespace ll

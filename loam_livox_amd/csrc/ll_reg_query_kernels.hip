@@ -363,6 +363,44 @@ __global__ __launch_bounds__(KB_THREADS) void reg_build_maps_kernel(RegDev rd, R
     build_one(rd, rc, gc, gs, b, (kind ? rd.cap_c : 0) + q);
 }
 
+// Motion deblur with a map per slot (ll_reg_set_time_ranges): the two per-query steps that read the time range -- the transform
+// (transform_query -> point_to_map_undistort) and the blur ratio of the block constants (build_one's sblur) -- with scan b's own pair
+// from ts_tab[b] in place of rc.min_ts / rc.max_ts.  The scan is uniform per workgroup, so the pair arrives through a scalar load
+// and lands in a copy of the constants; the arithmetic is transform_query's and build_one's, and the searches in between do not read
+// the range.  Kernels of their own: reg_transform_kernel and reg_build_maps_kernel keep their argument lists and their code.
+__global__ __launch_bounds__(KB_THREADS) void reg_transform_ranges_kernel(RegDev rd, RegConst rc, const float2 *__restrict__ ts_tab)
+{
+    const int b = blockIdx.y, kind = blockIdx.z;
+    const RegState *st = rd.state + b;
+    if (st->done) return;
+    const int n = kind ? rd.n_surf[b] : rd.n_corner[b];
+    const int q = blockIdx.x * KB_THREADS + threadIdx.x;
+    if (q >= n) return;
+    const float2 ts = ts_tab[b];
+    rc.min_ts = ts.x;
+    rc.max_ts = ts.y;
+    const int slot = (kind ? rd.cap_c : 0) + q;
+    float pw[3];
+    transform_query(st, rc, load_feature(rd, b, kind, q), pw);
+    if (subsample_skip_feature(rc.subsample_seed, kind, st->icp_iters, q, n, rc.max_blocks)) pw[0] = pw[1] = pw[2] = NAN;  // (as reg_transform_kernel)
+    rd.qw[(size_t)b * rd.cap + slot] = make_float4(pw[0], pw[1], pw[2], 0.f);
+}
+
+__global__ __launch_bounds__(KB_THREADS) void reg_build_ranges_kernel(RegDev rd, RegConst rc, const Grid *__restrict__ map_tab, const float2 *__restrict__ ts_tab)
+{
+    const int b = blockIdx.y, kind = blockIdx.z;
+    const RegState *st = rd.state + b;
+    if (st->done) return;
+    const int n = kind ? rd.n_surf[b] : rd.n_corner[b];
+    const int q = blockIdx.x * KB_THREADS + threadIdx.x;
+    if (q >= n) return;
+    const Grid gc = map_tab[2 * b], gs = map_tab[2 * b + 1];
+    const float2 ts = ts_tab[b];
+    rc.min_ts = ts.x;
+    rc.max_ts = ts.y;
+    build_one(rd, rc, gc, gs, b, (kind ? rd.cap_c : 0) + q);
+}
+
 // ---- launch wrappers -------------------------------------------------------------------------------------------
 void launch_reg_knn_build(const RegDev &rd, const RegConst &rc, const Grid &gc, const Grid &gs, int n_scans, int iter,
                           int max_nc, int max_ns, hipStream_t s)
@@ -431,13 +469,17 @@ void launch_reg_knn_build(const RegDev &rd, const RegConst &rc, const Grid &gc, 
 // wavefront for the batches the single-map launcher serves that way -- and every block is rebuilt.  The tile search and the reuse
 // lists have no table form (their work items are not bound to one scan per workgroup); the caller clears rc.knn_tile and
 // rc.knn_reuse.  Every search form returns the same neighbour lists, so a slot gets the bits of its single-map registration.
-void launch_reg_knn_build_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, int iter, int max_nc, int max_ns, hipStream_t s)
+void launch_reg_knn_build_maps(const RegDev &rd, const RegConst &rc, const Grid *map_tab, int n_scans, int iter, int max_nc, int max_ns, hipStream_t s,
+                               const float2 *ts_tab)
 {
     (void)iter;
     const int mx = max_nc > max_ns ? max_nc : max_ns;
     if (mx <= 0) return;
     const dim3 grid((mx + KB_THREADS - 1) / KB_THREADS, n_scans, 2);
-    hipLaunchKernelGGL(reg_transform_kernel, grid, dim3(KB_THREADS), 0, s, rd, rc, 0);
+    if (ts_tab)
+        hipLaunchKernelGGL(reg_transform_ranges_kernel, grid, dim3(KB_THREADS), 0, s, rd, rc, ts_tab);
+    else
+        hipLaunchKernelGGL(reg_transform_kernel, grid, dim3(KB_THREADS), 0, s, rd, rc, 0);
     int coop_kinds = 0;
     if (rc.knn_coop && n_scans <= LL_KNN_COOP_MAX_SCANS) {
         if (max_nc > 0) coop_kinds |= 1;
@@ -453,7 +495,10 @@ void launch_reg_knn_build_maps(const RegDev &rd, const RegConst &rc, const Grid 
         hipLaunchKernelGGL(reg_knn_maps_kernel, dim3((mk + KB_THREADS - 1) / KB_THREADS, n_scans, 2), dim3(KB_THREADS), 0, s, rd, rc, map_tab, iter,
                            coop_kinds);
     }
-    hipLaunchKernelGGL(reg_build_maps_kernel, grid, dim3(KB_THREADS), 0, s, rd, rc, map_tab);
+    if (ts_tab)
+        hipLaunchKernelGGL(reg_build_ranges_kernel, grid, dim3(KB_THREADS), 0, s, rd, rc, map_tab, ts_tab);
+    else
+        hipLaunchKernelGGL(reg_build_maps_kernel, grid, dim3(KB_THREADS), 0, s, rd, rc, map_tab);
 }
 
 }  // namespace ll

@@ -371,6 +371,12 @@ class Laser_mapping_batch:
     sequence.  Takes the arguments of Laser_mapping; Livox scans only, in history mode unless cell_matching=True (below): lidar_type
     other than "livox", matching_mode, loop_closure_if_enable and keep_cell_maps raise ValueError.
 
+    if_motion_deblur=1 registers every sequence with the reference's *_mb problem over its own time range -- from its previous frame's
+    last stamp to this frame's (m_last_time_stamp[s]; one Livox_laser.selection_last and one Point_cloud_registration.set_time_ranges per
+    enqueue) -- and if_undistort=1 builds every sequence's match buffer from deskewed clouds (History_buffer.set_undistort per sequence,
+    or one History_buffer_batch.set_undistort): Laser_mapping(if_motion_deblur=1, if_undistort=1) per sequence, bit for bit.
+    if_undistort=1 with full_maps=True raises ValueError.
+
     batched_history=True keeps all histories in ONE History_buffer_batch: the slots a step accepted go through one add and one
     refresh, whose launches and host waits do not grow with n_sequences (no thread pool, no per-sequence handles; refresh_threads is
     ignored).  Same bits per sequence; histories[s] is then a view of slot s that offers len() and map_cloud(kind).
@@ -438,6 +444,13 @@ class Laser_mapping_batch:
             raise ValueError("full_maps=True needs batched_history=True: the full-cloud maps live on the History_buffer_batch")
         if key_frames and not full_maps:
             raise ValueError("key_frames=True needs full_maps=True: a key frame is a set of cells of the sequence's full-cloud map")
+        # if_motion_deblur / if_undistort: Laser_mapping's switches per sequence (class docstring).  Both 0: the loop makes exactly the
+        # calls it makes without them.
+        self.if_motion_deblur, self.if_undistort = int(bool(a["if_motion_deblur"])), int(bool(a["if_undistort"]))
+        if self.if_undistort and full_maps:
+            raise ValueError("if_undistort=1 is not available with full_maps=True (and so not with key frames, loop closure or map "
+                             "refinement) in the batched loop: the append of the full selections and the scan log would need the full "
+                             "cloud with intensity := time stamp on the device; if_motion_deblur=1 alone is")
         if refresh_threads is None:
             refresh_threads = min(4, n_sequences)
         if not 1 <= int(refresh_threads) <= 16:
@@ -496,6 +509,10 @@ class Laser_mapping_batch:
         self.m_if_input_downsample_mode = a["input_downsample_mode"]
         self.history_add_t_step, self.history_add_angle_step = a["history_add_t_step"], a["history_add_angle_step"]
         _set_registrar_params(self.reg.params, **a)
+        if self.if_motion_deblur:
+            self.reg.params.if_motion_deblur = 1
+        self.m_last_time_stamp = np.zeros(S, np.float64)  # m_last_time_stamp of every sequence (laser_mapping.hpp:1345-1347)
+        self._ranges = None                               # this step's (minimum, maximum) time stamps per slot, with if_motion_deblur
         self.frame_index = np.zeros(S, np.int32)                                  # m_current_frame_index of every sequence
         self.poses = np.tile(np.array([0, 0, 0, 1, 0, 0, 0], np.float64), (S, 1))  # m_q_w_curr / m_t_w_curr
         self.map_sizes = [(0, 0)] * S
@@ -573,14 +590,29 @@ class Laser_mapping_batch:
         for s in range(S):  # an idle slot holds an empty scan: nothing is extracted for it
             self.fe.upload(arrs[s][None] if active[s] else empty, stamps[s:s + 1], first_scan=s)
 
+    def _time_ranges(self, stamps, active) -> None:
+        """find_min_max_intensity( full ) per sequence (laser_mapping.hpp:1336-1347): slot s runs from its previous frame's last stamp to
+        this frame's, whatever becomes of the registration; an idle slot keeps its stamp.  One selection_last for all slots."""
+        last = self.fe.selection_last(self.n_sequences, 2)  # (ascending: the last position carries the largest stamp)
+        lo, hi = self.m_last_time_stamp.copy(), self.m_last_time_stamp.copy()
+        for s in range(self.n_sequences):
+            if active[s]:
+                hi[s] = float(_point_time_stamp(stamps[s], int(last[s]), self.fe.params.time_internal_pts)) if last[s] >= 0 else 0.0
+                self.m_last_time_stamp[s] = hi[s]
+        self._ranges = (lo, hi)
+
     def _enqueue(self, maps, fi):
         S = self.n_sequences
+        if self.if_motion_deblur:  # one-shot: in front of every enqueue, the repeat of an aborted solve included
+            self.reg.set_time_ranges(*self._ranges)
         if self.m_if_input_downsample_mode:  # laser_mapping.hpp:1367-1373
             self.reg.enqueue_fe_downsampled_maps(maps, self.fe, self.vox[0], self.vox[1], self.line_res, self.plane_res, S, self.poses, self.poses, fi)
         else:
             self.reg.enqueue_fe_maps(maps, self.fe, S, self.poses, self.poses, fi)
 
     def _add_and_refresh(self, s, pose_before, pose_new):
+        """(with if_undistort the caller has handed sequence s's deskew record to histories[s] already, on its own thread: the copies
+        go through the one registrar, which the pool's threads must not share)"""
         import time
         t0 = time.perf_counter()
         h = self.histories[s]
@@ -593,7 +625,7 @@ class Laser_mapping_batch:
         sizes = h.refresh(self.maps[s])
         return s, sizes, t1 - t0, time.perf_counter() - t1
 
-    def _add_and_refresh_batched(self, jobs):
+    def _add_and_refresh_batched(self, jobs, undistort=False):
         """the accepted slots of a step through one add and one refresh; rejected and idle slots are inactive"""
         import time
         S = self.n_sequences
@@ -604,6 +636,8 @@ class Laser_mapping_batch:
             on[s] = True
             gate[s], new[s] = pose_before, pose_new  # m_q_w_curr is still the pre-registration pose at LM:1439-1451
         hb = self.history_batch
+        if undistort:
+            hb.set_undistort(self.reg)  # :1424,1430 for every slot
         if self.m_if_input_downsample_mode:
             added = hb.add_voxel(self.vox[0], self.vox[1], new, gate, on, self.history_add_t_step, self.history_add_angle_step)
         else:
@@ -641,6 +675,8 @@ class Laser_mapping_batch:
         fe.extract_batch(S)
         fe.resolve()
         fe.select_batch(S, -1, 0.0, 1.0)
+        if self.if_motion_deblur:
+            self._time_ranges(stamps, active)
         fi = self.frame_index.copy()  # init_pointcloud_registration runs before the increment
         self.frame_index[active] += 1
         maps = [self.maps[s] if active[s] else None for s in range(S)]
@@ -650,9 +686,14 @@ class Laser_mapping_batch:
         flags = getattr(reg, "debug_flags", 0)
         again = [s for s in range(S) if active[s] and reps[s].aborted]
         self.aborted_solves += len(again)
-        if again and not (flags & 32):
+        repeated = bool(again and not (flags & 32))
+        if repeated:
             # Laser_mapping's repeat of a registration the grouped solver abandoned: those slots once more on one workgroup each,
-            # the others idle
+            # the others idle.  With if_motion_deblur the repeat overwrites the deskew records of the slots it leaves idle, so all
+            # active slots repeat: every slot runs solve_big on one workgroup either way, the same bits.  (No solve is abandoned there
+            # today -- the grouped solver is not used -- but the repeat, its ranges included, is part of the loop's contract.)
+            if self.if_motion_deblur:
+                again = [s for s in range(S) if active[s]]
             reg.set_debug_flags(flags | 32)
             self._enqueue([self.maps[s] if s in again else None for s in range(S)], fi)
             res2, pc2, _, reps2 = reg.collect(S)
@@ -673,8 +714,15 @@ class Laser_mapping_batch:
             out[s] = 1 if res[s] else 0
             if res[s]:  # :1413-1416
                 jobs.append((s, self.poses[s].copy(), pc[s].copy()))
+        # if_undistort: the adds move their clouds with the registration's records (:1424,1430).  Without motion deblur a record is the
+        # plain transform with the pose the add receives, bit for bit, so the one step in which a repeat has overwritten the other
+        # slots' records goes without them.
+        undistort = bool(self.if_undistort and jobs and (self.if_motion_deblur or not repeated))
+        if undistort and not self.batched_history:
+            for s, _, _ in jobs:  # on this thread, before the pool starts: the copies go through the one registrar
+                self.histories[s].set_undistort(reg, s)
         if self.batched_history:
-            done = self._add_and_refresh_batched(jobs) if jobs else []
+            done = self._add_and_refresh_batched(jobs, undistort) if jobs else []
         elif self._pool is not None and len(jobs) > 1:
             done = list(self._pool.map(lambda j: self._add_and_refresh(*j), jobs))
         else:

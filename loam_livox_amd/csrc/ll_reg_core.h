@@ -130,12 +130,11 @@ LL_HD void interp_rodrigues(const double q[4], double *theta, double hat[9], dou
     hat[6] = -axis[1];
     hat[5] = -axis[0];
     hat[7] = axis[0];
+    // PCR:512, hat * hat: each entry (e0 + e1) + e2 as Eigen sums a 3 x 3 product -- no +0 in front, which would turn a sum of
+    // three -0 (an axis in a coordinate plane) into +0.  The values are the same either way and the sign of a zero entry reaches no
+    // coordinate (point_to_map_undistort adds it to +0 or to 1); the state is held to the reference's in bits (tests/test_ref_undistort.py)
     for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            double s = 0;
-            for (int k = 0; k < 3; k++) s += hat[i * 3 + k] * hat[k * 3 + j];
-            hat_sq[i * 3 + j] = s;
-        }
+        for (int j = 0; j < 3; j++) hat_sq[i * 3 + j] = (hat[i * 3] * hat[j] + hat[i * 3 + 1] * hat[3 + j]) + hat[i * 3 + 2] * hat[6 + j];
 }
 
 // pointAssociateToMap with its undistort branch (point_cloud_registration.hpp:622-661): the point p = (x, y, z, time stamp) moves with

@@ -21,7 +21,13 @@
  *     BIT-EXACT.  The only third-party arithmetic on that path is Eigen's 3-vector dot()/norm() order.
  *   - residual functors (ICP, rows a10/a11, incl. _mb): residuals and AutoDiff Jacobians to 1e-12.
  *   - registration driver (PCR:163-583, rows a7, a9 line check, a12, a14, a15): the reference's own control flow,
- *     pose / costs / thresholds / block counts to 1e-9.
+ *     pose / costs / thresholds / block counts to 1e-9; also from a start increment with w < 0, and the state left by a rejected
+ *     and by a gated registration (tests/test_ref_undistort.py).
+ *   - the undistort branch (PCR:607-661: compute_interpolatation_rodrigue, pointAssociateToMap with if_undistore = 1): the shim sets and
+ *     reads the reference object's state and calls both; orc_compute_interp and orc_cloud_associate equal it BIT-EXACT over angles
+ *     1e-300 .. 2 pi, both signs of w, stamps below / in / on / above the range and NaN (tests/test_ref_undistort.py), and on the
+ *     committed outputs tests/golden/ref_undistort.npz (tests/test_ref_undistort_golden.py).  Where |vec| < epsilon Eigen takes
+ *     stableNorm(); the stand-in's is norm(), so below ~1e-154 rad both sides fall to the zero-angle branch: pinned to the stand-in.
  * STILL UNPINNED (restated from the libraries' published behaviour, in ref_stubs/ and here alike):
  *   - PCL KdTreeFLANN::nearestKSearch (FLANN KDTreeSingleIndex, L2_Simple<float>):
  *     exact k-NN, squared distance accumulated in fp32 in x,y,z order, sorted ascending.
@@ -196,6 +202,15 @@ int orc_reg_solve(const orc_kdtree *tree_corner, const float *map_corner, int64_
                   const orc_reg_params *prm, const double pose_last[7], double pose_curr[7],
                   double pose_incre[7], orc_reg_report *rep);
 
+/* The same registration, and the state it leaves for pointAssociateToMap's undistort branch (m_interpolatation_theta, _omega_hat,
+ * _omega_hat_sq2; row-major): what PCR:509-513 computed from the last increment, kept through a rejection, zero where the gate
+ * returned before the first solve (the members are uninitialised in the reference; defined as zero, as the shim does). */
+int orc_reg_solve_state(const orc_kdtree *tree_corner, const float *map_corner, int64_t n_map_corner,
+                        const orc_kdtree *tree_surf, const float *map_surf, int64_t n_map_surf, int map_stride,
+                        const float *scan_corner, int n_corner, const float *scan_surf, int n_surf,
+                        const orc_reg_params *prm, const double pose_last[7], double pose_curr[7],
+                        double pose_incre[7], orc_reg_report *rep, double *theta, double hat[9], double hat_sq[9]);
+
 /* Pieces exposed for unit tests / cross-checks -------------------------------------- */
 
 /* One residual block in the form the cost functors hold it (ICP:238-380): kind 0 = line, 1 = plane.
@@ -233,6 +248,17 @@ void orc_point_to_map(const double pose[7], const float p[3], float out[3]);
 
 /* cloud transform, pointcloudAssociateToMap PCR:673-685 (no-deblur branch). xyzi in/out, n points. */
 void orc_cloud_transform(const double pose[7], const float *in_xyzi, float *out_xyzi, int n);
+
+/* compute_interpolatation_rodrigue (PCR:607-620) of q = {x,y,z,w}, Eigen's AngleAxis( QuaternionBase ): the angle from |vec| and |w|,
+ * then the axis turned for w < 0; hat = the normalised axis' cross-product matrix, hat_sq = hat * hat (PCR:512); row-major. */
+void orc_compute_interp(const double q_xyzw[4], double *theta, double hat[9], double hat_sq[9]);
+
+/* pointcloudAssociateToMap( in, out, if_undistore ) with all of PCR:622-661: s = refine_blur( intensity ) in float; the pose_curr
+ * branch when deblur or if_undistore is 0 or s == 1; otherwise Rodrigues' interpolation from pose_last with the given state
+ * (t_incre = the increment's translation).  s < 0 extrapolates.  xyzi in/out, intensity copied. */
+void orc_cloud_associate(int deblur, int if_undistore, float min_ts, float max_ts, const double pose_curr[7], const double pose_last[7],
+                         const double t_incre[3], double theta, const double hat[9], const double hat_sq[9], const float *in_xyzi,
+                         float *out_xyzi, int n);
 
 #ifdef __cplusplus
 }

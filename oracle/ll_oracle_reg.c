@@ -969,9 +969,9 @@ static void compute_interp(const quat *q_in, interp_state *st)
 {
     double v[3] = {q_in->x, q_in->y, q_in->z};
     double n = norm3(v), w = q_in->w, axis[3];
-    if (w < 0) n = -n; /* Eigen AngleAxis(QuaternionBase): if(q.w()<0) n = -n */
     if (n != 0.0) {
-        st->theta = 2.0 * atan2(n, fabs(w));
+        st->theta = 2.0 * atan2(n, fabs(w)); /* Eigen AngleAxis::operator=(QuaternionBase): the angle from |vec| and |w| ... */
+        if (w < 0) n = -n;                   /* ... then the axis turned for w < 0 */
         for (int i = 0; i < 3; i++) axis[i] = v[i] / n;
     } else {
         st->theta = 0;
@@ -989,11 +989,8 @@ static void compute_interp(const quat *q_in, interp_state *st)
     st->hat[1 * 3 + 2] = -axis[0];
     st->hat[2 * 3 + 1] = axis[0];
     for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            double s = 0;
-            for (int k = 0; k < 3; k++) s += st->hat[i * 3 + k] * st->hat[k * 3 + j];
-            st->hat_sq[i * 3 + j] = s; /* PCR:512 */
-        }
+        for (int j = 0; j < 3; j++) /* PCR:512; Eigen's 3 x 3 product: (e0 + e1) + e2, no +0 in front (the sign of a zero entry) */
+            st->hat_sq[i * 3 + j] = (st->hat[i * 3] * st->hat[j] + st->hat[i * 3 + 1] * st->hat[3 + j]) + st->hat[i * 3 + 2] * st->hat[6 + j];
 }
 
 /* pointAssociateToMap PCR:622-661 */
@@ -1019,6 +1016,38 @@ static void point_associate(int deblur, const double pose_curr[7], const double 
     out[2] = (float)(o[2] + pose_last[6]);
 }
 
+void orc_compute_interp(const double q_xyzw[4], double *theta, double hat[9], double hat_sq[9])
+{
+    quat q = {q_xyzw[0], q_xyzw[1], q_xyzw[2], q_xyzw[3]};
+    interp_state st;
+    compute_interp(&q, &st);
+    *theta = st.theta;
+    memcpy(hat, st.hat, sizeof(st.hat));
+    memcpy(hat_sq, st.hat_sq, sizeof(st.hat_sq));
+}
+
+/* pointcloudAssociateToMap PCR:673-685 with its undistort branch: refine_blur of the intensity (:681), then point_associate;
+ * if_undistore == 0 is the plain branch (:627); intensity copied (:659) */
+void orc_cloud_associate(int deblur, int if_undistore, float min_ts, float max_ts, const double pose_curr[7], const double pose_last[7],
+                         const double t_incre[3], double theta, const double hat[9], const double hat_sq[9], const float *in_xyzi,
+                         float *out_xyzi, int n)
+{
+    interp_state st;
+    st.theta = theta;
+    memcpy(st.hat, hat, sizeof(st.hat));
+    memcpy(st.hat_sq, hat_sq, sizeof(st.hat_sq));
+    for (int i = 0; i < n; i++) {
+        float o[3];
+        float inten = in_xyzi[4 * i + 3];
+        float s = refine_blur(deblur, inten, min_ts, max_ts);
+        point_associate(if_undistore ? deblur : 0, pose_curr, pose_last, t_incre, &st, &in_xyzi[4 * i], (double)s, o);
+        out_xyzi[4 * i] = o[0];
+        out_xyzi[4 * i + 1] = o[1];
+        out_xyzi[4 * i + 2] = o[2];
+        out_xyzi[4 * i + 3] = inten;
+    }
+}
+
 static int cmp_double(const void *a, const void *b)
 {
     double x = *(const double *)a, y = *(const double *)b;
@@ -1040,13 +1069,14 @@ static double inlier_threshold(const double *l1, int n, double ratio, double fal
     return r;
 }
 
-int orc_reg_solve(const orc_kdtree *tree_corner, const float *map_corner, int64_t n_map_corner,
-                  const orc_kdtree *tree_surf, const float *map_surf, int64_t n_map_surf, int map_stride,
-                  const float *scan_corner, int n_corner, const float *scan_surf, int n_surf,
-                  const orc_reg_params *prm, const double pose_last[7], double pose_curr[7],
-                  double pose_incre[7], orc_reg_report *rep)
+static int reg_solve_impl(const orc_kdtree *tree_corner, const float *map_corner, int64_t n_map_corner,
+                          const orc_kdtree *tree_surf, const float *map_surf, int64_t n_map_surf, int map_stride,
+                          const float *scan_corner, int n_corner, const float *scan_surf, int n_surf,
+                          const orc_reg_params *prm, const double pose_last[7], double pose_curr[7],
+                          double pose_incre[7], orc_reg_report *rep, interp_state *st_out)
 {
     memset(rep, 0, sizeof(*rep));
+    memset(st_out, 0, sizeof(*st_out)); /* a fresh object's state: PCR:58,67,68 are uninitialised, defined as zero */
     rep->accepted = 1;
     /* PCR:199 gate */
     if (!(n_map_corner > 0 && n_map_surf > 50 && prm->current_frame_index > prm->mapping_init_accumulate_frames)) {
@@ -1205,6 +1235,7 @@ int orc_reg_solve(const orc_kdtree *tree_corner, const float *map_corner, int64_
     rep->angular_diff_deg = angular_diff;
     rep->t_diff = t_diff;
     rep->inlier_threshold = inlier_thr * sum.final_cost / sum.initial_cost; /* PCR:559 */
+    *st_out = st; /* kept through a rejection: PCR:561-573 restores the pose only */
 
     free(blocks);
     free(active);
@@ -1220,4 +1251,30 @@ int orc_reg_solve(const orc_kdtree *tree_corner, const float *map_corner, int64_
         return 0;
     }
     return 1;
+}
+
+int orc_reg_solve(const orc_kdtree *tree_corner, const float *map_corner, int64_t n_map_corner,
+                  const orc_kdtree *tree_surf, const float *map_surf, int64_t n_map_surf, int map_stride,
+                  const float *scan_corner, int n_corner, const float *scan_surf, int n_surf,
+                  const orc_reg_params *prm, const double pose_last[7], double pose_curr[7],
+                  double pose_incre[7], orc_reg_report *rep)
+{
+    interp_state st;
+    return reg_solve_impl(tree_corner, map_corner, n_map_corner, tree_surf, map_surf, n_map_surf, map_stride, scan_corner, n_corner,
+                          scan_surf, n_surf, prm, pose_last, pose_curr, pose_incre, rep, &st);
+}
+
+int orc_reg_solve_state(const orc_kdtree *tree_corner, const float *map_corner, int64_t n_map_corner,
+                        const orc_kdtree *tree_surf, const float *map_surf, int64_t n_map_surf, int map_stride,
+                        const float *scan_corner, int n_corner, const float *scan_surf, int n_surf,
+                        const orc_reg_params *prm, const double pose_last[7], double pose_curr[7],
+                        double pose_incre[7], orc_reg_report *rep, double *theta, double hat[9], double hat_sq[9])
+{
+    interp_state st;
+    int ret = reg_solve_impl(tree_corner, map_corner, n_map_corner, tree_surf, map_surf, n_map_surf, map_stride, scan_corner, n_corner,
+                             scan_surf, n_surf, prm, pose_last, pose_curr, pose_incre, rep, &st);
+    *theta = st.theta;
+    memcpy(hat, st.hat, sizeof(st.hat));
+    memcpy(hat_sq, st.hat_sq, sizeof(st.hat_sq));
+    return ret;
 }

@@ -132,6 +132,10 @@ def lib():
         L.orc_blocks_eval.argtypes = [C.POINTER(Block), C.c_int, dp, dp, C.c_int, C.c_double, dp, dp, dp]
         L.orc_point_to_map.argtypes = [dp, fp, fp]
         L.orc_cloud_transform.argtypes = [dp, fp, fp, C.c_int]
+        L.orc_reg_solve_state.argtypes = L.orc_reg_solve.argtypes + [dp, dp, dp]
+        L.orc_reg_solve_state.restype = C.c_int
+        L.orc_compute_interp.argtypes = [dp, dp, dp, dp]
+        L.orc_cloud_associate.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, dp, dp, dp, C.c_double, dp, dp, fp, fp, C.c_int]
         _lib = L
     return _lib
 
@@ -273,6 +277,42 @@ def reg_solve(tree_c: KdTree, tree_s: KdTree, scan_corner: np.ndarray, scan_surf
                           tree_s.xyz.shape[0], tree_c.stride, _fp(sc), sc.shape[0], _fp(ss), ss.shape[0],
                           C.byref(prm), _dp(pl), _dp(pc), _dp(pi), C.byref(rep))
     return ret, pc, pi, rep
+
+
+def reg_solve_state(tree_c: KdTree, tree_s: KdTree, scan_corner, scan_surf, prm: RegParams, pose_last, pose_curr, pose_incre=None):
+    """reg_solve, and the state the registration leaves for the undistort branch: (ret, pose_curr, pose_incre, report,
+    dict(theta, omega_hat [3, 3], omega_hat_sq2 [3, 3]))"""
+    L = lib()
+    sc = np.ascontiguousarray(scan_corner, np.float32).reshape(-1, 4)
+    ss = np.ascontiguousarray(scan_surf, np.float32).reshape(-1, 4)
+    pl = np.ascontiguousarray(pose_last, np.float64).copy()
+    pc = np.ascontiguousarray(pose_curr, np.float64).copy()
+    pi = np.array([0, 0, 0, 1, 0, 0, 0], np.float64) if pose_incre is None else np.ascontiguousarray(pose_incre, np.float64).copy()
+    rep = RegReport()
+    th, hat, hat_sq = np.zeros(1), np.zeros((3, 3)), np.zeros((3, 3))
+    assert tree_c.stride == tree_s.stride
+    ret = L.orc_reg_solve_state(tree_c.h, _fp(tree_c.xyz), tree_c.xyz.shape[0], tree_s.h, _fp(tree_s.xyz), tree_s.xyz.shape[0], tree_c.stride,
+                                _fp(sc), sc.shape[0], _fp(ss), ss.shape[0], C.byref(prm), _dp(pl), _dp(pc), _dp(pi), C.byref(rep),
+                                _dp(th), _dp(hat), _dp(hat_sq))
+    return ret, pc, pi, rep, dict(theta=float(th[0]), omega_hat=hat, omega_hat_sq2=hat_sq)
+
+
+def compute_interp(q_xyzw):
+    """compute_interpolatation_rodrigue (PCR:607-620) -> (theta, hat [3, 3], hat_sq [3, 3])"""
+    q = np.ascontiguousarray(q_xyzw, np.float64)
+    th, hat, hat_sq = np.zeros(1), np.zeros((3, 3)), np.zeros((3, 3))
+    lib().orc_compute_interp(_dp(q), _dp(th), _dp(hat), _dp(hat_sq))
+    return float(th[0]), hat, hat_sq
+
+
+def cloud_associate(xyzi, pose_last, pose_curr, pose_incre, theta, hat, hat_sq, deblur, min_ts, max_ts, if_undistore=1):
+    """pointcloudAssociateToMap( in, out, if_undistore ) of a registrar in the given state (PCR:622-661, 673-685)"""
+    xyzi = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
+    a = [np.ascontiguousarray(v, np.float64) for v in (pose_curr, pose_last, np.asarray(pose_incre, np.float64)[4:7], hat, hat_sq)]
+    out = np.empty_like(xyzi)
+    lib().orc_cloud_associate(int(deblur), int(if_undistore), float(min_ts), float(max_ts), _dp(a[0]), _dp(a[1]), _dp(a[2]), float(theta),
+                              _dp(a[3]), _dp(a[4]), _fp(xyzi), _fp(out), xyzi.shape[0])
+    return out
 
 
 def make_block_line(f, a, b, s=1.0) -> Block:

@@ -69,6 +69,10 @@ def lib():
         L.ref_reg_set_maps.argtypes = [vp, fp, C.c_int64, fp, C.c_int64, C.c_int]
         L.ref_reg_solve.argtypes = [vp, fp, C.c_int, fp, C.c_int, dp, dp, dp, dp]
         L.ref_reg_cloud_transform.argtypes = [vp, dp, fp, fp, C.c_int]
+        L.ref_reg_get_state.argtypes = [vp, dp, dp, dp, dp, dp, dp]
+        L.ref_reg_set_state.argtypes = [vp, C.c_double, dp, dp, dp, dp, dp, C.c_int, C.c_float, C.c_float]
+        L.ref_reg_compute_interp.argtypes = [vp, dp, dp, dp, dp]
+        L.ref_reg_cloud_associate.argtypes = [vp, fp, fp, C.c_int, C.c_int]
         L.ref_reg_refine_blur.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
         L.ref_reg_refine_blur.restype = C.c_float
         L.ref_reg_inlier_threshold.argtypes = [vp, dp, C.c_int, C.c_double]
@@ -208,6 +212,32 @@ class RefRegistration:
         xyzi = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
         out = np.empty_like(xyzi)
         self.L.ref_reg_cloud_transform(self.h, _dp(np.ascontiguousarray(pose, np.float64)), _fp(xyzi), _fp(out), xyzi.shape[0])
+        return out
+
+    def state(self):
+        """What the object holds for pointAssociateToMap's undistort branch: dict(theta, omega_hat [3, 3], omega_hat_sq2 [3, 3],
+        pose_incre [7], pose_last [7], pose_curr [7])."""
+        th, hat, hat_sq, pi, pl, pc = np.zeros(1), np.zeros((3, 3)), np.zeros((3, 3)), np.zeros(7), np.zeros(7), np.zeros(7)
+        self.L.ref_reg_get_state(self.h, _dp(th), _dp(hat), _dp(hat_sq), _dp(pi), _dp(pl), _dp(pc))
+        return dict(theta=float(th[0]), omega_hat=hat, omega_hat_sq2=hat_sq, pose_incre=pi, pose_last=pl, pose_curr=pc)
+
+    def set_state(self, theta, omega_hat, omega_hat_sq2, pose_incre, pose_last, pose_curr, if_motion_deblur, min_ts, max_ts):
+        a = [np.ascontiguousarray(v, np.float64) for v in (omega_hat, omega_hat_sq2, pose_incre, pose_last, pose_curr)]
+        assert [v.size for v in a] == [9, 9, 7, 7, 7]
+        self.L.ref_reg_set_state(self.h, float(theta), *(_dp(v) for v in a), int(if_motion_deblur), float(min_ts), float(max_ts))
+
+    def compute_interp(self, q_xyzw):
+        """compute_interpolatation_rodrigue (PCR:607-620) on q = (x, y, z, w) -> (theta, hat [3, 3], hat * hat [3, 3])"""
+        q = np.ascontiguousarray(q_xyzw, np.float64)
+        th, hat, hat_sq = np.zeros(1), np.zeros((3, 3)), np.zeros((3, 3))
+        self.L.ref_reg_compute_interp(self.h, _dp(q), _dp(th), _dp(hat), _dp(hat_sq))
+        return float(th[0]), hat, hat_sq
+
+    def cloud_associate(self, xyzi, if_undistore):
+        """pointcloudAssociateToMap( in, out, if_undistore ) with the object's state as it stands"""
+        xyzi = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
+        out = np.empty_like(xyzi)
+        self.L.ref_reg_cloud_associate(self.h, _fp(xyzi), _fp(out), xyzi.shape[0], int(if_undistore))
         return out
 
     def refine_blur(self, deblur, in_blur, min_blur, max_blur):

@@ -298,6 +298,86 @@ void ref_reg_cloud_transform( void *h, const double pose[ 7 ], const float *in_x
     cloud_to( out, out_xyzi );
 }
 
+// ---- taps for the undistort branch (PCR:607-661).  Every member is public: these only read, set and call them.
+static void mat3_to( const Eigen::Matrix<double, 3, 3> &m, double o[ 9 ] )
+{
+    for ( int i = 0; i < 3; i++ )
+        for ( int j = 0; j < 3; j++ )
+            o[ 3 * i + j ] = m( i, j );
+}
+static void mat3_from( const double o[ 9 ], Eigen::Matrix<double, 3, 3> &m )
+{
+    for ( int i = 0; i < 3; i++ )
+        for ( int j = 0; j < 3; j++ )
+            m( i, j ) = o[ 3 * i + j ];
+}
+
+// state out: what compute_interpolatation_rodrigue left (PCR:509-513), the increment buffer and both poses {qx,qy,qz,qw,tx,ty,tz};
+// matrices row-major
+void ref_reg_get_state( void *h, double *theta, double hat[ 9 ], double hat_sq[ 9 ], double pose_incre[ 7 ], double pose_last[ 7 ], double pose_curr[ 7 ] )
+{
+    Point_cloud_registration &r = ( ( RefReg * ) h )->reg;
+    *theta = r.m_interpolatation_theta;
+    mat3_to( r.m_interpolatation_omega_hat, hat );
+    mat3_to( r.m_interpolatation_omega_hat_sq2, hat_sq );
+    for ( int i = 0; i < 7; i++ )
+        pose_incre[ i ] = r.m_para_buffer_incremental[ i ];
+    const Eigen::Quaterniond *q[ 2 ] = { &r.m_q_w_last, &r.m_q_w_curr };
+    const Eigen::Vector3d *   t[ 2 ] = { &r.m_t_w_last, &r.m_t_w_curr };
+    double *                  o[ 2 ] = { pose_last, pose_curr };
+    for ( int k = 0; k < 2; k++ )
+    {
+        o[ k ][ 0 ] = q[ k ]->x();
+        o[ k ][ 1 ] = q[ k ]->y();
+        o[ k ][ 2 ] = q[ k ]->z();
+        o[ k ][ 3 ] = q[ k ]->w();
+        o[ k ][ 4 ] = t[ k ]->x();
+        o[ k ][ 5 ] = t[ k ]->y();
+        o[ k ][ 6 ] = t[ k ]->z();
+    }
+}
+
+// state in: the same fields, m_if_motion_deblur and the time range, so that any state reaches pointAssociateToMap
+void ref_reg_set_state( void *h, double theta, const double hat[ 9 ], const double hat_sq[ 9 ], const double pose_incre[ 7 ], const double pose_last[ 7 ],
+                        const double pose_curr[ 7 ], int if_motion_deblur, float min_time_stamp, float max_time_stamp )
+{
+    Point_cloud_registration &r = ( ( RefReg * ) h )->reg;
+    r.m_interpolatation_theta = theta;
+    mat3_from( hat, r.m_interpolatation_omega_hat );
+    mat3_from( hat_sq, r.m_interpolatation_omega_hat_sq2 );
+    for ( int i = 0; i < 7; i++ )
+        r.m_para_buffer_incremental[ i ] = pose_incre[ i ];
+    r.m_q_w_last = Eigen::Quaterniond( pose_last[ 3 ], pose_last[ 0 ], pose_last[ 1 ], pose_last[ 2 ] );
+    r.m_t_w_last = Eigen::Vector3d( pose_last[ 4 ], pose_last[ 5 ], pose_last[ 6 ] );
+    r.m_q_w_curr = Eigen::Quaterniond( pose_curr[ 3 ], pose_curr[ 0 ], pose_curr[ 1 ], pose_curr[ 2 ] );
+    r.m_t_w_curr = Eigen::Vector3d( pose_curr[ 4 ], pose_curr[ 5 ], pose_curr[ 6 ] );
+    r.m_if_motion_deblur = if_motion_deblur;
+    r.m_minimum_pt_time_stamp = min_time_stamp;
+    r.m_maximum_pt_time_stamp = max_time_stamp;
+}
+
+// compute_interpolatation_rodrigue (PCR:607-620) on q = {x,y,z,w}, into locals: the object's state is not touched.  hat_sq as PCR:512.
+void ref_reg_compute_interp( void *h, const double q_xyzw[ 4 ], double *theta, double hat[ 9 ], double hat_sq[ 9 ] )
+{
+    Point_cloud_registration &  r = ( ( RefReg * ) h )->reg;
+    Eigen::Quaterniond          q( q_xyzw[ 3 ], q_xyzw[ 0 ], q_xyzw[ 1 ], q_xyzw[ 2 ] );
+    Eigen::Matrix<double, 3, 1> omega;
+    Eigen::Matrix<double, 3, 3> m_hat, m_hat_sq;
+    r.compute_interpolatation_rodrigue( q, omega, *theta, m_hat );
+    m_hat_sq = m_hat * m_hat;
+    mat3_to( m_hat, hat );
+    mat3_to( m_hat_sq, hat_sq );
+}
+
+// pointcloudAssociateToMap (PCR:673-685) with the object's state as it stands
+void ref_reg_cloud_associate( void *h, const float *in_xyzi, float *out_xyzi, int n, int if_undistore )
+{
+    Point_cloud_registration &r = ( ( RefReg * ) h )->reg;
+    Cloud                     in = cloud_from( in_xyzi, n ), out;
+    r.pointcloudAssociateToMap( in, out, if_undistore );
+    cloud_to( out, out_xyzi );
+}
+
 // refine_blur (PCR:128-141)
 float ref_reg_refine_blur( void *h, int deblur, float in_blur, float min_blur, float max_blur )
 {

@@ -553,24 +553,8 @@ int hc_reg_solve(const hc_grid *gc, const hc_grid *gs, const float *corner, int 
                 if (subsample_skip_feature((unsigned int)p->subsample_seed, kind, it, q, n, p->max_blocks)) continue;  // PCR:232-238, 339-345
                 float pw[3];
                 const float sblur = refine_blur(p->if_motion_deblur, f[3], p->min_ts, p->max_ts);
-                if (p->if_motion_deblur == 0 || (double)sblur == 1.0) {
-                    point_to_map(pose_curr, f[0], f[1], f[2], pw);
-                } else {  // Rodrigues interpolation, PCR:641-646
-                    const double sd = (double)sblur;
-                    const double T[3] = {inc[4] * (sd * 1.0), inc[5] * (sd * 1.0), inc[6] * (sd * 1.0)};
-                    const double th = interp_theta * sd, sn = sin(th), cs1 = 1.0 - cos(th);
-                    const double pc3[3] = {(double)f[0], (double)f[1], (double)f[2]};
-                    double inner[3], o[3];
-                    for (int i = 0; i < 3; i++) {
-                        double acc = 0.0;
-                        for (int j = 0; j < 3; j++) acc += (((i == j) ? 1.0 : 0.0) + sn * hat[i * 3 + j] + cs1 * hat_sq[i * 3 + j]) * pc3[j];
-                        inner[i] = acc + T[i];
-                    }
-                    quat_rot(pose_last, inner, o);
-                    pw[0] = (float)(o[0] + pose_last[4]);
-                    pw[1] = (float)(o[1] + pose_last[5]);
-                    pw[2] = (float)(o[2] + pose_last[6]);
-                }
+                const f4 fp4 = {f[0], f[1], f[2], f[3]};  // PCR:622-661, the function transform_query runs
+                point_to_map_undistort(pose_last, pose_curr, &inc[4], interp_theta, hat, hat_sq, p->if_motion_deblur, p->min_ts, p->max_ts, fp4, pw);
                 Knn5 r;
                 const float md2 = kind ? fp : fl;
                 KnnRef &ref = refs[kind][q];
@@ -687,28 +671,7 @@ int hc_reg_solve(const hc_grid *gc, const hc_grid *gs, const float *corner, int 
         n_blocks_last = 0;
         for (const hc_blk &b : blk) n_blocks_last += b.active;
         for (int i = 0; i < 7; i++) inc[i] = c.x[i];
-        if (p->if_motion_deblur) {  // compute_interpolatation_rodrigue, PCR:607-620
-            double n = sqrt(inc[0] * inc[0] + inc[1] * inc[1] + inc[2] * inc[2]), axis[3];
-            if (inc[3] < 0) n = -n;
-            if (n != 0.0) {
-                interp_theta = 2.0 * atan2(n, fabs(inc[3]));
-                for (int i = 0; i < 3; i++) axis[i] = inc[i] / n;
-            } else {
-                interp_theta = 0.0;
-                axis[0] = 1.0;
-                axis[1] = axis[2] = 0.0;
-            }
-            const double an = sqrt(dot3(axis, axis));
-            for (int i = 0; i < 3; i++) axis[i] /= an;
-            for (int i = 0; i < 9; i++) hat[i] = 0.0;
-            hat[1] = -axis[2]; hat[3] = axis[2]; hat[2] = axis[1]; hat[6] = -axis[1]; hat[5] = -axis[0]; hat[7] = axis[0];
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++) {
-                    double sacc = 0;
-                    for (int k = 0; k < 3; k++) sacc += hat[i * 3 + k] * hat[k * 3 + j];
-                    hat_sq[i * 3 + j] = sacc;
-                }
-        }
+        if (p->if_motion_deblur) interp_rodrigues(inc, &interp_theta, hat, hat_sq);  // compute_interpolatation_rodrigue, PCR:607-620: the solver's call
         double tw[3], qc[4];
         quat_rot(pose_last, &inc[4], tw);
         pose_curr[4] = tw[0] + pose_last[4];

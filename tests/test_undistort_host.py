@@ -15,6 +15,7 @@ import pytest
 from loam_livox_amd import api, capi, mapping
 from tests import api_standin
 from tests import undistort_ref as ur
+from tests.undistort_pin import build_host_lib, host_interp, host_plain, host_undistort
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "loam_livox_hip.h")
@@ -23,42 +24,11 @@ NEW_SYMBOLS = {"ll_reg_interpolation": 6, "ll_cloud_undistort": 5, "ll_cloud_und
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("undistort") / "libundistort_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", so,
-                           os.path.join(ROOT, "tests", "undistort_host.cpp")])
-    L = C.CDLL(so)
-    vp = C.c_void_p
-    L.uh_undistort.argtypes = [vp, vp, vp, C.c_double, vp, vp, C.c_int, C.c_float, C.c_float, vp, C.c_int, vp]
-    L.uh_point_to_map.argtypes = [vp, vp, C.c_int, vp]
-    L.uh_interp.argtypes = [vp, vp, vp, vp]
-    return L
+    return build_host_lib(tmp_path_factory.mktemp("undistort"))
 
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
-
-
-def host_interp(L, q):
-    q = np.ascontiguousarray(q, np.float64)
-    th, hat, hat_sq = np.zeros(1), np.zeros(9), np.zeros(9)
-    L.uh_interp(_p(q), _p(th), _p(hat), _p(hat_sq))
-    return float(th[0]), hat.reshape(3, 3), hat_sq.reshape(3, 3)
-
-
-def host_undistort(L, xyzi, pose_last, pose_curr, inc_t, theta, hat, hat_sq, deblur, min_ts, max_ts):
-    xyzi = np.ascontiguousarray(xyzi, np.float32)
-    a = [np.ascontiguousarray(v, np.float64) for v in (pose_last, pose_curr, inc_t, hat, hat_sq)]
-    out = np.zeros_like(xyzi)
-    L.uh_undistort(_p(a[0]), _p(a[1]), _p(a[2]), float(theta), _p(a[3]), _p(a[4]), int(deblur), float(min_ts), float(max_ts), _p(xyzi), len(xyzi), _p(out))
-    return out
-
-
-def host_plain(L, pose, xyzi):
-    xyzi = np.ascontiguousarray(xyzi, np.float32)
-    pose = np.ascontiguousarray(pose, np.float64)
-    out = np.zeros_like(xyzi)
-    L.uh_point_to_map(_p(pose), _p(xyzi), len(xyzi), _p(out))
-    return out
 
 
 def q_mul(a, b):

@@ -1,6 +1,7 @@
 """What the deskew tests share (tests/test_undistort_host.py, tests/test_gpu_undistort.py): a float64 numpy restatement of
 point_cloud_registration.hpp:622-661 (pointAssociateToMap with if_undistore = 1) and :607-620 (compute_interpolatation_rodrigue), and the
-rule the device's floats are held to against it.
+rule the device's floats are held to against it.  The restatement itself is held to the reference's compiled class under the same rule
+(tests/test_ref_undistort.py, tests/test_ref_undistort_golden.py).
 
 The rule.  Both sides round a double to float.  The doubles differ by a few fp64 ulps (other sin / cos / atan2 implementations, a rotation
 matrix here against Eigen's v + w uv + q x uv there), so the floats are equal unless the double lies within ~1e-15 relative of a rounding
